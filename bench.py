@@ -12,6 +12,11 @@ rebuilds per sweep, :770,:804 - redundant recomputation with bit-identical resul
 With --gpus N>1 (launched by torch.distributed.run) the N=4096 series are sharded over the
 ranks (strong scaling) and the bond gradient is all-reduced with RCCL once per optimiser step.
 
+A plain run sets up, warms up, times --steps sweeps and prints the headline (`value`, `ms_per_step`, ...).  --full adds
+everything else the line used to carry: device encoding, train KLD / accuracy, per-kernel roofline and quoted counters, the
+other cache-rebuild setting, concurrent and independent fits, the configs[3] sharded measurement and the CPU baseline.
+--dump-outputs DIR writes the MPS the last timed sweep left (DIR/site_<j>.npy); inputs are seeded, so runs compare.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -120,6 +125,37 @@ def host_cpu_model():
     return "unknown"
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: data of all .npy files together (the headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, one DIR/<name>.npy per array, in
+    float64 (float32 where the engine computed in it; complex arrays as <name>_re / <name>_im).  Two builds given the same
+    arguments see the same inputs, so their files compare element for element.  Beyond the byte budget every array is cut
+    to the same fraction of its elements, at positions drawn from a fixed seed."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind == "c":
+            flat[name + "_re"], flat[name + "_im"] = a.real, a.imag
+        else:
+            flat[name] = a
+    flat = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in flat.items()}
+    total = sum(a.nbytes for a in flat.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for name, a in flat.items():
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def mps_outputs(W):
+    """The trained MPS as the sweep leaves it: site_<j> for every site (bond dimensions are in the shapes)."""
+    return {f"site_{j:03d}": w for j, w in enumerate(W)}
+
+
 def random_chain(T, d, chi, rng):
     """Complex Gaussian site tensors in left-canonical form (the carried factor renormalised at every site), one class,
     label index on the last site: the shape of a Fourier-encoded MPS out of the reference's legacy trainer."""
@@ -177,6 +213,8 @@ def impute_workload(args, mt, torch, dist, world, rank, dev_index, host_reduce):
         dist.barrier()
         dev_s, wall = host_reduce([dev_s, wall], dist.ReduceOp.MAX)
     eng.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"imputed": x, "wmad": e})
     ms_step = 1e3 * dev_s / args.steps
     value = world * sites * args.steps / dev_s
     t_env, t_den = eng_phases            # seconds of the last pass on this rank
@@ -368,6 +406,8 @@ def typed_workload(args, mt, torch, rank, dev_index):
     mse, kld, acc, _ = eng.eval(0)
     chi_now, _ = eng.get_chi()
     Wend = eng.get_mps()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mps_outputs(Wend))
     info = eng.info()              # after the timed sweeps: the counters of the eigensolver paths (subspace attempted / accepted, fall-backs)
     eng.set_profile(0x7FF)
     eng.sweep()
@@ -585,6 +625,13 @@ def main():
                          "imputation of a held-out 50 %% block from both models; never the headline value")
     ap.add_argument("--allreduce", choices=["auto", "rccl", "oneshot"], default="auto",
                     help="collective of the sharded sweep: RCCL, the one-shot direct-write kernel, or whichever one trial sweep shows faster")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure of the training sweep: device encoding, train KLD / accuracy, per-kernel "
+                         "roofline and quoted counters, the other cache-rebuild setting, concurrent / independent fits, the configs[3] "
+                         "sharded side measurement, replica digests and the CPU baseline.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy (the sweep: the "
+                         "MPS' site tensors; imputation: imputed values and WMAD errors)")
     args = ap.parse_args()
     args.rebuild_caches = not args.no_rebuild_caches       # `value` is the like-for-like sweep: RealRealHighDimension.jl:770,804 are inside the timed :727-808
 
@@ -656,6 +703,9 @@ def main():
         if world > 1:
             note("--dtype side line runs on one GPU")
             sys.exit(2)
+        if args.study and args.dump_outputs:
+            note("--study has no timed steps whose outputs --dump-outputs could write")
+            sys.exit(2)
         line = tolerance_study(args, mt) if args.study else typed_workload(args, mt, torch, rank, dev_index)
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
         return
@@ -684,7 +734,7 @@ def main():
     # side measurement (not part of the timed sweeps): device-side preprocessing + encoding of the same raw matrix
     # (SURVEY 8f row 2), into the unused test slot; algorithmic bytes = 8 N T (1 + d)
     encode_info = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             eng.encode_dataset(1, full.original_data, full.label_index, C, basis="Legendre_No_Norm", d=d)      # warm-up
             _, enc_s = eng.encode_dataset(1, full.original_data, full.label_index, C, basis="Legendre_No_Norm", d=d)
@@ -794,6 +844,38 @@ def main():
     elapsed = t1 - t0
     if dist is not None:
         elapsed = host_reduce([elapsed], dist.ReduceOp.MAX)[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mps_outputs(eng.get_mps()))     # every rank holds the same MPS
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": ("full sweeps/sec (N=4096,T=100,chi=32,d=4)" if (N, T, chi, d) == (4096, 100, 32, 4)
+                       else f"full sweeps/sec (N={N},T={T},chi={chi},d={d}) - NOT the headline configuration"),
+            "value": args.steps / elapsed, "unit": "sweeps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"DMRG training sweep, noisy trendy sine 2-class, N={N}, T={T}, chi_max={chi}, d={d} Legendre, "
+                                   f"KLD+TSGO eta=0.01, fp64; " + ("configs[2] of BASELINE.json" if (N, T, chi, d) == (4096, 100, 32, 4)
+                                                                   else "a side measurement, not the configuration the metric is quoted on"),
+                       "N": N, "T": T, "chi_max": chi, "d": d, "C": C, "rebuild_caches": bool(args.rebuild_caches),
+                       "parallelism": f"batch-shard x{world}" if world > 1 else "single GPU"},
+            "device_ms_per_step": 1e3 * dev_s / args.steps,
+            "allreduce": allreduce,
+            "eig_fallbacks_total": fallbacks, "launch_chain": info,
+            "timed_region": "K sweeps with profiling off" + (" (hipGraph replay)" if info.get("graph") else " (plain stream)") +
+                            ("; per-kernel figures from separate event-instrumented sweeps after it" if args.full else ""),
+        }
+    if not args.full:
+        # a plain run ends with the headline: the side figures, checks and profiles below are --full's
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     mse, kld, acc, _ = eng.eval(0)
     chi_now, _ = eng.get_chi()
     # every rank holds the whole MPS and applied the same all-reduced updates: after the TIMED sweeps the replicas must still be
@@ -819,7 +901,6 @@ def main():
     prof = eng.get_profile()
     eng.set_profile(0)
 
-    out = None
     if rank == 0:
         model = kernel_model(N / world, d, chi, C, info)
         us_tot, cnt = prof[dominant]
@@ -873,26 +954,13 @@ def main():
                                                 "hbm_bytes_per_launch": hit[0].get("hbm_bytes_per_launch_corrected")}
             if dominant in pmc_quoted["kernels"]:
                 traffic, traffic_src = pmc_quoted["kernels"][dominant]["hbm_bytes_per_launch"], pmc_file
-        out = {
-            "metric": ("full sweeps/sec (N=4096,T=100,chi=32,d=4)" if (N, T, chi, d) == (4096, 100, 32, 4)
-                       else f"full sweeps/sec (N={N},T={T},chi={chi},d={d}) - NOT the headline configuration"),
-            "value": args.steps / elapsed, "unit": "sweeps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"DMRG training sweep, noisy trendy sine 2-class, N={N}, T={T}, chi_max={chi}, d={d} Legendre, "
-                                   f"KLD+TSGO eta=0.01, fp64; " + ("configs[2] of BASELINE.json" if (N, T, chi, d) == (4096, 100, 32, 4)
-                                                                   else "a side measurement, not the configuration the metric is quoted on"),
-                       "N": N, "T": T, "chi_max": chi, "d": d, "C": C, "rebuild_caches": bool(args.rebuild_caches),
-                       "parallelism": f"batch-shard x{world}" if world > 1 else "single GPU",
-                       "bond_dims_max": int(chi_now.max())},
-            "device_ms_per_step": 1e3 * dev_s / args.steps,
+        out["config"]["bond_dims_max"] = int(chi_now.max())
+        out.update({
             "train_KL_div_after": kld, "train_acc_after": acc,
             "allreduce": dict(allreduce, nranks_seen=int(info.get("ranks", 1)), us_per_optimiser_step=(breakdown["allreduce"][0] / max(breakdown["allreduce"][1], 1)
                                                                  if breakdown.get("allreduce", (0, 0))[1] else None), replicas=replicas),
-            "eig_fallbacks_total": fallbacks, "eig_phases_us_last_bond": eng.eig_phases(), "launch_chain": info,
+            "eig_phases_us_last_bond": eng.eig_phases(),
             "tail_phases_us": eng.tail_phases() if info.get("four_launch_chain") else None,
-            "timed_region": "K sweeps with profiling off" + (" (hipGraph replay)" if info.get("graph") else " (plain stream)") +
-                            "; per-kernel figures from separate event-instrumented sweeps after it",
             # the whole SVD (gram + eig_tri + eig_vec + eig_fin) against SURVEY 8(d)'s dense-SVD count 4mn^2 + 8n^3
             "svd_group": {"algorithmic_flops_dense_svd": 4.0 * (chi * C * d) * (d * chi) ** 2 + 8.0 * (d * chi) ** 3,
                           "avg_us": round(sum(breakdown[k][0] / max(breakdown[k][1], 1) for k in ("gram", "eig_tri", "eig_vec", "eig_fin")
@@ -916,7 +984,7 @@ def main():
             "kernels": kernels,
             "pmc_quoted": pmc_quoted,
             "device_encode": encode_info,
-        }
+        })
 
     # ---- extra with several ranks: BASELINE configs[3] - N = 32768 series sharded over the ranks (weak-scaling shape: the
     # per-rank batch that makes the sharded kernels matter) - with the all-reduce time per optimiser step and the Amdahl

@@ -7,10 +7,10 @@ out=gpurun_out/r06/ab_chain4
 mkdir -p $out
 for rb in "" "--no-rebuild-caches"; do
   tag=${rb:+_no_rebuild}
-  MPST_CHAIN4=0 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 $rb > $out/chain6$tag.json 2> $out/chain6$tag.err
-  MPST_CHAIN4=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 $rb > $out/chain4$tag.json 2> $out/chain4$tag.err
+  MPST_CHAIN4=0 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 $rb > $out/chain6$tag.json 2> $out/chain6$tag.err
+  MPST_CHAIN4=1 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 $rb > $out/chain4$tag.json 2> $out/chain4$tag.err
 done
-MPST_ENV_WALK=0 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 > $out/chain4_rebuild_per_site_launches.json 2> $out/chain4_persite.err
+MPST_ENV_WALK=0 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --concurrent 1 > $out/chain4_rebuild_per_site_launches.json 2> $out/chain4_persite.err
 python - <<'PY'
 import json, glob, os
 for f in sorted(glob.glob("gpurun_out/r06/ab_chain4/*.json")):

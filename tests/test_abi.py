@@ -78,9 +78,9 @@ def test_product_package_does_not_import_the_oracle():
 def test_collective_library_is_bound_at_run_time_not_linked():
     """RCCL is opened with dlopen when first needed (the copy already in the process wins), so the shared library
     carries no DT_NEEDED entry for it; the probe reports which file was bound and both version numbers."""
-    so = os.path.join(ROOT, "mpstime.jl_amd", "csrc", "libmpstime_hip.so")
-    needed = subprocess.run(["readelf", "-d", so], capture_output=True, text=True).stdout
-    assert "librccl" not in needed
+    so = mt._lib.LIB_PATH                                   # the library the package loads (csrc/Makefile: LIB)
+    needed = subprocess.run(["readelf", "-d", so], capture_output=True, text=True, check=True).stdout
+    assert "(NEEDED)" in needed and "librccl" not in needed
     info = mt.comm_library()
     assert info["ok"], info
     assert "librccl" in info["library"]
