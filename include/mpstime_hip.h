@@ -61,6 +61,7 @@ typedef enum {
                                    class of failure tune() retries on (hyperparameters/tuning.jl:73-86) */
     MPST_ERR_NOMEM = -5
 } mpst_status;
+enum { MPST_ERR_DOMAIN = -6 };   /* rho_correct: RDM eigenvalue < -sqrt(eps) or trace off by > 0.01 (Julia: DomainError) */
 
 enum { MPST_LOSS_KLD = 0, MPST_LOSS_MSE = 1 };   /* src/Structs/options.jl:318-327 */
 enum { MPST_OPT_TSGO = 0, MPST_OPT_GD = 1 };     /* src/Structs/options.jl:298-311 */
@@ -317,6 +318,18 @@ typedef struct {
 } mpst_impute_model;
 int  mpst_impute_model_run(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                            int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds);
+
+/* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
+ * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the
+ * label slice of class c, normalised (expand_label_index, utils.jl:356-370).  Natural log throughout.
+ * bipartite_spectrum / single_site_spectrum (analyse.jl:47-64, :122-138) on the model of m (m->N, m->phi, m->label_idx unused):
+ * bee_out[C][T] (entry T-1 repeats bond T-2, as the reference's last cut does), see_out[C][T]; either may be NULL. */
+int  mpst_entanglement(void* ctx, const mpst_impute_model* m, double* bee_out, double* see_out);
+/* see_variation (analyse.jl:168-194) for class cls on the m->N encoded series m->phi [N][T][d]: out[N][T][T] = [instance][k][site],
+ * the single-site entropies after sites 0..k-1 were measured at the instance's values (row 0: single_site_spectrum; zero at
+ * sites < k; NaN rows where the measured state vanishes).  m->label_idx is ignored.  seconds (may be NULL) = device time.
+ * MPST_ERR_DOMAIN names the class, instance, k, site and offending value in mpst_last_error. */
+int  mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, double* out, double* seconds);
 
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),

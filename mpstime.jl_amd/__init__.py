@@ -2,7 +2,7 @@
 Encodings API.  The hot path lives in libmpstime_hip.so (csrc/); everything here is the
 host-side mirror of the reference's interface for that path."""
 from . import _lib
-from ._lib import MPSTError, SVDError
+from ._lib import MPSTError, SVDError, DomainError
 from .engine import SweepEngine, comm_library, sweep_batch, sweep_batch_multi
 from .options import MPSOptions, safe_options
 from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, model_encoding, symbolic_encoding,
@@ -15,10 +15,12 @@ from .distributed import Shard, split_encoded
 from .imputation import (ImputationProblem, init_imputation_problem, MPS_impute, impute_dataset, kNN_impute, mar,
                          invert_test_transform)
 from .jld2 import JLD2File, read_jld2, load_trained_mps_jld2
+from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
 from . import options
 
 __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "MPSOptions", "safe_options", "EncodedTimeSeriesSet", "Encoding", "encode_dataset",
            "model_encoding", "symbolic_encoding", "transform_data", "TrainedMPS", "fitMPS", "fit_encoded", "classify",
            "generate_startingMPS", "trendy_sine", "Shard", "split_encoded", "MPSTError", "SVDError", "ImputationProblem",
            "init_imputation_problem", "save_trained_mps", "load_trained_mps", "mps_content_digest", "MPS_impute", "impute_dataset", "kNN_impute", "mar", "invert_test_transform",
-           "JLD2File", "read_jld2", "load_trained_mps_jld2"]
+           "JLD2File", "read_jld2", "load_trained_mps_jld2",
+           "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation"]

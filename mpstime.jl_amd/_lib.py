@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpstime_hip.so")
 
 MPST_OK, MPST_ERR_INVALID, MPST_ERR_UNSUPPORTED, MPST_ERR_DEVICE, MPST_ERR_SVD, MPST_ERR_NOMEM = 0, -1, -2, -3, -4, -5
+MPST_ERR_DOMAIN = -6
 LOSS = {"KLD": 0, "MSE": 1}
 OPT = {"TSGO": 0, "GD": 1}
 F64, F32, C128, C64 = 0, 1, 2, 3       # mpst_set_dataset's dtype (include/mpstime_hip.h)
@@ -95,6 +96,8 @@ SYMBOLS = {
     "mpst_impute": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint8), _dp, _dp, _i32, C.POINTER(ImputeOpts), _dp, _dp, _dp, _dp]),
     "mpst_impute_model_run": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _vp, _i32, C.POINTER(ImputeOpts), _dp, _dp,
                                         _dp, _dp]),
+    "mpst_entanglement": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
+    "mpst_see_variation": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
     "mpst_get_impute_phases": (C.c_int, [_vp, _dp]),
     "mpst_get_impute_info": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "mpst_selftest_mfma": (C.c_int, [_vp, _dp, _dp, _i32, _dp]),
@@ -141,3 +144,8 @@ class MPSTError(RuntimeError):
 class SVDError(MPSTError):
     """Bond-tensor decomposition failed - the failure class `tune` retries on
     (src/Training/hyperparameters/tuning.jl:73-86)."""
+
+
+class DomainError(MPSTError, ValueError):
+    """rho_correct found a single-site reduced density matrix with an eigenvalue below -sqrt(eps), or a trace off by more
+    than 0.01 after clamping (src/Analysis/analyse.jl:69-91; Julia: DomainError)."""

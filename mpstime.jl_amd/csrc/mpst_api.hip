@@ -2416,6 +2416,61 @@ int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* 
     return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds);
 }
 
+// ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------
+static int analysis_model(Ctx* c, const mpst_impute_model* h, bool need_phi, AnalysisHost* out) {
+    if (!h || !h->site || !h->chi || (need_phi && !h->phi)) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (h->T < 1 || h->d < 1 || h->C < 1 || (need_phi && h->N <= 0)) return fail(c, MPST_ERR_INVALID, "empty model or data");
+    if (h->dtype == MPST_DTYPE_C64)
+        return fail(c, MPST_ERR_UNSUPPORTED, "entanglement analysis of a complex model: the reference computes it in Float64 only");
+    if (h->dtype != MPST_DTYPE_F64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64");
+    if (h->compute != MPST_COMPUTE_F64) return fail(c, MPST_ERR_UNSUPPORTED, "entanglement analysis runs in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (h->d > 16) return fail(c, MPST_ERR_UNSUPPORTED, "d = %d > 16", h->d);
+    if (h->label_site < 0 || h->label_site >= h->T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
+    if (h->chi[0] != 1 || h->chi[h->T] != 1) return fail(c, MPST_ERR_INVALID, "chi[0] and chi[T] must be 1");
+    for (int j = 0; j <= h->T; ++j) {
+        if (h->chi[j] < 1) return fail(c, MPST_ERR_INVALID, "chi[%d] < 1", j);
+        if (h->chi[j] > 128) return fail(c, MPST_ERR_UNSUPPORTED, "chi[%d] = %d > 128", j, h->chi[j]);
+    }
+    for (int j = 0; j < h->T; ++j)
+        if (!h->site[j]) return fail(c, MPST_ERR_INVALID, "site[%d] is NULL", j);
+    *out = AnalysisHost{h->T, h->d, h->C, h->label_site, h->chi, (const double* const*)h->site};
+    return 0;
+}
+
+static int analysis_domain(Ctx* c, const AnalysisDomain& dm) {
+    if (dm.kind == 1)
+        return fail(c, MPST_ERR_DOMAIN, "RDM contains large negative eigenvalues outside of the tolerance 1.4901161193847656e-8: "
+                    "lambda = %.17g (class %d, instance %lld, k %d, site %d)", dm.value, dm.cls, (long long)dm.inst, dm.k, dm.site);
+    return fail(c, MPST_ERR_DOMAIN, "Tr(rho_corrected) > 1.0! (%.17g) (class %d, instance %lld, k %d, site %d)", dm.value, dm.cls,
+                (long long)dm.inst, dm.k, dm.site);
+}
+
+int mpst_entanglement(void* ctx, const mpst_impute_model* m, double* bee_out, double* see_out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    AnalysisHost h;
+    int rc = analysis_model(c, m, false, &h);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    AnalysisDomain dm{};
+    HIPC(c, analysis_entanglement(h, c->stream, bee_out, see_out, &dm));
+    return dm.kind ? analysis_domain(c, dm) : 0;
+}
+
+int mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, double* out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    AnalysisHost h;
+    int rc = analysis_model(c, m, true, &h);
+    if (rc) return rc;
+    if (!out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (cls < 0 || cls >= m->C) return fail(c, MPST_ERR_INVALID, "class %d out of range [0, %d)", cls, m->C);
+    HIPC(c, hipSetDevice(c->device));
+    AnalysisDomain dm{};
+    HIPC(c, analysis_see_variation(h, cls, (const double*)m->phi, m->N, c->stream, out, seconds, &dm));
+    return dm.kind ? analysis_domain(c, dm) : 0;
+}
+
 int mpst_normalize(void* ctx) {
     Ctx* c = (Ctx*)ctx;
     int rc = check_ready(c);

@@ -677,4 +677,20 @@ void big_eig_destroy(BigEig* b);
 int launch_eig_big(const View& v, int lid, int going_left, BigEig* b, hipStream_t s);
 int launch_eig_big_raw(const double* G, int n, double* lam, double* E, int32_t* info, BigEig* b, hipStream_t s);
 
+// mpst_analysis.hip: entanglement analysis (src/Analysis/analyse.jl) of a real model handed over on the host
+struct AnalysisHost {
+    int T, d, C, label_site;
+    const int32_t* chi;                 // [T+1]
+    const double* const* site;          // ABI layout (s, l, r[, c]), column-major
+};
+struct AnalysisDomain {                 // rho_correct's DomainError: kind 1 eigenvalue < -sqrt(eps), 2 trace off by > 0.01
+    int kind, cls, k, site;
+    int64_t inst;                       // -1: the unmeasured class MPS
+    double value;
+};
+int analysis_lds_ld();
+hipError_t analysis_entanglement(const AnalysisHost& h, hipStream_t s, double* bee, double* see, AnalysisDomain* dom);
+hipError_t analysis_see_variation(const AnalysisHost& h, int cls, const double* phi, int64_t N, hipStream_t s, double* out, double* seconds,
+                                  AnalysisDomain* dom);
+
 }  // namespace mpst

@@ -16,6 +16,7 @@ module MPSTimeHIP
 
 using ITensors          # the reference's only tensor dependency (src/MPSTime.jl:9, Project.toml:50 pins ITensors = 0.6.22, which still
                         # carries MPS / siteinds / linkinds itself; ITensorMPS is NOT a dependency of MPSTime.jl)
+import MPSTime
 import MPSTime: EncodedTimeSeriesSet, PState, AbstractMPSOptions, MPSOptions, Options, TrainedMPS,
                 safe_options, find_label, get_siteinds, KLDLoss, MSELoss, BBOpt
 
@@ -275,6 +276,81 @@ function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::In
     finally
         ccall((:mpst_destroy, LIB), Cvoid, (Ptr{Cvoid},), c)
     end
+end
+
+# ---- entanglement analysis (src/Analysis/analyse.jl) ---------------------------------------------------------------------
+const MPST_ERR_DOMAIN = -6
+
+function check_analysis(ctx, rc)
+    rc == MPST_ERR_DOMAIN && throw(DomainError(unsafe_string(ccall((:mpst_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))))
+    check(ctx, rc)
+end
+
+function with_context(f, device)
+    ctx = Ref{Ptr{Cvoid}}(C_NULL)
+    check(C_NULL, ccall((:mpst_create, LIB), Cint, (Ref{Ptr{Cvoid}}, Cint), ctx, device))
+    try
+        return f(ctx[])
+    finally
+        ccall((:mpst_destroy, LIB), Cvoid, (Ptr{Cvoid},), ctx[])
+    end
+end
+
+"(bee, see), each a (T, C) matrix in natural log: mpst_entanglement on the trained model (Float64 only)."
+function entanglement(tm::TrainedMPS; device::Integer=0)
+    sites, chi, label_site, label_idx, _ = pack_mps(tm.mps, Float64)
+    T, d, C = length(sites), size(sites[1], 1), dim(label_idx)
+    bee = zeros(Float64, T, C); see = zeros(Float64, T, C)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        GC.@preserve sites ptrs chi begin
+            model = Ref(MpstImputeModel(0, T, d, C, label_site, 0, 0, pointer(ptrs), pointer(chi), C_NULL, Ptr{Int32}(C_NULL)))
+            check_analysis(c, ccall((:mpst_entanglement, LIB), Cint, (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{Float64}, Ptr{Float64}),
+                                    c, model, bee, see))
+        end
+    end
+    return bee, see
+end
+
+"bipartite_spectrum(mps::TrainedMPS; logfn) (analyse.jl:47-64) on the GPU."
+function bipartite_spectrum(tm::TrainedMPS; logfn::Function=log, device::Integer=0)
+    logfn in (log, log2, log10) || throw(ArgumentError("logfn must be one of: log, log2, or log10"))
+    bee, _ = entanglement(tm; device=device)
+    scale = logfn === log ? 1.0 : (logfn === log2 ? 1 / log(2) : 1 / log(10))
+    return [bee[:, c] .* scale for c in 1:size(bee, 2)]
+end
+
+"single_site_spectrum(mps::TrainedMPS) (analyse.jl:122-138) on the GPU."
+function single_site_spectrum(tm::TrainedMPS; device::Integer=0)
+    _, see = entanglement(tm; device=device)
+    return [see[:, c] for c in 1:size(see, 2)]
+end
+
+"""see_variation(mps::TrainedMPS, measure_series, class) (analyse.jl:168-194) on the GPU: the same pre-processing and encoding
+(init_imputation_problem, transform_train_data / transform_test_data, get_state), the result indexed [instance, k+1, site]."""
+function see_variation(tm::TrainedMPS, measure_series::Matrix, class::Int=0; device::Integer=0)
+    imp = MPSTime.init_imputation_problem(tm, measure_series, verbosity=0)
+    _, norms = MPSTime.transform_train_data(imp.X_train; opts=imp.opts)
+    scaled, _ = MPSTime.transform_test_data(measure_series, norms; opts=imp.opts)
+    sites, chi, label_site, label_idx, _ = pack_mps(tm.mps, Float64)
+    T, d, C = length(sites), size(sites[1], 1), dim(label_idx)
+    N = size(scaled, 1)
+    phi = Array{Float64}(undef, d, T, N)
+    for i in 1:N, j in 1:T
+        phi[:, j, i] .= MPSTime.get_state(scaled[i, j], imp.opts, j, imp.enc_args)
+    end
+    out = Array{Float64}(undef, T, T, N)            # [site, k, instance] column-major = [instance][k][site] row-major
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        GC.@preserve sites ptrs chi phi begin
+            model = Ref(MpstImputeModel(N, T, d, C, label_site, 0, 0, pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)),
+                                        Ptr{Int32}(C_NULL)))
+            check_analysis(c, ccall((:mpst_see_variation, LIB), Cint, (Ptr{Cvoid}, Ref{MpstImputeModel}, Int32, Ptr{Float64}, Ref{Float64}),
+                                    c, model, Int32(class), out, secs))
+        end
+    end
+    return permutedims(out, (3, 2, 1))
 end
 
 end # module
