@@ -214,8 +214,9 @@ int  mpst_build_caches(void* ctx);
 /* One full sweep = RealRealHighDimension.jl:727-808. */
 int  mpst_sweep(void* ctx, mpst_sweep_stats* out);
 
-/* One sweep of K independent fits of the same shape in ONE launch chain: contexts with the same T, d, C, chi_max, capacity,
- * class counts and loss on one device (hyper-parameter candidates that share the shape - eta, cutoff, the data, the starting MPS
+/* One sweep of K independent fits of the same shape in ONE launch chain: contexts with the same T, d, C, chi_max, capacity
+ * and loss on one device; the number of series and the class counts may differ, as between the folds of a stratified k-fold split
+ * (a fit whose series count moves its gradient share count is refused: batch it with its likes) (hyper-parameter candidates that share the shape - eta, cutoff, the data, the starting MPS
  * may differ -, CV folds, restarts; the reference runs such fits as separate @distributed tasks, hyperparameters/tuning.jl).
  * Every kernel launch carries all K fits, so a sweep costs the ~1200 launches of ONE fit: K separate contexts driven from K host
  * threads reach 2.3x a single fit on one MI355X (the dispatch rate is the limit), one batched chain about 5-6x for K = 8.
@@ -251,6 +252,17 @@ int  mpst_eval(void* ctx, int which, double* mse, double* kld, double* acc, int6
 /* classify(mps, states), src/summary.jl:116-136: predicted class slot per series,
  * and optionally the raw overlaps yhat[N][C] (complex context: [N][C][2], (re, im)). */
 int  mpst_classify(void* ctx, int which, int32_t* pred /*[N]*/, double* yhat /*[N][C] or NULL*/);
+
+/* The scoring step of tune / evaluate (hyperparameters/tuning.jl:1-207, hyperopt_utils.jl:152-231; classify and MSE_loss_acc of
+ * src/summary.jl:4-136) for K models at once, each on its OWN data set `which`: one kernel launch walks every chain (a workgroup
+ * keeps the environments of its 16 series on chip over all sites, the label site last), a second one forms the losses and the
+ * confusion matrices - against T + 2 launches per model of mpst_eval / mpst_classify.  Float64 real contexts on one device and
+ * one rank that share T, d and C, with d * capacity <= 128 (the batched chain's limit); the sets' sizes and the bond dimensions
+ * may differ.  MPST_ERR_UNSUPPORTED otherwise - score such fits with mpst_classify.  The contexts' training caches are left
+ * alone: a sweep after the call continues as if it had not happened.
+ * pred[k] ([N_k] class slots), yhat[k] ([N_k][C] overlaps): NULL arrays or entries are skipped; loss3 ([K][3]: mean MSE, mean
+ * KLD, accuracy) and conf ([K][C][C], [truth][prediction]) may be NULL.  Errors are reported on ctxs[0]. */
+int  mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const* pred, double* const* yhat, double* loss3, int64_t* conf);
 
 /* Imputation of missing values, batched over the instances of data set `which`:
  * impute_median / impute_mode / impute_ITS of src/Imputation/MPS_methods.jl:198-330, i.e. precondition (:42-99) +

@@ -3,7 +3,7 @@ Encodings API.  The hot path lives in libmpstime_hip.so (csrc/); everything here
 host-side mirror of the reference's interface for that path."""
 from . import _lib
 from ._lib import MPSTError, SVDError, DomainError
-from .engine import SweepEngine, comm_library, sweep_batch, sweep_batch_multi
+from .engine import SweepEngine, comm_library, sweep_batch, sweep_batch_multi, classify_batch
 from .options import MPSOptions, safe_options
 from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, model_encoding, symbolic_encoding,
                         transform_data, transform_train_data, transform_test_data, legendre_encode,
@@ -16,6 +16,8 @@ from .imputation import (ImputationProblem, init_imputation_problem, MPS_impute,
                          invert_test_transform)
 from .jld2 import JLD2File, read_jld2, load_trained_mps_jld2
 from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
+from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
+                     BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
 from . import options
 
 __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "MPSOptions", "safe_options", "EncodedTimeSeriesSet", "Encoding", "encode_dataset",
@@ -23,4 +25,7 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "generate_startingMPS", "trendy_sine", "Shard", "split_encoded", "MPSTError", "SVDError", "ImputationProblem",
            "init_imputation_problem", "save_trained_mps", "load_trained_mps", "mps_content_digest", "MPS_impute", "impute_dataset", "kNN_impute", "mar", "invert_test_transform",
            "JLD2File", "read_jld2", "load_trained_mps_jld2",
-           "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation"]
+           "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation",
+           "classify_batch", "tune", "evaluate", "eval_loss", "fit_batch", "BatchFit", "MPSRandomSearch", "TuningLoss", "ClassificationLoss",
+           "MisclassificationRate", "BalancedMisclassificationRate", "ImputationLoss", "make_windows", "make_stratified_cvfolds",
+           "classify_many"]

@@ -92,6 +92,7 @@ SYMBOLS = {
     "mpst_bond_step": (C.c_int, [_vp, _i32, _i32, C.POINTER(mpst_bond_debug)]),
     "mpst_eval": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.POINTER(_i64)]),
     "mpst_classify": (C.c_int, [_vp, C.c_int, C.POINTER(_i32), _dp]),
+    "mpst_classify_batch": (C.c_int, [C.POINTER(_vp), _i32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _dp, C.POINTER(_i64)]),
     "mpst_normalize": (C.c_int, [_vp]),
     "mpst_impute": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint8), _dp, _dp, _i32, C.POINTER(ImputeOpts), _dp, _dp, _dp, _dp]),
     "mpst_impute_model_run": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _vp, _i32, C.POINTER(ImputeOpts), _dp, _dp,

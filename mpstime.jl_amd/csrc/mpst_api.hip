@@ -208,6 +208,8 @@ struct Ctx {
     // variant), the captured sweep and what it was captured for (context pointers and their epochs)
     int batch_hint = 1;            // mpst_set_batch_hint: this context will be advanced in batches of about that many fits
     View* batch_views = nullptr;
+    uint8_t* score_buf = nullptr;  // mpst_classify_batch with this context as the lead: the jobs and every fit's results in one block
+    int64_t score_cap = 0;
     int batch_cap = 0;
     hipGraphExec_t batch_graph = nullptr;
     std::vector<std::pair<uint64_t, uint64_t>> batch_key;   // (uid, epoch) per member: an address can be handed out again, a uid cannot
@@ -974,6 +976,7 @@ void mpst_destroy(void* ctx) {
     if (c->sweep_graph) (void)hipGraphExecDestroy(c->sweep_graph);
     if (c->batch_graph) (void)hipGraphExecDestroy(c->batch_graph);
     dfree(&c->batch_views);
+    dfree(&c->score_buf);
     if (c->comm && rccl_ready(nullptr)) rccl_ready(nullptr)->CommDestroy(c->comm);
     ipc_release(c);
     free_dataset(c->ds[0]); free_dataset(c->ds[1]);
@@ -1764,11 +1767,12 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
         if (!chain_ok)
             return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_sweep_batch runs the headline chain only (Float64, d*chi_max <= 128, <= 8192 series, one rank, "
                                                  "update_iters = 1, no track_cost / rebuild_caches / profiling)", k);
-        const DataSet &a = c0->ds[MPST_TRAIN], &b = c->ds[MPST_TRAIN];
-        const bool same = c->device == c0->device && c->T == c0->T && c->d == c0->d && c->C == c0->C && c->cap == c0->cap && a.N == b.N && a.ntiles == b.ntiles &&
-                          a.counts == b.counts && c->opt.loss == c0->opt.loss && c->opt.train_classes_separately == c0->opt.train_classes_separately &&
+        // the fits may differ in their series (N, class counts, tiles: every kernel reads those from the fit's own View, the grids are sized
+        // for the largest fit); whatever fixes an order of summation is either the context's (b2_ksplit, b2_nw, b2_norm_parts) or shared
+        const bool same = c->device == c0->device && c->T == c0->T && c->d == c0->d && c->C == c0->C && c->cap == c0->cap &&
+                          c->opt.loss == c0->opt.loss && c->opt.train_classes_separately == c0->opt.train_classes_separately &&
                           c->opt.chi_max == c0->opt.chi_max && c->b2_ksplit == c0->b2_ksplit && (c->batch_hint > 1) == (c0->batch_hint > 1) && c->b2_norm_parts == c0->b2_norm_parts;
-        if (!same) return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs in shape from context 0 (T, d, C, capacity, chi_max, class counts, loss): batch fits of one shape", k);
+        if (!same) return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs in shape from context 0 (T, d, C, capacity, chi_max, loss, gradient shares): batch fits of one shape", k);
         HIPC(c0, hipStreamSynchronize(c->stream));
     }
     HIPC(c0, hipSetDevice(c0->device));
@@ -1780,7 +1784,8 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
     }
     std::vector<std::pair<uint64_t, uint64_t>> key;
     for (int k = 0; k < K; ++k) key.push_back({((Ctx*)ctxs[k])->uid, ((Ctx*)ctxs[k])->epoch});
-    const View v0 = make_view(c0, MPST_TRAIN);
+    View v0 = make_view(c0, MPST_TRAIN);         // the launchers' geometry: the shared shape, and the tiles of the largest fit
+    for (int k = 1; k < K; ++k) v0.ntiles = std::max(v0.ntiles, ((Ctx*)ctxs[k])->ds[MPST_TRAIN].ntiles);
     if (!c0->batch_graph || key != c0->batch_key) {
         if (c0->batch_graph) {
             (void)hipGraphExecDestroy(c0->batch_graph);
@@ -1805,7 +1810,6 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
         for (int k = 0; k < K && !bad; ++k)
             if (hipMemsetAsync((char*)((Ctx*)ctxs[k])->sc + offsetof(DevScalars, status), 0, 12, s) != hipSuccess) bad = 1;
         const int nb = c0->T - 1;
-        const int64_t cs = (int64_t)v0.N * v0.cap;
         for (int q = 0; q < 2 * nb && !bad; ++q) {
             const int lid = q < nb ? nb - 1 - q : q - nb, left = q < nb, rid = lid + 1;
             const bool have = q > 0 && q != nb;                        // as mpst_sweep's fused chain: nothing was chained at the turning point
@@ -1817,8 +1821,9 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
             launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
             launch_eig_b(v0, dv, K, lid, left, 0, s);
             launch_eig_b(v0, dv, K, lid, left, 2, s);
-            if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? (int64_t)(rid + 1) * cs : -1, rid + 1, rid, (int64_t)rid * cs, chain, s);
-            else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? (int64_t)(lid - 1) * cs : -1, lid, lid + 1, (int64_t)lid * cs, chain, s);
+            // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
+            if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
+            else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
         }
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(s, &g);
@@ -2064,6 +2069,86 @@ int mpst_classify(void* ctx, int which, int32_t* pred, double* yhat) {
             HIPC(c, hipMemcpy(yhat, c->yeval, (size_t)v.N * c->C * c->zw * sizeof(double), hipMemcpyDeviceToHost));
         }
     }
+    return 0;
+}
+
+// Scoring of K models, each on its own data set `which`, in two launches for the whole batch (mpst_score.hip): what tune / evaluate
+// do with every candidate x fold (hyperparameters/tuning.jl:1-207, hyperopt_utils.jl:152-231; summary.jl:4-136).  Float64 real
+// contexts on one device that share T, d, C, with d * capacity <= 128; the sets' sizes and the bond dimensions may differ.  Only the
+// lead context's scoring block is written: the training caches, the evaluation scratch and the streams' order are left alone.
+int mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const* pred, double* const* yhat, double* loss3, int64_t* conf) {
+    if (!ctxs || K < 1 || K > 64) return fail(nullptr, MPST_ERR_INVALID, "mpst_classify_batch: 1..64 contexts");
+    Ctx* c0 = (Ctx*)ctxs[0];
+    if (!c0) return MPST_ERR_INVALID;
+    if (which != 0 && which != 1) return fail(c0, MPST_ERR_INVALID, "which must be 0 or 1");
+    int rc;
+    int64_t maxN = 0, totN = 0;
+    for (int k = 0; k < K; ++k) {
+        Ctx* c = (Ctx*)ctxs[k];
+        if (!c) return fail(c0, MPST_ERR_INVALID, "context %d is NULL", k);
+        if ((rc = check_ready(c))) {
+            if (c != c0) c0->err = c->err;
+            return rc;
+        }
+        if (c->typed || c->zw == 2 || multi(c))
+            return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_classify_batch scores Float64 real fits on one rank (use mpst_classify)", k);
+        if (!score_walk_supported(c->T, c->d, c->cap, c->C))
+            return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_classify_batch needs d * capacity <= 128 and bond dimensions <= 64 (use mpst_classify)", k);
+        if (c->device != c0->device || c->T != c0->T || c->d != c0->d || c->C != c0->C)
+            return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs from context 0 in device, T, d or C: score such fits in separate calls", k);
+        const int64_t n = c->ds[which].N;
+        if (n <= 0) return fail(c0, MPST_ERR_INVALID, "context %d: data set %d is empty", k, which);
+        maxN = std::max(maxN, n);
+        totN += n;
+        HIPC(c0, hipStreamSynchronize(c->stream));
+    }
+    HIPC(c0, hipSetDevice(c0->device));
+    HIPC(c0, score_init_attrs());
+    // one block: jobs | out3 [K][3] | conf [K][C][C] | yhat of every fit | pred of every fit
+    const int C = c0->C;
+    const size_t o_out3 = ((size_t)K * sizeof(ScoreJob) + 15) & ~(size_t)15;
+    const size_t o_conf = o_out3 + (size_t)K * 3 * sizeof(double);
+    const size_t o_yhat = o_conf + (size_t)K * C * C * sizeof(int64_t);
+    const size_t o_pred = o_yhat + (size_t)totN * C * sizeof(double);
+    const size_t bytes = o_pred + (size_t)totN * sizeof(int32_t);
+    if (c0->score_cap < (int64_t)bytes) {
+        if ((rc = dalloc(c0, &c0->score_buf, (int64_t)bytes))) return rc;
+        c0->score_cap = (int64_t)bytes;
+    }
+    std::vector<ScoreJob> jobs((size_t)K);
+    std::vector<int64_t> first((size_t)K + 1, 0);
+    for (int k = 0; k < K; ++k) {
+        Ctx* c = (Ctx*)ctxs[k];
+        const DataSet& s = c->ds[which];
+        ScoreJob& j = jobs[k];
+        j.T = c->T; j.d = c->d; j.C = c->C; j.pad = 0;
+        j.N = s.N;
+        j.phi = s.phi; j.label = s.label; j.chi = c->chi; j.label_site = c->label_site;
+        j.sites = c->sites; j.site_stride = c->site_stride;
+        j.yhat = (double*)(c0->score_buf + o_yhat) + first[k] * C;
+        j.pred = (int32_t*)(c0->score_buf + o_pred) + first[k];
+        j.out3 = (double*)(c0->score_buf + o_out3) + 3 * k;
+        j.conf = (int64_t*)(c0->score_buf + o_conf) + (int64_t)k * C * C;
+        first[k + 1] = first[k] + s.N;
+    }
+    HIPC(c0, hipMemcpy(c0->score_buf, jobs.data(), jobs.size() * sizeof(ScoreJob), hipMemcpyHostToDevice));
+    launch_score_b((const ScoreJob*)c0->score_buf, K, maxN, c0->stream);
+    HIPC(c0, hipGetLastError());
+    HIPC(c0, hipStreamSynchronize(c0->stream));
+    std::vector<uint8_t> host(bytes - o_out3);
+    HIPC(c0, hipMemcpy(host.data(), c0->score_buf + o_out3, host.size(), hipMemcpyDeviceToHost));
+    const double* h3 = (const double*)host.data();
+    const int64_t* hc = (const int64_t*)(host.data() + (o_conf - o_out3));
+    const double* hy = (const double*)(host.data() + (o_yhat - o_out3));
+    const int32_t* hp = (const int32_t*)(host.data() + (o_pred - o_out3));
+    for (int k = 0; k < K; ++k) {
+        const int64_t n = first[k + 1] - first[k];
+        if (loss3)
+            for (int i = 0; i < 3; ++i) loss3[3 * k + i] = h3[3 * k + i] / (double)n;
+        if (pred && pred[k]) memcpy(pred[k], hp + first[k], (size_t)n * sizeof(int32_t));
+        if (yhat && yhat[k]) memcpy(yhat[k], hy + first[k] * C, (size_t)n * C * sizeof(double));
+    }
+    if (conf) memcpy(conf, hc, (size_t)K * C * C * sizeof(int64_t));
     return 0;
 }
 

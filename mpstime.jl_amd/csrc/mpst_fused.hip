@@ -858,7 +858,7 @@ __device__ __forceinline__ void yhat_s_body(const View& v, int lid, int nslc, in
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i16 = lane & 15, kq = lane >> 4;
     const int gw = bid_x % ngw, sl = bid_x / ngw;       // consecutive ids (XCDs) walk different series groups
-    if (sl * YS_W >= b.Y) return;
+    if (sl * YS_W >= b.Y || 8 * gw >= v.ntiles) return; // (a walker beyond the fit's groups: a batch is launched for its largest fit)
     const int pass = mse ? bid_y : 0;
     const int col = sl * YS_W + i16;
     const bool cv = col < b.Y;
@@ -2269,15 +2269,16 @@ __global__ __launch_bounds__(256, 2) void k_env_split(View v, int lid, int going
                                                    int prev_bond, int out_bond, double* __restrict__ out, int nsplit, int ntb, int tp) {
     env_split_body(v, lid, going_left, site, left_side, prev, prev_bond, out_bond, out, nsplit, ntb, tp, (int)blockIdx.x);
 }
-// batched: the environment rows are addressed by element offsets into the fit's own LE / RE (prev_off < 0: boundary)
-__global__ __launch_bounds__(256, 2) void k_env_split_b(const View* __restrict__ vs, int lid, int going_left, int site, int left_side, int64_t prev_off,
-                                                     int prev_bond, int out_bond, int64_t out_off, int nsplit, int ntb, int tp) {
+// batched: the environment rows are addressed by site in the fit's own LE / RE (prev_site < 0: boundary)
+__global__ __launch_bounds__(256, 2) void k_env_split_b(const View* __restrict__ vs, int lid, int going_left, int site, int left_side, int prev_site,
+                                                     int prev_bond, int out_bond, int out_site, int nsplit, int ntb, int tp) {
     // a fit's workgroups all read its eigenvectors E (32 KB each) and, the split / chain ones, bt_new: one XCD per fit (xcd_contiguous)
     int bx = (int)blockIdx.x, by = 0, bz = (int)blockIdx.z;
     xcd_contiguous(bx, by, bz);
     const View& v = vs[bz];       // by reference: a local copy would live in per-lane scratch (the class tables are indexed dynamically)
     double* base = left_side ? v.LE : v.RE;
-    env_split_body(v, lid, going_left, site, left_side, prev_off >= 0 ? base + prev_off : nullptr, prev_bond, out_bond, base + out_off, nsplit, ntb, tp, bx);
+    const int64_t cs = v.N * v.cap;          // the fit's own stride between sites: the fits of a batch may differ in their series
+    env_split_body(v, lid, going_left, site, left_side, prev_site >= 0 ? base + prev_site * cs : nullptr, prev_bond, out_bond, base + out_site * cs, nsplit, ntb, tp, bx);
 }
 template <int LM, bool D4, bool V2> __global__ __launch_bounds__(YS_T) void k_yhat_s(View v, int lid, int nslc, int ngw) {
     yhat_s_body<LM, D4, V2>(v, lid, nslc, ngw, (int)blockIdx.x, (int)blockIdx.y);
@@ -2386,7 +2387,9 @@ void launch_yhat_s(const View& v, int lid, hipStream_t s) {
 }
 void launch_loss_sum(const View& v, hipStream_t s) { hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(64), 0, s, v); }
 
-// ---- batched launchers: v = the shape every fit of the batch shares, vs = the K Views on the device ----
+// ---- batched launchers: v = the shape every fit of the batch shares with ntiles of the LARGEST fit, vs = the K Views on the device.
+// The fits may differ in their series: ngw, ntb and tp only deal tiles to workgroups (no sum runs across tiles), a workgroup beyond its
+// fit's own tiles leaves; what orders a sum (b2_ksplit, b2_nw) is the context's own ----
 void launch_yhat_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s) {
     const int nslc = cdivf(v.d * v.cap, YS_W);
     const int ngroups = cdivf(v.ntiles, 8);
@@ -2412,8 +2415,8 @@ void launch_gram_upd_b(const View& v, const View* vs, int K, int lid, int going_
     const int dm = v.d * v.cap;
     hipLaunchKernelGGL(k_gram_upd_b, dim3(cdivf(dm, 16) * cdivf(dm, 16), 1, K), dim3(256), 0, s, vs, lid, going_left, first_iter);
 }
-void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int64_t prev_off, int prev_bond,
-                        int out_bond, int64_t out_off, int chain, hipStream_t s) {
+void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int prev_site, int prev_bond,
+                        int out_bond, int out_site, int chain, hipStream_t s) {
     const int dm = v.d * v.cap;
     const int nsplit = cdivf(v.C * cdivf(dm, 16) * cdivf(v.cap, 16), 4);
     const int nchain = chain ? v.C * v.d * cdivf(v.cap, 16) : 0;
@@ -2423,8 +2426,8 @@ void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going
     const int tp = (v.cap <= 32 && v.ntiles * K >= 512 && v.ntiles >= 2 * std::max(1, envb / K)) ? 2 : 1;
     const size_t lds = std::max((size_t)tp * 16 * FXS, chain ? (size_t)4 * CHAIN_J * 256 : (size_t)0) * sizeof(double);
     const int ntb = std::max(1, std::min(v.ntiles, std::max(1, envb / K)));
-    hipLaunchKernelGGL(k_env_split_b, dim3(ntb + nsplit + nchain, 1, K), dim3(256), lds, s, vs, lid, going_left, site, left_side, prev_off, prev_bond,
-                       out_bond, out_off, nsplit, ntb, tp);
+    hipLaunchKernelGGL(k_env_split_b, dim3(ntb + nsplit + nchain, 1, K), dim3(256), lds, s, vs, lid, going_left, site, left_side, prev_site, prev_bond,
+                       out_bond, out_site, nsplit, ntb, tp);
 }
 void launch_grad_s(const View& v, int lid, hipStream_t s) {
     const int aw = b2_aw(v), nbc = cdivf(v.cap, aw);

@@ -551,10 +551,28 @@ bool env_walk_supported(const View& v);
 void launch_yhat_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
 void launch_grad_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
 void launch_gram_upd_b(const View& v, const View* vs, int K, int lid, int going_left, int first_iter, hipStream_t s);
-void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int64_t prev_off, int prev_bond,
-                        int out_bond, int64_t out_off, int chain, hipStream_t s);
+void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int prev_site, int prev_bond,
+                        int out_bond, int out_site, int chain, hipStream_t s);
 void launch_eig_b(const View& v, const View* vs, int K, int lid, int going_left, int stage, hipStream_t s);
 void launch_bt_assemble_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
+// batched one-launch scoring (mpst_score.hip): one model and one data set per job, blockIdx.z picks the job
+struct ScoreJob {
+    int32_t T, d, C, pad;
+    int64_t N;                  // series of the scored set
+    const double* phi;          // [T][N][d]
+    const int32_t* label;       // [N]
+    const int32_t* chi;         // [T+1] device bond dimensions
+    const int32_t* label_site;
+    const double* sites;        // T slots of site_stride doubles, [c][l][s][r] compact
+    int64_t site_stride;
+    double* yhat;               // out [N][C]
+    int32_t* pred;              // out [N]
+    double* out3;               // out {sum mse, sum kld, correct}
+    int64_t* conf;              // out [C][C]
+};
+bool score_walk_supported(int T, int d, int cap, int C);
+hipError_t score_init_attrs();
+void launch_score_b(const ScoreJob* jobs, int K, int64_t maxN, hipStream_t s);     // the chain walk, then the reduction: two launches
 // one-shot direct-write all-reduce over peer-mapped inboxes (mpst_allreduce.hip)
 constexpr int AR_MAX_RANKS = 8;
 struct ArParams {

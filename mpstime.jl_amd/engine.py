@@ -435,7 +435,11 @@ def sweep_batch(engines):
     st = (L.mpst_sweep_stats * K)()
     rc = lib.mpst_sweep_batch(arr, K, st)
     if rc:
-        engines[0]._chk(rc)
+        try:
+            engines[0]._chk(rc)
+        except L.SVDError as err:        # which fits failed (the others are intact): fit_batch goes on with those
+            err.svd_status = [int(s.svd_status) for s in st]
+            raise
     return [{"seconds": s.seconds, "max_chi": s.max_chi, "eig_sweeps_total": s.eig_sweeps_total, "eig_fallbacks": s.eig_fallbacks} for s in st]
 
 
@@ -452,6 +456,38 @@ def sweep_batch_multi(engines, groups=None):
     if rc:
         engines[0]._chk(rc)
     return [{"seconds": s.seconds, "max_chi": s.max_chi, "eig_sweeps_total": s.eig_sweeps_total, "eig_fallbacks": s.eig_fallbacks} for s in st]
+
+
+def classify_batch(engines, which=1, return_overlaps=False):
+    """mpst_classify_batch: K models scored on their own data sets ``which`` in two kernel launches for the whole batch (one walks
+    every chain, one forms the losses) instead of T + 2 launches per model.  ``engines``: Float64 SweepEngines on one device
+    with the same T, d, C and d * chi <= 128; set sizes and bond dimensions may differ.  Returns one dict per engine:
+    ``pred`` (N_k,) class slots, ``mse`` / ``kld`` / ``acc`` as ``eval``, ``conf`` (C, C) [truth][prediction], and ``yhat``
+    (N_k, C) overlaps with ``return_overlaps``.  The engines' training caches are left alone.  Raises
+    MPSTError(MPST_ERR_UNSUPPORTED) for fits outside these limits - score those with ``classify`` / ``eval``."""
+    lib = L.load()
+    K = len(engines)
+    Cn = engines[0].C
+    arr = (C.c_void_p * K)(*[e.ctx.value for e in engines])
+    preds = [np.zeros(e.N[which], dtype=np.int32) for e in engines]
+    pp = (C.c_void_p * K)(*[p.ctypes.data for p in preds])
+    yh, yp = None, None
+    if return_overlaps:
+        yh = [np.zeros((e.N[which], Cn)) for e in engines]
+        yp = (C.c_void_p * K)(*[y.ctypes.data for y in yh])
+    loss3 = np.zeros((K, 3))
+    conf = np.zeros((K, Cn, Cn), dtype=np.int64)
+    rc = lib.mpst_classify_batch(arr, K, int(which), pp, yp, loss3.ctypes.data_as(C.POINTER(C.c_double)),
+                                 conf.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc:
+        engines[0]._chk(rc)
+    out = []
+    for k in range(K):
+        r = {"pred": preds[k], "mse": float(loss3[k, 0]), "kld": float(loss3[k, 1]), "acc": float(loss3[k, 2]), "conf": conf[k]}
+        if return_overlaps:
+            r["yhat"] = yh[k]
+        out.append(r)
+    return out
 
 
 def comm_library():

@@ -65,13 +65,15 @@ _INFO_TEST_KEYS = ("test_acc", "test_KL_div", "test_conf")
 
 def fit_encoded(W, training_states_meta: EncodedTimeSeriesSet, testing_states_meta: Optional[EncodedTimeSeriesSet],
                 opts: MPSOptions = MPSOptions(), engine: Optional[SweepEngine] = None, device: int = 0,
-                shard=None, preloaded: bool = False):
+                shard=None, preloaded: bool = False, batch_hint: Optional[int] = None):
     """fitMPS(W::MPS, training_states_meta, testing_states_meta, opts) (:587-890).
 
     Returns (TrainedMPS, training_information, testing_states_meta).  training_information has the
     reference's keys and lengths (nsweeps+2 when log_level > 0; time_taken 0.0 first, NaN last).
     ``shard`` = (rank, world_size, communicator-setup callable) for batch sharding (see distributed.py).
     ``preloaded``: the engine already holds both data sets (device-side encoding, fitMPS(device_encode=True)).
+    ``batch_hint``: the engine's gradient share count as for a fit advanced in batches of about that many
+    (SweepEngine.set_batch_hint): what ``fit_batch`` (tuning.py) sets, so that a fit gives the same bits alone and in a batch.
     """
     opts = safe_options(opts)
     eopt = engine_options(opts)
@@ -93,6 +95,8 @@ def fit_encoded(W, training_states_meta: EncodedTimeSeriesSet, testing_states_me
     own_engine = engine is None
     eng = engine or SweepEngine(device)
     try:
+        if batch_hint:
+            eng.set_batch_hint(batch_hint)
         eng.set_options(rebuild_caches=False, track_cost=opts.track_cost, **eopt)
         gcounts = None
         if shard is not None:
@@ -184,6 +188,15 @@ def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = M
     ``device_encode=True`` (the closed-form bases: Legendre, Fourier, Stoudenmire, Sahand, Uniform) preprocesses and encodes on the GPU
     (mpst_encode_dataset): the raw matrices are uploaded, the product states are downloaded once for the
     returned EncodedTimeSeriesSets."""
+    W, X_train, y_train, X_test, y_test, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding, W)
+    if device_encode:
+        return _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_keys, **kw)
+    train_states, test_states = _encode_fit(X_train, y_train, X_test, y_test, opts, enc, class_keys)
+    return fit_encoded(W, train_states, test_states, opts, **kw)                                         # :556-560
+
+
+def _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding=None, W=None):
+    """The checks of fitMPS (:383-486), the class keys and the starting MPS (opts.init_rng): shared with fit_batch (tuning.py)."""
     opts = safe_options(opts)
     X_train = np.asarray(X_train, dtype=np.float64)
     N, T = X_train.shape
@@ -211,13 +224,16 @@ def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = M
     num_classes = len(classes)
     if W is None:
         W = generate_startingMPS(opts.chi_init, T, opts.d, num_classes, opts.init_rng, numpy_dtype(opts.dtype))   # :433-435
-    if device_encode:
-        return _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_keys, **kw)
+    return W, X_train, y_train, X_test, y_test, opts, enc, class_keys
+
+
+def _encode_fit(X_train, y_train, X_test, y_test, opts, enc, class_keys):
+    """transform_data + encode_dataset of fitMPS (:445, :489) on the host"""
     Xtr_s, Xte_s, norms, oob = transform_data(X_train, X_test, opts, enc.range)                          # :445
     train_states = encode_dataset(X_train, Xtr_s, y_train, enc, opts.d, class_keys)                      # :489
     test_states = encode_dataset(X_test, Xte_s, y_test, enc, opts.d, class_keys) if X_test.size else \
         EncodedTimeSeriesSet.empty()
-    return fit_encoded(W, train_states, test_states, opts, **kw)                                         # :556-560
+    return train_states, test_states
 
 
 def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_keys, engine=None, device=0, **kw):
@@ -253,19 +269,25 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
             eng.close()
 
 
+def classify_states(mps: TrainedMPS, X_or_states) -> EncodedTimeSeriesSet:
+    """The product states classify scores (summary.jl:155-177): the raw series through the model's own preprocessing, in
+    the order given (all under one label)."""
+    if isinstance(X_or_states, EncodedTimeSeriesSet):
+        return X_or_states
+    opts = safe_options(mps.opts)
+    X_test = np.asarray(X_or_states, dtype=np.float64)
+    enc = model_encoding(opts.encoding)
+    _, Xte_s, _, _ = transform_data(mps.train_data.original_data, X_test, opts, enc.range)          # :160
+    n = X_test.shape[0]
+    return encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0})                     # :175 (unsorted: all one label)
+
+
 def classify(mps: TrainedMPS, X_or_states, engine: Optional[SweepEngine] = None, device: int = 0):
     """classify(mps, test_states) (summary.jl:116-136) and classify(mps, X_test) (:155-177):
     predicted labels (original label values) by maximum overlap |yhat|^2."""
     opts = safe_options(mps.opts)
     labels = np.unique(mps.train_data.labels)
-    if isinstance(X_or_states, EncodedTimeSeriesSet):
-        states = X_or_states
-    else:
-        X_test = np.asarray(X_or_states, dtype=np.float64)
-        enc = model_encoding(opts.encoding)
-        _, Xte_s, _, _ = transform_data(mps.train_data.original_data, X_test, opts, enc.range)          # :160
-        n = X_test.shape[0]
-        states = encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0})                     # :175 (unsorted: all one label)
+    states = classify_states(mps, X_or_states)
     if len(states) == 0:
         return np.zeros(0, dtype=labels.dtype)
     own = engine is None
