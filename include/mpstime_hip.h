@@ -49,7 +49,10 @@ extern "C" {
 #endif
 
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
- *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against. */
+ *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
+ *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
+ *    ones (mpst_impute_traj, mpst_impute_model_traj) and entries appended to a getter that takes its length
+ *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
 typedef enum {
@@ -331,6 +334,27 @@ typedef struct {
 int  mpst_impute_model_run(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                            int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds);
 
+/* Several trajectories per instance (impute_ITS(...; num_trajectories), src/Imputation/MPS_methods.jl:304-347): the instance is
+ * conditioned on its known values ONCE - the environment pass, one workgroup per instance exactly as in the calls above - and
+ * K chains (instance, trajectory) are then sampled from that one conditioned MPS, the K chains of an instance next to each other.
+ * mpst_impute_traj is mpst_impute, mpst_impute_model_traj is mpst_impute_model_run, with
+ *   K               trajectories per instance; K < 1: MPST_ERR_INVALID.  K = 1 with u is the single-trajectory call, bit for bit.
+ *   o->method       MPST_IMPUTE_QUANTILE or MPST_IMPUTE_ITS_REJECT; the other methods have one answer per instance:
+ *                   MPST_ERR_UNSUPPORTED
+ *   u[N][K][T][max_trials]  uniform numbers in [0, 1) (max_trials = 1 for QUANTILE), or NULL: they are then generated on the device
+ *   seed, row_id[N] (u == NULL) Philox4x32-10 with the key (seed low word, seed high word) and the counter
+ *                   (row id low word, row id high word, trajectory, site + trial * 2^20), sites and trajectories counted from 0;
+ *                   the uniform number is ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 of the output words w0, w1.  row_id names the
+ *                   caller's rows (NULL: the index in the data set's order), so a draw depends neither on how the call was cut
+ *                   into blocks, nor on which rows were sent along, nor on their order.  T <= 2^20, max_trials <= 4096.
+ *   x_out[N][K][T], err_out[N][K][T]  as above, per chain; err_out is the chain's WMAD at every imputed site for ITS_REJECT */
+int  mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                      const mpst_impute_opts* o, int32_t K, const double* u, int64_t seed, const int64_t* row_id, double* x_out,
+                      double* err_out, double* seconds);
+int  mpst_impute_model_traj(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                            int32_t ngrid, const mpst_impute_opts* o, int32_t K, const double* u, int64_t seed, const int64_t* row_id,
+                            double* x_out, double* err_out, double* seconds);
+
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the
  * label slice of class c, normalised (expand_label_index, utils.jl:356-370).  Natural log throughout.
@@ -351,7 +375,9 @@ int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid
  * (src/Imputation/sampling_utils.jl:162-199) were evaluated in closed form instead of from the table of grid states;
  * out[1] = 1 when the sweep over the sites (impute_at!, src/Imputation/MPS_methods.jl:103-177) ran for sixteen instances per
- * workgroup (closed-form densities and panels that fit the LDS; otherwise one instance per workgroup - same results). */
+ * workgroup (closed-form densities and panels that fit the LDS; otherwise one instance per workgroup - same results);
+ * out[2] = the workgroups of the environment pass (one per instance, whatever the number of trajectories), out[3] = the chains
+ * (instance, trajectory) the sweep ran for. */
 int  mpst_get_impute_info(void* ctx, int32_t* out, int32_t n);
 
 int  mpst_normalize(void* ctx);

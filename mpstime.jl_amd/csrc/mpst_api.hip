@@ -197,6 +197,8 @@ struct Ctx {
     double impute_phase_s[2] = {0, 0};   // last imputation call: environment pass, density sweep
     int impute_batched = 0;              // ... and whether its sweep ran sixteen instances per workgroup (k_imp_leftb)
     int impute_trig = 0;                 // ... and whether its densities were evaluated in closed form (Fourier states on a uniform grid)
+    int impute_env_wgs = 0;              // ... the workgroups of its environment pass (one per instance with a missing site or not: the grid)
+    int impute_chains = 0;               // ... and the chains (instance, trajectory) its sweep was launched for
     int64_t prof_cnt[16] = {0};
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     // one full sweep captured as a hipGraph (bond dimensions live on the device and every grid is sized
@@ -2248,17 +2250,32 @@ static bool legendre_grid(const double* gx, const double* gp, int n, int d, doub
     return true;
 }
 
-// shared tail of the two imputation entry points: option checks, scratch, launches, results
+// The trajectories of a call (mpst_impute_traj / mpst_impute_model_traj): K chains per instance, their uniform numbers from the
+// caller (u) or from the device generator (seed, row_id).  The single-trajectory entry points pass {1, false, 0, null}.
+struct ImputeTraj {
+    int32_t K;
+    bool seeded;
+    uint64_t seed;
+    const int64_t* row_id;
+};
+
+// shared tail of the imputation entry points: option checks, scratch, launches, results
 static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const double* grid_x, const void* grid_phi, int32_t ngrid,
-                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
+                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
+                      const ImputeTraj& tj = ImputeTraj{1, false, 0, nullptr}) {
     if (!missing || !grid_x || !grid_phi || !x_out || !o || ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
     const int method = o->method;
     if (method < MPST_IMPUTE_MEDIAN || method > MPST_IMPUTE_ITS_REJECT) return fail(c, MPST_ERR_INVALID, "unknown imputation method");
     if (o->order != MPST_IMPUTE_FORWARDS && o->order != MPST_IMPUTE_BACKWARDS) return fail(c, MPST_ERR_INVALID, "impute_order must be forwards (0) or backwards (1)");
     const bool sampling = method == MPST_IMPUTE_QUANTILE || method == MPST_IMPUTE_ITS_REJECT;
-    if (sampling && !u) return fail(c, MPST_ERR_INVALID, "the sampling methods need the uniform numbers u[N][T][max_trials]");
+    if (sampling && !u && !tj.seeded) return fail(c, MPST_ERR_INVALID, "the sampling methods need the uniform numbers u[N][T][max_trials]");
     const int ntrial = method == MPST_IMPUTE_ITS_REJECT ? o->max_trials : 1;
     if (ntrial < 1) return fail(c, MPST_ERR_INVALID, "max_trials must be at least 1");
+    const int64_t K = tj.K;
+    const bool seeded = sampling && !u && tj.seeded;
+    if (seeded && (m.T > IMPUTE_SEED_MAX_SITES || ntrial > IMPUTE_SEED_MAX_TRIALS))
+        return fail(c, MPST_ERR_UNSUPPORTED, "the device generator's counter holds T <= %d sites and max_trials <= %d (got %d, %d): pass u",
+                    IMPUTE_SEED_MAX_SITES, IMPUTE_SEED_MAX_TRIALS, m.T, ntrial);
     if (method == MPST_IMPUTE_ITS_REJECT && !(o->rejection_threshold >= 0.0)) return fail(c, MPST_ERR_INVALID, "rejection_threshold must be non-negative");
     if (method == MPST_IMPUTE_MEAN) {
         const int mb = o->mean_basis;
@@ -2283,7 +2300,9 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         for (int j = 0; j < T; ++j) mm += missing[i * T + j] ? 1 : 0;
         maxm = std::max(maxm, mm);
     }
-    std::vector<double> xo((size_t)N * T, 0.0), eo((size_t)N * T, 0.0);
+    const size_t nout = (size_t)N * K * T;           // x_out / err_out: [N][K][T]
+    std::vector<double> xo(nout, 0.0), eo(nout, 0.0);
+    c->impute_env_wgs = c->impute_chains = 0;
     // Instances are dealt out to workgroups in the order of where their missing sites begin (in the direction of the sweep):
     // workgroups that are resident together then walk the chain in step and find the site tensor the first of them fetched
     // still in the L2 (a 262 KB tensor per site at configs[4], re-read by every instance).  Results do not depend on the order.
@@ -2305,34 +2324,46 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         // 27 GB of environments of configs[4] (8192 instances x 100 missing sites x 32 KB) are one chunk on a 288 GB device,
         // 512 workgroups of the batched sweep instead of seven launches of 82
         const int64_t welems = impute_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
-        const int64_t per_bytes = ((int64_t)maxm * m.cap * m.cap * zw + welems) * (int64_t)esz + 2ll * ngrid * (int64_t)sizeof(double);
+        // (per instance: its environments once, p_k and S_k for each of its K chains.  A chunk is a run of whole instances, i.e. of
+        // chunk * K chains; the outputs and uniform numbers of the extra trajectories come out of the same budget)
+        const int64_t per_bytes = ((int64_t)maxm * m.cap * m.cap * zw + welems) * (int64_t)esz + 2ll * K * ngrid * (int64_t)sizeof(double);
         size_t free_b = 0, total_b = 0;
         HIPC(c, hipMemGetInfo(&free_b, &total_b));
         double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
         if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
+        if (K > 1) {
+            const double extra = (double)(N * (K - 1) * T) * (double)sizeof(double) * (2.0 + ((sampling && !seeded) ? (double)ntrial : 0.0));
+            budget = std::max(budget - extra, (double)per_bytes);
+        }
         int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / (double)per_bytes)));
+        chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
         if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
         uint8_t *dmiss = nullptr, *dR = nullptr, *dW = nullptr;
         int32_t* dord = nullptr;
+        int64_t* drow = nullptr;
         double *dgx = nullptr, *dgp = nullptr, *du = nullptr, *dp = nullptr, *dS = nullptr, *dx = nullptr, *de = nullptr, *dlin = nullptr;
         struct Temps {
-            uint8_t **m, **r, **w; double **b, **cc, **dd, **e, **f, **g, **h; int32_t** o; double** l;
-            ~Temps() { dfree(m); dfree(r); dfree(w); dfree(b); dfree(cc); dfree(dd); dfree(e); dfree(f); dfree(g); dfree(h); dfree(o); dfree(l); }
-        } temps{&dmiss, &dR, &dW, &dgx, &dgp, &du, &dp, &dS, &dx, &de, &dord, &dlin};
+            uint8_t **m, **r, **w; double **b, **cc, **dd, **e, **f, **g, **h; int32_t** o; double** l; int64_t** ri;
+            ~Temps() { dfree(m); dfree(r); dfree(w); dfree(b); dfree(cc); dfree(dd); dfree(e); dfree(f); dfree(g); dfree(h); dfree(o); dfree(l); dfree(ri); }
+        } temps{&dmiss, &dR, &dW, &dgx, &dgp, &du, &dp, &dS, &dx, &de, &dord, &dlin, &drow};
         int rc;
         if ((rc = dalloc(c, &dmiss, N * T)) || (rc = dalloc(c, &dR, (int64_t)(chunk * maxm * m.cap * m.cap * zw * esz))) ||
-            (rc = dalloc(c, &dgx, ngrid)) || (rc = dalloc(c, &dgp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, &dp, chunk * ngrid)) ||
-            (rc = dalloc(c, &dS, chunk * ngrid)) || (rc = dalloc(c, &dx, N * T)) || (rc = dalloc(c, &de, N * T))) return rc;
-        if (sampling && (rc = dalloc(c, &du, N * T * ntrial))) return rc;
+            (rc = dalloc(c, &dgx, ngrid)) || (rc = dalloc(c, &dgp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, &dp, chunk * K * ngrid)) ||
+            (rc = dalloc(c, &dS, chunk * K * ngrid)) || (rc = dalloc(c, &dx, N * K * T)) || (rc = dalloc(c, &de, N * K * T))) return rc;
+        if (sampling && !seeded && (rc = dalloc(c, &du, N * K * T * ntrial))) return rc;
+        if (seeded && tj.row_id) {
+            if ((rc = dalloc(c, &drow, N))) return rc;
+            HIPC(c, hipMemcpy(drow, tj.row_id, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice));
+        }
         if ((rc = dalloc(c, &dord, N))) return rc;
         HIPC(c, hipMemcpy(dord, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
         if (welems && (rc = dalloc(c, &dW, (int64_t)(chunk * welems * esz)))) return rc;
         HIPC(c, hipMemcpy(dmiss, missing, (size_t)N * T, hipMemcpyHostToDevice));
         HIPC(c, hipMemcpy(dgx, grid_x, (size_t)ngrid * sizeof(double), hipMemcpyHostToDevice));
         HIPC(c, hipMemcpy(dgp, grid_phi, (size_t)ngrid * d * zw * sizeof(double), hipMemcpyHostToDevice));
-        if (sampling) HIPC(c, hipMemcpy(du, u, (size_t)N * T * ntrial * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(c, hipMemset(dx, 0, (size_t)N * T * sizeof(double)));
-        HIPC(c, hipMemset(de, 0, (size_t)N * T * sizeof(double)));
+        if (sampling && !seeded) HIPC(c, hipMemcpy(du, u, (size_t)N * K * T * ntrial * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemset(dx, 0, nout * sizeof(double)));
+        HIPC(c, hipMemset(de, 0, nout * sizeof(double)));
         HIPC(c, hipEventRecord(c->ev_start, c->stream));
         double gx0 = 0.0, gdx = 0.0;
         std::vector<double> lin;
@@ -2344,7 +2375,8 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
             HIPC(c, hipMemcpy(dlin, lin.data(), lin.size() * sizeof(double), hipMemcpyHostToDevice));
         }
         const ImputeParams q{dmiss, dR, dW, dgx, dgp, du, dp, dS, dx, de, maxm, ngrid, method, o->get_err, o->order == MPST_IMPUTE_BACKWARDS ? 1 : 0,
-                             ntrial, o->mean_basis, o->rejection_threshold, trig, gx0, gdx, dord, dlin};
+                             ntrial, o->mean_basis, o->rejection_threshold, trig, gx0, gdx, dord, dlin,
+                             (int)K, seeded ? 1 : 0, (unsigned long long)tj.seed, drow};
         // one event between the two kernels of every chunk: the split of the pass into its environment and density halves
         // (mpst_get_impute_phases) costs nothing against kernels of tens of milliseconds
         struct Evs {
@@ -2357,7 +2389,10 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
             evs.e.push_back(mid);
             HIPC(c, hipEventCreate(&end));
             evs.e.push_back(end);
-            c->impute_batched = launch_impute(m, q, i0, std::min(chunk, N - i0), c->stream, mid);
+            const int64_t cnt = std::min(chunk, N - i0);
+            c->impute_batched = launch_impute(m, q, i0, cnt, c->stream, mid);
+            c->impute_env_wgs += (int)cnt;
+            c->impute_chains += (int)(cnt * K);
             HIPC(c, hipEventRecord(end, c->stream));
         }
         HIPC(c, hipEventRecord(c->ev_stop, c->stream));
@@ -2403,15 +2438,22 @@ int mpst_get_impute_phases(void* ctx, double* seconds_out) {
 int mpst_get_impute_info(void* ctx, int32_t* out, int32_t n) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !out || n < 0) return MPST_ERR_INVALID;
-    const int32_t full[2] = {c->impute_trig, c->impute_batched};
-    for (int i = 0; i < n && i < 2; ++i) out[i] = full[i];
+    const int32_t full[4] = {c->impute_trig, c->impute_batched, c->impute_env_wgs, c->impute_chains};
+    for (int i = 0; i < n && i < 4; ++i) out[i] = full[i];
     return 0;
 }
 
-int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
-                const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return MPST_ERR_INVALID;
+// K trajectories per instance: the argument checks the two *_traj entry points share
+static int check_traj(Ctx* c, const mpst_impute_opts* o, int32_t K) {
+    if (K < 1) return fail(c, MPST_ERR_INVALID, "num_trajectories must be at least 1 (got %d)", (int)K);
+    if (o && o->method != MPST_IMPUTE_QUANTILE && o->method != MPST_IMPUTE_ITS_REJECT)
+        return fail(c, MPST_ERR_UNSUPPORTED, "trajectories are drawn by the sampling methods (MPST_IMPUTE_QUANTILE, MPST_IMPUTE_ITS_REJECT): "
+                                             "the median, mode and mean of an instance are one series");
+    return 0;
+}
+
+static int impute_ctx(Ctx* c, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds, const ImputeTraj& tj) {
     if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
     if (!c->have_mps || !c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options / mpst_set_mps must be called first");
     const DataSet& s = c->ds[which];
@@ -2420,7 +2462,23 @@ int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid
     const View v = make_view(c, which);
     const ImpModel m{v.sites, v.site_stride, v.chi, v.label_site, v.phi, v.label, s.N, c->T, c->d, c->cap, c->zw == 2 ? 1 : 0,
                      (c->dtype == MPST_F32 || c->dtype == MPST_C64) ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds);
+    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj);
+}
+
+int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr});
+}
+
+int mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                     const mpst_impute_opts* o, int32_t K, const double* u, int64_t seed, const int64_t* row_id, double* x_out,
+                     double* err_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (int rc = check_traj(c, o, K)) return rc;
+    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{K, u == nullptr, (uint64_t)seed, row_id});
 }
 
 // Host arrays of a model in the boundary layouts (site: (s, l, r[, c]) column-major like mpst_set_mps; phi: [N][T][d]) to
@@ -2451,10 +2509,9 @@ static void pack_model(const mpst_impute_model* h, int cap, int64_t stride, bool
 }
 }  // extern "C++"
 
-int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
-                          int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return MPST_ERR_INVALID;
+static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                        int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
+                        const ImputeTraj& tj) {
     if (!h || !h->site || !h->chi || !h->phi || !h->label_idx) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (h->N <= 0 || h->T < 1 || h->d < 1 || h->C < 1) return fail(c, MPST_ERR_INVALID, "empty model or data");
     if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
@@ -2498,7 +2555,23 @@ int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* 
     HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
     const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds);
+    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj);
+}
+
+int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                          int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr});
+}
+
+int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                           int32_t ngrid, const mpst_impute_opts* o, int32_t K, const double* u, int64_t seed, const int64_t* row_id,
+                           double* x_out, double* err_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (int rc = check_traj(c, o, K)) return rc;
+    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{K, u == nullptr, (uint64_t)seed, row_id});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

@@ -774,7 +774,60 @@ struct ImpArgs {
     double x0, dxu;             // TRIG kernels: the uniform grid x_k = x0 + k dxu
     const double* lin;          // TRIG, real models: [2d-1][d][d] Legendre linearisation table (scaled by the states' norms), else null
     int dbg;                    // k_imp_leftb: parts switched off for timing (0 outside -DMPST_LAB builds)
+    // chains: ntraj trajectories per instance, adjacent.  Chain c of the chunk belongs to the instance ord[c / ntraj] (whose
+    // environments sit in slot c / ntraj of Rbuf) and is its trajectory c % ntraj; u, x_out and err_out are [N][ntraj][T](...)
+    int ntraj;
+    int use_seed;               // sampling methods with u == null: uniform numbers from philox_uniform(seed, row id, trajectory, site, trial)
+    unsigned long long seed;
+    const int64_t* row_id;      // [N] the caller's row ids (the generator's counter) or null: the index in the data set
 };
+// what a chain reads through its instance and what it addresses by itself
+struct ImpChain {
+    int64_t inst;               // instance: missing, phi, label
+    int64_t rslot;              // chunk-local slot of the instance's environments in Rbuf
+    int64_t row;                // inst * ntraj + trajectory: the row of u, x_out, err_out
+    int traj;
+};
+__device__ __forceinline__ ImpChain imp_chain(const ImpArgs& g, int64_t c) {
+    ImpChain ch;
+    ch.rslot = g.ntraj == 1 ? c : c / g.ntraj;
+    ch.inst = g.ord[ch.rslot];
+    ch.traj = (int)(c - ch.rslot * g.ntraj);
+    ch.row = ch.inst * g.ntraj + ch.traj;
+    return ch;
+}
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): a counter-based generator,
+// ten rounds of two 32 x 32 -> 64 bit multiplications on a 128-bit counter under a 64-bit key that is bumped by the Weyl constants
+// after every round.  No state: the draw of (row id, trajectory, site, trial) under a seed is a pure function of the five.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[1] = (uint32_t)p1;
+        c[3] = (uint32_t)p0;
+        c[0] = n0;
+        c[2] = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+// counter = (row id low word, row id high word, trajectory, site | trial << 20), key = (seed low word, seed high word); the
+// uniform number in [0, 1) takes the top 27 bits of output word 0 and the top 26 bits of word 1: 53 bits, every value exact
+constexpr int IMP_SEED_SITE_BITS = 20;
+static_assert((1 << IMP_SEED_SITE_BITS) == IMPUTE_SEED_MAX_SITES && (1 << (32 - IMP_SEED_SITE_BITS)) == IMPUTE_SEED_MAX_TRIALS, "counter word 3");
+__device__ __forceinline__ double philox_uniform(unsigned long long seed, int64_t row, int traj, int site, int trial) {
+    uint32_t c[4] = {(uint32_t)(uint64_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)traj,
+                     (uint32_t)site | ((uint32_t)trial << IMP_SEED_SITE_BITS)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (double)(((uint64_t)(c[0] >> 5) << 26) | (uint64_t)(c[1] >> 6)) * (1.0 / 9007199254740992.0);
+}
+// trial t of chain `ch` at site j
+__device__ __forceinline__ double imp_uniform(const ImpArgs& g, const ImpChain& ch, int T, int j, int t) {
+    if (g.use_seed) return philox_uniform(g.seed, g.row_id ? g.row_id[ch.inst] : ch.inst, ch.traj, j, t);
+    return g.u[(ch.row * T + j) * g.ntrial + t];
+}
 enum { IMP_MEDIAN = 0, IMP_MODE = 1, IMP_QUANTILE = 2, IMP_MEAN = 3, IMP_ITS_REJECT = 4 };
 enum { IMP_BASIS_LEGENDRE = 0, IMP_BASIS_LEGENDRE_NO_NORM = 1, IMP_BASIS_FOURIER = 2, IMP_BASIS_STOUDENMIRE = 3, IMP_BASIS_SAHAND = 4,
        IMP_BASIS_UNIFORM = 5 };
@@ -810,7 +863,8 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
     __shared__ double tmr[TRIG ? IMP_MAXD * IMP_MAXD : 1], tmi[TRIG ? IMP_MAXD * IMP_MAXD : 1];      // rho^H rho
     __shared__ double lc[(TRIG && !CX) ? 2 * IMP_MAXD : 1], lpart[(TRIG && !CX) ? 2 * IMP_MAXD * 8 : 1];       // Legendre: c_l, partial sums
     constexpr int ZW = CX ? 2 : 1;
-    const int64_t i = g.ord[blockIdx.x];
+    const ImpChain ch = imp_chain(g, blockIdx.x);        // this workgroup's chain; p / S scratch is the chain's own (blockIdx.x)
+    const int64_t i = ch.inst;
     const int T = v.T, d = v.d, cm = v.cap, tid = threadIdx.x;
     const uint8_t* mi = g.missing + i * T;
     int nm = 0;
@@ -922,7 +976,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
                 if constexpr (CX) Ln.i[o] = ti;
             }
         } else {
-            const R* Rm = (const R*)g.Rbuf + ((int64_t)blockIdx.x * g.max_missing + (nm - 1 - seen)) * cm * cm * ZW;      // [Do][Do] compact
+            const R* Rm = (const R*)g.Rbuf + (ch.rslot * g.max_missing + (nm - 1 - seen)) * cm * cm * ZW;      // [Do][Do] compact, the instance's
             ++seen;
             // U = LW R;  rho = U LW^H   (R: this instance's environment of the site, read once from memory - same load pattern)
             {
@@ -1502,7 +1556,6 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
                 const int lo = kc - jhit, hi = kc + jhit;
                 return (lo >= 0) ? fabs(g.grid_x[lo] - xc) : fabs(g.grid_x[min(hi, n - 1)] - xc);
             };
-            const double* ui = g.u ? g.u + ((int64_t)i * T + j) * g.ntrial : nullptr;
             int ksel = 0;
             double xsel = 0.0, err = 0.0;
             bool state_from_grid = true;
@@ -1514,7 +1567,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
                 ksel = quantile(0.5);                                        // get_median_from_rdm, :159-196
                 if (g.get_wmad) err = wmad(ksel);
             } else if (g.method == IMP_QUANTILE) {
-                ksel = quantile(ui[0]);                                      // get_sample_from_rdm without rejection, :262-270
+                ksel = quantile(imp_uniform(g, ch, T, j, 0));               // get_sample_from_rdm without rejection, :262-270
             } else if (g.method == IMP_ITS_REJECT) {
                 // get_sample_from_rdm with a rejection threshold (:271-290): median and WMAD first, then up to max_trials
                 // inverse-transform samples, the first within threshold * WMAD of the median is kept (else the last drawn)
@@ -1523,7 +1576,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
                 const double xm = g.grid_x[kmed];
                 ksel = kmed;
                 for (int t = 0; t < g.ntrial; ++t) {
-                    ksel = quantile(ui[t]);
+                    ksel = quantile(imp_uniform(g, ch, T, j, t));
                     if (fabs(g.grid_x[ksel] - xm) < g.reject_thr * w) break;
                 }
                 err = w;
@@ -1633,8 +1686,8 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
                 }
             }
             if (tid == 0) {
-                g.x_out[i * T + j] = xsel;
-                g.err_out[i * T + j] = err;
+                g.x_out[ch.row * T + j] = xsel;
+                g.err_out[ch.row * T + j] = err;
             }
             __syncthreads();
             // project onto the chosen state: L <- sum_s conj(ms_s) (L W)[s]   (Am = ms' * A, MPS_methods.jl:161)
@@ -1760,7 +1813,10 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
     }
     if (mid) (void)hipEventRecord(mid, s);
     ImpArgs g{q.missing, q.Rbuf, q.grid_x, q.grid_phi, q.u, q.pbuf, q.sbuf, q.x_out, q.err_out, q.max_missing, q.ngrid, q.method,
-              q.get_wmad, q.rev, q.ntrial, q.mean_basis, q.reject_thr, q.order + i0, q.x0, q.dxu, q.lin, 0};
+              q.get_wmad, q.rev, q.ntrial, q.mean_basis, q.reject_thr, q.order + i0, q.x0, q.dxu, q.lin, 0,
+              q.ntraj, q.use_seed, q.seed, q.row_id};
+    // the environment pass above ran once per instance; the sweep runs once per chain (ntraj adjacent chains per instance)
+    const int64_t nchain = count * q.ntraj;
 #ifdef MPST_LAB
     // lab builds only (make EXTRA=-DMPST_LAB): MPST_IMB_DBG switches parts of k_imp_leftb off for timing - results are then
     // WRONG by construction, so the shipped library never reads the variable
@@ -1778,10 +1834,10 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
                                                      : (q.mean_basis == IMP_BASIS_LEGENDRE || q.mean_basis == IMP_BASIS_LEGENDRE_NO_NORM ||
                                                         q.mean_basis == IMP_BASIS_UNIFORM));
     if (q.trig && !no_batch && force_occ == 0 && mean_ok && imb_fits(v.cap, v.d, CX, F32)) {
-        const dim3 grid((unsigned)((count + IMB_B - 1) / IMB_B));
+        const dim3 grid((unsigned)((nchain + IMB_B - 1) / IMB_B));
         const size_t lds_b = imb_layout(v.cap, v.d, CX, F32).bytes;
-        if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX>), grid, dim3(IMB_T), lds_b, s, v, g, (int)count);
-        else hipLaunchKernelGGL((k_imp_leftb<R, CX, false>), grid, dim3(IMB_T), lds_b, s, v, g, (int)count);
+        if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
+        else hipLaunchKernelGGL((k_imp_leftb<R, CX, false>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
         return 1;
     }
     if constexpr (!CX) {
@@ -1789,9 +1845,9 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
             // Legendre states on a uniform grid: the linearisation table rides in LDS behind the panels
             const size_t lds_t = left_lds_bytes(v.cap, CX, F32) + (size_t)(2 * v.d - 1) * v.d * v.d * sizeof(double);
             // (three workgroups per CU: d = 4, chi = 32: 15.9 / 14.6 / 13.3 ms at 1 / 2 / 3; d = 12, chi = 40: 27.5 / 27.6 / 26.6)
-            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)count), dim3(IMP_T), lds_t, s, v, g);
-            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)count), dim3(IMP_T), lds_t, s, v, g);
-            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)count), dim3(IMP_T), lds_t, s, v, g);
+            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
+            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
+            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
             return 0;
         }
     }
@@ -1800,19 +1856,19 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
             // closed-form densities: no density loop, so no reason to keep the whole register file for one workgroup
             // three workgroups per CU (170 VGPRs): same-box A/B at configs[4] with 16 / 8 loads per output in flight:
             // OCC 2: 83.5 / 148 ms, OCC 3: 76.2 / 97 ms, OCC 4 (spilling): 121 / 102 ms
-            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else if (force_occ == 4) hipLaunchKernelGGL((k_imp_left<R, CX, 4, true>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+            else if (force_occ == 4) hipLaunchKernelGGL((k_imp_left<R, CX, 4, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
             return 0;
         }
     }
     // (real models with d > 8 - the reference's imputation examples use Legendre d = 10 ... 12 - likewise: d = 12, chi = 40: 147 ms with
     // two spilling workgroups per CU, 44 ms with one; 774 ms before the density loop had unrolled forms beyond d = 8)
     if (force_occ == 1 || (force_occ != 2 && ((CX && v.d > 5) || (!CX && v.d > 8))))
-        hipLaunchKernelGGL((k_imp_left<R, CX, 1>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+        hipLaunchKernelGGL((k_imp_left<R, CX, 1>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
     else
-        hipLaunchKernelGGL((k_imp_left<R, CX, 2>), dim3((unsigned)count), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+        hipLaunchKernelGGL((k_imp_left<R, CX, 2>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
     return 0;
 }
 

@@ -165,6 +165,7 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
     using acc_t = typename Mx<R>::acc_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int s_inst[IMB_B], s_cls[IMB_B], s_nm[IMB_B], s_seen[IMB_B], s_last[IMB_B];
+    __shared__ int s_rslot[IMB_B], s_traj[IMB_B];           // the chain's instance slot (environments) and trajectory
     constexpr int ZW = CX ? 2 : 1;
     constexpr bool F32 = std::is_same<R, float>::value;
     constexpr int KU = (F32 ? 16 : 8) / ZW;           // k-slots per batch of operand loads (four batches of registers are alive at a time)
@@ -199,8 +200,10 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
         const int64_t idx = (int64_t)blockIdx.x * IMB_B + tid;
         int nm = 0, last = -1, cls = -1;
         int64_t inst = 0;
+        ImpChain ch{0, 0, 0, 0};
         if (idx < count) {
-            inst = g.ord[idx];
+            ch = imp_chain(g, idx);
+            inst = ch.inst;
             const uint8_t* mi = g.missing + inst * T;
             for (int step = 0; step < T; ++step)
                 if (mi[g.rev ? T - 1 - step : step]) {
@@ -210,6 +213,8 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
             cls = v.label[inst];
         }
         s_inst[tid] = (int)inst;
+        s_rslot[tid] = (int)ch.rslot;
+        s_traj[tid] = ch.traj;
         s_cls[tid] = nm > 0 ? cls : -1;
         s_nm[tid] = nm;
         s_seen[tid] = 0;
@@ -243,8 +248,8 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
         const bool act0 = nm0 > 0 && sn0 < nm0, act1 = nm1 > 0 && sn1 < nm1;       // an instance, and something left to impute
         const int64_t ins0 = s_inst[bq0], ins1 = s_inst[bq1];
         const bool mis0 = act0 && g.missing[ins0 * T + j] != 0, mis1 = act1 && g.missing[ins1 * T + j] != 0;
-        const R* RmS0 = (const R*)g.Rbuf + (((int64_t)blockIdx.x * IMB_B + bq0) * g.max_missing + (nm0 - 1 - sn0)) * cm * cm * ZW;
-        const R* RmS1 = (const R*)g.Rbuf + (((int64_t)blockIdx.x * IMB_B + bq1) * g.max_missing + (nm1 - 1 - sn1)) * cm * cm * ZW;
+        const R* RmS0 = (const R*)g.Rbuf + ((int64_t)s_rslot[bq0] * g.max_missing + (nm0 - 1 - sn0)) * cm * cm * ZW;
+        const R* RmS1 = (const R*)g.Rbuf + ((int64_t)s_rslot[bq1] * g.max_missing + (nm1 - 1 - sn1)) * cm * cm * ZW;
         const int nms = (mis0 ? 1 : 0) + (mis1 ? 1 : 0);
         const int slotA = mis0 ? 0 : 1;               // the slot of the first / second missing instance (the second is slot 1 if any)
         // the U products of the missing instances as a list of units (instance, 16 columns, batch of k-slots): the loads of a
@@ -685,7 +690,7 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
                     const int lo = kc - jhit, hi = kc + jhit;
                     return (lo >= 0) ? fabs(g.grid_x[lo] - xc) : fabs(g.grid_x[min(hi, n - 1)] - xc);
                 };
-                const double* ui = g.u ? g.u + ((int64_t)i * T + j) * g.ntrial : nullptr;
+                const ImpChain ch{i, s_rslot[b], i * g.ntraj + s_traj[b], s_traj[b]};
                 int ksel = 0;
                 double xsel = 0.0, err = 0.0;
                 bool state_from_grid = true;
@@ -698,14 +703,14 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
                     ksel = quantile(0.5);
                     if (g.get_wmad) err = wmad(ksel);
                 } else if (g.method == IMP_QUANTILE) {
-                    ksel = quantile(ui[0]);
+                    ksel = quantile(imp_uniform(g, ch, T, j, 0));
                 } else if (g.method == IMP_ITS_REJECT) {
                     const int kmed = quantile(0.5);
                     const double w = wmad(kmed);
                     const double xm = g.grid_x[kmed];
                     ksel = kmed;
                     for (int t = 0; t < g.ntrial; ++t) {
-                        ksel = quantile(ui[t]);
+                        ksel = quantile(imp_uniform(g, ch, T, j, t));
                         if (fabs(g.grid_x[ksel] - xm) < g.reject_thr * w) break;
                     }
                     err = w;
@@ -768,8 +773,8 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
                     }
                 }
                 if (lane == 0) {
-                    g.x_out[i * T + j] = xsel;
-                    g.err_out[i * T + j] = err;
+                    g.x_out[ch.row * T + j] = xsel;
+                    g.err_out[ch.row * T + j] = err;
                 }
             }
             wave_lds_sync();

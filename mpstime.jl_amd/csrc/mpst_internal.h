@@ -676,10 +676,17 @@ struct ImputeParams {
     double x0, dxu;
     const int32_t* order;       // device [N]: the order in which the instances are dealt out to workgroups
     const double* lin;          // device [2d-1][d][d]: Legendre linearisation table (trig, real models), else null
+    // trajectories per instance (chains): u / x_out / err_out are [N][ntraj][T](..), pbuf / sbuf [chunk * ntraj][ngrid]; the sampling
+    // methods draw from u or, with use_seed, from the counter-based generator keyed by (seed; row id, trajectory, site, trial)
+    int ntraj, use_seed;
+    unsigned long long seed;
+    const int64_t* row_id;      // device [N] or null (the index in the data set)
 };
 int impute_chi_limit(bool cx, bool f32);
 int64_t impute_work_elems(int cap, bool cx, bool f32);     // per-instance scratch elements of the large-chi environment kernel
-int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid = nullptr);   // 1: the sweep ran sixteen instances per workgroup (k_imp_leftb)
+// environment pass for the instances order[i0 .. i0 + count), the sweep for their count * ntraj chains
+int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid = nullptr);   // 1: the sweep ran sixteen chains per workgroup (k_imp_leftb)
+constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin
 void launch_eig_tail(const View& v, int lid, int going_left, int rawn, const double* Gt, int ld, double* Vall, double* dd, double* ee,

@@ -276,24 +276,56 @@ class SweepEngine:
                                          yh.ctypes.data_as(C.POINTER(C.c_double))))
         return (pred, yh) if return_overlaps else pred
 
+    @staticmethod
+    def _traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id):
+        """(K, u, seed, row_id array or None) of a call with ``num_trajectories``: u (N, K, T[, max_trials]) or, with u None, the
+        device generator under ``seed`` with the caller's ``row_id`` (N,)."""
+        K = int(num_trajectories)
+        if K < 1:
+            raise ValueError("num_trajectories must be at least 1")
+        if int(method) not in (2, 4):
+            raise ValueError("num_trajectories needs a sampling method (2 quantile, 4 inverse-transform sampling with rejection)")
+        uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+        if uu is not None:
+            assert uu.size == N * K * T * (int(max_trials) if int(method) == 4 else 1)
+        elif seed is None:
+            raise ValueError("num_trajectories needs the uniform numbers u or a seed for the device generator")
+        rid = None if row_id is None else np.ascontiguousarray(row_id, dtype=np.int64)
+        if rid is not None:
+            assert rid.shape == (N,)
+        sd = int(seed or 0) & (2 ** 64 - 1)
+        return K, uu, sd - 2 ** 64 if sd >= 2 ** 63 else sd, rid
+
     def impute(self, which, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
-               rejection_threshold=0.0, mean_basis=1):
+               rejection_threshold=0.0, mean_basis=1, num_trajectories=None, seed=None, row_id=None):
         """mpst_impute: (x, err, seconds); x / err are (N, T) with the imputed value / its uncertainty at every missing
         site.  method 0 median, 1 mode, 2 quantile of u (N, T), 3 mean, 4 inverse-transform sampling with rejection
-        (u (N, T, max_trials)); order 0 forwards, 1 backwards."""
+        (u (N, T, max_trials)); order 0 forwards, 1 backwards.  With ``num_trajectories`` = K (mpst_impute_traj, sampling methods
+        only) x / err are (N, K, T): K chains per instance from one conditioning, u (N, K, T[, max_trials]) or u None and the
+        device generator keyed by ``seed`` and the caller's ``row_id`` (N,) (default: the index in the data set)."""
         m = np.ascontiguousarray(missing, dtype=np.uint8)
         N, T = m.shape
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=np.complex128 if self.dtype.kind == "c" else np.float64)   # grid states: fp64 (pairs)
         assert gp.shape == (len(gx), self.d) and N == self.N[which] and T == self.T
+        dp = C.POINTER(C.c_double)
+        o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
+        sec = C.c_double()
+        if num_trajectories is not None:
+            K, uu, sd, rid = self._traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id)
+            x = np.zeros((N, K, T))
+            err = np.zeros((N, K, T))
+            self._chk(self.lib.mpst_impute_traj(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
+                                                C.cast(gp.ctypes.data, dp), len(gx), C.byref(o), K,
+                                                uu.ctypes.data_as(dp) if uu is not None else None, sd,
+                                                rid.ctypes.data_as(C.POINTER(C.c_int64)) if rid is not None else None,
+                                                x.ctypes.data_as(dp), err.ctypes.data_as(dp), C.byref(sec)))
+            return x, err, sec.value
         uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
         if uu is not None:
             assert uu.size == N * T * (int(max_trials) if int(method) == 4 else 1)
         x = np.zeros((N, T))
         err = np.zeros((N, T))
-        sec = C.c_double()
-        dp = C.POINTER(C.c_double)
-        o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
         self._chk(self.lib.mpst_impute(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
                                        C.cast(gp.ctypes.data, dp), len(gx), C.byref(o),
                                        uu.ctypes.data_as(dp) if uu is not None else None, x.ctypes.data_as(dp),
@@ -301,11 +333,12 @@ class SweepEngine:
         return x, err, sec.value
 
     def impute_model(self, W, phi, label_index, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
-                     rejection_threshold=0.0, mean_basis=None, compute="f64", label_site=None):
+                     rejection_threshold=0.0, mean_basis=None, compute="f64", label_site=None, num_trajectories=None, seed=None,
+                     row_id=None):
         """mpst_impute_model_run: the imputation engine on a model handed over in one call.  ``W``: site tensors
         (Dl, d, Dr), the label site (Dl, d, Dr, C); ``phi`` (N, T, d) encoded known values; real or complex (then
         ``grid_phi`` is complex too).  ``compute`` "f64" or "f32" (fp32 chain contractions, fp64 densities).
-        Returns (x, err, seconds)."""
+        Returns (x, err, seconds); with ``num_trajectories`` = K (mpst_impute_model_traj) x / err are (N, K, T), see ``impute``."""
         cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
         dt = np.complex128 if cx else np.float64
         T = len(W)
@@ -326,8 +359,11 @@ class SweepEngine:
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=dt)
         assert gp.shape == (len(gx), d)
+        traj = None
+        if num_trajectories is not None:
+            traj = self._traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id)
         uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
-        if uu is not None:
+        if uu is not None and traj is None:
             assert uu.size == N * T * (int(max_trials) if int(method) == 4 else 1)
         if mean_basis is None:
             mean_basis = 2 if cx else 1
@@ -335,10 +371,20 @@ class SweepEngine:
                               C.cast(ptrs, C.POINTER(C.c_void_p)), chi.ctypes.data_as(C.POINTER(C.c_int32)),
                               ph.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.POINTER(C.c_int32)))
         o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
-        x = np.zeros((N, T))
-        err = np.zeros((N, T))
         sec = C.c_double()
         dp = C.POINTER(C.c_double)
+        if traj is not None:
+            K, uu, sd, rid = traj
+            x = np.zeros((N, K, T))
+            err = np.zeros((N, K, T))
+            self._chk(self.lib.mpst_impute_model_traj(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
+                                                      gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o), K,
+                                                      uu.ctypes.data_as(dp) if uu is not None else None, sd,
+                                                      rid.ctypes.data_as(C.POINTER(C.c_int64)) if rid is not None else None,
+                                                      x.ctypes.data_as(dp), err.ctypes.data_as(dp), C.byref(sec)))
+            return x, err, sec.value
+        x = np.zeros((N, T))
+        err = np.zeros((N, T))
         self._chk(self.lib.mpst_impute_model_run(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
                                                  gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o),
                                                  uu.ctypes.data_as(dp) if uu is not None else None, x.ctypes.data_as(dp),
@@ -353,10 +399,11 @@ class SweepEngine:
 
     def impute_info(self):
         """how the last imputation call ran: {"closed_form_densities": bool (Fourier / Legendre grid states on a uniform grid),
-        "batched_sweep": bool (sixteen instances per workgroup)}"""
-        out = (C.c_int32 * 2)()
-        self._chk(self.lib.mpst_get_impute_info(self.ctx, out, 2))
-        return {"closed_form_densities": bool(out[0]), "batched_sweep": bool(out[1])}
+        "batched_sweep": bool (sixteen chains per workgroup), "env_workgroups": workgroups of the environment pass (one per
+        instance), "chains": (instance, trajectory) pairs the sweep ran for}"""
+        out = (C.c_int32 * 4)()
+        self._chk(self.lib.mpst_get_impute_info(self.ctx, out, 4))
+        return {"closed_form_densities": bool(out[0]), "batched_sweep": bool(out[1]), "env_workgroups": int(out[2]), "chains": int(out[3])}
 
     def normalize(self):
         self._chk(self.lib.mpst_normalize(self.ctx))

@@ -117,9 +117,30 @@ def _scaled_instances(imp: ImputationProblem, rows, masks):
     return enc, norms, raw, full, scaled, oob
 
 
+def _check_trajectories(method, num_trajectories):
+    """num_trajectories of impute_ITS (MPS_methods.jl:304-347): None (one series per instance, today's shapes) or K >= 1 chains
+    per instance, which only the sampling method draws."""
+    if num_trajectories is None:
+        return None
+    K = int(num_trajectories)
+    if K < 1:
+        raise ValueError("num_trajectories must be at least 1")
+    if method != "ITS":
+        raise ValueError(f"num_trajectories needs method 'ITS': {method!r} gives one series per instance")
+    return K
+
+
+def _draw_uniforms(rng, N, T, trials, K=None):
+    """The host-drawn uniform numbers of the sampling method: (N, T, trials), or (N, K, T, trials) for K trajectories - chain
+    (i, k) reads u[i, k] exactly as a single-trajectory call reads u[i]."""
+    shape = (N, T, trials) if K is None else (N, K, T, trials)
+    return np.ascontiguousarray((rng or np.random.default_rng()).uniform(0.0, 1.0, shape))
+
+
 def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median", rows=None, invert_transform: bool = True,
                    get_wmad: bool = True, rng=None, engine: Optional[SweepEngine] = None, device: int = 0, return_seconds=False,
-                   impute_order: str = "forwards", rejection_threshold=None, max_trials: int = 10, compute: str = "f64", shard=None):
+                   impute_order: str = "forwards", rejection_threshold=None, max_trials: int = 10, compute: str = "f64", shard=None,
+                   num_trajectories=None, rseed=None):
     """Impute every instance of ``imp.X_test[rows]`` (default: all) at the sites where ``missing_mask`` is True, each
     with the MPS of its class.  Returns (X_imputed, pred_err) in the original units (``invert_transform``) or in the
     encoding's domain; pred_err is the weighted median absolute deviation for ``method="median"``, the standard
@@ -127,7 +148,18 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     (``rejection_threshold`` None is the reference's ``:none``).  Complex encodings (Fourier, Sahand) and
     ``compute="f32"`` (fp32 chain contractions, fp64 densities) go through ``mpst_impute_model_run``.  With a ``shard``
     (distributed.Shard) every rank imputes its slice of the rows - instances are independent, there is no collective on
-    the data path - and the results are gathered on every rank."""
+    the data path - and the results are gathered on every rank.
+
+    ``num_trajectories`` = K (``method="ITS"`` only; impute_ITS's keyword): every instance is conditioned once and K chains
+    are sampled from it.  X_imputed is then (N, K, T) - known sites from the scaled series, ``invert_transform`` applied
+    to every trajectory with its instance's own out-of-bounds rescale - and, with a ``rejection_threshold``, pred_err holds the
+    chains' weighted median absolute deviations in the same shape (None without).  ``rseed`` given: the uniform numbers come
+    from the device generator keyed by (rseed; row, trajectory, site, trial) with ``rows`` as the row ids, so a chain does not
+    depend on which other rows are imputed with it or on how they are dealt over ranks; ``rseed`` None: they are drawn from
+    ``rng`` on the host."""
+    K = _check_trajectories(method, num_trajectories)
+    if rseed is not None and K is None:
+        raise ValueError("rseed seeds the device generator of a call with num_trajectories")
     if method not in METHODS:
         raise ValueError("Invalid method. Choose :mean, :mode, :median, :kNearestNeighbour, :flatBaseline or :ITS"
                          if method not in ("kNearestNeighbour", "flatBaseline") else
@@ -140,7 +172,8 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     if shard is not None and shard.world > 1:
         return _impute_sharded(imp, mask, method, rows, shard, invert_transform=invert_transform, get_wmad=get_wmad, rng=rng,
                                engine=engine, device=device, return_seconds=return_seconds, impute_order=impute_order,
-                               rejection_threshold=rejection_threshold, max_trials=max_trials, compute=compute)
+                               rejection_threshold=rejection_threshold, max_trials=max_trials, compute=compute,
+                               num_trajectories=num_trajectories, rseed=rseed)
     enc, norms, raw, full, scaled, oob = _scaled_instances(imp, rows, mask)
     lab = np.array([imp.class_map[c] for c in np.asarray(imp.y_test)[rows].tolist()], dtype=np.int32)
     order = np.argsort(lab, kind="stable")                      # the engine wants class-sorted data sets
@@ -154,7 +187,8 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     if method == "ITS":
         if rejection_threshold is not None:
             code, trials, thr = 4, int(max_trials), float(rejection_threshold)
-        u = np.ascontiguousarray((rng or np.random.default_rng()).uniform(0.0, 1.0, (N, T, trials)))
+        if rseed is None:
+            u = _draw_uniforms(rng, N, T, trials, K)
     if method == "mean":
         codes = {"Legendre_Norm": 0, "Legendre_No_Norm": 1, "Fourier": 2, "Stoudenmire": 3, "Sahand": 4, "Uniform": 5}    # MPST_BASIS_*
         if enc.name not in codes:
@@ -165,6 +199,8 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     eng = engine or SweepEngine(device)
     try:
         kw = dict(order=ORDERS[impute_order], max_trials=trials, rejection_threshold=thr, mean_basis=basis)
+        if K is not None:
+            kw.update(num_trajectories=K, seed=rseed, row_id=np.asarray(rows, dtype=np.int64)[order])
         if cx or compute != "f64":
             x, err, secs = eng.impute_model(imp.mps, phi, lab[order], m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code,
                                             get_wmad, u, compute=compute, **kw)
@@ -180,6 +216,17 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     inv = np.empty_like(order)
     inv[order] = np.arange(len(order))
     x, err = x[inv], err[inv]
+    if K is not None:
+        ts = np.where(mask[:, None, :], x, scaled[:, None, :])
+        pred = err if rejection_threshold is not None else None
+        if invert_transform:
+            inv_k = lambda a: np.stack([invert_test_transform(a[:, k], oob, norms, imp.opts, enc.range) for k in range(K)], axis=1)
+            hi = inv_k(ts + pred) if pred is not None else None
+            ts = inv_k(ts)
+            if pred is not None:
+                pred = hi - ts
+        out = (ts, pred)
+        return out + (secs,) if return_seconds else out
     ts = np.where(mask, x, scaled)                               # x_samps: known values as given, imputed ones filled in
     pred = err if (method in ("median", "mean") and get_wmad) else None
     if invert_transform:
@@ -197,11 +244,12 @@ def _impute_sharded(imp, mask, method, rows, shard, return_seconds=False, rng=No
     """Rows i with i % world == rank on every rank (the classes stay balanced), results gathered with the host-side
     process group.  The uniform numbers of the sampling method (ITS) come from one seed shared by all ranks (rank 0's draw
     from `rng`, broadcast) and one stream per rank derived from it - reproducible for a given `rng` state and world size, not
-    the single-process stream."""
+    the single-process stream.  With `rseed` (a call with `num_trajectories`) the numbers come from the device generator keyed
+    by the caller's row ids instead: the gathered result IS the single-process result."""
     import torch.distributed as dist
     mine = np.arange(shard.rank, len(rows), shard.world)
     shard_rng = None
-    if method == "ITS":
+    if method == "ITS" and kw.get("rseed") is None:
         # one seed for the whole call - rank 0's draw (from `rng` if given), broadcast over the host-side group - and one
         # stream per rank derived from it: a sharded run with the same `rng` state and world size repeats itself
         seed = [int((rng or np.random.default_rng()).integers(0, 2 ** 62))]
@@ -215,8 +263,10 @@ def _impute_sharded(imp, mask, method, rows, shard, return_seconds=False, rng=No
     parts = [None] * shard.world
     dist.all_gather_object(parts, (mine, ts, pred, secs), group=shard.group)
     T = mask.shape[1]
-    full = np.zeros((len(rows), T))
-    perr = np.zeros((len(rows), T))
+    K = kw.get("num_trajectories")
+    shape = (len(rows), T) if K is None else (len(rows), int(K), T)
+    full = np.zeros(shape)
+    perr = np.zeros(shape)
     have_err = False
     for idx, t, e, _ in parts:
         if t is None:
@@ -251,7 +301,9 @@ def MPS_impute(imp: ImputationProblem, class_, instance: int, missing_sites, met
                impute_order: str = "forwards", NN_baseline: bool = True, n_baselines: int = 1, get_metrics: bool = True,
                engine: Optional[SweepEngine] = None, device: int = 0, **kw):
     """MPS_impute(imp, class, instance, missing_sites, method) (imputation.jl:467-550) without the plots:
-    returns (ts, pred_err, target, metrics) with ``ts`` / ``pred_err`` lists of series as in the reference."""
+    returns (ts, pred_err, target, metrics) with ``ts`` / ``pred_err`` lists of series as in the reference.  With
+    ``method="ITS", num_trajectories=K, rseed=...`` (and ``rejection_threshold`` / ``max_trials``) the lists and ``metrics`` have K
+    entries, one per trajectory (imputation.jl:311-312, 512-522); the nearest-neighbour baseline goes on ``metrics[0]`` only."""
     missing_sites = np.asarray(missing_sites, dtype=np.int64)
     cl = np.flatnonzero(np.asarray(imp.y_test) == class_)
     row = int(cl[instance])
@@ -268,8 +320,14 @@ def MPS_impute(imp: ImputationProblem, class_, instance: int, missing_sites, met
     else:
         t, e = impute_dataset(imp, mask, method, rows=[row], invert_transform=invert_transform, engine=engine, device=device,
                               impute_order=impute_order,
-                              **{k: v for k, v in kw.items() if k in ("get_wmad", "rng", "rejection_threshold", "max_trials")})
-        ts, pred = [t[0]], [None if e is None else e[0]]
+                              **{k: v for k, v in kw.items() if k in ("get_wmad", "rng", "rejection_threshold", "max_trials",
+                                                                      "num_trajectories") or
+                                 (k == "rseed" and kw.get("num_trajectories") is not None)})       # (rseed seeds the trajectories' generator)
+        if kw.get("num_trajectories") is not None:          # one series per trajectory (imputation.jl:311-312)
+            ts = [t[0, k] for k in range(t.shape[1])]
+            pred = [None if e is None else e[0, k] for k in range(t.shape[1])]
+        else:
+            ts, pred = [t[0]], [None if e is None else e[0]]
         if invert_transform:
             target = imp.X_test[row]
         else:

@@ -250,11 +250,18 @@ Every instance of `phi` ((d, T, N), encoded known values; the columns of `missin
 with the class MPS of its label, on the GPU.  `sites[j]` is `Array(mps[j], s_j, l_{j-1}, l_j[, label])`, `xvals` /
 `xvals_enc` ((d, ngrid)) are `imp.x_guess_range`.  Returns `(x, err)`, both (T, N), in the encoding's domain;
 `invert_test_transform` (src/utils.jl:299) stays with the caller.
+
+`num_trajectories = K` (impute_ITS's keyword, src/Imputation/MPS_methods.jl:304-347; methods 2 and 4 only): every instance is
+conditioned once and K chains are sampled from it; `x` and `err` are then (T, K, N).  The uniform numbers are `u`
+((max_trials, T, K, N)) or, with `u === nothing`, come from the device generator under `rseed`, keyed by `row_id` (the caller's
+row of every instance, default 0:N-1) so that a subset or a permutation of the rows draws the same chains.
 """
 function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::Integer, phi::Array, label_idx::Vector{Int32},
                       missing::Matrix{UInt8}, xvals::Vector{Float64}, xvals_enc::Matrix;
                       method::Integer=0, order::Integer=0, get_err::Bool=true, max_trials::Integer=10, rejection_threshold::Float64=0.0,
-                      u::Union{Nothing,Array{Float64}}=nothing, compute::Integer=0, device::Integer=0)
+                      u::Union{Nothing,Array{Float64}}=nothing, compute::Integer=0, device::Integer=0,
+                      num_trajectories::Union{Nothing,Integer}=nothing, rseed::Integer=0,
+                      row_id::Union{Nothing,Vector{Int64}}=nothing)
     d, T, N = size(phi)
     cx = eltype(phi) <: Complex
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
@@ -262,11 +269,21 @@ function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::In
     c = ctx[]
     try
         ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
-        x = zeros(Float64, T, N); err = zeros(Float64, T, N); secs = Ref(0.0)
+        K = num_trajectories === nothing ? 1 : Int(num_trajectories)
+        x = num_trajectories === nothing ? zeros(Float64, T, N) : zeros(Float64, T, K, N)
+        err = zeros(Float64, size(x)...); secs = Ref(0.0)
         GC.@preserve sites ptrs chi phi label_idx begin
             model = Ref(MpstImputeModel(N, T, d, maximum(label_idx) + 1, label_site - 1, cx ? 1 : 0, compute,
                                         pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)), pointer(label_idx)))
             o = Ref(MpstImputeOpts(method, order, get_err ? 1 : 0, max_trials, cx ? 2 : 1, 0, rejection_threshold))
+            if num_trajectories !== nothing
+                check(c, ccall((:mpst_impute_model_traj, LIB), Cint,
+                               (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{UInt8}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ref{MpstImputeOpts}, Int32,
+                                Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                               c, model, missing, xvals, xvals_enc, length(xvals), o, K, u === nothing ? C_NULL : pointer(u),
+                               reinterpret(Int64, UInt64(rseed)), row_id === nothing ? C_NULL : pointer(row_id), x, err, secs))
+                return x, err
+            end
             check(c, ccall((:mpst_impute_model_run, LIB), Cint,
                            (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{UInt8}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ref{MpstImputeOpts}, Ptr{Float64},
                             Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
