@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -354,6 +354,34 @@ int  mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double
 int  mpst_impute_model_traj(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                             int32_t ngrid, const mpst_impute_opts* o, int32_t K, const double* u, int64_t seed, const int64_t* row_id,
                             double* x_out, double* err_out, double* seconds);
+
+/* The distribution behind the median (get_cdfs, src/Imputation/imputation.jl:581-622; get_rdms_with_med / impute_med_and_get_cdf!,
+ * src/Imputation/MPS_methods.jl:350-466; get_cdf, src/Imputation/sampling_utils.jl:205-241): the median imputer, and with it, for every
+ * missing site, read off the SAME conditional distribution the median was read from - p_k = |rho phi(x_k)|^2, cdf = cumul_integrate(xs,
+ * p, TrapezoidalEvenFast()), cdf /= cdf[end] -
+ *   - the grid values at nq more levels: q_out[i][j][l] = x_k with k = argmin_k |cdf_k - levels[l]|, the rule MPST_IMPUTE_QUANTILE
+ *     applies to a uniform number and the median applies to 0.5.  The chain is re-conditioned on the median alone, a level never
+ *     feeds back.  One pass gives the quantile band (e.g. 5 % / 95 %) of every missing site of every instance;
+ *   - the normalised cdf itself on the grid indices 0, s, 2s, ... and always ngrid - 1 (s = cdf_stride):
+ *         ncdf = (ngrid - 2) / cdf_stride + 2      (integer division; s = 1: the whole grid, ncdf = ngrid)
+ *     cdf_out[i][r][:] belongs to the r-th missing site of instance i in ASCENDING site order, whatever o->order is (the reference
+ *     writes cdfs[i] by position in the conditioned MPS, MPS_methods.jl:413); rows beyond an instance's missing count are zero.
+ * mpst_impute_dist is mpst_impute, mpst_impute_model_dist is mpst_impute_model_run (no u: the median draws nothing), with
+ *   o->method       MPST_IMPUTE_MEDIAN; anything else: MPST_ERR_UNSUPPORTED (get_cdfs: "only supports method=:median", imputation.jl:594)
+ *   nq, levels[nq]  0 <= nq <= 16, every level strictly inside (0, 1), in any order; else MPST_ERR_INVALID
+ *   q_out[N][T][nq] in the encoding's domain, 0 at known sites; NULL iff nq == 0
+ *   cdf_stride      0: no cdf, cdf_out NULL.  s >= 1: as above
+ *   cdf_rows        rows per instance of cdf_out[N][cdf_rows][ncdf]; an instance with more missing sites: MPST_ERR_INVALID
+ *   x_out, err_out, seconds  as in the sibling call.
+ * Real and complex models, MPST_COMPUTE_F64 and _F32, chi_max <= 128, d <= 16.  With nq == 0 and cdf_stride == 0 the call launches
+ * the kernels of the sibling call with method = median: same grids, same arithmetic, same bits.  The cdf rows are staged on the
+ * device block by block (MPST_ERR_NOMEM if not even one instance fits: raise cdf_stride). */
+int  mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                      const mpst_impute_opts* o, double* x_out, double* err_out, double* seconds, int32_t nq, const double* levels,
+                      double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out);
+int  mpst_impute_model_dist(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                            int32_t ngrid, const mpst_impute_opts* o, double* x_out, double* err_out, double* seconds, int32_t nq,
+                            const double* levels, double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out);
 
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the

@@ -13,7 +13,7 @@ from .training import (TrainedMPS, fitMPS, fit_encoded, classify, generate_start
                        load_trained_mps, mps_content_digest)
 from .distributed import Shard, split_encoded
 from .imputation import (ImputationProblem, init_imputation_problem, MPS_impute, impute_dataset, kNN_impute, mar,
-                         invert_test_transform)
+                         invert_test_transform, get_cdfs)
 from .jld2 import JLD2File, read_jld2, load_trained_mps_jld2
 from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
@@ -23,7 +23,7 @@ from . import options
 __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "MPSOptions", "safe_options", "EncodedTimeSeriesSet", "Encoding", "encode_dataset",
            "model_encoding", "symbolic_encoding", "transform_data", "TrainedMPS", "fitMPS", "fit_encoded", "classify",
            "generate_startingMPS", "trendy_sine", "Shard", "split_encoded", "MPSTError", "SVDError", "ImputationProblem",
-           "init_imputation_problem", "save_trained_mps", "load_trained_mps", "mps_content_digest", "MPS_impute", "impute_dataset", "kNN_impute", "mar", "invert_test_transform",
+           "init_imputation_problem", "save_trained_mps", "load_trained_mps", "mps_content_digest", "MPS_impute", "impute_dataset", "kNN_impute", "mar", "invert_test_transform", "get_cdfs",
            "JLD2File", "read_jld2", "load_trained_mps_jld2",
            "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation",
            "classify_batch", "tune", "evaluate", "eval_loss", "fit_batch", "BatchFit", "MPSRandomSearch", "TuningLoss", "ClassificationLoss",

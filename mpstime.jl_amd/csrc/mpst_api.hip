@@ -2259,11 +2259,36 @@ struct ImputeTraj {
     const int64_t* row_id;
 };
 
+// The distribution outputs of a call (mpst_impute_dist / mpst_impute_model_dist); the other entry points pass null.
+struct ImputeDist {
+    int32_t nq;
+    const double* levels;
+    double* q_out;
+    int32_t cdf_stride, cdf_rows;
+    double* cdf_out;
+};
+constexpr int IMPUTE_MAX_LEVELS = 16;
+static int64_t impute_ncdf(int32_t ngrid, int32_t stride) { return stride > 0 ? (int64_t)(ngrid - 2) / stride + 2 : 0; }
+
 // shared tail of the imputation entry points: option checks, scratch, launches, results
 static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const double* grid_x, const void* grid_phi, int32_t ngrid,
                       const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
-                      const ImputeTraj& tj = ImputeTraj{1, false, 0, nullptr}) {
+                      const ImputeTraj& tj = ImputeTraj{1, false, 0, nullptr}, const ImputeDist* dd = nullptr) {
     if (!missing || !grid_x || !grid_phi || !x_out || !o || ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
+    if (dd) {
+        // get_cdfs refuses every other method (imputation.jl:594-596)
+        if (o->method != MPST_IMPUTE_MEDIAN) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs are read off the median imputer's distribution: method must be MPST_IMPUTE_MEDIAN");
+        if (dd->nq < 0 || dd->nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)dd->nq);
+        if (dd->nq > 0 && (!dd->levels || !dd->q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
+        for (int l = 0; l < dd->nq; ++l)
+            if (!(dd->levels[l] > 0.0 && dd->levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, dd->levels[l]);
+        if (dd->cdf_stride < 0 || dd->cdf_rows < 0) return fail(c, MPST_ERR_INVALID, "cdf_stride and cdf_rows must not be negative");
+        if (dd->cdf_stride > 0 && !dd->cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_stride > 0 needs cdf_out[N][cdf_rows][ncdf]");
+        if (dd->cdf_stride == 0 && dd->cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_out must be NULL when cdf_stride is 0");
+        if (tj.K != 1) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs belong to the single-series median call");
+    }
+    const int nq = dd ? dd->nq : 0, cdf_stride = dd ? dd->cdf_stride : 0, cdf_rows = dd ? dd->cdf_rows : 0;
+    const int64_t ncdf = impute_ncdf(ngrid, cdf_stride);
     const int method = o->method;
     if (method < MPST_IMPUTE_MEDIAN || method > MPST_IMPUTE_ITS_REJECT) return fail(c, MPST_ERR_INVALID, "unknown imputation method");
     if (o->order != MPST_IMPUTE_FORWARDS && o->order != MPST_IMPUTE_BACKWARDS) return fail(c, MPST_ERR_INVALID, "impute_order must be forwards (0) or backwards (1)");
@@ -2299,7 +2324,11 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         int mm = 0;
         for (int j = 0; j < T; ++j) mm += missing[i * T + j] ? 1 : 0;
         maxm = std::max(maxm, mm);
+        if (cdf_stride > 0 && mm > cdf_rows)
+            return fail(c, MPST_ERR_INVALID, "instance %lld has %d missing sites, cdf_out holds cdf_rows = %d", (long long)i, mm, cdf_rows);
     }
+    if (nq > 0) memset(dd->q_out, 0, (size_t)N * T * nq * sizeof(double));
+    if (cdf_stride > 0) memset(dd->cdf_out, 0, (size_t)N * cdf_rows * (size_t)ncdf * sizeof(double));
     const size_t nout = (size_t)N * K * T;           // x_out / err_out: [N][K][T]
     std::vector<double> xo(nout, 0.0), eo(nout, 0.0);
     c->impute_env_wgs = c->impute_chains = 0;
@@ -2326,7 +2355,11 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         const int64_t welems = impute_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
         // (per instance: its environments once, p_k and S_k for each of its K chains.  A chunk is a run of whole instances, i.e. of
         // chunk * K chains; the outputs and uniform numbers of the extra trajectories come out of the same budget)
-        const int64_t per_bytes = ((int64_t)maxm * m.cap * m.cap * zw + welems) * (int64_t)esz + 2ll * K * ngrid * (int64_t)sizeof(double);
+        // (the cdf rows of an instance are staged with its block - the block's slots, copied out and scattered after its sweep - so
+        // they are part of per_bytes; the levels' q_out is [N][T][nq] for the whole call, like x_out, and comes off the budget)
+        const int64_t cdf_inst = (int64_t)cdf_rows * ncdf;           // doubles per instance
+        const int64_t per_bytes = ((int64_t)maxm * m.cap * m.cap * zw + welems) * (int64_t)esz + 2ll * K * ngrid * (int64_t)sizeof(double) +
+                                  cdf_inst * (int64_t)sizeof(double);
         size_t free_b = 0, total_b = 0;
         HIPC(c, hipMemGetInfo(&free_b, &total_b));
         double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
@@ -2335,6 +2368,11 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
             const double extra = (double)(N * (K - 1) * T) * (double)sizeof(double) * (2.0 + ((sampling && !seeded) ? (double)ntrial : 0.0));
             budget = std::max(budget - extra, (double)per_bytes);
         }
+        if (nq > 0) budget = std::max(budget - (double)(N * T * nq) * (double)sizeof(double), (double)per_bytes);
+        if (dd && (double)per_bytes > 0.9 * (double)free_b)       // (the calls without distribution outputs are left as they were)
+            return fail(c, MPST_ERR_NOMEM, "one instance needs %.3f GB of device scratch (%d environments, densities%s), %.3f GB are free: "
+                        "not even a block of one instance fits", (double)per_bytes / (double)(1ull << 30), maxm,
+                        cdf_inst ? ", cdf rows: raise cdf_stride" : "", (double)free_b / (double)(1ull << 30));
         int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / (double)per_bytes)));
         chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
         if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
@@ -2342,11 +2380,20 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         int32_t* dord = nullptr;
         int64_t* drow = nullptr;
         double *dgx = nullptr, *dgp = nullptr, *du = nullptr, *dp = nullptr, *dS = nullptr, *dx = nullptr, *de = nullptr, *dlin = nullptr;
+        double *dlev = nullptr, *dq = nullptr, *dcdf = nullptr;
         struct Temps {
-            uint8_t **m, **r, **w; double **b, **cc, **dd, **e, **f, **g, **h; int32_t** o; double** l; int64_t** ri;
-            ~Temps() { dfree(m); dfree(r); dfree(w); dfree(b); dfree(cc); dfree(dd); dfree(e); dfree(f); dfree(g); dfree(h); dfree(o); dfree(l); dfree(ri); }
-        } temps{&dmiss, &dR, &dW, &dgx, &dgp, &du, &dp, &dS, &dx, &de, &dord, &dlin, &drow};
+            uint8_t **m, **r, **w; double **b, **cc, **dd, **e, **f, **g, **h; int32_t** o; double** l; int64_t** ri; double **lv, **q, **cf;
+            ~Temps() { dfree(m); dfree(r); dfree(w); dfree(b); dfree(cc); dfree(dd); dfree(e); dfree(f); dfree(g); dfree(h); dfree(o); dfree(l); dfree(ri);
+                       dfree(lv); dfree(q); dfree(cf); }
+        } temps{&dmiss, &dR, &dW, &dgx, &dgp, &du, &dp, &dS, &dx, &de, &dord, &dlin, &drow, &dlev, &dq, &dcdf};
         int rc;
+        if (nq > 0) {
+            if ((rc = dalloc(c, &dlev, nq)) || (rc = dalloc(c, &dq, N * T * nq))) return rc;
+            HIPC(c, hipMemcpy(dlev, dd->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+            HIPC(c, hipMemset(dq, 0, (size_t)N * T * nq * sizeof(double)));
+        }
+        if (cdf_inst > 0 && (rc = dalloc(c, &dcdf, chunk * cdf_inst))) return rc;
+        std::vector<double> cdf_stage(cdf_inst > 0 ? (size_t)(chunk * cdf_inst) : 0);
         if ((rc = dalloc(c, &dmiss, N * T)) || (rc = dalloc(c, &dR, (int64_t)(chunk * maxm * m.cap * m.cap * zw * esz))) ||
             (rc = dalloc(c, &dgx, ngrid)) || (rc = dalloc(c, &dgp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, &dp, chunk * K * ngrid)) ||
             (rc = dalloc(c, &dS, chunk * K * ngrid)) || (rc = dalloc(c, &dx, N * K * T)) || (rc = dalloc(c, &de, N * K * T))) return rc;
@@ -2376,15 +2423,23 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         }
         const ImputeParams q{dmiss, dR, dW, dgx, dgp, du, dp, dS, dx, de, maxm, ngrid, method, o->get_err, o->order == MPST_IMPUTE_BACKWARDS ? 1 : 0,
                              ntrial, o->mean_basis, o->rejection_threshold, trig, gx0, gdx, dord, dlin,
-                             (int)K, seeded ? 1 : 0, (unsigned long long)tj.seed, drow};
+                             (int)K, seeded ? 1 : 0, (unsigned long long)tj.seed, drow, dlev, dq, dcdf, nq, cdf_stride, cdf_rows, (int)ncdf};
         // one event between the two kernels of every chunk: the split of the pass into its environment and density halves
         // (mpst_get_impute_phases) costs nothing against kernels of tens of milliseconds
         struct Evs {
             std::vector<hipEvent_t> e;
             ~Evs() { for (auto x : e) (void)hipEventDestroy(x); }
-        } evs;
+        } evs, begins;
         for (int64_t i0 = 0; i0 < N; i0 += chunk) {
             hipEvent_t mid = nullptr, end = nullptr;
+            if (cdf_inst > 0) {
+                // rows beyond an instance's missing sites stay zero; the block's own start, so that the copy below is in no phase
+                hipEvent_t beg = nullptr;
+                HIPC(c, hipMemsetAsync(dcdf, 0, (size_t)(chunk * cdf_inst) * sizeof(double), c->stream));
+                HIPC(c, hipEventCreate(&beg));
+                begins.e.push_back(beg);
+                HIPC(c, hipEventRecord(beg, c->stream));
+            }
             HIPC(c, hipEventCreate(&mid));
             evs.e.push_back(mid);
             HIPC(c, hipEventCreate(&end));
@@ -2394,6 +2449,13 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
             c->impute_env_wgs += (int)cnt;
             c->impute_chains += (int)(cnt * K);
             HIPC(c, hipEventRecord(end, c->stream));
+            if (cdf_inst > 0) {
+                // slot s of the block holds the rows of instance order[i0 + s]
+                HIPC(c, hipMemcpyAsync(cdf_stage.data(), dcdf, (size_t)(cnt * cdf_inst) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                HIPC(c, hipStreamSynchronize(c->stream));
+                for (int64_t sl = 0; sl < cnt; ++sl)
+                    memcpy(dd->cdf_out + (size_t)order[i0 + sl] * cdf_inst, cdf_stage.data() + (size_t)sl * cdf_inst, (size_t)cdf_inst * sizeof(double));
+            }
         }
         HIPC(c, hipEventRecord(c->ev_stop, c->stream));
         HIPC(c, hipGetLastError());
@@ -2404,7 +2466,7 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
         for (size_t k = 0; k < evs.e.size(); k += 2) {
             float a = 0.f, b = 0.f;
-            HIPC(c, hipEventElapsedTime(&a, k == 0 ? c->ev_start : evs.e[k - 1], evs.e[k]));
+            HIPC(c, hipEventElapsedTime(&a, !begins.e.empty() ? begins.e[k / 2] : (k == 0 ? c->ev_start : evs.e[k - 1]), evs.e[k]));
             HIPC(c, hipEventElapsedTime(&b, evs.e[k], evs.e[k + 1]));
             c->impute_phase_s[0] += 1e-3 * a;
             c->impute_phase_s[1] += 1e-3 * b;
@@ -2419,6 +2481,7 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         }
         HIPC(c, hipMemcpy(xo.data(), dx, xo.size() * sizeof(double), hipMemcpyDeviceToHost));
         HIPC(c, hipMemcpy(eo.data(), de, eo.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (nq > 0) HIPC(c, hipMemcpy(dd->q_out, dq, (size_t)N * T * nq * sizeof(double), hipMemcpyDeviceToHost));
     } else if (seconds) {
         *seconds = 0.0;
     }
@@ -2453,7 +2516,8 @@ static int check_traj(Ctx* c, const mpst_impute_opts* o, int32_t K) {
 }
 
 static int impute_ctx(Ctx* c, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
-                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds, const ImputeTraj& tj) {
+                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds, const ImputeTraj& tj,
+                      const ImputeDist* dd = nullptr) {
     if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
     if (!c->have_mps || !c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options / mpst_set_mps must be called first");
     const DataSet& s = c->ds[which];
@@ -2462,7 +2526,16 @@ static int impute_ctx(Ctx* c, int which, const uint8_t* missing, const double* g
     const View v = make_view(c, which);
     const ImpModel m{v.sites, v.site_stride, v.chi, v.label_site, v.phi, v.label, s.N, c->T, c->d, c->cap, c->zw == 2 ? 1 : 0,
                      (c->dtype == MPST_F32 || c->dtype == MPST_C64) ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj);
+    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj, dd);
+}
+
+int mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
+                     const mpst_impute_opts* o, double* x_out, double* err_out, double* seconds, int32_t nq, const double* levels,
+                     double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    const ImputeDist dd{nq, levels, q_out, cdf_stride, cdf_rows, cdf_out};
+    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr}, &dd);
 }
 
 int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
@@ -2511,7 +2584,7 @@ static void pack_model(const mpst_impute_model* h, int cap, int64_t stride, bool
 
 static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                         int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
-                        const ImputeTraj& tj) {
+                        const ImputeTraj& tj, const ImputeDist* dd = nullptr) {
     if (!h || !h->site || !h->chi || !h->phi || !h->label_idx) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (h->N <= 0 || h->T < 1 || h->d < 1 || h->C < 1) return fail(c, MPST_ERR_INVALID, "empty model or data");
     if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
@@ -2555,7 +2628,16 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missi
     HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
     const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj);
+    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj, dd);
+}
+
+int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
+                           int32_t ngrid, const mpst_impute_opts* o, double* x_out, double* err_out, double* seconds, int32_t nq,
+                           const double* levels, double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    const ImputeDist dd{nq, levels, q_out, cdf_stride, cdf_rows, cdf_out};
+    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr}, &dd);
 }
 
 int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,

@@ -780,7 +780,14 @@ struct ImpArgs {
     int use_seed;               // sampling methods with u == null: uniform numbers from philox_uniform(seed, row id, trajectory, site, trial)
     unsigned long long seed;
     const int64_t* row_id;      // [N] the caller's row ids (the generator's counter) or null: the index in the data set
+    // DIST kernels (mpst_impute_dist, median only, ntraj = 1): the grid values at nq more levels of every missing site's conditional
+    // cdf and the cdf itself at the grid indices 0, cdf_stride, 2 cdf_stride, ... and ngrid - 1 (ncdf of them)
+    const double* levels;       // [nq], inside (0, 1)
+    double* q_out;              // [N][T][nq]
+    double* cdf_out;            // [chunk][cdf_rows][ncdf] by the instance's slot in the chunk; row r: its r-th missing site in ascending order
+    int nq, cdf_stride, cdf_rows, ncdf;
 };
+constexpr int IMP_MAXQ = 16;    // levels per call
 // what a chain reads through its instance and what it addresses by itself
 struct ImpChain {
     int64_t inst;               // instance: missing, phi, label
@@ -851,7 +858,12 @@ enum { IMP_BASIS_LEGENDRE = 0, IMP_BASIS_LEGENDRE_NO_NORM = 1, IMP_BASIS_FOURIER
 //   derivatives by their three-term recurrences.
 // Neither the 20 001 x d table of grid states nor p_k and S_k ever exist: the median, the quantiles and the WMAD evaluate S at the
 // O(log n) indices their searches visit, the mode and the mean evaluate p at every grid value from 2 d coefficients in LDS.
-template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_bounds__(IMP_T, OCC) void k_imp_left(ImpModel v, ImpArgs g) {
+//
+// DIST = the distribution outputs of mpst_impute_dist next to the median (get_cdfs, src/Imputation/imputation.jl:581-622;
+// impute_med_and_get_cdf!, MPS_methods.jl:350-466; get_cdf, sampling_utils.jl:205-241): more levels through the median's own
+// quantile() and the normalised cdf from the median's own cdf_at().  A template flag, not a branch: the instantiations without it
+// compile exactly as before (the table kernels are at their register limit).
+template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __global__ __launch_bounds__(IMP_T, OCC) void k_imp_left(ImpModel v, ImpArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     R* smem = reinterpret_cast<R*>(smem_raw);
     __shared__ double red[4];
@@ -859,6 +871,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
     __shared__ double rhoi[CX ? IMP_MAXD * IMP_MAXD : 1]; // imaginary part
     __shared__ double wtot[4];                              // totals of the four quarters of the grid (prefix sums)
     __shared__ int isel[4];
+    __shared__ double lev[DIST ? IMP_MAXQ : 1];             // DIST: the levels
     __shared__ double tcr[TRIG ? IMP_MAXD : 1], tci[TRIG ? IMP_MAXD : 1], tbr[TRIG ? IMP_MAXD : 1], tbi[TRIG ? IMP_MAXD : 1];
     __shared__ double tmr[TRIG ? IMP_MAXD * IMP_MAXD : 1], tmi[TRIG ? IMP_MAXD * IMP_MAXD : 1];      // rho^H rho
     __shared__ double lc[(TRIG && !CX) ? 2 * IMP_MAXD : 1], lpart[(TRIG && !CX) ? 2 * IMP_MAXD * 8 : 1];       // Legendre: c_l, partial sums
@@ -889,6 +902,9 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
     const int n = g.ngrid;
     const int wave = tid >> 6, lane = tid & 63;
     const double dx = g.grid_x[1] - g.grid_x[0];
+    if constexpr (DIST) {
+        if (tid < g.nq) lev[tid] = g.levels[tid];
+    }
     if (tid == 0) {
         L.r[0] = R(1);
         if constexpr (CX) L.i[0] = R(0);
@@ -1566,6 +1582,25 @@ template <typename R, bool CX, int OCC, bool TRIG = false> __global__ __launch_b
             } else if (g.method == IMP_MEDIAN) {
                 ksel = quantile(0.5);                                        // get_median_from_rdm, :159-196
                 if (g.get_wmad) err = wmad(ksel);
+                if constexpr (DIST) {
+                    // the levels: the median's search once more per level on the density that is already there; the chain is
+                    // conditioned on the median alone
+                    for (int l = 0; l < g.nq; ++l) {
+                        const int kl = quantile(lev[l]);
+                        if (tid == 0) g.q_out[(ch.row * T + j) * g.nq + l] = g.grid_x[kl];
+                    }
+                    // the cdf (cdf /= cdf[end], sampling_utils.jl:205-241) at every cdf_stride-th grid index and the last one, one pass,
+                    // consecutive threads store consecutive doubles.  Row = the site's rank among the instance's missing sites in
+                    // ascending order (cdfs[i] by position, MPS_methods.jl:413), whatever the direction of the sweep.
+                    if (g.cdf_stride > 0) {
+                        const int row = g.rev ? nm - seen : seen - 1;
+                        double* co_ = g.cdf_out + ((int64_t)ch.rslot * g.cdf_rows + row) * g.ncdf;       // (staged per block: the chain's slot)
+                        for (int m = tid; m < g.ncdf; m += IMP_T) {
+                            const int k = m == g.ncdf - 1 ? n - 1 : m * g.cdf_stride;
+                            co_[m] = cdf_at(k) / Z;
+                        }
+                    }
+                }
             } else if (g.method == IMP_QUANTILE) {
                 ksel = quantile(imp_uniform(g, ch, T, j, 0));               // get_sample_from_rdm without rejection, :262-270
             } else if (g.method == IMP_ITS_REJECT) {
@@ -1757,6 +1792,21 @@ hipError_t impute_init_attrs(int device) {
                                  (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
     if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,                    \
                                  (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;
+#define IMP_ATTR_DIST(R, CX, F32)                                                                                                  \
+    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
+    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
+    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
+                                 (int)(left_lds_bytes(CAP_LIMIT, CX, F32) + (CX ? 0 : 31 * IMP_MAXD * IMP_MAXD * sizeof(double))))) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<R, CX, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
+    IMP_ATTR_DIST(double, false, false)
+    IMP_ATTR_DIST(double, true, false)
+    IMP_ATTR_DIST(float, false, true)
+    IMP_ATTR_DIST(float, true, true)
+#undef IMP_ATTR_DIST
+    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<double, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<float, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
 #define IMP_ATTR_TRIG(R, F32)                                                                                                      \
     if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
                                  (int)left_lds_bytes(CAP_LIMIT, true, F32))) != hipSuccess) return e;                              \
@@ -1814,7 +1864,7 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
     if (mid) (void)hipEventRecord(mid, s);
     ImpArgs g{q.missing, q.Rbuf, q.grid_x, q.grid_phi, q.u, q.pbuf, q.sbuf, q.x_out, q.err_out, q.max_missing, q.ngrid, q.method,
               q.get_wmad, q.rev, q.ntrial, q.mean_basis, q.reject_thr, q.order + i0, q.x0, q.dxu, q.lin, 0,
-              q.ntraj, q.use_seed, q.seed, q.row_id};
+              q.ntraj, q.use_seed, q.seed, q.row_id, q.levels, q.q_out, q.cdf_out, q.nq, q.cdf_stride, q.cdf_rows, q.ncdf};
     // the environment pass above ran once per instance; the sweep runs once per chain (ntraj adjacent chains per instance)
     const int64_t nchain = count * q.ntraj;
 #ifdef MPST_LAB
@@ -1833,12 +1883,35 @@ static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0,
     const bool mean_ok = q.method != IMP_MEAN || (CX ? q.mean_basis == IMP_BASIS_FOURIER
                                                      : (q.mean_basis == IMP_BASIS_LEGENDRE || q.mean_basis == IMP_BASIS_LEGENDRE_NO_NORM ||
                                                         q.mean_basis == IMP_BASIS_UNIFORM));
-    if (q.trig && !no_batch && force_occ == 0 && mean_ok && imb_fits(v.cap, v.d, CX, F32)) {
+    // the distribution outputs (mpst_impute_dist with levels or a cdf): the DIST instantiations, on the routes the plain median takes.
+    // A call with a cdf leaves the batched sweep - there a wave's 20 001-point store would hold up the fifteen other chains of its
+    // workgroup (A/B in DESIGN 16; MPST_IMP_DIST_CDF_BATCH=1 keeps it there, the losing variant of that A/B)
+    const bool dist = q.nq > 0 || q.cdf_stride > 0;
+    const bool cdf_batch = getenv("MPST_IMP_DIST_CDF_BATCH") != nullptr;
+    const bool batch_ok = !dist || q.cdf_stride == 0 || cdf_batch;
+    if (q.trig && !no_batch && force_occ == 0 && mean_ok && batch_ok && imb_fits(v.cap, v.d, CX, F32)) {
         const dim3 grid((unsigned)((nchain + IMB_B - 1) / IMB_B));
         const size_t lds_b = imb_layout(v.cap, v.d, CX, F32).bytes;
+        if (dist) {
+            if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX, true>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
+            else hipLaunchKernelGGL((k_imp_leftb<R, CX, false, true>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
+            return 1;
+        }
         if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
         else hipLaunchKernelGGL((k_imp_leftb<R, CX, false>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
         return 1;
+    }
+    if (dist) {
+        // (the occupancy each route runs at by default; MPST_IMP_OCC is a lab switch of the plain kernels)
+        if (q.trig) {
+            const size_t lds_t = left_lds_bytes(v.cap, CX, F32) + (CX ? 0 : (size_t)(2 * v.d - 1) * v.d * v.d * sizeof(double));
+            hipLaunchKernelGGL((k_imp_left<R, CX, 3, true, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
+        } else if ((CX && v.d > 5) || (!CX && v.d > 8)) {
+            hipLaunchKernelGGL((k_imp_left<R, CX, 1, false, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+        } else {
+            hipLaunchKernelGGL((k_imp_left<R, CX, 2, false, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
+        }
+        return 0;
     }
     if constexpr (!CX) {
         if (q.trig) {

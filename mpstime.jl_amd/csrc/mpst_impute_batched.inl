@@ -159,13 +159,15 @@ template <typename F> __device__ __forceinline__ int imb_count_leading(int n, F 
     return lo + __popcll(__ballot(ok) & EVEN);
 }
 
-template <typename R, bool CX, bool EMB>
+// DIST: the levels and (MPST_IMP_DIST_CDF_BATCH) the cdf of mpst_impute_dist, see k_imp_left
+template <typename R, bool CX, bool EMB, bool DIST = false>
 __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, int count) {
     static_assert(CX || !EMB, "the [Re; Im] row embedding is for complex models");
     using acc_t = typename Mx<R>::acc_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int s_inst[IMB_B], s_cls[IMB_B], s_nm[IMB_B], s_seen[IMB_B], s_last[IMB_B];
     __shared__ int s_rslot[IMB_B], s_traj[IMB_B];           // the chain's instance slot (environments) and trajectory
+    __shared__ double s_lev[DIST ? IMP_MAXQ : 1];            // DIST: the levels
     constexpr int ZW = CX ? 2 : 1;
     constexpr bool F32 = std::is_same<R, float>::value;
     constexpr int KU = (F32 ? 16 : 8) / ZW;           // k-slots per batch of operand loads (four batches of registers are alive at a time)
@@ -195,6 +197,9 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
     for (int e = tid; e < ZW * (nl + nw + IMB_NW * nu); e += IMB_T) rsm[e] = R(0);
     if constexpr (!CX) {
         for (int e = tid; e < lay.ntab; e += IMB_T) Atab[e] = g.lin[e];
+    }
+    if constexpr (DIST) {
+        if (tid >= 64 && tid < 64 + g.nq) s_lev[tid - 64] = g.levels[tid - 64];
     }
     if (tid < IMB_B) {
         const int64_t idx = (int64_t)blockIdx.x * IMB_B + tid;
@@ -702,6 +707,23 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
                 } else if (g.method == IMP_MEDIAN) {
                     ksel = quantile(0.5);
                     if (g.get_wmad) err = wmad(ksel);
+                    if constexpr (DIST) {
+                        // the levels with the wave's 64 lanes, as the median; the chain is conditioned on the median alone
+                        for (int l = 0; l < g.nq; ++l) {
+                            const int kl = quantile(s_lev[l]);
+                            if (lane == 0) g.q_out[(ch.row * T + j) * g.nq + l] = g.grid_x[kl];
+                        }
+                        // (only with MPST_IMP_DIST_CDF_BATCH: the builder routes calls with a cdf to k_imp_left)
+                        if (g.cdf_stride > 0) {
+                            const int sn = slot ? sn1 : sn0, nmb = slot ? nm1 : nm0;      // (sn: the missing sites before this one)
+                            const int row = g.rev ? nmb - 1 - sn : sn;
+                            double* co_ = g.cdf_out + ((int64_t)s_rslot[b] * g.cdf_rows + row) * g.ncdf;
+                            for (int m = lane; m < g.ncdf; m += 64) {
+                                const int k = m == g.ncdf - 1 ? n - 1 : m * g.cdf_stride;
+                                co_[m] = D.cdf(k) / Z;
+                            }
+                        }
+                    }
                 } else if (g.method == IMP_QUANTILE) {
                     ksel = quantile(imp_uniform(g, ch, T, j, 0));
                 } else if (g.method == IMP_ITS_REJECT) {

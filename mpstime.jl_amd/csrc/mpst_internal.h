@@ -681,6 +681,11 @@ struct ImputeParams {
     int ntraj, use_seed;
     unsigned long long seed;
     const int64_t* row_id;      // device [N] or null (the index in the data set)
+    // mpst_impute_dist (median, ntraj = 1): levels [nq], q_out [N][T][nq], cdf_out [chunk][cdf_rows][ncdf] (the block's slots) on the device; nq = 0 and
+    // cdf_stride = 0: the plain kernels
+    const double* levels;
+    double *q_out, *cdf_out;
+    int nq, cdf_stride, cdf_rows, ncdf;
 };
 int impute_chi_limit(bool cx, bool f32);
 int64_t impute_work_elems(int cap, bool cx, bool f32);     // per-instance scratch elements of the large-chi environment kernel

@@ -31,6 +31,36 @@ def _site_from_abi(buf, Dl, d, Dr, Cj):
 DTYPES = {np.dtype(np.float64): L.F64, np.dtype(np.float32): L.F32, np.dtype(np.complex128): L.C128, np.dtype(np.complex64): L.C64}
 
 
+MAX_LEVELS = 16      # levels per mpst_impute_dist call (include/mpstime_hip.h)
+
+
+def check_levels(levels):
+    """``levels`` of an imputation call as a float64 array, or None: at most MAX_LEVELS numbers strictly inside (0, 1), in any order.
+    Raises ValueError otherwise - on the host, before any device call."""
+    if levels is None:
+        return None
+    lv = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.float64)
+    if lv.ndim != 1 or lv.size == 0:
+        raise ValueError("levels must be a non-empty sequence of numbers")
+    if lv.size > MAX_LEVELS:
+        raise ValueError(f"at most {MAX_LEVELS} levels per call (got {lv.size})")
+    if not np.all((lv > 0.0) & (lv < 1.0)):
+        raise ValueError(f"levels must lie strictly inside (0, 1) (got {lv.tolist()})")
+    return lv
+
+
+def cdf_points(ngrid, stride):
+    """grid indices a cdf of stride ``stride`` is stored at: 0, s, 2s, ... and always ngrid - 1."""
+    return (int(ngrid) - 2) // int(stride) + 2
+
+
+def cdf_indices(ngrid, stride):
+    n = cdf_points(ngrid, stride)
+    k = np.arange(n) * int(stride)
+    k[-1] = int(ngrid) - 1
+    return k
+
+
 def _dtype_of(x):
     """Element type of an array-like as the engine sees it (opts.dtype): float64 unless it already is one of the four."""
     dt = np.asarray(x).dtype
@@ -296,13 +326,35 @@ class SweepEngine:
         sd = int(seed or 0) & (2 ** 64 - 1)
         return K, uu, sd - 2 ** 64 if sd >= 2 ** 63 else sd, rid
 
+    @staticmethod
+    def _dist_args(missing, ngrid, method, levels, cdf_stride, num_trajectories):
+        """(levels array or None, q (N, T, nq) or None, cdf_stride, cdf_rows, cdf (N, cdf_rows, ncdf) or None) of a call with
+        ``levels`` / ``cdf_stride`` (mpst_impute_dist); raises ValueError on what the library would refuse."""
+        lv = check_levels(levels)
+        s = int(cdf_stride)
+        if s < 0:
+            raise ValueError("cdf_stride must not be negative")
+        if int(method) != 0:
+            raise ValueError("levels / cdf_stride are read off the median imputer's distribution: method must be 0 (median)")
+        if num_trajectories is not None:
+            raise ValueError("levels / cdf_stride cannot be combined with num_trajectories")
+        N, T = missing.shape
+        q = np.zeros((N, T, len(lv))) if lv is not None else None
+        rows = int(missing.astype(bool).sum(axis=1).max()) if (s > 0 and N > 0) else 0
+        cdf = np.zeros((N, rows, cdf_points(ngrid, s))) if s > 0 else None
+        return lv, q, s, rows, cdf
+
     def impute(self, which, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
-               rejection_threshold=0.0, mean_basis=1, num_trajectories=None, seed=None, row_id=None):
+               rejection_threshold=0.0, mean_basis=1, num_trajectories=None, seed=None, row_id=None, levels=None, cdf_stride=0):
         """mpst_impute: (x, err, seconds); x / err are (N, T) with the imputed value / its uncertainty at every missing
         site.  method 0 median, 1 mode, 2 quantile of u (N, T), 3 mean, 4 inverse-transform sampling with rejection
         (u (N, T, max_trials)); order 0 forwards, 1 backwards.  With ``num_trajectories`` = K (mpst_impute_traj, sampling methods
         only) x / err are (N, K, T): K chains per instance from one conditioning, u (N, K, T[, max_trials]) or u None and the
-        device generator keyed by ``seed`` and the caller's ``row_id`` (N,) (default: the index in the data set)."""
+        device generator keyed by ``seed`` and the caller's ``row_id`` (N,) (default: the index in the data set).
+        With ``levels`` (up to 16 numbers inside (0, 1)) and / or ``cdf_stride`` >= 1 (mpst_impute_dist, median only) the return value is
+        (x, err, seconds, q, cdf): q (N, T, nq) the grid value at every level of every missing site's conditional cdf (0 at known
+        sites) or None, cdf (N, cdf_rows, ncdf) that cdf at the grid indices 0, s, 2s, ... and ngrid - 1, row r = the r-th missing
+        site of the instance in ascending order, cdf_rows = the largest missing count, or None."""
         m = np.ascontiguousarray(missing, dtype=np.uint8)
         N, T = m.shape
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
@@ -311,6 +363,17 @@ class SweepEngine:
         dp = C.POINTER(C.c_double)
         o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
         sec = C.c_double()
+        if levels is not None or cdf_stride:
+            lv, q, s, rows, cdf = self._dist_args(m, len(gx), method, levels, cdf_stride, num_trajectories)
+            x = np.zeros((N, T))
+            err = np.zeros((N, T))
+            self._chk(self.lib.mpst_impute_dist(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
+                                                C.cast(gp.ctypes.data, dp), len(gx), C.byref(o), x.ctypes.data_as(dp),
+                                                err.ctypes.data_as(dp), C.byref(sec), 0 if lv is None else len(lv),
+                                                lv.ctypes.data_as(dp) if lv is not None else None,
+                                                q.ctypes.data_as(dp) if q is not None else None, s, rows,
+                                                cdf.ctypes.data_as(dp) if cdf is not None else None))
+            return x, err, sec.value, q, cdf
         if num_trajectories is not None:
             K, uu, sd, rid = self._traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id)
             x = np.zeros((N, K, T))
@@ -334,11 +397,16 @@ class SweepEngine:
 
     def impute_model(self, W, phi, label_index, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
                      rejection_threshold=0.0, mean_basis=None, compute="f64", label_site=None, num_trajectories=None, seed=None,
-                     row_id=None):
+                     row_id=None, levels=None, cdf_stride=0):
         """mpst_impute_model_run: the imputation engine on a model handed over in one call.  ``W``: site tensors
         (Dl, d, Dr), the label site (Dl, d, Dr, C); ``phi`` (N, T, d) encoded known values; real or complex (then
         ``grid_phi`` is complex too).  ``compute`` "f64" or "f32" (fp32 chain contractions, fp64 densities).
-        Returns (x, err, seconds); with ``num_trajectories`` = K (mpst_impute_model_traj) x / err are (N, K, T), see ``impute``."""
+        Returns (x, err, seconds); with ``num_trajectories`` = K (mpst_impute_model_traj) x / err are (N, K, T), see ``impute``;
+        with ``levels`` / ``cdf_stride`` (mpst_impute_model_dist) (x, err, seconds, q, cdf), see ``impute``."""
+        dist = None
+        if levels is not None or cdf_stride:
+            mm = np.ascontiguousarray(missing, dtype=np.uint8)
+            dist = self._dist_args(mm, len(grid_x), method, levels, cdf_stride, num_trajectories)
         cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
         dt = np.complex128 if cx else np.float64
         T = len(W)
@@ -373,6 +441,17 @@ class SweepEngine:
         o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
         sec = C.c_double()
         dp = C.POINTER(C.c_double)
+        if dist is not None:
+            lv, q, s, rows, cdf = dist
+            x = np.zeros((N, T))
+            err = np.zeros((N, T))
+            self._chk(self.lib.mpst_impute_model_dist(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
+                                                      gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o), x.ctypes.data_as(dp),
+                                                      err.ctypes.data_as(dp), C.byref(sec), 0 if lv is None else len(lv),
+                                                      lv.ctypes.data_as(dp) if lv is not None else None,
+                                                      q.ctypes.data_as(dp) if q is not None else None, s, rows,
+                                                      cdf.ctypes.data_as(dp) if cdf is not None else None))
+            return x, err, sec.value, q, cdf
         if traj is not None:
             K, uu, sd, rid = traj
             x = np.zeros((N, K, T))

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib as L
 from .encodings import model_encoding, transform_test_data, transform_train_data
-from .engine import SweepEngine
+from .engine import SweepEngine, check_levels
 from .options import MPSOptions, engine_options, safe_options
 
 METHODS = {"median": 0, "mode": 1, "ITS": 2, "mean": 3}
@@ -140,7 +140,7 @@ def _draw_uniforms(rng, N, T, trials, K=None):
 def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median", rows=None, invert_transform: bool = True,
                    get_wmad: bool = True, rng=None, engine: Optional[SweepEngine] = None, device: int = 0, return_seconds=False,
                    impute_order: str = "forwards", rejection_threshold=None, max_trials: int = 10, compute: str = "f64", shard=None,
-                   num_trajectories=None, rseed=None):
+                   num_trajectories=None, rseed=None, quantiles=None):
     """Impute every instance of ``imp.X_test[rows]`` (default: all) at the sites where ``missing_mask`` is True, each
     with the MPS of its class.  Returns (X_imputed, pred_err) in the original units (``invert_transform``) or in the
     encoding's domain; pred_err is the weighted median absolute deviation for ``method="median"``, the standard
@@ -156,7 +156,18 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     chains' weighted median absolute deviations in the same shape (None without).  ``rseed`` given: the uniform numbers come
     from the device generator keyed by (rseed; row, trajectory, site, trial) with ``rows`` as the row ids, so a chain does not
     depend on which other rows are imputed with it or on how they are dealt over ranks; ``rseed`` None: they are drawn from
-    ``rng`` on the host."""
+    ``rng`` on the host.
+
+    ``quantiles`` = (q1, ...) (``method="median"`` only, up to 16 levels inside (0, 1)): the return value is (X_imputed, pred_err,
+    bands) with bands (N, T, nq) the grid value at every level of every missing site's conditional distribution - the distribution
+    the median was read from, conditioned on the known values and the medians chosen before it; the pass that imputes builds them.
+    Known sites carry the known value in every level; ``invert_transform`` maps every level like X_imputed, with the instance's own
+    out-of-bounds rescale (the transform is monotone: levels stay ordered)."""
+    levels = check_levels(quantiles)
+    if levels is not None and method != "median":
+        raise ValueError(f"quantiles are read off the median imputer's distribution: method must be 'median', not {method!r}")
+    if levels is not None and num_trajectories is not None:
+        raise ValueError("quantiles cannot be combined with num_trajectories")
     K = _check_trajectories(method, num_trajectories)
     if rseed is not None and K is None:
         raise ValueError("rseed seeds the device generator of a call with num_trajectories")
@@ -173,7 +184,7 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
         return _impute_sharded(imp, mask, method, rows, shard, invert_transform=invert_transform, get_wmad=get_wmad, rng=rng,
                                engine=engine, device=device, return_seconds=return_seconds, impute_order=impute_order,
                                rejection_threshold=rejection_threshold, max_trials=max_trials, compute=compute,
-                               num_trajectories=num_trajectories, rseed=rseed)
+                               num_trajectories=num_trajectories, rseed=rseed, quantiles=quantiles)
     enc, norms, raw, full, scaled, oob = _scaled_instances(imp, rows, mask)
     lab = np.array([imp.class_map[c] for c in np.asarray(imp.y_test)[rows].tolist()], dtype=np.int32)
     order = np.argsort(lab, kind="stable")                      # the engine wants class-sorted data sets
@@ -201,15 +212,22 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
         kw = dict(order=ORDERS[impute_order], max_trials=trials, rejection_threshold=thr, mean_basis=basis)
         if K is not None:
             kw.update(num_trajectories=K, seed=rseed, row_id=np.asarray(rows, dtype=np.int64)[order])
+        if levels is not None:
+            kw.update(levels=levels)
+        qv = None
         if cx or compute != "f64":
-            x, err, secs = eng.impute_model(imp.mps, phi, lab[order], m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code,
-                                            get_wmad, u, compute=compute, **kw)
+            out = eng.impute_model(imp.mps, phi, lab[order], m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code,
+                                   get_wmad, u, compute=compute, **kw)
+            x, err, secs = out[:3]
         else:
             Cn = int(imp.mps[-1].shape[3])
             eng.set_options(**engine_options(imp.opts))
             eng.set_dataset(1, phi, lab[order], Cn)
             eng.set_mps(imp.mps)
-            x, err, secs = eng.impute(1, m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code, get_wmad, u, **kw)
+            out = eng.impute(1, m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code, get_wmad, u, **kw)
+            x, err, secs = out[:3]
+        if levels is not None:
+            qv = out[3]
     finally:
         if own:
             eng.close()
@@ -237,6 +255,11 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
         if pred is not None:
             pred = hi - ts
     out = (ts, pred)
+    if levels is not None:
+        bands = np.where(mask[:, :, None], qv[inv], scaled[:, :, None])
+        if invert_transform:
+            bands = np.stack([invert_test_transform(bands[:, :, l], oob, norms, imp.opts, enc.range) for l in range(bands.shape[2])], axis=2)
+        out = out + (bands,)
     return out + (secs,) if return_seconds else out
 
 
@@ -255,28 +278,90 @@ def _impute_sharded(imp, mask, method, rows, shard, return_seconds=False, rng=No
         seed = [int((rng or np.random.default_rng()).integers(0, 2 ** 62))]
         dist.broadcast_object_list(seed, src=0, group=shard.group)
         shard_rng = np.random.default_rng([seed[0], shard.rank])
-    ts = pred = None
+    ts = pred = bands = None
     secs = 0.0
+    nq = None if kw.get("quantiles") is None else len(np.atleast_1d(kw["quantiles"]))
     if len(mine):
         out = impute_dataset(imp, mask[mine], method, rows=np.asarray(rows)[mine], return_seconds=True, rng=shard_rng, **kw)
-        ts, pred, secs = out
+        ts, pred, secs = out[0], out[1], out[-1]
+        if nq is not None:
+            bands = out[2]
     parts = [None] * shard.world
-    dist.all_gather_object(parts, (mine, ts, pred, secs), group=shard.group)
+    dist.all_gather_object(parts, (mine, ts, pred, secs, bands), group=shard.group)
     T = mask.shape[1]
     K = kw.get("num_trajectories")
     shape = (len(rows), T) if K is None else (len(rows), int(K), T)
     full = np.zeros(shape)
     perr = np.zeros(shape)
     have_err = False
-    for idx, t, e, _ in parts:
+    fullb = np.zeros((len(rows), T, nq)) if nq is not None else None
+    for idx, t, e, _, bd in parts:
         if t is None:
             continue
         full[idx] = t
         if e is not None:
             perr[idx] = e
             have_err = True
+        if fullb is not None:
+            fullb[idx] = bd
     out = (full, perr if have_err else None)
+    if fullb is not None:
+        out = out + (fullb,)
     return out + (max(p[3] for p in parts),) if return_seconds else out
+
+
+def get_cdfs(imp: ImputationProblem, class_, instance: int, missing_sites, method: str = "median", impute_order: str = "forwards",
+             get_wmad: bool = True, stride: int = 1, engine: Optional[SweepEngine] = None, device: int = 0):
+    """get_cdfs(imp, class, instance, missing_sites, method) (imputation.jl:581-622): the median imputer on one instance and, for
+    every missing site, the cumulative distribution its median was read from.  Returns (cdfs, ts, pred_err,
+    target_timeseries_full): ``cdfs`` a list with one array per missing site in ascending site order - the normalised cdf on the
+    grid ``imp.x_guess_range.xvals`` (``stride`` s > 1: at the grid indices 0, s, 2s, ... and the last one) -, ``ts = [x_samps]`` and
+    ``pred_err = [wmads]`` in the ENCODING's domain (the reference's get_cdfs does not invert the transform), and the fully
+    transformed target series.  As in the reference the masked region is overwritten with ``mean(X_test)`` before the test
+    transform (:609; get_predictions / impute_dataset use the training mean there)."""
+    if method != "median":
+        raise ValueError("get_cdfs only supports method=:median")
+    if impute_order not in ORDERS:
+        raise ValueError('impute_order must be either ":forwards" or ":backwards"')
+    if int(stride) < 1:
+        raise ValueError("stride must be at least 1")
+    missing_sites = np.asarray(missing_sites, dtype=np.int64)
+    cl = np.flatnonzero(np.asarray(imp.y_test) == class_)
+    row = int(cl[instance])
+    T = imp.X_test.shape[1]
+    mask = np.zeros((1, T), dtype=bool)
+    mask[0, missing_sites] = True
+    enc = model_encoding(imp.opts.encoding)
+    _, norms = transform_train_data(imp.X_train, imp.opts, enc.range)
+    raw = imp.X_test[[row]]
+    full, _ = transform_test_data(raw, norms, imp.opts, enc.range)
+    masked = raw.copy()
+    masked[mask] = np.mean(imp.X_test)
+    scaled, _ = transform_test_data(masked, norms, imp.opts, enc.range)
+    lab = np.array([imp.class_map[class_]], dtype=np.int32)
+    phi = enc.encode(scaled, imp.opts.d)
+    xr = imp.x_guess_range
+    cx = np.iscomplexobj(phi) or np.iscomplexobj(xr.xvals_enc) or any(np.iscomplexobj(t) for t in imp.mps)
+    phi = np.ascontiguousarray(phi, dtype=np.complex128 if cx else np.float64)
+    m8 = np.ascontiguousarray(mask, dtype=np.uint8)
+    own = engine is None
+    eng = engine or SweepEngine(device)
+    try:
+        if cx:
+            x, err, _, _, cdf = eng.impute_model(imp.mps, phi, lab, m8, xr.xvals, xr.xvals_enc, 0, get_wmad, order=ORDERS[impute_order],
+                                                 cdf_stride=int(stride))
+        else:
+            eng.set_options(**engine_options(imp.opts))
+            eng.set_dataset(1, phi, lab, int(imp.mps[-1].shape[3]))
+            eng.set_mps(imp.mps)
+            x, err, _, _, cdf = eng.impute(1, m8, xr.xvals, xr.xvals_enc, 0, get_wmad, order=ORDERS[impute_order], cdf_stride=int(stride))
+    finally:
+        if own:
+            eng.close()
+    nmiss = int(mask.sum())
+    cdfs = [cdf[0, r].copy() for r in range(nmiss)]
+    ts = np.where(mask[0], x[0], scaled[0])
+    return cdfs, [ts], [err[0] if get_wmad else None], full[0]
 
 
 def kNN_impute(imp: ImputationProblem, class_, instance: int, missing_sites, k: int = 1):

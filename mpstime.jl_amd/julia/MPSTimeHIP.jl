@@ -255,13 +255,19 @@ with the class MPS of its label, on the GPU.  `sites[j]` is `Array(mps[j], s_j, 
 conditioned once and K chains are sampled from it; `x` and `err` are then (T, K, N).  The uniform numbers are `u`
 ((max_trials, T, K, N)) or, with `u === nothing`, come from the device generator under `rseed`, keyed by `row_id` (the caller's
 row of every instance, default 0:N-1) so that a subset or a permutation of the rows draws the same chains.
+
+`levels` (up to 16 numbers inside (0, 1)) and / or `cdf_stride = s >= 1` (method 0 only; get_cdfs, src/Imputation/imputation.jl:581-622):
+returns `(x, err, q, cdf)` with `q` (nq, T, N) the grid value at every level of every missing site's conditional cdf (0 at known
+sites) and `cdf` (ncdf, cdf_rows, N), ncdf = (ngrid - 2) ÷ s + 2, that cdf at the grid indices 0, s, 2s, ... and ngrid - 1 for the
+r-th missing site of the instance in ascending order (`nothing` for whichever was not asked for).
 """
 function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::Integer, phi::Array, label_idx::Vector{Int32},
                       missing::Matrix{UInt8}, xvals::Vector{Float64}, xvals_enc::Matrix;
                       method::Integer=0, order::Integer=0, get_err::Bool=true, max_trials::Integer=10, rejection_threshold::Float64=0.0,
                       u::Union{Nothing,Array{Float64}}=nothing, compute::Integer=0, device::Integer=0,
                       num_trajectories::Union{Nothing,Integer}=nothing, rseed::Integer=0,
-                      row_id::Union{Nothing,Vector{Int64}}=nothing)
+                      row_id::Union{Nothing,Vector{Int64}}=nothing,
+                      levels::Union{Nothing,Vector{Float64}}=nothing, cdf_stride::Integer=0)
     d, T, N = size(phi)
     cx = eltype(phi) <: Complex
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
@@ -276,6 +282,19 @@ function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::In
             model = Ref(MpstImputeModel(N, T, d, maximum(label_idx) + 1, label_site - 1, cx ? 1 : 0, compute,
                                         pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)), pointer(label_idx)))
             o = Ref(MpstImputeOpts(method, order, get_err ? 1 : 0, max_trials, cx ? 2 : 1, 0, rejection_threshold))
+            if levels !== nothing || cdf_stride > 0
+                nq = levels === nothing ? 0 : length(levels)
+                rows = cdf_stride > 0 ? Int(maximum(sum(missing .!= 0, dims=1))) : 0
+                q = nq > 0 ? zeros(Float64, nq, T, N) : nothing
+                cdf = cdf_stride > 0 ? zeros(Float64, (length(xvals) - 2) ÷ cdf_stride + 2, rows, N) : nothing
+                check(c, ccall((:mpst_impute_model_dist, LIB), Cint,
+                               (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{UInt8}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ref{MpstImputeOpts}, Ptr{Float64},
+                                Ptr{Float64}, Ref{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}),
+                               c, model, missing, xvals, xvals_enc, length(xvals), o, x, err, secs, nq,
+                               nq > 0 ? pointer(levels) : C_NULL, nq > 0 ? pointer(q) : C_NULL, cdf_stride, rows,
+                               cdf_stride > 0 ? pointer(cdf) : C_NULL))
+                return x, err, q, cdf
+            end
             if num_trajectories !== nothing
                 check(c, ccall((:mpst_impute_model_traj, LIB), Cint,
                                (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{UInt8}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ref{MpstImputeOpts}, Int32,
@@ -293,6 +312,30 @@ function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::In
     finally
         ccall((:mpst_destroy, LIB), Cvoid, (Ptr{Cvoid},), c)
     end
+end
+
+"""
+    impute_dist(c, which, missing, xvals, xvals_enc; order, get_err, levels, cdf_stride)
+
+The same outputs on a context `c` that holds the trained MPS and data set `which` (0 train, 1 test), as `mpst_impute` takes them
+(real models; `xvals_enc` is (d, ngrid) Float64).  Returns `(x, err, q, cdf)` as `impute_batch` does.
+"""
+function impute_dist(c::Ptr{Cvoid}, which::Integer, missing::Matrix{UInt8}, xvals::Vector{Float64}, xvals_enc::Matrix{Float64};
+                     order::Integer=0, get_err::Bool=true, levels::Union{Nothing,Vector{Float64}}=nothing, cdf_stride::Integer=0)
+    T, N = size(missing)
+    nq = levels === nothing ? 0 : length(levels)
+    rows = cdf_stride > 0 ? Int(maximum(sum(missing .!= 0, dims=1))) : 0
+    x = zeros(Float64, T, N); err = zeros(Float64, T, N); secs = Ref(0.0)
+    q = nq > 0 ? zeros(Float64, nq, T, N) : nothing
+    cdf = cdf_stride > 0 ? zeros(Float64, (length(xvals) - 2) ÷ cdf_stride + 2, rows, N) : nothing
+    o = Ref(MpstImputeOpts(0, order, get_err ? 1 : 0, 1, 1, 0, 0.0))
+    check(c, ccall((:mpst_impute_dist, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Int32, Ref{MpstImputeOpts}, Ptr{Float64}, Ptr{Float64},
+                    Ref{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}),
+                   c, which, missing, xvals, xvals_enc, length(xvals), o, x, err, secs, nq,
+                   nq > 0 ? pointer(levels) : C_NULL, nq > 0 ? pointer(q) : C_NULL, cdf_stride, rows,
+                   cdf_stride > 0 ? pointer(cdf) : C_NULL))
+    return x, err, q, cdf
 end
 
 # ---- entanglement analysis (src/Analysis/analyse.jl) ---------------------------------------------------------------------
