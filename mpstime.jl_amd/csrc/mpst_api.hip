@@ -250,6 +250,22 @@ void dfree(T** p) {
     *p = nullptr;
 }
 
+// A device allocation or an event that lives for one call: released when it goes out of scope, whichever return that is.  Move-only
+// (the move constructor leaves no copy operations).
+template <typename H, typename A, hipError_t (*Release)(A)>
+struct DevOwned {
+    H h = nullptr;
+    DevOwned() = default;
+    DevOwned(DevOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    ~DevOwned() { if (h) (void)Release(h); }
+    operator H() const { return h; }
+};
+template <typename T>
+using DevBuf = DevOwned<T*, void*, hipFree>;
+using DevEvent = DevOwned<hipEvent_t, hipEvent_t, hipEventDestroy>;
+template <typename T>
+int dalloc(Ctx* c, DevBuf<T>& b, int64_t n) { return dalloc(c, &b.h, n); }
+
 // (E) buffers: `n` elements of c->esz bytes behind a double* name
 int dalloc_e(struct Ctx* c, double** p, int64_t n);
 
@@ -2250,57 +2266,65 @@ static bool legendre_grid(const double* gx, const double* gp, int n, int d, doub
     return true;
 }
 
-// The trajectories of a call (mpst_impute_traj / mpst_impute_model_traj): K chains per instance, their uniform numbers from the
-// caller (u) or from the device generator (seed, row_id).  The single-trajectory entry points pass {1, false, 0, null}.
-struct ImputeTraj {
-    int32_t K;
-    bool seeded;
-    uint64_t seed;
-    const int64_t* row_id;
-};
-
-// The distribution outputs of a call (mpst_impute_dist / mpst_impute_model_dist); the other entry points pass null.
-struct ImputeDist {
-    int32_t nq;
-    const double* levels;
-    double* q_out;
-    int32_t cdf_stride, cdf_rows;
-    double* cdf_out;
+// One imputation call as the six entry points hand it on: the arrays of the caller (host), the trajectories (mpst_impute_traj /
+// mpst_impute_model_traj: K chains per instance, their uniform numbers from the caller's u or, seeded, from the device generator
+// keyed by seed and row_id) and the distribution outputs (mpst_impute_dist / mpst_impute_model_dist).
+struct ImputeRequest {
+    const uint8_t* missing = nullptr;
+    const double* grid_x = nullptr;
+    const void* grid_phi = nullptr;
+    int32_t ngrid = 0;
+    const mpst_impute_opts* o = nullptr;
+    const double* u = nullptr;
+    double *x_out = nullptr, *err_out = nullptr, *seconds = nullptr;
+    int32_t K = 1;
+    bool seeded = false; uint64_t seed = 0;
+    const int64_t* row_id = nullptr;
+    bool dist = false;          // a *_dist call (also one with nq = 0 and cdf_stride = 0)
+    int32_t nq = 0, cdf_stride = 0, cdf_rows = 0;
+    const double* levels = nullptr;
+    double *q_out = nullptr, *cdf_out = nullptr;
 };
 constexpr int IMPUTE_MAX_LEVELS = 16;
-static int64_t impute_ncdf(int32_t ngrid, int32_t stride) { return stride > 0 ? (int64_t)(ngrid - 2) / stride + 2 : 0; }
 
-// shared tail of the imputation entry points: option checks, scratch, launches, results
-static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const double* grid_x, const void* grid_phi, int32_t ngrid,
-                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
-                      const ImputeTraj& tj = ImputeTraj{1, false, 0, nullptr}, const ImputeDist* dd = nullptr) {
-    if (!missing || !grid_x || !grid_phi || !x_out || !o || ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
-    if (dd) {
+// what a valid request comes to, and how its instances are dealt out
+struct ImputePlan {
+    bool sampling, seeded;      // a sampling method; its uniform numbers come from the device generator
+    int64_t ncdf, cdf_inst;     // cdf points per missing site; doubles of cdf rows per instance
+    int ntrial, maxm;           // trials per site; most missing sites of an instance
+    std::vector<int32_t> order; // the instances in the order they are dealt out to workgroups
+    int64_t welems, chunk;      // scratch elements per instance of the large-chi environment kernel; instances per launch
+};
+
+// the checks of a request, in the order callers rely on; on the way it fills the plan's sizes (ncdf ... maxm) and raises the kernels' LDS limits
+static int impute_validate(Ctx* c, const ImpModel& m, const ImputeRequest& r, ImputePlan* p) {
+    const mpst_impute_opts* o = r.o;
+    if (!r.missing || !r.grid_x || !r.grid_phi || !r.x_out || !o || r.ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
+    if (r.dist) {
         // get_cdfs refuses every other method (imputation.jl:594-596)
         if (o->method != MPST_IMPUTE_MEDIAN) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs are read off the median imputer's distribution: method must be MPST_IMPUTE_MEDIAN");
-        if (dd->nq < 0 || dd->nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)dd->nq);
-        if (dd->nq > 0 && (!dd->levels || !dd->q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
-        for (int l = 0; l < dd->nq; ++l)
-            if (!(dd->levels[l] > 0.0 && dd->levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, dd->levels[l]);
-        if (dd->cdf_stride < 0 || dd->cdf_rows < 0) return fail(c, MPST_ERR_INVALID, "cdf_stride and cdf_rows must not be negative");
-        if (dd->cdf_stride > 0 && !dd->cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_stride > 0 needs cdf_out[N][cdf_rows][ncdf]");
-        if (dd->cdf_stride == 0 && dd->cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_out must be NULL when cdf_stride is 0");
-        if (tj.K != 1) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs belong to the single-series median call");
+        if (r.nq < 0 || r.nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)r.nq);
+        if (r.nq > 0 && (!r.levels || !r.q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
+        for (int l = 0; l < r.nq; ++l)
+            if (!(r.levels[l] > 0.0 && r.levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, r.levels[l]);
+        if (r.cdf_stride < 0 || r.cdf_rows < 0) return fail(c, MPST_ERR_INVALID, "cdf_stride and cdf_rows must not be negative");
+        if (r.cdf_stride > 0 && !r.cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_stride > 0 needs cdf_out[N][cdf_rows][ncdf]");
+        if (r.cdf_stride == 0 && r.cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_out must be NULL when cdf_stride is 0");
+        if (r.K != 1) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs belong to the single-series median call");
     }
-    const int nq = dd ? dd->nq : 0, cdf_stride = dd ? dd->cdf_stride : 0, cdf_rows = dd ? dd->cdf_rows : 0;
-    const int64_t ncdf = impute_ncdf(ngrid, cdf_stride);
+    p->ncdf = r.cdf_stride > 0 ? (int64_t)(r.ngrid - 2) / r.cdf_stride + 2 : 0;
+    p->cdf_inst = (int64_t)r.cdf_rows * p->ncdf;
     const int method = o->method;
     if (method < MPST_IMPUTE_MEDIAN || method > MPST_IMPUTE_ITS_REJECT) return fail(c, MPST_ERR_INVALID, "unknown imputation method");
     if (o->order != MPST_IMPUTE_FORWARDS && o->order != MPST_IMPUTE_BACKWARDS) return fail(c, MPST_ERR_INVALID, "impute_order must be forwards (0) or backwards (1)");
-    const bool sampling = method == MPST_IMPUTE_QUANTILE || method == MPST_IMPUTE_ITS_REJECT;
-    if (sampling && !u && !tj.seeded) return fail(c, MPST_ERR_INVALID, "the sampling methods need the uniform numbers u[N][T][max_trials]");
-    const int ntrial = method == MPST_IMPUTE_ITS_REJECT ? o->max_trials : 1;
-    if (ntrial < 1) return fail(c, MPST_ERR_INVALID, "max_trials must be at least 1");
-    const int64_t K = tj.K;
-    const bool seeded = sampling && !u && tj.seeded;
-    if (seeded && (m.T > IMPUTE_SEED_MAX_SITES || ntrial > IMPUTE_SEED_MAX_TRIALS))
+    p->sampling = method == MPST_IMPUTE_QUANTILE || method == MPST_IMPUTE_ITS_REJECT;
+    if (p->sampling && !r.u && !r.seeded) return fail(c, MPST_ERR_INVALID, "the sampling methods need the uniform numbers u[N][T][max_trials]");
+    p->ntrial = method == MPST_IMPUTE_ITS_REJECT ? o->max_trials : 1;
+    if (p->ntrial < 1) return fail(c, MPST_ERR_INVALID, "max_trials must be at least 1");
+    p->seeded = p->sampling && !r.u && r.seeded;
+    if (p->seeded && (m.T > IMPUTE_SEED_MAX_SITES || p->ntrial > IMPUTE_SEED_MAX_TRIALS))
         return fail(c, MPST_ERR_UNSUPPORTED, "the device generator's counter holds T <= %d sites and max_trials <= %d (got %d, %d): pass u",
-                    IMPUTE_SEED_MAX_SITES, IMPUTE_SEED_MAX_TRIALS, m.T, ntrial);
+                    IMPUTE_SEED_MAX_SITES, IMPUTE_SEED_MAX_TRIALS, m.T, p->ntrial);
     if (method == MPST_IMPUTE_ITS_REJECT && !(o->rejection_threshold >= 0.0)) return fail(c, MPST_ERR_INVALID, "rejection_threshold must be non-negative");
     if (method == MPST_IMPUTE_MEAN) {
         const int mb = o->mean_basis;
@@ -2315,178 +2339,234 @@ static int run_impute(Ctx* c, const ImpModel& m, const uint8_t* missing, const d
         return fail(c, MPST_ERR_UNSUPPORTED, "the imputation engine holds chi_max <= %d (this element type) and d <= 16 (got %d, %d)", lim, m.cap, m.d);
     hipError_t ea = impute_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
-    const int64_t N = m.N;
-    const int T = m.T, d = m.d;
-    const int zw = m.is_complex ? 2 : 1;
-    const size_t esz = m.compute_f32 ? 4 : 8;
-    int maxm = 0;
-    for (int64_t i = 0; i < N; ++i) {
+    p->maxm = 0;
+    for (int64_t i = 0; i < m.N; ++i) {
         int mm = 0;
-        for (int j = 0; j < T; ++j) mm += missing[i * T + j] ? 1 : 0;
-        maxm = std::max(maxm, mm);
-        if (cdf_stride > 0 && mm > cdf_rows)
-            return fail(c, MPST_ERR_INVALID, "instance %lld has %d missing sites, cdf_out holds cdf_rows = %d", (long long)i, mm, cdf_rows);
+        for (int j = 0; j < m.T; ++j) mm += r.missing[i * m.T + j] ? 1 : 0;
+        p->maxm = std::max(p->maxm, mm);
+        if (r.cdf_stride > 0 && mm > r.cdf_rows)
+            return fail(c, MPST_ERR_INVALID, "instance %lld has %d missing sites, cdf_out holds cdf_rows = %d", (long long)i, mm, r.cdf_rows);
     }
-    if (nq > 0) memset(dd->q_out, 0, (size_t)N * T * nq * sizeof(double));
-    if (cdf_stride > 0) memset(dd->cdf_out, 0, (size_t)N * cdf_rows * (size_t)ncdf * sizeof(double));
-    const size_t nout = (size_t)N * K * T;           // x_out / err_out: [N][K][T]
-    std::vector<double> xo(nout, 0.0), eo(nout, 0.0);
-    c->impute_env_wgs = c->impute_chains = 0;
-    // Instances are dealt out to workgroups in the order of where their missing sites begin (in the direction of the sweep):
-    // workgroups that are resident together then walk the chain in step and find the site tensor the first of them fetched
-    // still in the L2 (a 262 KB tensor per site at configs[4], re-read by every instance).  Results do not depend on the order.
-    std::vector<int32_t> order((size_t)N);
-    {
-        std::vector<int32_t> key((size_t)N, T);
-        const bool backwards = o->order == MPST_IMPUTE_BACKWARDS;
-        for (int64_t i = 0; i < N; ++i) {
-            order[i] = (int32_t)i;
-            for (int j = 0; j < T; ++j)
-                if (missing[i * T + (backwards ? T - 1 - j : j)]) { key[i] = j; break; }
+    return 0;
+}
+
+// Instances are dealt out to workgroups in the order of where their missing sites begin (in the direction of the sweep):
+// workgroups that are resident together then walk the chain in step and find the site tensor the first of them fetched
+// still in the L2 (a 262 KB tensor per site at configs[4], re-read by every instance).  Results do not depend on the order.
+static void impute_plan_order(const ImpModel& m, const ImputeRequest& r, ImputePlan* p) {
+    const int64_t N = m.N, T = m.T;
+    p->order.resize((size_t)N);
+    std::vector<int32_t> key((size_t)N, T);
+    const bool backwards = r.o->order == MPST_IMPUTE_BACKWARDS;
+    for (int64_t i = 0; i < N; ++i) {
+        p->order[i] = (int32_t)i;
+        for (int j = 0; j < T; ++j)
+            if (r.missing[i * T + (backwards ? T - 1 - j : j)]) { key[i] = j; break; }
+    }
+    if (getenv("MPST_IMP_NO_ORDER") == nullptr)
+        std::stable_sort(p->order.begin(), p->order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+}
+
+// instances are processed in chunks so that the per-instance scratch (environments of the missing sites, p_k and
+// its prefix sums) stays below half of the free device memory, at most 48 GB (MPST_IMPUTE_CHUNK_GB overrides): the
+// 27 GB of environments of configs[4] (8192 instances x 100 missing sites x 32 KB) are one chunk on a 288 GB device,
+// 512 workgroups of the batched sweep instead of seven launches of 82
+static int impute_plan_chunk(Ctx* c, const ImpModel& m, const ImputeRequest& r, size_t free_b, ImputePlan* p) {
+    const int64_t N = m.N, K = r.K;
+    const int T = m.T, zw = m.is_complex ? 2 : 1;
+    const size_t esz = m.compute_f32 ? 4 : 8;
+    p->welems = impute_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
+    // (per instance: its environments once, p_k and S_k for each of its K chains.  A chunk is a run of whole instances, i.e. of
+    // chunk * K chains; the outputs and uniform numbers of the extra trajectories come out of the same budget)
+    // (the cdf rows of an instance are staged with its block - the block's slots, copied out and scattered after its sweep - so
+    // they are part of per_bytes; the levels' q_out is [N][T][nq] for the whole call, like x_out, and comes off the budget)
+    const int64_t per_bytes = ((int64_t)p->maxm * m.cap * m.cap * zw + p->welems) * (int64_t)esz + 2ll * K * r.ngrid * (int64_t)sizeof(double) +
+                              p->cdf_inst * (int64_t)sizeof(double);
+    double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
+    if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
+    if (K > 1) {
+        const double extra = (double)(N * (K - 1) * T) * (double)sizeof(double) * (2.0 + ((p->sampling && !p->seeded) ? (double)p->ntrial : 0.0));
+        budget = std::max(budget - extra, (double)per_bytes);
+    }
+    if (r.nq > 0) budget = std::max(budget - (double)(N * T * r.nq) * (double)sizeof(double), (double)per_bytes);
+    if (r.dist && (double)per_bytes > 0.9 * (double)free_b)       // (the calls without distribution outputs are left as they were)
+        return fail(c, MPST_ERR_NOMEM, "one instance needs %.3f GB of device scratch (%d environments, densities%s), %.3f GB are free: "
+                    "not even a block of one instance fits", (double)per_bytes / (double)(1ull << 30), p->maxm,
+                    p->cdf_inst ? ", cdf rows: raise cdf_stride" : "", (double)free_b / (double)(1ull << 30));
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / (double)per_bytes)));
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
+    if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
+    p->chunk = chunk;
+    return 0;
+}
+
+// the device side of a call: the caller's arrays, the scratch of a chunk, the results
+struct ImputeBufs {
+    DevBuf<uint8_t> miss, R, W;
+    DevBuf<int32_t> ord;
+    DevBuf<int64_t> row;
+    DevBuf<double> gx, gp, u, p, S, x, e, lin, lev, q, cdf;
+};
+
+static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, ImputeBufs* b) {
+    const int64_t N = m.N, K = r.K, chunk = p.chunk;
+    const int T = m.T, d = m.d, zw = m.is_complex ? 2 : 1, ngrid = r.ngrid;
+    const size_t esz = m.compute_f32 ? 4 : 8, nout = (size_t)N * K * T;
+    const bool have_u = p.sampling && !p.seeded;
+    int rc;
+    if (r.nq > 0) {
+        if ((rc = dalloc(c, b->lev, r.nq)) || (rc = dalloc(c, b->q, N * T * r.nq))) return rc;
+        HIPC(c, hipMemcpy(b->lev, r.levels, (size_t)r.nq * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemset(b->q, 0, (size_t)N * T * r.nq * sizeof(double)));
+    }
+    if (p.cdf_inst > 0 && (rc = dalloc(c, b->cdf, chunk * p.cdf_inst))) return rc;
+    if ((rc = dalloc(c, b->miss, N * T)) || (rc = dalloc(c, b->R, (int64_t)(chunk * p.maxm * m.cap * m.cap * zw * esz))) ||
+        (rc = dalloc(c, b->gx, ngrid)) || (rc = dalloc(c, b->gp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, b->p, chunk * K * ngrid)) ||
+        (rc = dalloc(c, b->S, chunk * K * ngrid)) || (rc = dalloc(c, b->x, N * K * T)) || (rc = dalloc(c, b->e, N * K * T))) return rc;
+    if (have_u && (rc = dalloc(c, b->u, N * K * T * p.ntrial))) return rc;
+    if (p.seeded && r.row_id) {
+        if ((rc = dalloc(c, b->row, N))) return rc;
+        HIPC(c, hipMemcpy(b->row, r.row_id, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    if ((rc = dalloc(c, b->ord, N))) return rc;
+    HIPC(c, hipMemcpy(b->ord, p.order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (p.welems && (rc = dalloc(c, b->W, (int64_t)(chunk * p.welems * esz)))) return rc;
+    HIPC(c, hipMemcpy(b->miss, r.missing, (size_t)N * T, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(b->gx, r.grid_x, (size_t)ngrid * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(b->gp, r.grid_phi, (size_t)ngrid * d * zw * sizeof(double), hipMemcpyHostToDevice));
+    if (have_u) HIPC(c, hipMemcpy(b->u, r.u, (size_t)N * K * T * p.ntrial * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemset(b->x, 0, nout * sizeof(double)));
+    HIPC(c, hipMemset(b->e, 0, nout * sizeof(double)));
+    return 0;
+}
+
+// closed form or table, decided from the grid the caller handed over (the Legendre table goes to the device); the kernels' arguments by name
+static int impute_params(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, ImputeBufs* b, ImputeParams* q) {
+    std::vector<double> lin;
+    ImpArgs& g = q->g;
+    q->trig = m.is_complex ? (fourier_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu) ? 1 : 0)
+                           : (legendre_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu, &lin) ? 1 : 0);
+    c->impute_trig = q->trig;
+    if (!lin.empty()) {
+        if (int rc = dalloc(c, b->lin, (int64_t)lin.size())) return rc;
+        HIPC(c, hipMemcpy(b->lin, lin.data(), lin.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    q->work = b->W;
+    q->order = b->ord;
+    g.missing = b->miss;
+    g.Rbuf = b->R;
+    g.grid_x = b->gx;
+    g.grid_phi = b->gp;
+    g.u = b->u;
+    g.pbuf = b->p;
+    g.sbuf = b->S;
+    g.x_out = b->x;
+    g.err_out = b->e;
+    g.max_missing = p.maxm;
+    g.ngrid = r.ngrid;
+    g.method = r.o->method;
+    g.get_wmad = r.o->get_err;
+    g.rev = r.o->order == MPST_IMPUTE_BACKWARDS ? 1 : 0;
+    g.ntrial = p.ntrial;
+    g.mean_basis = r.o->mean_basis;
+    g.reject_thr = r.o->rejection_threshold;
+    g.lin = b->lin;
+    g.ntraj = (int)r.K;
+    g.use_seed = p.seeded ? 1 : 0;
+    g.seed = (unsigned long long)r.seed;
+    g.row_id = b->row;
+    g.levels = b->lev;
+    g.q_out = b->q;
+    g.cdf_out = b->cdf;
+    g.nq = r.nq;
+    g.cdf_stride = r.cdf_stride;
+    g.cdf_rows = r.cdf_rows;
+    g.ncdf = (int)p.ncdf;
+    return 0;
+}
+
+// The launches, a chunk of instances at a time; the cdf rows of a chunk are staged in its slots and scattered to the caller's array after
+// its sweep.  One event between the two kernels of every chunk: the split of the pass into its environment and density halves
+// (mpst_get_impute_phases) costs nothing against kernels of tens of milliseconds
+static int impute_chunks(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, const ImputeParams& q) {
+    const int64_t N = m.N, chunk = p.chunk, cdf_inst = p.cdf_inst;
+    std::vector<double> cdf_stage(cdf_inst > 0 ? (size_t)(chunk * cdf_inst) : 0);
+    std::vector<DevEvent> evs, begins;
+    auto add_event = [](std::vector<DevEvent>& v) { v.emplace_back(); return hipEventCreate(&v.back().h); };
+    for (int64_t i0 = 0; i0 < N; i0 += chunk) {
+        if (cdf_inst > 0) {
+            // rows beyond an instance's missing sites stay zero; the block's own start, so that the copy below is in no phase
+            HIPC(c, hipMemsetAsync(q.g.cdf_out, 0, (size_t)(chunk * cdf_inst) * sizeof(double), c->stream));
+            HIPC(c, add_event(begins));
+            HIPC(c, hipEventRecord(begins.back(), c->stream));
         }
-        if (getenv("MPST_IMP_NO_ORDER") == nullptr)
-            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+        HIPC(c, add_event(evs));
+        const hipEvent_t mid = evs.back();
+        HIPC(c, add_event(evs));
+        const int64_t cnt = std::min(chunk, N - i0);
+        c->impute_batched = launch_impute(m, q, i0, cnt, c->stream, mid);
+        if (c->impute_batched < 0) return fail(c, MPST_ERR_DEVICE, "no imputation kernel is built for this call's route");
+        c->impute_env_wgs += (int)cnt;
+        c->impute_chains += (int)(cnt * r.K);
+        HIPC(c, hipEventRecord(evs.back(), c->stream));
+        if (cdf_inst > 0) {
+            // slot s of the block holds the rows of instance order[i0 + s]
+            HIPC(c, hipMemcpyAsync(cdf_stage.data(), q.g.cdf_out, (size_t)(cnt * cdf_inst) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPC(c, hipStreamSynchronize(c->stream));
+            for (int64_t sl = 0; sl < cnt; ++sl)
+                memcpy(r.cdf_out + (size_t)p.order[i0 + sl] * cdf_inst, cdf_stage.data() + (size_t)sl * cdf_inst, (size_t)cdf_inst * sizeof(double));
+        }
     }
-    if (maxm > 0) {
-        // instances are processed in chunks so that the per-instance scratch (environments of the missing sites, p_k and
-        // its prefix sums) stays below half of the free device memory, at most 48 GB (MPST_IMPUTE_CHUNK_GB overrides): the
-        // 27 GB of environments of configs[4] (8192 instances x 100 missing sites x 32 KB) are one chunk on a 288 GB device,
-        // 512 workgroups of the batched sweep instead of seven launches of 82
-        const int64_t welems = impute_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
-        // (per instance: its environments once, p_k and S_k for each of its K chains.  A chunk is a run of whole instances, i.e. of
-        // chunk * K chains; the outputs and uniform numbers of the extra trajectories come out of the same budget)
-        // (the cdf rows of an instance are staged with its block - the block's slots, copied out and scattered after its sweep - so
-        // they are part of per_bytes; the levels' q_out is [N][T][nq] for the whole call, like x_out, and comes off the budget)
-        const int64_t cdf_inst = (int64_t)cdf_rows * ncdf;           // doubles per instance
-        const int64_t per_bytes = ((int64_t)maxm * m.cap * m.cap * zw + welems) * (int64_t)esz + 2ll * K * ngrid * (int64_t)sizeof(double) +
-                                  cdf_inst * (int64_t)sizeof(double);
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    if (r.seconds) *r.seconds = 1e-3 * ms;
+    c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
+    for (size_t k = 0; k < evs.size(); k += 2) {
+        float a = 0.f, b = 0.f;
+        HIPC(c, hipEventElapsedTime(&a, !begins.empty() ? begins[k / 2].h : (k == 0 ? c->ev_start : evs[k - 1].h), evs[k]));
+        HIPC(c, hipEventElapsedTime(&b, evs[k], evs[k + 1]));
+        c->impute_phase_s[0] += 1e-3 * a;
+        c->impute_phase_s[1] += 1e-3 * b;
+    }
+    return 0;
+}
+
+// shared tail of the imputation entry points: option checks, plan, scratch, launches, results
+static int run_impute(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
+    ImputePlan p;
+    if (int rc = impute_validate(c, m, r, &p)) return rc;
+    const int64_t N = m.N, T = m.T;
+    if (r.nq > 0) memset(r.q_out, 0, (size_t)N * T * r.nq * sizeof(double));
+    if (r.cdf_stride > 0) memset(r.cdf_out, 0, (size_t)N * r.cdf_rows * (size_t)p.ncdf * sizeof(double));
+    std::vector<double> xo((size_t)N * r.K * T, 0.0), eo(xo.size(), 0.0);           // x_out / err_out: [N][K][T]
+    c->impute_env_wgs = c->impute_chains = 0;
+    impute_plan_order(m, r, &p);
+    if (p.maxm > 0) {
         size_t free_b = 0, total_b = 0;
         HIPC(c, hipMemGetInfo(&free_b, &total_b));
-        double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
-        if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
-        if (K > 1) {
-            const double extra = (double)(N * (K - 1) * T) * (double)sizeof(double) * (2.0 + ((sampling && !seeded) ? (double)ntrial : 0.0));
-            budget = std::max(budget - extra, (double)per_bytes);
-        }
-        if (nq > 0) budget = std::max(budget - (double)(N * T * nq) * (double)sizeof(double), (double)per_bytes);
-        if (dd && (double)per_bytes > 0.9 * (double)free_b)       // (the calls without distribution outputs are left as they were)
-            return fail(c, MPST_ERR_NOMEM, "one instance needs %.3f GB of device scratch (%d environments, densities%s), %.3f GB are free: "
-                        "not even a block of one instance fits", (double)per_bytes / (double)(1ull << 30), maxm,
-                        cdf_inst ? ", cdf rows: raise cdf_stride" : "", (double)free_b / (double)(1ull << 30));
-        int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / (double)per_bytes)));
-        chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
-        if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
-        uint8_t *dmiss = nullptr, *dR = nullptr, *dW = nullptr;
-        int32_t* dord = nullptr;
-        int64_t* drow = nullptr;
-        double *dgx = nullptr, *dgp = nullptr, *du = nullptr, *dp = nullptr, *dS = nullptr, *dx = nullptr, *de = nullptr, *dlin = nullptr;
-        double *dlev = nullptr, *dq = nullptr, *dcdf = nullptr;
-        struct Temps {
-            uint8_t **m, **r, **w; double **b, **cc, **dd, **e, **f, **g, **h; int32_t** o; double** l; int64_t** ri; double **lv, **q, **cf;
-            ~Temps() { dfree(m); dfree(r); dfree(w); dfree(b); dfree(cc); dfree(dd); dfree(e); dfree(f); dfree(g); dfree(h); dfree(o); dfree(l); dfree(ri);
-                       dfree(lv); dfree(q); dfree(cf); }
-        } temps{&dmiss, &dR, &dW, &dgx, &dgp, &du, &dp, &dS, &dx, &de, &dord, &dlin, &drow, &dlev, &dq, &dcdf};
+        ImputeBufs b;
+        ImputeParams q{};
         int rc;
-        if (nq > 0) {
-            if ((rc = dalloc(c, &dlev, nq)) || (rc = dalloc(c, &dq, N * T * nq))) return rc;
-            HIPC(c, hipMemcpy(dlev, dd->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
-            HIPC(c, hipMemset(dq, 0, (size_t)N * T * nq * sizeof(double)));
-        }
-        if (cdf_inst > 0 && (rc = dalloc(c, &dcdf, chunk * cdf_inst))) return rc;
-        std::vector<double> cdf_stage(cdf_inst > 0 ? (size_t)(chunk * cdf_inst) : 0);
-        if ((rc = dalloc(c, &dmiss, N * T)) || (rc = dalloc(c, &dR, (int64_t)(chunk * maxm * m.cap * m.cap * zw * esz))) ||
-            (rc = dalloc(c, &dgx, ngrid)) || (rc = dalloc(c, &dgp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, &dp, chunk * K * ngrid)) ||
-            (rc = dalloc(c, &dS, chunk * K * ngrid)) || (rc = dalloc(c, &dx, N * K * T)) || (rc = dalloc(c, &de, N * K * T))) return rc;
-        if (sampling && !seeded && (rc = dalloc(c, &du, N * K * T * ntrial))) return rc;
-        if (seeded && tj.row_id) {
-            if ((rc = dalloc(c, &drow, N))) return rc;
-            HIPC(c, hipMemcpy(drow, tj.row_id, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice));
-        }
-        if ((rc = dalloc(c, &dord, N))) return rc;
-        HIPC(c, hipMemcpy(dord, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (welems && (rc = dalloc(c, &dW, (int64_t)(chunk * welems * esz)))) return rc;
-        HIPC(c, hipMemcpy(dmiss, missing, (size_t)N * T, hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(dgx, grid_x, (size_t)ngrid * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(dgp, grid_phi, (size_t)ngrid * d * zw * sizeof(double), hipMemcpyHostToDevice));
-        if (sampling && !seeded) HIPC(c, hipMemcpy(du, u, (size_t)N * K * T * ntrial * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(c, hipMemset(dx, 0, nout * sizeof(double)));
-        HIPC(c, hipMemset(de, 0, nout * sizeof(double)));
+        if ((rc = impute_plan_chunk(c, m, r, free_b, &p)) || (rc = impute_upload(c, m, r, p, &b))) return rc;
         HIPC(c, hipEventRecord(c->ev_start, c->stream));
-        double gx0 = 0.0, gdx = 0.0;
-        std::vector<double> lin;
-        const int trig = m.is_complex ? (fourier_grid(grid_x, (const double*)grid_phi, ngrid, d, &gx0, &gdx) ? 1 : 0)
-                                      : (legendre_grid(grid_x, (const double*)grid_phi, ngrid, d, &gx0, &gdx, &lin) ? 1 : 0);
-        c->impute_trig = trig;
-        if (!lin.empty()) {
-            if ((rc = dalloc(c, &dlin, (int64_t)lin.size()))) return rc;
-            HIPC(c, hipMemcpy(dlin, lin.data(), lin.size() * sizeof(double), hipMemcpyHostToDevice));
+        if ((rc = impute_params(c, m, r, p, &b, &q)) || (rc = impute_chunks(c, m, r, p, q))) return rc;
+        if (const char* e = getenv("MPST_IMB_DBG"); e && (atoi(e) & 8)) {   // lab: phase clocks of the batched sweep (k_imp_leftb, workgroup 0 of the last chunk)
+            double ph[6] = {0, 0, 0, 0, 0, 0};
+            HIPC(c, hipMemcpy(ph, b.p, sizeof(ph), hipMemcpyDeviceToHost));
+            fprintf(stderr, "[imb] phase A %.0f us, barrier %.0f, B1 %.0f, B2 %.0f, barrier %.0f\n", ph[0] * 0.01, ph[1] * 0.01, ph[2] * 0.01,
+                    ph[3] * 0.01, ph[4] * 0.01);
         }
-        const ImputeParams q{dmiss, dR, dW, dgx, dgp, du, dp, dS, dx, de, maxm, ngrid, method, o->get_err, o->order == MPST_IMPUTE_BACKWARDS ? 1 : 0,
-                             ntrial, o->mean_basis, o->rejection_threshold, trig, gx0, gdx, dord, dlin,
-                             (int)K, seeded ? 1 : 0, (unsigned long long)tj.seed, drow, dlev, dq, dcdf, nq, cdf_stride, cdf_rows, (int)ncdf};
-        // one event between the two kernels of every chunk: the split of the pass into its environment and density halves
-        // (mpst_get_impute_phases) costs nothing against kernels of tens of milliseconds
-        struct Evs {
-            std::vector<hipEvent_t> e;
-            ~Evs() { for (auto x : e) (void)hipEventDestroy(x); }
-        } evs, begins;
-        for (int64_t i0 = 0; i0 < N; i0 += chunk) {
-            hipEvent_t mid = nullptr, end = nullptr;
-            if (cdf_inst > 0) {
-                // rows beyond an instance's missing sites stay zero; the block's own start, so that the copy below is in no phase
-                hipEvent_t beg = nullptr;
-                HIPC(c, hipMemsetAsync(dcdf, 0, (size_t)(chunk * cdf_inst) * sizeof(double), c->stream));
-                HIPC(c, hipEventCreate(&beg));
-                begins.e.push_back(beg);
-                HIPC(c, hipEventRecord(beg, c->stream));
-            }
-            HIPC(c, hipEventCreate(&mid));
-            evs.e.push_back(mid);
-            HIPC(c, hipEventCreate(&end));
-            evs.e.push_back(end);
-            const int64_t cnt = std::min(chunk, N - i0);
-            c->impute_batched = launch_impute(m, q, i0, cnt, c->stream, mid);
-            c->impute_env_wgs += (int)cnt;
-            c->impute_chains += (int)(cnt * K);
-            HIPC(c, hipEventRecord(end, c->stream));
-            if (cdf_inst > 0) {
-                // slot s of the block holds the rows of instance order[i0 + s]
-                HIPC(c, hipMemcpyAsync(cdf_stage.data(), dcdf, (size_t)(cnt * cdf_inst) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                HIPC(c, hipStreamSynchronize(c->stream));
-                for (int64_t sl = 0; sl < cnt; ++sl)
-                    memcpy(dd->cdf_out + (size_t)order[i0 + sl] * cdf_inst, cdf_stage.data() + (size_t)sl * cdf_inst, (size_t)cdf_inst * sizeof(double));
-            }
-        }
-        HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-        HIPC(c, hipGetLastError());
-        HIPC(c, hipEventSynchronize(c->ev_stop));
-        float ms = 0.f;
-        HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        if (seconds) *seconds = 1e-3 * ms;
-        c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
-        for (size_t k = 0; k < evs.e.size(); k += 2) {
-            float a = 0.f, b = 0.f;
-            HIPC(c, hipEventElapsedTime(&a, !begins.e.empty() ? begins.e[k / 2] : (k == 0 ? c->ev_start : evs.e[k - 1]), evs.e[k]));
-            HIPC(c, hipEventElapsedTime(&b, evs.e[k], evs.e[k + 1]));
-            c->impute_phase_s[0] += 1e-3 * a;
-            c->impute_phase_s[1] += 1e-3 * b;
-        }
-        if (const char* e = getenv("MPST_IMB_DBG")) {
-            if (atoi(e) & 8) {           // lab: phase clocks of the batched sweep (k_imp_leftb, workgroup 0 of the last chunk)
-                double ph[6] = {0, 0, 0, 0, 0, 0};
-                HIPC(c, hipMemcpy(ph, dp, sizeof(ph), hipMemcpyDeviceToHost));
-                fprintf(stderr, "[imb] phase A %.0f us, barrier %.0f, B1 %.0f, B2 %.0f, barrier %.0f\n", ph[0] * 0.01, ph[1] * 0.01, ph[2] * 0.01,
-                        ph[3] * 0.01, ph[4] * 0.01);
-            }
-        }
-        HIPC(c, hipMemcpy(xo.data(), dx, xo.size() * sizeof(double), hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(eo.data(), de, eo.size() * sizeof(double), hipMemcpyDeviceToHost));
-        if (nq > 0) HIPC(c, hipMemcpy(dd->q_out, dq, (size_t)N * T * nq * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (seconds) {
-        *seconds = 0.0;
+        HIPC(c, hipMemcpy(xo.data(), b.x, xo.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(eo.data(), b.e, eo.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (r.nq > 0) HIPC(c, hipMemcpy(r.q_out, b.q, (size_t)N * T * r.nq * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (r.seconds) {
+        *r.seconds = 0.0;
     }
-    memcpy(x_out, xo.data(), xo.size() * sizeof(double));
-    if (err_out) memcpy(err_out, eo.data(), eo.size() * sizeof(double));
+    memcpy(r.x_out, xo.data(), xo.size() * sizeof(double));
+    if (r.err_out) memcpy(r.err_out, eo.data(), eo.size() * sizeof(double));
     return 0;
 }
 
@@ -2515,9 +2595,8 @@ static int check_traj(Ctx* c, const mpst_impute_opts* o, int32_t K) {
     return 0;
 }
 
-static int impute_ctx(Ctx* c, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
-                      const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds, const ImputeTraj& tj,
-                      const ImputeDist* dd = nullptr) {
+// the model of a context's data set
+static int impute_ctx(Ctx* c, int which, const ImputeRequest& r) {
     if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
     if (!c->have_mps || !c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options / mpst_set_mps must be called first");
     const DataSet& s = c->ds[which];
@@ -2526,7 +2605,7 @@ static int impute_ctx(Ctx* c, int which, const uint8_t* missing, const double* g
     const View v = make_view(c, which);
     const ImpModel m{v.sites, v.site_stride, v.chi, v.label_site, v.phi, v.label, s.N, c->T, c->d, c->cap, c->zw == 2 ? 1 : 0,
                      (c->dtype == MPST_F32 || c->dtype == MPST_C64) ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj, dd);
+    return run_impute(c, m, r);
 }
 
 int mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
@@ -2534,15 +2613,21 @@ int mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double*
                      double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    const ImputeDist dd{nq, levels, q_out, cdf_stride, cdf_rows, cdf_out};
-    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr}, &dd);
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.x_out = x_out, r.err_out = err_out, r.seconds = seconds, r.dist = true, r.nq = nq, r.levels = levels, r.q_out = q_out;
+    r.cdf_stride = cdf_stride, r.cdf_rows = cdf_rows, r.cdf_out = cdf_out;
+    return impute_ctx(c, which, r);
 }
 
 int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
                 const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr});
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
+    return impute_ctx(c, which, r);
 }
 
 int mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
@@ -2551,7 +2636,11 @@ int mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double*
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (int rc = check_traj(c, o, K)) return rc;
-    return impute_ctx(c, which, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{K, u == nullptr, (uint64_t)seed, row_id});
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
+    r.K = K, r.seeded = u == nullptr, r.seed = (uint64_t)seed, r.row_id = row_id;
+    return impute_ctx(c, which, r);
 }
 
 // Host arrays of a model in the boundary layouts (site: (s, l, r[, c]) column-major like mpst_set_mps; phi: [N][T][d]) to
@@ -2582,9 +2671,8 @@ static void pack_model(const mpst_impute_model* h, int cap, int64_t stride, bool
 }
 }  // extern "C++"
 
-static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
-                        int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds,
-                        const ImputeTraj& tj, const ImputeDist* dd = nullptr) {
+// the model from host arrays: packed, uploaded for the call, freed after it
+static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest& r) {
     if (!h || !h->site || !h->chi || !h->phi || !h->label_idx) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (h->N <= 0 || h->T < 1 || h->d < 1 || h->C < 1) return fail(c, MPST_ERR_INVALID, "empty model or data");
     if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
@@ -2604,15 +2692,11 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missi
     HIPC(c, hipSetDevice(c->device));
     const int64_t stride = (int64_t)h->C * cap * h->d * cap;
     const size_t esz = (f32 ? 4 : 8) * (cx ? 2 : 1);
-    uint8_t *dsites = nullptr, *dphi = nullptr;
-    int32_t *dchi = nullptr, *dls = nullptr, *dlab = nullptr;
-    struct Temps {
-        uint8_t **a, **b; int32_t **x, **y, **z;
-        ~Temps() { dfree(a); dfree(b); dfree(x); dfree(y); dfree(z); }
-    } temps{&dsites, &dphi, &dchi, &dls, &dlab};
+    DevBuf<uint8_t> dsites, dphi;
+    DevBuf<int32_t> dchi, dls, dlab;
     int rc;
-    if ((rc = dalloc(c, &dsites, (int64_t)(stride * h->T * esz))) || (rc = dalloc(c, &dphi, (int64_t)(h->N * h->T * h->d * esz))) ||
-        (rc = dalloc(c, &dchi, h->T + 1)) || (rc = dalloc(c, &dls, 1)) || (rc = dalloc(c, &dlab, h->N))) return rc;
+    if ((rc = dalloc(c, dsites, (int64_t)(stride * h->T * esz))) || (rc = dalloc(c, dphi, (int64_t)(h->N * h->T * h->d * esz))) ||
+        (rc = dalloc(c, dchi, h->T + 1)) || (rc = dalloc(c, dls, 1)) || (rc = dalloc(c, dlab, h->N))) return rc;
     if (f32) {
         std::vector<float> hs, hp;
         pack_model<float>(h, cap, stride, cx, hs, hp);
@@ -2628,7 +2712,7 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const uint8_t* missi
     HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
     const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return run_impute(c, m, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, tj, dd);
+    return run_impute(c, m, r);
 }
 
 int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2636,15 +2720,21 @@ int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t*
                            const double* levels, double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    const ImputeDist dd{nq, levels, q_out, cdf_stride, cdf_rows, cdf_out};
-    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr}, &dd);
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.x_out = x_out, r.err_out = err_out, r.seconds = seconds, r.dist = true, r.nq = nq, r.levels = levels, r.q_out = q_out;
+    r.cdf_stride = cdf_stride, r.cdf_rows = cdf_rows, r.cdf_out = cdf_out;
+    return impute_model(c, h, r);
 }
 
 int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                           int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{1, false, 0, nullptr});
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
+    return impute_model(c, h, r);
 }
 
 int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2653,7 +2743,11 @@ int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t*
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (int rc = check_traj(c, o, K)) return rc;
-    return impute_model(c, h, missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds, ImputeTraj{K, u == nullptr, (uint64_t)seed, row_id});
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
+    r.K = K, r.seeded = u == nullptr, r.seed = (uint64_t)seed, r.row_id = row_id;
+    return impute_model(c, h, r);
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

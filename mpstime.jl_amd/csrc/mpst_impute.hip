@@ -758,35 +758,6 @@ __global__ __launch_bounds__(IMP_T) void k_imp_right_big(ImpModel v, const uint8
 }
 
 // ---- the sweep with the imputation itself ---------------------------------------------------------------------------------
-struct ImpArgs {
-    const uint8_t* missing;     // [N][T]
-    const void* Rbuf;           // [chunk][max_missing][cap*cap] elements of the chain type
-    const double* grid_x;       // [ngrid]
-    const double* grid_phi;     // [ngrid][d] doubles (real model) or (re, im) pairs (complex model)
-    const double* u;            // [N][T][ntrial] uniform numbers (quantile / ITS) or null
-    double* pbuf;               // [chunk][ngrid] scratch: p_k
-    double* sbuf;               // [chunk][ngrid] scratch: prefix sums S_k
-    double* x_out;              // [N][T]
-    double* err_out;            // [N][T]
-    int max_missing, ngrid, method, get_wmad, rev, ntrial, mean_basis;
-    double reject_thr;
-    const int32_t* ord;         // the instances of this chunk (run_impute orders them by where their missing sites begin)
-    double x0, dxu;             // TRIG kernels: the uniform grid x_k = x0 + k dxu
-    const double* lin;          // TRIG, real models: [2d-1][d][d] Legendre linearisation table (scaled by the states' norms), else null
-    int dbg;                    // k_imp_leftb: parts switched off for timing (0 outside -DMPST_LAB builds)
-    // chains: ntraj trajectories per instance, adjacent.  Chain c of the chunk belongs to the instance ord[c / ntraj] (whose
-    // environments sit in slot c / ntraj of Rbuf) and is its trajectory c % ntraj; u, x_out and err_out are [N][ntraj][T](...)
-    int ntraj;
-    int use_seed;               // sampling methods with u == null: uniform numbers from philox_uniform(seed, row id, trajectory, site, trial)
-    unsigned long long seed;
-    const int64_t* row_id;      // [N] the caller's row ids (the generator's counter) or null: the index in the data set
-    // DIST kernels (mpst_impute_dist, median only, ntraj = 1): the grid values at nq more levels of every missing site's conditional
-    // cdf and the cdf itself at the grid indices 0, cdf_stride, 2 cdf_stride, ... and ngrid - 1 (ncdf of them)
-    const double* levels;       // [nq], inside (0, 1)
-    double* q_out;              // [N][T][nq]
-    double* cdf_out;            // [chunk][cdf_rows][ncdf] by the instance's slot in the chunk; row r: its r-th missing site in ascending order
-    int nq, cdf_stride, cdf_rows, ncdf;
-};
 constexpr int IMP_MAXQ = 16;    // levels per call
 // what a chain reads through its instance and what it addresses by itself
 struct ImpChain {
@@ -1777,177 +1748,180 @@ static int impute_lds_chi_limit(bool cx, bool f32) {
 int impute_chi_limit(bool, bool) { return CAP_LIMIT; }
 int64_t impute_work_elems(int cap, bool cx, bool f32) { return cap > impute_lds_chi_limit(cx, f32) ? 4ll * cap * cap * (cx ? 2 : 1) : 0; }
 
+// ---- the route of a call: which kernels, at which block size / occupancy / dynamic LDS -----------------------------------
+struct ImputeSwitches {
+    int force_occ;              // MPST_IMP_OCC=1|2|4 (read once, a lab switch): the occupancy of the plain one-chain kernels, no batched sweep
+    bool no_batch;              // MPST_IMP_NO_BATCH=1 (every call, a test hook): the one-chain kernel where the batched sweep would run
+    bool cdf_batch;             // MPST_IMP_DIST_CDF_BATCH=1 (every call): a call with a cdf stays in the batched sweep
+};
+static ImputeSwitches impute_switches() {
+    static const int force_occ = [] { const char* e = getenv("MPST_IMP_OCC"); return e ? atoi(e) : 0; }();
+    return ImputeSwitches{force_occ, getenv("MPST_IMP_NO_BATCH") != nullptr, getenv("MPST_IMP_DIST_CDF_BATCH") != nullptr};
+}
+struct ImputeRoute {
+    bool env_big;               // environment pass: k_imp_right_big (global scratch), else k_imp_right in LDS
+    int env_threads;            // ... with that many threads
+    size_t env_lds;
+    bool batched, emb;          // sweep: k_imp_leftb<EMB>, sixteen chains per workgroup, else k_imp_left, a workgroup per chain
+    int occ;                    // ... built for that many workgroups per CU
+    bool trig, dist;            // k_imp_left<TRIG, DIST>, k_imp_leftb<DIST> (which only runs on closed-form grids)
+    size_t lds;                 // dynamic LDS of the sweep kernel
+};
+static ImputeRoute impute_route(const ImpModel& v, const ImputeParams& q, const ImputeSwitches& sw) {
+    const bool CX = v.is_complex != 0, F32 = v.compute_f32 != 0;
+    ImputeRoute r{};
+    r.env_big = v.cap > impute_lds_chi_limit(CX, F32);
+    // a wave per 16 x 16 tile: 16, 9 (on 8 waves), 4 or 1 tiles
+    const int tpr = (v.cap + 15) >> 4;
+    r.env_threads = tpr >= 4 ? 1024 : (tpr == 3 ? 512 : 256);
+    r.env_lds = r.env_big ? 0 : right_lds_bytes(v.cap, CX, F32);
+    r.trig = q.trig != 0;
+    const bool mean_ok = q.g.method != IMP_MEAN || (CX ? q.g.mean_basis == IMP_BASIS_FOURIER
+                                                       : (q.g.mean_basis == IMP_BASIS_LEGENDRE || q.g.mean_basis == IMP_BASIS_LEGENDRE_NO_NORM ||
+                                                          q.g.mean_basis == IMP_BASIS_UNIFORM));
+    // the distribution outputs (mpst_impute_dist with levels or a cdf): the DIST instantiations, on the routes the plain median takes.
+    // A call with a cdf leaves the batched sweep - there a wave's 20 001-point store would hold up the fifteen other chains of its
+    // workgroup (A/B in DESIGN 16; MPST_IMP_DIST_CDF_BATCH=1 keeps it there, the losing variant of that A/B)
+    r.dist = q.g.nq > 0 || q.g.cdf_stride > 0;
+    const bool batch_ok = !r.dist || q.g.cdf_stride == 0 || sw.cdf_batch;
+    // closed-form densities: sixteen instances per workgroup
+    if (r.trig && !sw.no_batch && sw.force_occ == 0 && mean_ok && batch_ok && imb_fits(v.cap, v.d, CX, F32)) {
+        r.batched = true;
+        r.emb = CX && v.d <= 8;
+        r.lds = imb_layout(v.cap, v.d, CX, F32).bytes;
+        return r;
+    }
+    // Legendre states on a uniform grid (closed form, real models): the linearisation table rides in LDS behind the panels
+    r.lds = left_lds_bytes(v.cap, CX, F32) + ((r.trig && !CX) ? (size_t)(2 * v.d - 1) * v.d * v.d * sizeof(double) : 0);
+    // (the distribution kernels run at the occupancy their route has by default; MPST_IMP_OCC is a lab switch of the plain kernels)
+    const int forced = r.dist ? 0 : sw.force_occ;
+    if (r.trig) {
+        // closed-form densities: no density loop, so no reason to keep the whole register file for one workgroup
+        // complex models, three workgroups per CU (170 VGPRs): same-box A/B at configs[4] with 16 / 8 loads per output in flight:
+        // OCC 2: 83.5 / 148 ms, OCC 3: 76.2 / 97 ms, OCC 4 (spilling): 121 / 102 ms
+        // (real models, three workgroups per CU: d = 4, chi = 32: 15.9 / 14.6 / 13.3 ms at 1 / 2 / 3; d = 12, chi = 40: 27.5 / 27.6 / 26.6)
+        r.occ = (forced == 1 || forced == 2 || (forced == 4 && CX)) ? forced : 3;
+        return r;
+    }
+    // two workgroups per CU (128 VGPRs each, 70-183 of them spilled) against one (256 VGPRs, no spill): the spilling
+    // build wins where the density loop is latency-bound - real models and complex ones with d <= 5 - because a second
+    // workgroup hides more than the scratch traffic costs (same-box A/B: profiles/r03_impute_occupancy_ab.txt;
+    // MPST_IMP_OCC=1|2 forces either)
+    // (real models with d > 8 - the reference's imputation examples use Legendre d = 10 ... 12 - likewise: d = 12, chi = 40: 147 ms with
+    // two spilling workgroups per CU, 44 ms with one; 774 ms before the density loop had unrolled forms beyond d = 8)
+    r.occ = (forced == 1 || forced == 2) ? forced : (((CX && v.d > 5) || (!CX && v.d > 8)) ? 1 : 2);
+    return r;
+}
+
+// ---- from the route to the launch ------------------------------------------------------------------------------------------------
+// Every instantiation a route can name stands in one of the three lists below, once.  imp_raise_lds expands them to raise each
+// entry's dynamic-LDS limit to the most it can be launched with, imp_env / imp_sweep expand them to launch the entry the route
+// names - so what can be launched cannot lack its attribute.
+// WHEN is the compile-time condition on the model's type (the complex-only variants are not built for real models).
+#define IMP_RIGHT_LIST(X) X(256) X(512) X(1024)
+#define IMP_LEFT_LIST(X) /* WHEN, OCC, TRIG, DIST */                                                                               \
+    X(true, 1, false, false) X(true, 2, false, false) X(true, 1, false, true) X(true, 2, false, true)                               \
+    X(true, 1, true, false) X(true, 2, true, false) X(true, 3, true, false) X(CX, 4, true, false) X(true, 3, true, true)
+#define IMP_LEFTB_LIST(X) /* WHEN, EMB, DIST */ X(true, false, false) X(CX, true, false) X(true, false, true) X(CX, true, true)
+
+template <typename R, bool CX>
+static hipError_t imp_raise_lds() {
+    constexpr bool F32 = std::is_same<R, float>::value;
+    const size_t right_max = right_lds_bytes(impute_lds_chi_limit(CX, F32), CX, F32), left_max = left_lds_bytes(CAP_LIMIT, CX, F32);
+    const size_t table_max = CX ? 0 : (2 * IMP_MAXD - 1) * IMP_MAXD * IMP_MAXD * sizeof(double);
+#define RAISE(KERNEL, BYTES)                                                                                                        \
+    if (hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)); e != hipSuccess) return e;
+#define X(BS) RAISE((k_imp_right<R, CX, BS>), right_max)
+    IMP_RIGHT_LIST(X)
+#undef X
+#define X(WHEN, OCC, TRIG, DIST) if constexpr (WHEN) { RAISE((k_imp_left<R, CX, OCC, TRIG, DIST>), left_max + (TRIG ? table_max : 0)) }
+    IMP_LEFT_LIST(X)
+#undef X
+#define X(WHEN, EMB, DIST) if constexpr (WHEN) { RAISE((k_imp_leftb<R, CX, EMB, DIST>), IMB_LDS_MAX) }
+    IMP_LEFTB_LIST(X)
+#undef X
+#undef RAISE
+    return hipSuccess;
+}
+
 hipError_t impute_init_attrs(int device) {
     static std::atomic<unsigned long long> done{0};
     if (device >= 0 && device < 64 && (done.load(std::memory_order_acquire) >> device) & 1ull) return hipSuccess;
-    hipError_t e;
-#define IMP_ATTR(R, CX, F32)                                                                                                       \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_right<R, CX, 256>, hipFuncAttributeMaxDynamicSharedMemorySize,                \
-                                 (int)right_lds_bytes(impute_lds_chi_limit(CX, F32), CX, F32))) != hipSuccess) return e;          \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_right<R, CX, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,                \
-                                 (int)right_lds_bytes(impute_lds_chi_limit(CX, F32), CX, F32))) != hipSuccess) return e;          \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_right<R, CX, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                                 (int)right_lds_bytes(impute_lds_chi_limit(CX, F32), CX, F32))) != hipSuccess) return e;          \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,                    \
-                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,                    \
-                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;
-#define IMP_ATTR_DIST(R, CX, F32)                                                                                                  \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                 (int)left_lds_bytes(CAP_LIMIT, CX, F32))) != hipSuccess) return e;                                \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, CX, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                 (int)(left_lds_bytes(CAP_LIMIT, CX, F32) + (CX ? 0 : 31 * IMP_MAXD * IMP_MAXD * sizeof(double))))) != hipSuccess) return e; \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<R, CX, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
-    IMP_ATTR_DIST(double, false, false)
-    IMP_ATTR_DIST(double, true, false)
-    IMP_ATTR_DIST(float, false, true)
-    IMP_ATTR_DIST(float, true, true)
-#undef IMP_ATTR_DIST
-    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<double, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<float, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
-#define IMP_ATTR_TRIG(R, F32)                                                                                                      \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                 (int)left_lds_bytes(CAP_LIMIT, true, F32))) != hipSuccess) return e;                              \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, true, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                 (int)left_lds_bytes(CAP_LIMIT, true, F32))) != hipSuccess) return e;                              \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                 (int)left_lds_bytes(CAP_LIMIT, true, F32))) != hipSuccess) return e;                              \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                 (int)left_lds_bytes(CAP_LIMIT, true, F32))) != hipSuccess) return e;
-    IMP_ATTR_TRIG(double, false)
-    IMP_ATTR_TRIG(float, true)
-#undef IMP_ATTR_TRIG
-#define IMP_ATTR_LEG(R, F32, OCC)                                                                                                  \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_left<R, false, OCC, true>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                 (int)(left_lds_bytes(CAP_LIMIT, false, F32) + 31 * IMP_MAXD * IMP_MAXD * sizeof(double)))) != hipSuccess) return e;
-    IMP_ATTR_LEG(double, false, 1)
-    IMP_ATTR_LEG(double, false, 2)
-    IMP_ATTR_LEG(double, false, 3)
-    IMP_ATTR_LEG(float, true, 1)
-    IMP_ATTR_LEG(float, true, 2)
-    IMP_ATTR_LEG(float, true, 3)
-#undef IMP_ATTR_LEG
-#define IMB_ATTR(R, CX, EMB)                                                                                                       \
-    if ((e = hipFuncSetAttribute((const void*)k_imp_leftb<R, CX, EMB>, hipFuncAttributeMaxDynamicSharedMemorySize, IMB_LDS_MAX)) != hipSuccess) return e;
-    IMB_ATTR(double, false, false)
-    IMB_ATTR(double, true, false)
-    IMB_ATTR(double, true, true)
-    IMB_ATTR(float, false, false)
-    IMB_ATTR(float, true, false)
-    IMB_ATTR(float, true, true)
-#undef IMB_ATTR
-    IMP_ATTR(double, false, false)
-    IMP_ATTR(double, true, false)
-    IMP_ATTR(float, false, true)
-    IMP_ATTR(float, true, true)
-#undef IMP_ATTR
+    for (hipError_t e : {imp_raise_lds<double, false>(), imp_raise_lds<double, true>(), imp_raise_lds<float, false>(), imp_raise_lds<float, true>()})
+        if (e != hipSuccess) return e;
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
 }
 
+// the instances order[i0 .. i0 + count) on a stream, an event between the two kernels
+struct ImputeChunk { int64_t i0, count; hipStream_t s; hipEvent_t mid; };
+
 template <typename R, bool CX>
-static int launch_impute_t(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid) {
-    constexpr bool F32 = std::is_same<R, float>::value;
-    if (v.cap > impute_lds_chi_limit(CX, F32))
-        hipLaunchKernelGGL((k_imp_right_big<R, CX>), dim3((unsigned)count), dim3(IMP_T), 0, s, v, q.missing, (R*)q.Rbuf, (R*)q.work,
-                           q.max_missing, q.order + i0, q.rev);
-    else {
-        // a wave per 16 x 16 tile: 16, 9 (on 8 waves), 4 or 1 tiles
-        const int tpr = (v.cap + 15) >> 4;
-        const size_t lds = right_lds_bytes(v.cap, CX, F32);
-        if (tpr >= 4) hipLaunchKernelGGL((k_imp_right<R, CX, 1024>), dim3((unsigned)count), dim3(1024), lds, s, v, q.missing, (R*)q.Rbuf, q.max_missing, q.order + i0, q.rev);
-        else if (tpr == 3) hipLaunchKernelGGL((k_imp_right<R, CX, 512>), dim3((unsigned)count), dim3(512), lds, s, v, q.missing, (R*)q.Rbuf, q.max_missing, q.order + i0, q.rev);
-        else hipLaunchKernelGGL((k_imp_right<R, CX, 256>), dim3((unsigned)count), dim3(256), lds, s, v, q.missing, (R*)q.Rbuf, q.max_missing, q.order + i0, q.rev);
+static hipError_t imp_env(const ImputeRoute& rt, const ImpModel& v, const ImputeParams& q, const ImputeChunk& ch) {
+    const dim3 grid((unsigned)ch.count);
+    if (rt.env_big) {
+        hipLaunchKernelGGL((k_imp_right_big<R, CX>), grid, dim3(IMP_T), 0, ch.s, v, q.g.missing, (R*)q.g.Rbuf, (R*)q.work, q.g.max_missing,
+                           q.order + ch.i0, q.g.rev);
+        return hipSuccess;
     }
-    if (mid) (void)hipEventRecord(mid, s);
-    ImpArgs g{q.missing, q.Rbuf, q.grid_x, q.grid_phi, q.u, q.pbuf, q.sbuf, q.x_out, q.err_out, q.max_missing, q.ngrid, q.method,
-              q.get_wmad, q.rev, q.ntrial, q.mean_basis, q.reject_thr, q.order + i0, q.x0, q.dxu, q.lin, 0,
-              q.ntraj, q.use_seed, q.seed, q.row_id, q.levels, q.q_out, q.cdf_out, q.nq, q.cdf_stride, q.cdf_rows, q.ncdf};
-    // the environment pass above ran once per instance; the sweep runs once per chain (ntraj adjacent chains per instance)
-    const int64_t nchain = count * q.ntraj;
+#define X(BS)                                                                                                                       \
+    if (rt.env_threads == BS) {                                                                                                     \
+        hipLaunchKernelGGL((k_imp_right<R, CX, BS>), grid, dim3(BS), rt.env_lds, ch.s, v, q.g.missing, (R*)q.g.Rbuf, q.g.max_missing, \
+                           q.order + ch.i0, q.g.rev);                                                                               \
+        return hipSuccess;                                                                                                          \
+    }
+    IMP_RIGHT_LIST(X)
+#undef X
+    return hipErrorInvalidValue;
+}
+
+template <typename R, bool CX>
+static hipError_t imp_sweep(const ImputeRoute& rt, const ImpModel& v, const ImpArgs& g, const ImputeChunk& ch) {
+    // the environment pass ran once per instance; the sweep runs once per chain (ntraj adjacent chains per instance)
+    const int64_t nchain = ch.count * g.ntraj;
+#define X(WHEN, OCC, TRIG, DIST)                                                                                                    \
+    if constexpr (WHEN) {                                                                                                           \
+        if (!rt.batched && rt.occ == OCC && rt.trig == TRIG && rt.dist == DIST) {                                                   \
+            hipLaunchKernelGGL((k_imp_left<R, CX, OCC, TRIG, DIST>), dim3((unsigned)nchain), dim3(IMP_T), rt.lds, ch.s, v, g);     \
+            return hipSuccess;                                                                                                      \
+        }                                                                                                                           \
+    }
+    IMP_LEFT_LIST(X)
+#undef X
+#define X(WHEN, EMB, DIST)                                                                                                          \
+    if constexpr (WHEN) {                                                                                                           \
+        if (rt.batched && rt.emb == EMB && rt.dist == DIST) {                                                                       \
+            hipLaunchKernelGGL((k_imp_leftb<R, CX, EMB, DIST>), dim3((unsigned)((nchain + IMB_B - 1) / IMB_B)), dim3(IMB_T), rt.lds, ch.s, \
+                               v, g, (int)nchain);                                                                                  \
+            return hipSuccess;                                                                                                      \
+        }                                                                                                                           \
+    }
+    IMP_LEFTB_LIST(X)
+#undef X
+    return hipErrorInvalidValue;
+}
+
+// both kernels of a chunk
+template <typename R, bool CX>
+static hipError_t imp_run(const ImputeRoute& rt, const ImpModel& v, const ImputeParams& q, const ImputeChunk& ch) {
+    if (hipError_t e = imp_env<R, CX>(rt, v, q, ch); e != hipSuccess) return e;
+    if (ch.mid) (void)hipEventRecord(ch.mid, ch.s);
+    ImpArgs g = q.g;
+    g.ord = q.order + ch.i0;
 #ifdef MPST_LAB
     // lab builds only (make EXTRA=-DMPST_LAB): MPST_IMB_DBG switches parts of k_imp_leftb off for timing - results are then
     // WRONG by construction, so the shipped library never reads the variable
     static const int imb_dbg = [] { const char* e = getenv("MPST_IMB_DBG"); return e ? atoi(e) : 0; }();
     g.dbg = imb_dbg;
 #endif
-    // two workgroups per CU (128 VGPRs each, 70-183 of them spilled) against one (256 VGPRs, no spill): the spilling
-    // build wins where the density loop is latency-bound - real models and complex ones with d <= 5 - because a second
-    // workgroup hides more than the scratch traffic costs (same-box A/B: profiles/r03_impute_occupancy_ab.txt;
-    // MPST_IMP_OCC=1|2 forces either)
-    static const int force_occ = [] { const char* e = getenv("MPST_IMP_OCC"); return e ? atoi(e) : 0; }();
-    // closed-form densities: sixteen instances per workgroup (MPST_IMP_NO_BATCH=1: the one-instance kernel, a test hook)
-    const bool no_batch = getenv("MPST_IMP_NO_BATCH") != nullptr;
-    const bool mean_ok = q.method != IMP_MEAN || (CX ? q.mean_basis == IMP_BASIS_FOURIER
-                                                     : (q.mean_basis == IMP_BASIS_LEGENDRE || q.mean_basis == IMP_BASIS_LEGENDRE_NO_NORM ||
-                                                        q.mean_basis == IMP_BASIS_UNIFORM));
-    // the distribution outputs (mpst_impute_dist with levels or a cdf): the DIST instantiations, on the routes the plain median takes.
-    // A call with a cdf leaves the batched sweep - there a wave's 20 001-point store would hold up the fifteen other chains of its
-    // workgroup (A/B in DESIGN 16; MPST_IMP_DIST_CDF_BATCH=1 keeps it there, the losing variant of that A/B)
-    const bool dist = q.nq > 0 || q.cdf_stride > 0;
-    const bool cdf_batch = getenv("MPST_IMP_DIST_CDF_BATCH") != nullptr;
-    const bool batch_ok = !dist || q.cdf_stride == 0 || cdf_batch;
-    if (q.trig && !no_batch && force_occ == 0 && mean_ok && batch_ok && imb_fits(v.cap, v.d, CX, F32)) {
-        const dim3 grid((unsigned)((nchain + IMB_B - 1) / IMB_B));
-        const size_t lds_b = imb_layout(v.cap, v.d, CX, F32).bytes;
-        if (dist) {
-            if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX, true>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
-            else hipLaunchKernelGGL((k_imp_leftb<R, CX, false, true>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
-            return 1;
-        }
-        if (CX && v.d <= 8) hipLaunchKernelGGL((k_imp_leftb<R, CX, CX>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
-        else hipLaunchKernelGGL((k_imp_leftb<R, CX, false>), grid, dim3(IMB_T), lds_b, s, v, g, (int)nchain);
-        return 1;
-    }
-    if (dist) {
-        // (the occupancy each route runs at by default; MPST_IMP_OCC is a lab switch of the plain kernels)
-        if (q.trig) {
-            const size_t lds_t = left_lds_bytes(v.cap, CX, F32) + (CX ? 0 : (size_t)(2 * v.d - 1) * v.d * v.d * sizeof(double));
-            hipLaunchKernelGGL((k_imp_left<R, CX, 3, true, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
-        } else if ((CX && v.d > 5) || (!CX && v.d > 8)) {
-            hipLaunchKernelGGL((k_imp_left<R, CX, 1, false, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-        } else {
-            hipLaunchKernelGGL((k_imp_left<R, CX, 2, false, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-        }
-        return 0;
-    }
-    if constexpr (!CX) {
-        if (q.trig) {
-            // Legendre states on a uniform grid: the linearisation table rides in LDS behind the panels
-            const size_t lds_t = left_lds_bytes(v.cap, CX, F32) + (size_t)(2 * v.d - 1) * v.d * v.d * sizeof(double);
-            // (three workgroups per CU: d = 4, chi = 32: 15.9 / 14.6 / 13.3 ms at 1 / 2 / 3; d = 12, chi = 40: 27.5 / 27.6 / 26.6)
-            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
-            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
-            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)nchain), dim3(IMP_T), lds_t, s, v, g);
-            return 0;
-        }
-    }
-    if constexpr (CX) {
-        if (q.trig) {
-            // closed-form densities: no density loop, so no reason to keep the whole register file for one workgroup
-            // three workgroups per CU (170 VGPRs): same-box A/B at configs[4] with 16 / 8 loads per output in flight:
-            // OCC 2: 83.5 / 148 ms, OCC 3: 76.2 / 97 ms, OCC 4 (spilling): 121 / 102 ms
-            if (force_occ == 1) hipLaunchKernelGGL((k_imp_left<R, CX, 1, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else if (force_occ == 2) hipLaunchKernelGGL((k_imp_left<R, CX, 2, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else if (force_occ == 4) hipLaunchKernelGGL((k_imp_left<R, CX, 4, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            else hipLaunchKernelGGL((k_imp_left<R, CX, 3, true>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-            return 0;
-        }
-    }
-    // (real models with d > 8 - the reference's imputation examples use Legendre d = 10 ... 12 - likewise: d = 12, chi = 40: 147 ms with
-    // two spilling workgroups per CU, 44 ms with one; 774 ms before the density loop had unrolled forms beyond d = 8)
-    if (force_occ == 1 || (force_occ != 2 && ((CX && v.d > 5) || (!CX && v.d > 8))))
-        hipLaunchKernelGGL((k_imp_left<R, CX, 1>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-    else
-        hipLaunchKernelGGL((k_imp_left<R, CX, 2>), dim3((unsigned)nchain), dim3(IMP_T), left_lds_bytes(v.cap, CX, F32), s, v, g);
-    return 0;
+    return imp_sweep<R, CX>(rt, v, g, ch);
 }
 
 int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid) {
-    if (v.is_complex) return v.compute_f32 ? launch_impute_t<float, true>(v, q, i0, count, s, mid) : launch_impute_t<double, true>(v, q, i0, count, s, mid);
-    return v.compute_f32 ? launch_impute_t<float, false>(v, q, i0, count, s, mid) : launch_impute_t<double, false>(v, q, i0, count, s, mid);
+    const ImputeRoute rt = impute_route(v, q, impute_switches());
+    const ImputeChunk ch{i0, count, s, mid};
+    const hipError_t e = v.is_complex ? (v.compute_f32 ? imp_run<float, true>(rt, v, q, ch) : imp_run<double, true>(rt, v, q, ch))
+                                      : (v.compute_f32 ? imp_run<float, false>(rt, v, q, ch) : imp_run<double, false>(rt, v, q, ch));
+    return e == hipSuccess ? (rt.batched ? 1 : 0) : -1;
 }
-
 }  // namespace mpst

@@ -664,33 +664,47 @@ struct ImpModel {
     int64_t N;
     int32_t T, d, cap, is_complex, compute_f32;
 };
-struct ImputeParams {
-    const uint8_t* missing;     // device [N][T]
-    void* Rbuf;                 // device [chunk][max_missing][cap*cap] elements
-    void* work;                 // device [chunk][4][cap*cap] elements when the bond dimension exceeds the LDS kernel's, else null
-    const double *grid_x, *grid_phi, *u;    // grid_phi: [ngrid][d] doubles or (re, im) pairs
-    double *pbuf, *sbuf, *x_out, *err_out;
+// what the sweep kernels (k_imp_left, k_imp_leftb) take by value; the API layer fills it by name, the launcher sets `ord` for the chunk
+struct ImpArgs {
+    const uint8_t* missing;     // [N][T]
+    const void* Rbuf;           // [chunk][max_missing][cap*cap] elements of the chain type
+    const double* grid_x;       // [ngrid]
+    const double* grid_phi;     // [ngrid][d] doubles (real model) or (re, im) pairs (complex model)
+    const double* u;            // [N][T][ntrial] uniform numbers (quantile / ITS) or null
+    double* pbuf;               // [chunk][ngrid] scratch: p_k
+    double* sbuf;               // [chunk][ngrid] scratch: prefix sums S_k
+    double* x_out;              // [N][T]
+    double* err_out;            // [N][T]
     int max_missing, ngrid, method, get_wmad, rev, ntrial, mean_basis;
     double reject_thr;
-    int trig;                   // the grid states are the Fourier basis on the uniform grid x0 + k dxu: densities in closed form
-    double x0, dxu;
-    const int32_t* order;       // device [N]: the order in which the instances are dealt out to workgroups
-    const double* lin;          // device [2d-1][d][d]: Legendre linearisation table (trig, real models), else null
-    // trajectories per instance (chains): u / x_out / err_out are [N][ntraj][T](..), pbuf / sbuf [chunk * ntraj][ngrid]; the sampling
-    // methods draw from u or, with use_seed, from the counter-based generator keyed by (seed; row id, trajectory, site, trial)
-    int ntraj, use_seed;
+    const int32_t* ord;         // the instances of this chunk (run_impute orders them by where their missing sites begin)
+    double x0, dxu;             // TRIG kernels: the uniform grid x_k = x0 + k dxu
+    const double* lin;          // TRIG, real models: [2d-1][d][d] Legendre linearisation table (scaled by the states' norms), else null
+    int dbg;                    // k_imp_leftb: parts switched off for timing (0 outside -DMPST_LAB builds)
+    // chains: ntraj trajectories per instance, adjacent.  Chain c of the chunk belongs to the instance ord[c / ntraj] (whose
+    // environments sit in slot c / ntraj of Rbuf) and is its trajectory c % ntraj; u, x_out and err_out are [N][ntraj][T](...)
+    int ntraj;
+    int use_seed;               // sampling methods with u == null: uniform numbers from philox_uniform(seed, row id, trajectory, site, trial)
     unsigned long long seed;
-    const int64_t* row_id;      // device [N] or null (the index in the data set)
-    // mpst_impute_dist (median, ntraj = 1): levels [nq], q_out [N][T][nq], cdf_out [chunk][cdf_rows][ncdf] (the block's slots) on the device; nq = 0 and
-    // cdf_stride = 0: the plain kernels
-    const double* levels;
-    double *q_out, *cdf_out;
+    const int64_t* row_id;      // [N] the caller's row ids (the generator's counter) or null: the index in the data set
+    // DIST kernels (mpst_impute_dist, median only, ntraj = 1): the grid values at nq more levels of every missing site's conditional
+    // cdf and the cdf itself at the grid indices 0, cdf_stride, 2 cdf_stride, ... and ngrid - 1 (ncdf of them)
+    const double* levels;       // [nq], inside (0, 1)
+    double* q_out;              // [N][T][nq]
+    double* cdf_out;            // [chunk][cdf_rows][ncdf] by the instance's slot in the chunk; row r: its r-th missing site in ascending order
     int nq, cdf_stride, cdf_rows, ncdf;
+};
+// a whole call as the launcher sees it: the kernels' arguments and what only the host side of the launch reads
+struct ImputeParams {
+    ImpArgs g;                  // (g.ord: launch_impute points it at the chunk)
+    void* work;                 // device [chunk][4][cap*cap] elements when the bond dimension exceeds the LDS kernel's, else null
+    int trig;                   // the grid states are the Fourier / Legendre basis on the uniform grid x0 + k dxu: densities in closed form
+    const int32_t* order;       // device [N]: the order in which the instances are dealt out to workgroups
 };
 int impute_chi_limit(bool cx, bool f32);
 int64_t impute_work_elems(int cap, bool cx, bool f32);     // per-instance scratch elements of the large-chi environment kernel
 // environment pass for the instances order[i0 .. i0 + count), the sweep for their count * ntraj chains
-int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid = nullptr);   // 1: the sweep ran sixteen chains per workgroup (k_imp_leftb)
+int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid = nullptr);   // 1: the sweep ran sixteen chains per workgroup (k_imp_leftb), 0: one each, -1: the route names no built kernel
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin

@@ -344,6 +344,36 @@ class SweepEngine:
         cdf = np.zeros((N, rows, cdf_points(ngrid, s))) if s > 0 else None
         return lv, q, s, rows, cdf
 
+    def _impute(self, entries, head, arrays, a, dist=None):
+        """The call behind ``impute`` and ``impute_model``, which differ only in how the model is supplied: ``entries`` names their
+        (plain, *_traj, *_dist) entry points, ``head`` holds the arguments between the context and the mask; ``arrays`` = (mask (N, T) uint8,
+        grid values, grid states), contiguous; ``a``: their other arguments by name; ``dist``: ``_dist_args``' result where the caller ran it."""
+        m, gx, gp = arrays
+        N, T = m.shape
+        dp = C.POINTER(C.c_double)
+        ptr = lambda v, t=dp: None if v is None else v.ctypes.data_as(t)
+        shape, mid, tail, more = (N, T), (), (), ()
+        if a["levels"] is not None or a["cdf_stride"]:
+            name = entries[2]
+            lv, q, s, rows, cdf = dist or self._dist_args(m, len(gx), a["method"], a["levels"], a["cdf_stride"], a["num_trajectories"])
+            tail, more = (0 if lv is None else len(lv), ptr(lv), ptr(q), s, rows, ptr(cdf)), (q, cdf)
+        elif a["num_trajectories"] is not None:
+            name = entries[1]
+            K, uu, sd, rid = self._traj_args(N, T, a["method"], a["max_trials"], a["u"], a["num_trajectories"], a["seed"], a["row_id"])
+            shape, mid = (N, K, T), (K, ptr(uu), sd, ptr(rid, C.POINTER(C.c_int64)))
+        else:
+            name = entries[0]
+            uu = None if a["u"] is None else np.ascontiguousarray(a["u"], dtype=np.float64)
+            if uu is not None:
+                assert uu.size == N * T * (int(a["max_trials"]) if int(a["method"]) == 4 else 1)
+            mid = (ptr(uu),)
+        o = L.ImputeOpts(int(a["method"]), int(a["order"]), int(bool(a["get_wmad"])), int(a["max_trials"]), int(a["mean_basis"]), 0,
+                         float(a["rejection_threshold"]))
+        x, err, sec = np.zeros(shape), np.zeros(shape), C.c_double()
+        self._chk(getattr(self.lib, name)(self.ctx, *head, ptr(m, C.POINTER(C.c_uint8)), ptr(gx), C.cast(gp.ctypes.data, dp), len(gx),
+                                          C.byref(o), *mid, ptr(x), ptr(err), C.byref(sec), *tail))
+        return (x, err, sec.value) + more
+
     def impute(self, which, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
                rejection_threshold=0.0, mean_basis=1, num_trajectories=None, seed=None, row_id=None, levels=None, cdf_stride=0):
         """mpst_impute: (x, err, seconds); x / err are (N, T) with the imputed value / its uncertainty at every missing
@@ -356,44 +386,13 @@ class SweepEngine:
         sites) or None, cdf (N, cdf_rows, ncdf) that cdf at the grid indices 0, s, 2s, ... and ngrid - 1, row r = the r-th missing
         site of the instance in ascending order, cdf_rows = the largest missing count, or None."""
         m = np.ascontiguousarray(missing, dtype=np.uint8)
-        N, T = m.shape
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=np.complex128 if self.dtype.kind == "c" else np.float64)   # grid states: fp64 (pairs)
-        assert gp.shape == (len(gx), self.d) and N == self.N[which] and T == self.T
-        dp = C.POINTER(C.c_double)
-        o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
-        sec = C.c_double()
-        if levels is not None or cdf_stride:
-            lv, q, s, rows, cdf = self._dist_args(m, len(gx), method, levels, cdf_stride, num_trajectories)
-            x = np.zeros((N, T))
-            err = np.zeros((N, T))
-            self._chk(self.lib.mpst_impute_dist(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                                C.cast(gp.ctypes.data, dp), len(gx), C.byref(o), x.ctypes.data_as(dp),
-                                                err.ctypes.data_as(dp), C.byref(sec), 0 if lv is None else len(lv),
-                                                lv.ctypes.data_as(dp) if lv is not None else None,
-                                                q.ctypes.data_as(dp) if q is not None else None, s, rows,
-                                                cdf.ctypes.data_as(dp) if cdf is not None else None))
-            return x, err, sec.value, q, cdf
-        if num_trajectories is not None:
-            K, uu, sd, rid = self._traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id)
-            x = np.zeros((N, K, T))
-            err = np.zeros((N, K, T))
-            self._chk(self.lib.mpst_impute_traj(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                                C.cast(gp.ctypes.data, dp), len(gx), C.byref(o), K,
-                                                uu.ctypes.data_as(dp) if uu is not None else None, sd,
-                                                rid.ctypes.data_as(C.POINTER(C.c_int64)) if rid is not None else None,
-                                                x.ctypes.data_as(dp), err.ctypes.data_as(dp), C.byref(sec)))
-            return x, err, sec.value
-        uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
-        if uu is not None:
-            assert uu.size == N * T * (int(max_trials) if int(method) == 4 else 1)
-        x = np.zeros((N, T))
-        err = np.zeros((N, T))
-        self._chk(self.lib.mpst_impute(self.ctx, which, m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                       C.cast(gp.ctypes.data, dp), len(gx), C.byref(o),
-                                       uu.ctypes.data_as(dp) if uu is not None else None, x.ctypes.data_as(dp),
-                                       err.ctypes.data_as(dp), C.byref(sec)))
-        return x, err, sec.value
+        assert gp.shape == (len(gx), self.d) and m.shape == (self.N[which], self.T)
+        args = dict(method=method, order=order, get_wmad=get_wmad, max_trials=max_trials, mean_basis=mean_basis,
+                    rejection_threshold=rejection_threshold, u=u, num_trajectories=num_trajectories, seed=seed, row_id=row_id, levels=levels,
+                    cdf_stride=cdf_stride)
+        return self._impute(("mpst_impute", "mpst_impute_traj", "mpst_impute_dist"), (which,), (m, gx, gp), args)
 
     def impute_model(self, W, phi, label_index, missing, grid_x, grid_phi, method=0, get_wmad=True, u=None, order=0, max_trials=1,
                      rejection_threshold=0.0, mean_basis=None, compute="f64", label_site=None, num_trajectories=None, seed=None,
@@ -403,10 +402,9 @@ class SweepEngine:
         ``grid_phi`` is complex too).  ``compute`` "f64" or "f32" (fp32 chain contractions, fp64 densities).
         Returns (x, err, seconds); with ``num_trajectories`` = K (mpst_impute_model_traj) x / err are (N, K, T), see ``impute``;
         with ``levels`` / ``cdf_stride`` (mpst_impute_model_dist) (x, err, seconds, q, cdf), see ``impute``."""
-        dist = None
-        if levels is not None or cdf_stride:
-            mm = np.ascontiguousarray(missing, dtype=np.uint8)
-            dist = self._dist_args(mm, len(grid_x), method, levels, cdf_stride, num_trajectories)
+        m = np.ascontiguousarray(missing, dtype=np.uint8)
+        # (levels / cdf_stride are checked before the model's shapes)
+        dist = self._dist_args(m, len(grid_x), method, levels, cdf_stride, num_trajectories) if levels is not None or cdf_stride else None
         cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
         dt = np.complex128 if cx else np.float64
         T = len(W)
@@ -421,54 +419,23 @@ class SweepEngine:
         ptrs = (C.c_void_p * T)(*[b.ctypes.data for b in bufs])
         ph = np.ascontiguousarray(phi, dtype=dt)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
-        m = np.ascontiguousarray(missing, dtype=np.uint8)
         N = ph.shape[0]
         assert ph.shape == (N, T, d) and m.shape == (N, T) and lab.shape == (N,)
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=dt)
         assert gp.shape == (len(gx), d)
-        traj = None
-        if num_trajectories is not None:
-            traj = self._traj_args(N, T, method, max_trials, u, num_trajectories, seed, row_id)
-        uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
-        if uu is not None and traj is None:
-            assert uu.size == N * T * (int(max_trials) if int(method) == 4 else 1)
+        if u is not None and num_trajectories is None:         # (also where levels / cdf_stride leave u unused)
+            assert np.size(u) == N * T * (int(max_trials) if int(method) == 4 else 1)
         if mean_basis is None:
             mean_basis = 2 if cx else 1
         model = L.ImputeModel(N, T, d, Cn, int(label_site), 1 if cx else 0, {"f64": 0, "f32": 1}[compute],
                               C.cast(ptrs, C.POINTER(C.c_void_p)), chi.ctypes.data_as(C.POINTER(C.c_int32)),
                               ph.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.POINTER(C.c_int32)))
-        o = L.ImputeOpts(int(method), int(order), int(bool(get_wmad)), int(max_trials), int(mean_basis), 0, float(rejection_threshold))
-        sec = C.c_double()
-        dp = C.POINTER(C.c_double)
-        if dist is not None:
-            lv, q, s, rows, cdf = dist
-            x = np.zeros((N, T))
-            err = np.zeros((N, T))
-            self._chk(self.lib.mpst_impute_model_dist(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                                      gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o), x.ctypes.data_as(dp),
-                                                      err.ctypes.data_as(dp), C.byref(sec), 0 if lv is None else len(lv),
-                                                      lv.ctypes.data_as(dp) if lv is not None else None,
-                                                      q.ctypes.data_as(dp) if q is not None else None, s, rows,
-                                                      cdf.ctypes.data_as(dp) if cdf is not None else None))
-            return x, err, sec.value, q, cdf
-        if traj is not None:
-            K, uu, sd, rid = traj
-            x = np.zeros((N, K, T))
-            err = np.zeros((N, K, T))
-            self._chk(self.lib.mpst_impute_model_traj(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                                      gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o), K,
-                                                      uu.ctypes.data_as(dp) if uu is not None else None, sd,
-                                                      rid.ctypes.data_as(C.POINTER(C.c_int64)) if rid is not None else None,
-                                                      x.ctypes.data_as(dp), err.ctypes.data_as(dp), C.byref(sec)))
-            return x, err, sec.value
-        x = np.zeros((N, T))
-        err = np.zeros((N, T))
-        self._chk(self.lib.mpst_impute_model_run(self.ctx, C.byref(model), m.ctypes.data_as(C.POINTER(C.c_uint8)), gx.ctypes.data_as(dp),
-                                                 gp.ctypes.data_as(C.c_void_p), len(gx), C.byref(o),
-                                                 uu.ctypes.data_as(dp) if uu is not None else None, x.ctypes.data_as(dp),
-                                                 err.ctypes.data_as(dp), C.byref(sec)))
-        return x, err, sec.value
+        args = dict(method=method, order=order, get_wmad=get_wmad, max_trials=max_trials, mean_basis=mean_basis,
+                    rejection_threshold=rejection_threshold, u=u, num_trajectories=num_trajectories, seed=seed, row_id=row_id, levels=levels,
+                    cdf_stride=cdf_stride)
+        return self._impute(("mpst_impute_model_run", "mpst_impute_model_traj", "mpst_impute_model_dist"), (C.byref(model),), (m, gx, gp),
+                            args, dist)
 
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call."""

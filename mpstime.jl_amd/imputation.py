@@ -103,16 +103,16 @@ def init_imputation_problem(W, X_test, y_test=None, dx: float = 1e-4, guess_rang
                              {c: i for i, c in enumerate(classes.tolist())})
 
 
-def _scaled_instances(imp: ImputationProblem, rows, masks):
+def _scaled_instances(imp: ImputationProblem, rows, masks, fill=None):
     """get_predictions' pre-processing (imputation.jl:283-297) for several instances at once: the missing region is
-    overwritten with the training mean BEFORE the test transform (its per-series out-of-bounds rescale sees the masked
-    series), the full series is transformed separately as the target in the encoding's domain."""
+    overwritten with ``fill`` (default: the training mean) BEFORE the test transform (its per-series out-of-bounds rescale sees
+    the masked series), the full series is transformed separately as the target in the encoding's domain."""
     enc = model_encoding(imp.opts.encoding)
     _, norms = transform_train_data(imp.X_train, imp.opts, enc.range)
     raw = imp.X_test[rows]
     full, _ = transform_test_data(raw, norms, imp.opts, enc.range)
     masked = raw.copy()
-    masked[masks] = np.mean(imp.X_train)
+    masked[masks] = np.mean(imp.X_train) if fill is None else fill
     scaled, oob = transform_test_data(masked, norms, imp.opts, enc.range)
     return enc, norms, raw, full, scaled, oob
 
@@ -135,6 +135,28 @@ def _draw_uniforms(rng, N, T, trials, K=None):
     (i, k) reads u[i, k] exactly as a single-trajectory call reads u[i]."""
     shape = (N, T, trials) if K is None else (N, K, T, trials)
     return np.ascontiguousarray((rng or np.random.default_rng()).uniform(0.0, 1.0, shape))
+
+
+def _run_engine(imp: ImputationProblem, data, kw, *, engine, device, compute):
+    """The engine on ``data`` = (phi, class indices, mask): a real fp64 model through a context and its data set, everything else
+    (complex states, fp32 compute) in one call that hands the model over.  ``kw``: the arguments of ``SweepEngine.impute``
+    behind the grid; returns what that returns."""
+    phi, lab, m8 = data
+    xr = imp.x_guess_range
+    cx = np.iscomplexobj(phi) or np.iscomplexobj(xr.xvals_enc) or any(np.iscomplexobj(t) for t in imp.mps)
+    phi = np.ascontiguousarray(phi, dtype=np.complex128 if cx else np.float64)
+    own = engine is None
+    eng = engine or SweepEngine(device)
+    try:
+        if cx or compute != "f64":
+            return eng.impute_model(imp.mps, phi, lab, m8, xr.xvals, xr.xvals_enc, compute=compute, **kw)
+        eng.set_options(**engine_options(imp.opts))
+        eng.set_dataset(1, phi, lab, int(imp.mps[-1].shape[3]))
+        eng.set_mps(imp.mps)
+        return eng.impute(1, m8, xr.xvals, xr.xvals_enc, **kw)
+    finally:
+        if own:
+            eng.close()
 
 
 def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median", rows=None, invert_transform: bool = True,
@@ -189,8 +211,6 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     lab = np.array([imp.class_map[c] for c in np.asarray(imp.y_test)[rows].tolist()], dtype=np.int32)
     order = np.argsort(lab, kind="stable")                      # the engine wants class-sorted data sets
     phi = enc.encode(scaled[order], imp.opts.d)
-    cx = np.iscomplexobj(phi) or np.iscomplexobj(imp.x_guess_range.xvals_enc) or any(np.iscomplexobj(t) for t in imp.mps)
-    phi = np.ascontiguousarray(phi, dtype=np.complex128 if cx else np.float64)
     m8 = np.ascontiguousarray(mask[order], dtype=np.uint8)
     N, T = m8.shape
     u = None
@@ -206,31 +226,13 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
             raise NotImplementedError("method 'mean' re-encodes the expectation value on the device: closed-form bases only "
                                       f"({', '.join(codes)}), not {enc.name}")
         basis = codes[enc.name]
-    own = engine is None
-    eng = engine or SweepEngine(device)
-    try:
-        kw = dict(order=ORDERS[impute_order], max_trials=trials, rejection_threshold=thr, mean_basis=basis)
-        if K is not None:
-            kw.update(num_trajectories=K, seed=rseed, row_id=np.asarray(rows, dtype=np.int64)[order])
-        if levels is not None:
-            kw.update(levels=levels)
-        qv = None
-        if cx or compute != "f64":
-            out = eng.impute_model(imp.mps, phi, lab[order], m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code,
-                                   get_wmad, u, compute=compute, **kw)
-            x, err, secs = out[:3]
-        else:
-            Cn = int(imp.mps[-1].shape[3])
-            eng.set_options(**engine_options(imp.opts))
-            eng.set_dataset(1, phi, lab[order], Cn)
-            eng.set_mps(imp.mps)
-            out = eng.impute(1, m8, imp.x_guess_range.xvals, imp.x_guess_range.xvals_enc, code, get_wmad, u, **kw)
-            x, err, secs = out[:3]
-        if levels is not None:
-            qv = out[3]
-    finally:
-        if own:
-            eng.close()
+    kw = dict(method=code, get_wmad=get_wmad, u=u, order=ORDERS[impute_order], max_trials=trials, rejection_threshold=thr, mean_basis=basis,
+              levels=levels)
+    if K is not None:
+        kw.update(num_trajectories=K, seed=rseed, row_id=np.asarray(rows, dtype=np.int64)[order])
+    out = _run_engine(imp, (phi, lab[order], m8), kw, engine=engine, device=device, compute=compute)
+    x, err, secs = out[:3]
+    qv = out[3] if levels is not None else None
     inv = np.empty_like(order)
     inv[order] = np.arange(len(order))
     x, err = x[inv], err[inv]
@@ -331,33 +333,11 @@ def get_cdfs(imp: ImputationProblem, class_, instance: int, missing_sites, metho
     T = imp.X_test.shape[1]
     mask = np.zeros((1, T), dtype=bool)
     mask[0, missing_sites] = True
-    enc = model_encoding(imp.opts.encoding)
-    _, norms = transform_train_data(imp.X_train, imp.opts, enc.range)
-    raw = imp.X_test[[row]]
-    full, _ = transform_test_data(raw, norms, imp.opts, enc.range)
-    masked = raw.copy()
-    masked[mask] = np.mean(imp.X_test)
-    scaled, _ = transform_test_data(masked, norms, imp.opts, enc.range)
+    enc, _, _, full, scaled, _ = _scaled_instances(imp, [row], mask, fill=np.mean(imp.X_test))
     lab = np.array([imp.class_map[class_]], dtype=np.int32)
-    phi = enc.encode(scaled, imp.opts.d)
-    xr = imp.x_guess_range
-    cx = np.iscomplexobj(phi) or np.iscomplexobj(xr.xvals_enc) or any(np.iscomplexobj(t) for t in imp.mps)
-    phi = np.ascontiguousarray(phi, dtype=np.complex128 if cx else np.float64)
-    m8 = np.ascontiguousarray(mask, dtype=np.uint8)
-    own = engine is None
-    eng = engine or SweepEngine(device)
-    try:
-        if cx:
-            x, err, _, _, cdf = eng.impute_model(imp.mps, phi, lab, m8, xr.xvals, xr.xvals_enc, 0, get_wmad, order=ORDERS[impute_order],
-                                                 cdf_stride=int(stride))
-        else:
-            eng.set_options(**engine_options(imp.opts))
-            eng.set_dataset(1, phi, lab, int(imp.mps[-1].shape[3]))
-            eng.set_mps(imp.mps)
-            x, err, _, _, cdf = eng.impute(1, m8, xr.xvals, xr.xvals_enc, 0, get_wmad, order=ORDERS[impute_order], cdf_stride=int(stride))
-    finally:
-        if own:
-            eng.close()
+    data = (enc.encode(scaled, imp.opts.d), lab, np.ascontiguousarray(mask, dtype=np.uint8))
+    kw = dict(method=0, get_wmad=get_wmad, order=ORDERS[impute_order], cdf_stride=int(stride))
+    x, err, _, _, cdf = _run_engine(imp, data, kw, engine=engine, device=device, compute="f64")
     nmiss = int(mask.sum())
     cdfs = [cdf[0, r].copy() for r in range(nmiss)]
     ts = np.where(mask[0], x[0], scaled[0])

@@ -31,8 +31,10 @@ def _problem(N, T, d, chi, C, seed, ngrid, cx):
     return W, xs, enc, enc(xs), X, y, enc(X), m, rng
 
 
-def _check(W, xs, grid_phi, phi, y, m, x_g, e_g, method, order="forwards", wmad=True, u=None, max_flips=2, **kw):
-    classes = I.expand_label_index(W)
+def _check(W, xs, grid_phi, phi, y, m, x_g, e_g, method, order="forwards", wmad=True, u=None, max_flips=2, ref=None, classes=None, **kw):
+    """``ref``: a dict that keeps the oracle's result per instance, for several runs on the same inputs; ``classes``: the MPS of
+    every class where the caller has them already."""
+    classes = classes or I.expand_label_index(W)
     dx = xs[1] - xs[0]
     nflip = 0
     for i in range(len(y)):
@@ -41,7 +43,11 @@ def _check(W, xs, grid_phi, phi, y, m, x_g, e_g, method, order="forwards", wmad=
         if len(sites) == 0:
             continue
         ui = None if u is None else (u[i, sites] if order == "forwards" else u[i, sites][::-1])
-        xo, eo = I.impute(classes[y[i]], phi[i], sites, xs, grid_phi, method, order, wmad, ui, **kw)
+        if ref is None or i not in ref:
+            out = I.impute(classes[y[i]], phi[i], sites, xs, grid_phi, method, order, wmad, ui, **kw)
+            if ref is not None:
+                ref[i] = out
+        xo, eo = out if ref is None else ref[i]
         diff = np.abs(x_g[i, sites] - xo)
         if order == "backwards":
             diff = diff[::-1]
@@ -487,3 +493,99 @@ def test_batched_sweep_equals_the_one_instance_kernel(engine_cls, compute, cx, d
         good = [i for i in range(N) if i not in bad]
         if ea is not None and k in (0, 4) and f64:
             assert np.abs(ea[good] - eb[good]).max() <= dx * 1.0000001
+
+
+def _full_bond_mps(T, d, chi, C, rng, cx):
+    """Random site tensors of unit Frobenius norm with bond dimension chi at every inner bond (no cap by d^j: the launch only sees the
+    shapes), the label index on the last site."""
+    dims = [1] + [chi] * (T - 1) + [1]
+    W = []
+    for j in range(T):
+        shape = (dims[j], d, dims[j + 1]) + ((C,) if j == T - 1 else ())
+        t = rng.standard_normal(shape) + (1j * rng.standard_normal(shape) if cx else 0.0)
+        W.append(t / np.linalg.norm(t))
+    return W
+
+
+# (cx, d, chi, first grid value, grid step): ngrid = 33 values each
+_LDS_SHAPES = {"legendre_d16_chi8": (False, 16, 8, -0.0016, 1e-4), "fourier_d2_chi128": (True, 2, 128, -1.0, 2.0 / 32),
+               "fourier_d2_chi32": (True, 2, 32, -1.0, 2.0 / 32)}
+
+
+@pytest.mark.parametrize("shape", list(_LDS_SHAPES))
+def test_launches_that_ask_for_more_than_64_kb_of_lds(engine_cls, shape, monkeypatch):
+    """The dynamic-LDS limit of a kernel only matters when a launch asks for more than the 64 KB (65 536 B) default: the smallest shapes
+    that do, from right_lds_bytes / left_lds_bytes / imb_layout in csrc (fp64; 17 instances = a full sixteen-chain workgroup and a
+    ragged one, T = 4, two missing sites each, 33 grid values).
+      legendre_d16_chi8 (real): k_imp_left<.., OCC 3, TRIG> takes (2 chi + 2 16 chi + 16) 8 = 2 304 B of panels + the linearisation
+        table (2d - 1) d^2 8 = 63 488 B = 65 792 B, with and without the distribution outputs.  The batched layout would need
+        209 168 B, more than the 162 816 B a workgroup can have, so d = 16 never takes the batched sweep and MPST_IMP_NO_BATCH changes
+        nothing here.  The closed form needs h^5 (2d - 2)^10 / 1e8 < 1e-12, i.e. h < 1.7e-4 at d = 16: the 33 values are 1e-4 apart
+        around 0.  (The table route of this shape asks for 2 304 B only and is left out.)
+      fourier_d2_chi128 (complex): k_imp_leftb<EMB> 147 984 B (median, levels); the one-chain kernels (2 chi + 2 16 chi + 16) 16 =
+        69 888 B: k_imp_left<.., OCC 3, TRIG> (a cdf leaves the batched sweep, MPST_IMP_NO_BATCH) and, with MPST_IMP_NO_TRIG (the table
+        of grid states, read per call), k_imp_left<.., OCC 2> plain and with the distribution outputs.  chi = 128 > 48: the
+        environment pass is the global-scratch kernel (no dynamic LDS).
+      fourier_d2_chi32 (complex): the environment pass in LDS, k_imp_right<.., 256> 2 4 32 (32 + 2) 8 = 69 632 B (its sweeps ask for
+        less than 64 KB).
+    Not reached by these shapes: the fp32 instantiations, k_imp_left<.., OCC 1> without the closed form (complex d > 5, real d > 8),
+    k_imp_leftb without EMB above 64 KB, k_imp_right with 512 / 1024 threads.
+    Every run against oracle/impute_numpy.py to the tolerance of the fp64 tests above (_check: 1e-12, or one grid step at an instance's
+    first differing site; the oracle is evaluated once per instance and shared by the runs; the class MPS are not normalised, the
+    conditional densities do not depend on their scale); levels and cdf rows of the first six instances (every pair of missing sites)
+    against tests/impute_dist_ref.py (one grid step, 1e-9)."""
+    from mpstime_jl_amd.engine import cdf_indices
+    from tests import impute_dist_ref as D
+    cx, d, chi, x0, h = _LDS_SHAPES[shape]
+    N, T, C, ngrid, levels, stride = 17, 4, 2, 33, (0.25, 0.75), 4
+    rng = np.random.default_rng(64 * 1024 + chi)
+    W = _full_bond_mps(T, d, chi, C, rng, cx)
+    enc = (lambda x: R.fourier_encode(x, d)) if cx else (lambda x: R.legendre_encode(x, d))
+    xs = x0 + h * np.arange(ngrid)
+    grid_phi, phi = enc(xs), enc(rng.uniform(-0.95, 0.95, (N, T)))
+    y = rng.integers(0, C, N).astype(np.int32)
+    pairs = [(a, b) for a in range(T) for b in range(a + 1, T)]
+    m = np.zeros((N, T), dtype=np.uint8)
+    for i in range(N):
+        m[i, list(pairs[i % len(pairs)])] = 1
+    batched = cx                                                # (the batched layout of the real shape does not fit, see above)
+    runs = []
+    eng = engine_cls(0)
+    try:
+        def run(want_trig, want_batched, **kw):
+            out = eng.impute_model(W, phi, y, m, xs, grid_phi, 0, True, **kw)
+            info = eng.impute_info()
+            assert info["closed_form_densities"] == want_trig and info["batched_sweep"] == want_batched, (kw, info)
+            runs.append(out)
+        run(True, batched)
+        run(True, batched, levels=levels)
+        run(True, False, cdf_stride=stride)
+        monkeypatch.setenv("MPST_IMP_NO_BATCH", "1")
+        run(True, False)
+        monkeypatch.delenv("MPST_IMP_NO_BATCH")
+        if cx:
+            monkeypatch.setenv("MPST_IMP_NO_TRIG", "1")
+            run(False, False)
+            run(False, False, levels=levels)
+            run(False, False, cdf_stride=stride)
+    finally:
+        eng.close()
+    classes = [W[:-1] + [W[-1][..., c]] for c in range(C)]
+    ref, dref = {}, {}                                          # the oracle once per instance, shared by the runs
+    for x, err, _, *dist in runs:
+        _check(W, xs, grid_phi, phi, y, m, x, err, "median", ref=ref, classes=classes)
+        if not dist:
+            continue
+        q, cdf = dist
+        for i in range(len(pairs)):                             # every pair of missing sites once
+            sites = np.flatnonzero(m[i])
+            if i not in dref:
+                dref[i] = D.impute_med_and_cdfs(classes[y[i]], phi[i], sites, xs, grid_phi, "forwards", levels)
+            med, _, cdfs, lidx, _ = dref[i]
+            if np.abs(x[i, sites] - med).max() > 1e-12:
+                continue                                        # (a one-step flip, counted by _check: later sites are conditioned on it)
+            if q is not None:
+                assert np.abs(q[i, sites] - xs[lidx]).max() <= h * 1.0000001
+            if cdf is not None:
+                assert cdf.shape == (N, 2, len(cdf_indices(ngrid, stride)))
+                assert np.abs(cdf[i] - cdfs[:, cdf_indices(ngrid, stride)]).max() < 1e-9
