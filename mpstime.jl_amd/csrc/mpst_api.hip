@@ -379,94 +379,55 @@ int ensure_eval(Ctx* c) {
     return 0;
 }
 
-// the element-typed context's workspace (mpst_typed.hip): (E) buffers in the element type, everything that decides the
-// truncation in fp64
-int ensure_workspace_typed(Ctx* c) {
+// ---- the training workspace: one builder, parameterised by the element type (c->zw, c->esz) ---------------------------------
+// The eigensolvers of bonds whose (embedded) Gram matrix of dimension n exceeds the LDS-resident solver.  Whatever the previous
+// workspace held goes first: the solvers and the snapshot of the optimistic sweep were sized for the previous MPS.
+int setup_big_eig(Ctx* c, int n, int ss_rows, int ss_cx) {
+    int rc;
+    if (c->big) { big_eig_destroy(c->big); c->big = nullptr; }
+    if (c->blk) { blocked_eig_destroy(c->blk); c->blk = nullptr; }
+    dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);
+    c->big_opt = false;
+    if (n <= MAX_DIM) return 0;
+    std::string e;
+    if ((rc = big_eig_create(&c->big, n, c->stream, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
+    const char* sel = getenv("MPST_BIG_EIG");
+    if (!(sel && (strcmp(sel, "jacobi") == 0 || strcmp(sel, "rocsolver") == 0)) && (rc = blocked_eig_create(&c->blk, n, &e)))
+        return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
+    // the randomised subspace solver in front of the exact one (complex Gram matrices arrive as embeddings)
+    if (c->blk && (rc = blocked_eig_enable_subspace(c->blk, ss_rows, c->cap, c->C, ss_cx, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
+    // MPST_BIG_SYNC=1: read the eigensolver's verdict after every bond (one host synchronisation per bond) instead of once per sweep
+    c->big_opt = c->blk && getenv("MPST_BIG_SYNC") == nullptr && getenv("MPST_BT_NO_COOP") == nullptr;
+    if (const char* ff = getenv("MPST_BIG_FORCE_FAIL")) c->big_force_fail = atoi(ff);       // test hook: the n-th solve of the context is marked failed
+    return 0;
+}
+
+// What only the element-typed context's workspace holds (mpst_typed.hip): its limits, the binary exponents of the environments,
+// the shares of its gradient and norm kernels.  Everything that decides the truncation stays in fp64.
+int workspace_typed(Ctx* c, int64_t Lmax) {
     const DataSet& tr = c->ds[MPST_TRAIN];
     const int dm = c->d * c->cap, zw = c->zw;
-    const int64_t Lmax = (int64_t)dm * dm;
     int rc;
     if (zw * dm > DIM_LIMIT || zw * c->cap > CAP_LIMIT)
         return fail(c, MPST_ERR_UNSUPPORTED, "complex element type: 2*d*chi_max = %d (2*chi_max = %d) exceeds the eigensolver's limits %d, %d", zw * dm, zw * c->cap, DIM_LIMIT, CAP_LIMIT);
     if (c->d > 32) return fail(c, MPST_ERR_UNSUPPORTED, "the element-typed sweep holds d <= 32");
     TView tv = make_tview(c, MPST_TRAIN);
     if (typed_max_lds(tv) > 144 * 1024) return fail(c, MPST_ERR_UNSUPPORTED, "chi_max = %d, d = %d exceed the LDS staging of the element-typed kernels for this element type", c->cap, c->d);
-    c->fused = false;
-    c->b2 = false;
-    if ((rc = dalloc_e(c, &c->LE, c->cache_elems))) return rc;
-    if ((rc = dalloc_e(c, &c->RE, c->cache_elems))) return rc;
+    c->fused = c->b2 = c->chain4_ok = false;
     if ((rc = dalloc(c, &c->xLE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, &c->xRE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, &c->yexp, tr.N))) return rc;
-    if ((rc = dalloc_e(c, &c->bt, c->C * Lmax))) return rc;
-    if ((rc = dalloc(c, &c->yhat, (int64_t)2 * c->C * tr.N))) return rc;
-    if ((rc = dalloc(c, &c->tile_loss, std::max<int64_t>((int64_t)c->C * tr.ntiles, 1)))) return rc;
     c->partial_elems = (int64_t)c->C * typed_grad_nsplit(tv, tr.nchunks) * Lmax;
-    if ((rc = dalloc_e(c, &c->partial, c->partial_elems))) return rc;
     c->n_norm_part = typed_norm_parts(tv);
-    if ((rc = dalloc(c, &c->norm_part, c->n_norm_part))) return rc;
-    if ((rc = dalloc(c, &c->loss_trace, (int64_t)2 * (c->T - 1) * (c->opt.update_iters + 1)))) return rc;
-    HIPC(c, hipMemset(c->loss_trace, 0, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double)));
-    if ((rc = dalloc(c, &c->gradbuf, 2 + c->C * Lmax * zw))) return rc;
-    HIPC(c, hipMemset(c->gradbuf, 0, (size_t)(2 + c->C * Lmax * zw) * sizeof(double)));
-    const int ne = std::max(zw * dm, MAX_DIM);
-    if ((rc = dalloc(c, &c->gram, (int64_t)ne * ne))) return rc;
-    if ((rc = dalloc(c, &c->lam, ne + 2))) return rc;
-    if ((rc = dalloc(c, &c->E, (int64_t)ne * zw * c->cap))) return rc;
     if ((rc = dalloc(c, &c->tnorm_scratch, (int64_t)6 * c->cap * c->cap))) return rc;
-    if (c->big) { big_eig_destroy(c->big); c->big = nullptr; }
-    if (c->blk) { blocked_eig_destroy(c->blk); c->blk = nullptr; }
-    dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);
-    c->big_opt = false;
-    if (zw * dm > MAX_DIM) {
-        std::string e;
-        if ((rc = big_eig_create(&c->big, zw * dm, c->stream, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        const char* sel = getenv("MPST_BIG_EIG");
-        if (!(sel && (strcmp(sel, "jacobi") == 0 || strcmp(sel, "rocsolver") == 0)) && (rc = blocked_eig_create(&c->blk, zw * dm, &e)))
-            return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        // real element types: the randomised subspace solver in front of the exact one (complex Gram matrices arrive as embeddings)
-        if (c->blk && (rc = blocked_eig_enable_subspace(c->blk, zw * c->C * dm, c->cap, c->C, zw == 2, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        c->big_opt = c->blk && getenv("MPST_BIG_SYNC") == nullptr && getenv("MPST_BT_NO_COOP") == nullptr;
-        if (const char* ff = getenv("MPST_BIG_FORCE_FAIL")) c->big_force_fail = atoi(ff);
-    }
-    if ((rc = dalloc(c, &c->eig_ws, (int64_t)eig_workspace_doubles()))) return rc;
-    HIPC(c, hipMemset(c->eig_ws, 0, eig_workspace_doubles() * sizeof(double)));
-    if ((rc = dalloc(c, &c->sc, 1))) return rc;
-    HIPC(c, hipMemset(c->sc, 0, sizeof(DevScalars)));
-    if ((rc = dalloc(c, &c->norm2, 1))) return rc;
-    hipError_t ea = init_kernel_attrs(c->device);
-    if (ea == hipSuccess) ea = eig_init_attrs(c->device);
-    if (ea == hipSuccess) ea = typed_init_attrs(c->device);
-    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
-    c->ws_ready = true;
-    c->eval_ready = false;
-    c->epoch++;
-    return ensure_eval(c);
+    return 0;
 }
 
-// (re)allocate everything whose size depends on (training set, options, capacity)
-int ensure_workspace(Ctx* c) {
-    if (!c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options must be called first");
-    if (!c->have_mps) return fail(c, MPST_ERR_INVALID, "mpst_set_mps must be called first");
-    if (c->ws_ready) return ensure_eval(c);
+// What only the Float64 context's workspace holds: which launch chain its bonds run (fused, sliced pair, four launches) and the
+// buffers of that chain.
+int workspace_f64(Ctx* c, int64_t Lmax) {
     const DataSet& tr = c->ds[MPST_TRAIN];
-    if (tr.N <= 0) return fail(c, MPST_ERR_INVALID, "no training data set (mpst_set_dataset)");
     const int dm = c->d * c->cap;
-    if (dm > DIM_LIMIT || c->cap > CAP_LIMIT)
-        return fail(c, MPST_ERR_UNSUPPORTED, "d*chi_max = %d (chi_max = %d) exceeds the engine's limits d*chi_max <= %d, chi_max <= %d", dm, c->cap, DIM_LIMIT, CAP_LIMIT);
-    if (c->C > MAX_C) return fail(c, MPST_ERR_UNSUPPORTED, "more than %d classes unsupported", MAX_C);
-    const int64_t Lmax = (int64_t)dm * dm;
     int rc;
-    if (c->ipc_local && 2 + c->C * Lmax * c->zw > c->ipc_slot) ipc_release(c);   // inbox slots too small for the new capacity: export again
-    c->caches_valid = false;
-    c->cache_elems = (int64_t)c->T * tr.N * c->cap;
-    if (c->typed) return ensure_workspace_typed(c);
-    if ((rc = dalloc(c, &c->LE, c->cache_elems))) return rc;
-    if ((rc = dalloc(c, &c->RE, c->cache_elems))) return rc;
-    if ((rc = dalloc(c, &c->bt, c->C * Lmax))) return rc;
-    if ((rc = dalloc(c, &c->yhat, (int64_t)c->C * tr.N))) return rc;
-    if ((rc = dalloc(c, &c->tile_loss, std::max<int64_t>((int64_t)c->C * tr.ntiles, std::max(tr.nparts[0], tr.nparts[1])))) ) return rc;
     c->fused = dm <= MAX_DIM && !c->opt.rescale_before && getenv("MPST_NO_FUSED") == nullptr;
-    const int pk = c->opt.loss == MPST_LOSS_MSE ? 1 : 0;
-    (void)pk;
     // Which pair forms the gradient on the fused chain.  The sliced kernels (k_yhat_s + k_grad_s) move tens of KB per workgroup
     // and no partial gradients: 26 us against 31 us per bond at N = 4096, 11.6 MB against 40 MB of HBM traffic.  Their cost per
     // series is higher though (every series is read by 8 slice- and 16 block-workgroups: 2.7 against 1.5 us per 1000 series),
@@ -505,7 +466,6 @@ int ensure_workspace(Ctx* c) {
         const int nbcap = ((dm + GB - 1) / GB) * ((dm + GB - 1) / GB);
         c->partial_elems = (int64_t)c->C * grad_nsplit(tr.nchunks, nbcap, c->C) * Lmax;    // one partial per k_grad workgroup share, independent of N
     }
-    if ((rc = dalloc(c, &c->partial, c->partial_elems))) return rc;
     if ((rc = dalloc(c, &c->btn, c->C * Lmax))) return rc;
     {
         const char* e4 = getenv("MPST_CHAIN4");
@@ -521,31 +481,44 @@ int ensure_workspace(Ctx* c) {
         if (c->chain4_ok) HIPC(c, hipMemset(c->tail_span, 0, 2 * 2048 * sizeof(unsigned long long)));
     }
     c->n_norm_part = (int)((c->C * Lmax + 63) / 64);      // RED_E entries per workgroup of k_fused_reduce
+    if ((rc = dalloc(c, &c->norm_scratch, (int64_t)3 * c->cap * c->cap))) return rc;
+    return 0;
+}
+
+// (re)allocate everything whose size depends on (training set, options, capacity).  (E) buffers hold elements of c->esz bytes;
+// the Gram matrix, its spectrum and the gradient message are fp64 in every element type (zw doubles per complex entry).
+int ensure_workspace(Ctx* c) {
+    if (!c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options must be called first");
+    if (!c->have_mps) return fail(c, MPST_ERR_INVALID, "mpst_set_mps must be called first");
+    if (c->ws_ready) return ensure_eval(c);
+    const DataSet& tr = c->ds[MPST_TRAIN];
+    if (tr.N <= 0) return fail(c, MPST_ERR_INVALID, "no training data set (mpst_set_dataset)");
+    const int dm = c->d * c->cap, zw = c->zw;
+    if (dm > DIM_LIMIT || c->cap > CAP_LIMIT)
+        return fail(c, MPST_ERR_UNSUPPORTED, "d*chi_max = %d (chi_max = %d) exceeds the engine's limits d*chi_max <= %d, chi_max <= %d", dm, c->cap, DIM_LIMIT, CAP_LIMIT);
+    if (c->C > MAX_C) return fail(c, MPST_ERR_UNSUPPORTED, "more than %d classes unsupported", MAX_C);
+    const int64_t Lmax = (int64_t)dm * dm;
+    int rc;
+    if (c->ipc_local && 2 + c->C * Lmax * zw > c->ipc_slot) ipc_release(c);   // inbox slots too small for the new capacity: export again
+    c->caches_valid = false;
+    c->cache_elems = (int64_t)c->T * tr.N * c->cap;
+    if ((rc = c->typed ? workspace_typed(c, Lmax) : workspace_f64(c, Lmax))) return rc;
+    if ((rc = dalloc_e(c, &c->LE, c->cache_elems))) return rc;
+    if ((rc = dalloc_e(c, &c->RE, c->cache_elems))) return rc;
+    if ((rc = dalloc_e(c, &c->bt, c->C * Lmax))) return rc;
+    if ((rc = dalloc(c, &c->yhat, (int64_t)(c->typed ? 2 : 1) * c->C * tr.N))) return rc;      // typed: (re, im) pairs
+    if ((rc = dalloc(c, &c->tile_loss, std::max<int64_t>((int64_t)c->C * tr.ntiles, c->typed ? 1 : std::max(tr.nparts[0], tr.nparts[1]))))) return rc;
+    if ((rc = dalloc_e(c, &c->partial, c->partial_elems))) return rc;
+    if ((rc = dalloc(c, &c->norm_part, c->typed ? c->n_norm_part : std::max(c->n_norm_part, c->b2_norm_parts)))) return rc;
     if ((rc = dalloc(c, &c->loss_trace, (int64_t)2 * (c->T - 1) * (c->opt.update_iters + 1)))) return rc;
     HIPC(c, hipMemset(c->loss_trace, 0, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double)));
-    if ((rc = dalloc(c, &c->norm_part, std::max(c->n_norm_part, c->b2_norm_parts)))) return rc;
-    if ((rc = dalloc(c, &c->gradbuf, 2 + c->C * Lmax))) return rc;
-    HIPC(c, hipMemset(c->gradbuf, 0, (size_t)(2 + c->C * Lmax) * sizeof(double)));
-    const int dmx = std::max(dm, MAX_DIM);
-    if ((rc = dalloc(c, &c->gram, (int64_t)dmx * dmx))) return rc;
-    if ((rc = dalloc(c, &c->lam, dmx + 2))) return rc;
-    if ((rc = dalloc(c, &c->E, (int64_t)dmx * c->cap))) return rc;
-    if ((rc = dalloc(c, &c->norm_scratch, (int64_t)3 * c->cap * c->cap))) return rc;
-    if (c->big) { big_eig_destroy(c->big); c->big = nullptr; }
-    if (c->blk) { blocked_eig_destroy(c->blk); c->blk = nullptr; }
-    dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);       // sized for the previous MPS
-    c->big_opt = false;
-    if (dm > MAX_DIM) {
-        std::string e;
-        if ((rc = big_eig_create(&c->big, dm, c->stream, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        const char* sel = getenv("MPST_BIG_EIG");
-        if (!(sel && (strcmp(sel, "jacobi") == 0 || strcmp(sel, "rocsolver") == 0)) && (rc = blocked_eig_create(&c->blk, dm, &e)))
-            return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        // MPST_BIG_SYNC=1: read the eigensolver's verdict after every bond (one host synchronisation per bond) instead of once per sweep
-        if (c->blk && (rc = blocked_eig_enable_subspace(c->blk, c->C * dm, c->cap, c->C, 0, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
-        c->big_opt = c->blk && getenv("MPST_BIG_SYNC") == nullptr && getenv("MPST_BT_NO_COOP") == nullptr;
-        if (const char* ff = getenv("MPST_BIG_FORCE_FAIL")) c->big_force_fail = atoi(ff);       // test hook: the n-th solve of the context is marked failed
-    }
+    if ((rc = dalloc(c, &c->gradbuf, 2 + c->C * Lmax * zw))) return rc;
+    HIPC(c, hipMemset(c->gradbuf, 0, (size_t)(2 + c->C * Lmax * zw) * sizeof(double)));
+    const int ne = std::max(zw * dm, MAX_DIM);
+    if ((rc = dalloc(c, &c->gram, (int64_t)ne * ne))) return rc;
+    if ((rc = dalloc(c, &c->lam, ne + 2))) return rc;
+    if ((rc = dalloc(c, &c->E, (int64_t)ne * zw * c->cap))) return rc;
+    if ((rc = setup_big_eig(c, zw * dm, zw * c->C * dm, zw == 2))) return rc;
     if ((rc = dalloc(c, &c->eig_ws, (int64_t)eig_workspace_doubles()))) return rc;
     HIPC(c, hipMemset(c->eig_ws, 0, eig_workspace_doubles() * sizeof(double)));
     if ((rc = dalloc(c, &c->sc, 1))) return rc;
@@ -553,7 +526,7 @@ int ensure_workspace(Ctx* c) {
     if ((rc = dalloc(c, &c->norm2, 1))) return rc;
     hipError_t ea = init_kernel_attrs(c->device);
     if (ea == hipSuccess) ea = eig_init_attrs(c->device);
-    if (ea == hipSuccess) ea = b2_init_attrs(c->device);
+    if (ea == hipSuccess) ea = c->typed ? typed_init_attrs(c->device) : b2_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
     c->ws_ready = true;
     c->eval_ready = false;
@@ -738,10 +711,55 @@ void enqueue_caches_typed(Ctx* c, int left_upto, int right_from) {
                     eoff(c, c->RE, (int64_t)j * cs), c->xRE + (int64_t)j * t.N, c->stream);
 }
 
+// ---- bond order of one sweep (RealRealHighDimension.jl:731, :776) -------------------------------------------------------
+// Slot k of a sweep over nb = T - 1 bonds: nb - 1 .. 0 going left, then 0 .. nb - 1 going right.  next_lid: the bond of slot
+// k + 1, whose tensor this bond's last launch may assemble (-1: none, or the caller took it away - `unchained`: the tensor is
+// rescaled first, or the caches are rebuilt in between); chains_into_next: that bond is the neighbour in the direction of travel
+// (everywhere but at the turning point, where the same bond comes again) - the fused chains hand a tensor on only then.
+struct BondSlot {
+    int lid, going_left, next_lid;
+    bool chains_into_next;
+    BondSlot unchained() const { return {lid, going_left, -1, false}; }
+};
+BondSlot bond_slot(int k, int nb) {
+    auto at = [nb](int q) { return q < nb ? nb - 1 - q : q - nb; };
+    BondSlot b{at(k), k < nb, k + 1 < 2 * nb ? at(k + 1) : -1, false};
+    b.chains_into_next = b.next_lid >= 0 && b.next_lid == (b.going_left ? b.lid - 1 : b.lid + 1);
+    return b;
+}
+// have_bt of the slot after `prev` (the caller's: it knows where it started and what it took away): the tensor is there iff the
+// launches enqueued for `prev`, in this call, were told to assemble it
+inline bool assembles_next(const BondSlot& prev, bool fused) { return fused ? prev.chains_into_next : prev.next_lid >= 0; }
+
+// ---- the chain decisions, each taken and reported (mpst_get_info) through one predicate ------------------------------------
+// The 2(T-1) x 11 launches of a sweep are replayed from a hipGraph: nothing in the sequence depends
+// on host-side state (bond dimensions are read on the device), and the pre-built dispatch packets
+// shorten the dependent kernel-to-kernel hand-over that dominates the small kernels.  Per-kernel
+// profiling and the RCCL leg keep the plain stream path.
+// (large bonds stay on the plain stream: replaying their ~8000 launches from a graph was measured to gain nothing - 725.0
+// against 724.5 ms per sweep at (8192, 200, 64, 8) - and a capture must not overlap other threads' legacy-stream copies)
+bool sweep_uses_graph(const Ctx* c) { return !multi(c) && !c->big && c->prof_mask == 0 && getenv("MPST_NO_GRAPH") == nullptr; }
+// four launches per bond: k_eig_fin, k_env_split and the NEXT bond's k_yhat_s in one (k_bond_tail, mpst_fused.hip)
+bool bond_uses_tail(const Ctx* c, const View& v, bool traced) {
+    return c->chain4_ok && !c->chain4_hold && c->b2 && !multi(c) && c->opt.update_iters == 1 && !traced && eig_merged() && bond_tail_supported(v);
+}
+// the context can join a batch (mpst_sweep_batch): the headline chain, six launches per bond
+bool batchable(const Ctx* c) {
+    return c->fused && c->b2 && !c->typed && !multi(c) && eig_merged() && c->opt.update_iters == 1 && !c->opt.track_cost && !c->opt.rebuild_caches &&
+           c->prof_mask == 0;
+}
+// the four-launch chain held back while a marked sweep / bond is redone on the six-launch chain: views made meanwhile carry no btnT
+struct Chain4Hold {
+    bool& h;
+    explicit Chain4Hold(Ctx* c) : h(c->chain4_hold) { h = true; }
+    ~Chain4Hold() { h = false; }
+};
+
 // ---- the per-bond launch chain (RealRealHighDimension.jl:733-762 / :777-801) ---------------
 // have_bt: the bond tensor of this bond was already assembled by the previous bond's environment
-// kernel; next_bt_lid >= 0: assemble that bond's tensor inside this bond's environment kernel.
-int enqueue_bond(Ctx* c, const View& v_in, int lid, int going_left, bool have_bt = false, int next_bt_lid = -1, int trace_row = -1) {
+// kernel; b.next_lid >= 0: assemble that bond's tensor inside this bond's environment kernel.
+int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = false, int trace_row = -1) {
+    const int lid = b.lid, going_left = b.going_left, next_bt_lid = b.next_lid;
     if (c->typed) return enqueue_bond_typed(c, lid, going_left, trace_row);
     hipStream_t s = c->stream;
     View v = v_in;
@@ -765,9 +783,8 @@ int enqueue_bond(Ctx* c, const View& v_in, int lid, int going_left, bool have_bt
     if (c->fused) {
         const int iters = c->opt.update_iters;
         // the next bond's tensor is assembled by this bond's last launch when the sweep moves on in the same direction
-        const int chain = (next_bt_lid >= 0 && next_bt_lid == (going_left ? lid - 1 : lid + 1)) ? 1 : 0;
-        // four launches per bond: k_eig_fin, k_env_split and the NEXT bond's k_yhat_s in one (k_bond_tail, mpst_fused.hip)
-        const bool use4 = c->chain4_ok && !c->chain4_hold && c->b2 && !multi(c) && iters == 1 && !v.trace && eig_merged() && bond_tail_supported(v);
+        const int chain = b.chains_into_next ? 1 : 0;
+        const bool use4 = bond_uses_tail(c, v, v.trace != nullptr);
         // ... whose overlaps are this bond's if the launch before this one was the neighbouring bond's tail
         const bool y_ready = use4 && c->ynext_lid == lid && c->ynext_epoch == c->epoch && c->ynext_seq == seq_before;
         c->ynext_lid = -1;
@@ -901,6 +918,48 @@ void enqueue_caches(Ctx* c, const View& v, int going_left) {
             launch_env(v, j, 0, j < c->T - 1 ? c->RE + (int64_t)(j + 1) * cs : nullptr, j + 1, ENV_M_SITE_T, j,
                        c->RE + (int64_t)j * cs, c->stream);
     }
+}
+
+// ---- a sweep as a hipGraph, and what it left ----------------------------------------------------------------------------------
+// What `enqueue` puts on the stream, captured (thread-local: other threads' work is none of this capture's) and instantiated into
+// *exec, whose previous graph goes first.  `enqueue` returns 0 or an error it has reported itself; a capture that does not end in a
+// graph is reported with `end_text` and the end of capture's error.
+using DevGraph = DevOwned<hipGraph_t, hipGraph_t, hipGraphDestroy>;
+template <typename F>
+int capture_graph(Ctx* c, hipStream_t s, hipGraphExec_t* exec, const char* end_text, F&& enqueue) {
+    if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
+    HIPC(c, hipStreamSynchronize(s));
+    HIPC(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    DevGraph g;
+    hipError_t e = hipStreamEndCapture(s, &g.h);
+    if (rc) return rc;
+    if (e != hipSuccess || !g) return fail(c, MPST_ERR_DEVICE, end_text, hipGetErrorString(e));
+    HIPC(c, hipGetLastError());     // a launch rejected during capture (bad configuration) surfaces here
+    if ((e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0)) != hipSuccess) {
+        *exec = nullptr;
+        return fail(c, MPST_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// What a sweep left in context c, read where its stream has just been synchronised.  read_scalars: the device scalars (a marked
+// sweep reads them, redoes its rest and reads them again); read_back: with those, the subspace solver's counters and the bond
+// dimensions (st->seconds is the caller's).  Device errors are reported on `rep` (a batch: its lead).
+int read_scalars(Ctx* c, Ctx* rep, DevScalars* sc) {
+    HIPC(rep, hipMemcpy(sc, c->sc, sizeof *sc, hipMemcpyDeviceToHost));
+    return 0;
+}
+int read_back(Ctx* c, Ctx* rep, const DevScalars* sc, mpst_sweep_stats* st) {
+    refresh_ss_counts(c);
+    std::vector<int32_t> chi(c->T + 1);
+    HIPC(rep, hipMemcpy(chi.data(), c->chi, chi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    st->svd_status = sc->status;
+    st->max_chi = *std::max_element(chi.begin(), chi.end());
+    st->eig_sweeps_total = sc->eig_sweeps_total;
+    st->eig_fallbacks = sc->eig_fallbacks;
+    if (sc->status) c->caches_valid = false;        // the state after a failed bond is unspecified: set_mps + build_caches to go on
+    return 0;
 }
 
 int check_ready(Ctx* c) {
@@ -1601,54 +1660,23 @@ int mpst_sweep(void* ctx, mpst_sweep_stats* out) {
         int r0 = enqueue_reset_status(c);
         if (r0) return r0;
         c->ynext_lid = -1;
-        // bond order of one sweep (:731, :776); unless the tensor is rescaled first or the caches are
-        // rebuilt in between, bond k+1's tensor is assembled by bond k's environment kernel
+        // unless the tensor is rescaled first or the caches are rebuilt in between, bond k+1's tensor is assembled by bond k's last launch
         const int nb = c->T - 1;
-        const bool chain = !v.rescale_before;
+        bool have = false;
         int r;
         for (int k = k0; k < 2 * nb; ++k) {
-            const int lid = k < nb ? nb - 1 - k : k - nb, left = k < nb;
-            const bool boundary_before = c->opt.rebuild_caches && (k == nb);
-            const bool boundary_after = c->opt.rebuild_caches && (k == nb - 1);
-            bool have = chain && k > k0 && !boundary_before;
-            if (c->fused && k == nb) have = false;      // turning point: the same bond again, nothing was chained
-            int next = -1;
-            if (chain && k + 1 < 2 * nb && !boundary_after) next = (k + 1) < nb ? nb - 1 - (k + 1) : (k + 1) - nb;
-            if ((r = enqueue_bond(c, v, lid, left, have, next, k))) return r;
-            if (c->opt.rebuild_caches && k == nb - 1) enqueue_caches(c, v, 0);      // :770
+            const bool rebuild_after = c->opt.rebuild_caches && k == nb - 1;
+            const BondSlot b = (v.rescale_before || rebuild_after) ? bond_slot(k, nb).unchained() : bond_slot(k, nb);
+            if ((r = enqueue_bond(c, v, b, have, k))) return r;
+            have = assembles_next(b, c->fused);
+            if (rebuild_after) enqueue_caches(c, v, 0);      // :770
         }
         if (c->opt.rebuild_caches) enqueue_caches(c, v, 1);                         // :804
         return 0;
     };
-    // The 2(T-1) x 11 launches of a sweep are replayed from a hipGraph: nothing in the sequence depends
-    // on host-side state (bond dimensions are read on the device), and the pre-built dispatch packets
-    // shorten the dependent kernel-to-kernel hand-over that dominates the small kernels.  Per-kernel
-    // profiling and the RCCL leg keep the plain stream path.
-    // (large bonds stay on the plain stream: replaying their ~8000 launches from a graph was measured to gain nothing - 725.0
-    // against 724.5 ms per sweep at (8192, 200, 64, 8) - and a capture must not overlap other threads' legacy-stream copies)
-    const bool use_graph = !multi(c) && !c->big && c->prof_mask == 0 && getenv("MPST_NO_GRAPH") == nullptr;
+    const bool use_graph = sweep_uses_graph(c);
     if (use_graph && (!c->sweep_graph || c->graph_epoch != c->epoch)) {
-        if (c->sweep_graph) {
-            (void)hipGraphExecDestroy(c->sweep_graph);
-            c->sweep_graph = nullptr;
-        }
-        HIPC(c, hipStreamSynchronize(c->stream));
-        HIPC(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sweep();
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(c->stream, &g);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc;
-        }
-        if (e != hipSuccess || !g) return fail(c, MPST_ERR_DEVICE, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        HIPC(c, hipGetLastError());     // a launch rejected during capture (bad configuration) surfaces here
-        e = hipGraphInstantiate(&c->sweep_graph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) {
-            c->sweep_graph = nullptr;
-            return fail(c, MPST_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-        }
+        if ((rc = capture_graph(c, c->stream, &c->sweep_graph, "hipStreamEndCapture failed: %s", [&] { return enqueue_sweep(); }))) return rc;
         c->graph_epoch = c->epoch;
     }
     // large bonds: no verdict is read inside the sweep (launch_eig_blocked_nosync); the state the sweep starts from is kept
@@ -1709,16 +1737,15 @@ int mpst_sweep(void* ctx, mpst_sweep_stats* out) {
     HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
     prof_collect(c);
     DevScalars sc;
-    HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
-    int tail_fallbacks = 0;
+    mpst_sweep_stats st{};
+    if ((rc = read_scalars(c, c, &sc))) return rc;
     if (sc.redo > 0 && !c->chain4_hold) {
         // four-launch chain: a tail launch whose verification failed (clustered kept eigenvalues: the case k_eig_fin hands to its Jacobi
         // solver) has marked the sweep and left the MPS, the caches and the chained tensor as the bond before it left them; so did every
         // tail launch after it.  The rest of the sweep runs on the six-launch chain, plain stream.
         c->tail_redos++;
-        tail_fallbacks = sc.eig_fallbacks;
-        c->chain4_hold = true;
-        struct Hold { bool& h; ~Hold() { h = false; } } hold{c->chain4_hold};
+        const int tail_fallbacks = sc.eig_fallbacks;
+        Chain4Hold hold(c);
         v = make_view(c, MPST_TRAIN);
         HIPC(c, hipEventRecord(c->ev_start, c->stream));
         if ((rc = enqueue_sweep(sc.redo - 1))) return rc;
@@ -1729,21 +1756,13 @@ int mpst_sweep(void* ctx, mpst_sweep_stats* out) {
         HIPC(c, hipEventElapsedTime(&ms2, c->ev_start, c->ev_stop));
         ms += ms2;
         prof_collect(c);
-        HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+        if ((rc = read_scalars(c, c, &sc))) return rc;
         sc.eig_fallbacks += tail_fallbacks;
     }
-    refresh_ss_counts(c);
-    std::vector<int32_t> chi(c->T + 1);
-    HIPC(c, hipMemcpy(chi.data(), c->chi, chi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (out) {
-        out->seconds = 1e-3 * ms;
-        out->svd_status = sc.status;
-        out->max_chi = *std::max_element(chi.begin(), chi.end());
-        out->eig_sweeps_total = sc.eig_sweeps_total;
-        out->eig_fallbacks = sc.eig_fallbacks;
-    }
+    if ((rc = read_back(c, c, &sc, &st))) return rc;
+    st.seconds = 1e-3 * ms;
+    if (out) *out = st;
     if (sc.status) {
-        c->caches_valid = false;        // the state after a failed bond is unspecified: set_mps + build_caches to go on
         if (sc.status == MPST_ERR_DEVICE && c->use_ipc) {
             c->use_ipc = false;         // flags / epochs / slots are in an undefined cross-rank state: never reuse them
             c->ipc_dead = true;
@@ -1780,9 +1799,7 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
         }
         if (!c->caches_valid) return fail(c0, MPST_ERR_INVALID, "context %d: call mpst_build_caches first", k);
         if (c->host_label_site != c->T - 1) return fail(c0, MPST_ERR_INVALID, "context %d: a sweep starts with the label index on the last site", k);
-        const bool chain_ok = c->fused && c->b2 && !c->typed && !multi(c) && eig_merged() && c->opt.update_iters == 1 && !c->opt.track_cost &&
-                              !c->opt.rebuild_caches && c->prof_mask == 0;
-        if (!chain_ok)
+        if (!batchable(c))
             return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_sweep_batch runs the headline chain only (Float64, d*chi_max <= 128, <= 8192 series, one rank, "
                                                  "update_iters = 1, no track_cost / rebuild_caches / profiling)", k);
         // the fits may differ in their series (N, class counts, tiles: every kernel reads those from the fit's own View, the grids are sized
@@ -1805,10 +1822,6 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
     View v0 = make_view(c0, MPST_TRAIN);         // the launchers' geometry: the shared shape, and the tiles of the largest fit
     for (int k = 1; k < K; ++k) v0.ntiles = std::max(v0.ntiles, ((Ctx*)ctxs[k])->ds[MPST_TRAIN].ntiles);
     if (!c0->batch_graph || key != c0->batch_key) {
-        if (c0->batch_graph) {
-            (void)hipGraphExecDestroy(c0->batch_graph);
-            c0->batch_graph = nullptr;
-        }
         std::vector<View> hv((size_t)2 * c0->batch_cap);
         for (int k = 0; k < K; ++k) {
             Ctx* c = (Ctx*)ctxs[k];
@@ -1818,44 +1831,35 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
             vg.n_norm_part = c->b2_norm_parts;
             hv[(size_t)c0->batch_cap + k] = vg;
         }
+        c0->batch_key.clear();                  // the views the old graph reads are overwritten from here on
         HIPC(c0, hipMemcpy(c0->batch_views, hv.data(), hv.size() * sizeof(View), hipMemcpyHostToDevice));
         const View* dv = c0->batch_views;
         const View* dvg = c0->batch_views + c0->batch_cap;
         hipStream_t s = c0->stream;
-        HIPC(c0, hipStreamSynchronize(s));
-        HIPC(c0, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int bad = 0;
-        for (int k = 0; k < K && !bad; ++k)
-            if (hipMemsetAsync((char*)((Ctx*)ctxs[k])->sc + offsetof(DevScalars, status), 0, 12, s) != hipSuccess) bad = 1;
-        const int nb = c0->T - 1;
-        for (int q = 0; q < 2 * nb && !bad; ++q) {
-            const int lid = q < nb ? nb - 1 - q : q - nb, left = q < nb, rid = lid + 1;
-            const bool have = q > 0 && q != nb;                        // as mpst_sweep's fused chain: nothing was chained at the turning point
-            const int next = q + 1 < 2 * nb ? ((q + 1) < nb ? nb - 1 - (q + 1) : (q + 1) - nb) : -1;
-            const int chain = (next >= 0 && next == (left ? lid - 1 : lid + 1)) ? 1 : 0;
-            if (!have) launch_bt_assemble_b(v0, dv, K, lid, s);
-            launch_yhat_s_b(v0, dv, K, lid, s);
-            launch_grad_s_b(v0, dv, K, lid, s);
-            launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
-            launch_eig_b(v0, dv, K, lid, left, 0, s);
-            launch_eig_b(v0, dv, K, lid, left, 2, s);
-            // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
-            if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
-            else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
-        }
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (bad || e != hipSuccess || !g) {
-            if (g) (void)hipGraphDestroy(g);
-            return fail(c0, MPST_ERR_DEVICE, "capture of the batched sweep failed: %s", hipGetErrorString(e));
-        }
-        HIPC(c0, hipGetLastError());
-        e = hipGraphInstantiate(&c0->batch_graph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) {
-            c0->batch_graph = nullptr;
-            return fail(c0, MPST_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-        }
+        auto enqueue_batch = [&]() -> int {
+            for (int k = 0; k < K; ++k) {
+                const hipError_t em = hipMemsetAsync((char*)((Ctx*)ctxs[k])->sc + offsetof(DevScalars, status), 0, 12, s);
+                if (em != hipSuccess) return fail(c0, MPST_ERR_DEVICE, "capture of the batched sweep failed: %s", hipGetErrorString(em));
+            }
+            const int nb = c0->T - 1;
+            bool have = false;
+            for (int q = 0; q < 2 * nb; ++q) {
+                const BondSlot b = bond_slot(q, nb);
+                const int lid = b.lid, left = b.going_left, rid = lid + 1, chain = b.chains_into_next ? 1 : 0;
+                if (!have) launch_bt_assemble_b(v0, dv, K, lid, s);
+                have = assembles_next(b, true);
+                launch_yhat_s_b(v0, dv, K, lid, s);
+                launch_grad_s_b(v0, dv, K, lid, s);
+                launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
+                launch_eig_b(v0, dv, K, lid, left, 0, s);
+                launch_eig_b(v0, dv, K, lid, left, 2, s);
+                // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
+                if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
+                else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
+            }
+            return 0;
+        };
+        if ((rc = capture_graph(c0, s, &c0->batch_graph, "capture of the batched sweep failed: %s", enqueue_batch))) return rc;
         c0->batch_key = key;
     }
     if (phase == 1) return 0;
@@ -1868,23 +1872,12 @@ static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out,
     HIPC(c0, hipEventElapsedTime(&ms, c0->ev_start, c0->ev_stop));
     int failed = -1;
     for (int k = 0; k < K; ++k) {
-        Ctx* c = (Ctx*)ctxs[k];
         DevScalars sc;
-        HIPC(c0, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
-        refresh_ss_counts(c);
-        std::vector<int32_t> chi(c->T + 1);
-        HIPC(c0, hipMemcpy(chi.data(), c->chi, chi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (out) {
-            out[k].seconds = 1e-3 * ms;            // of the whole batch: the fits advance together
-            out[k].svd_status = sc.status;
-            out[k].max_chi = *std::max_element(chi.begin(), chi.end());
-            out[k].eig_sweeps_total = sc.eig_sweeps_total;
-            out[k].eig_fallbacks = sc.eig_fallbacks;
-        }
-        if (sc.status) {
-            c->caches_valid = false;
-            if (failed < 0) failed = k;
-        }
+        mpst_sweep_stats st{};
+        if ((rc = read_scalars((Ctx*)ctxs[k], c0, &sc)) || (rc = read_back((Ctx*)ctxs[k], c0, &sc, &st))) return rc;
+        st.seconds = 1e-3 * ms;                    // of the whole batch: the fits advance together
+        if (out) out[k] = st;
+        if (sc.status && failed < 0) failed = k;
     }
     if (failed >= 0) return fail(c0, MPST_ERR_SVD, "bond-tensor decomposition failed in fit %d of the batch (its svd_status is set; the other fits are intact)", failed);
     return 0;
@@ -1989,22 +1982,22 @@ int mpst_bond_step(void* ctx, int32_t lid, int32_t going_left, mpst_bond_debug* 
         return fail(c, MPST_ERR_INVALID, "bond (%d,%d) does not hold the label index (it is on site %d)", lid, lid + 1, c->host_label_site);
     View v = make_view(c, MPST_TRAIN);
     if ((rc = enqueue_reset_status(c))) return rc;
-    if ((rc = enqueue_bond(c, v, lid, going_left ? 1 : 0))) return rc;
+    const BondSlot b{lid, going_left ? 1 : 0, -1, false};
+    if ((rc = enqueue_bond(c, v, b))) return rc;
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));
     DevScalars sc;
-    HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+    if ((rc = read_scalars(c, c, &sc))) return rc;
     if (sc.redo > 0) {
         // the tail launch of the four-launch chain left the bond alone (its verification failed): once more on the six-launch chain
         c->tail_redos++;
-        c->chain4_hold = true;
-        struct Hold { bool& h; ~Hold() { h = false; } } hold{c->chain4_hold};
+        Chain4Hold hold(c);
         View v6 = make_view(c, MPST_TRAIN);
         if ((rc = enqueue_reset_status(c))) return rc;
-        if ((rc = enqueue_bond(c, v6, lid, going_left ? 1 : 0))) return rc;
+        if ((rc = enqueue_bond(c, v6, b))) return rc;
         HIPC(c, hipGetLastError());
         HIPC(c, hipStreamSynchronize(c->stream));
-        HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+        if ((rc = read_scalars(c, c, &sc))) return rc;
     }
     refresh_ss_counts(c);
     c->host_label_site = going_left ? lid : lid + 1;
@@ -2855,7 +2848,7 @@ int mpst_get_info(void* ctx, int32_t* out) {
     out[3] = c->ds[MPST_TRAIN].nchunks;
     out[4] = c->cap;
     out[5] = c->nranks;
-    out[6] = (!multi(c) && !c->big && c->prof_mask == 0 && getenv("MPST_NO_GRAPH") == nullptr) ? 1 : 0;
+    out[6] = sweep_uses_graph(c) ? 1 : 0;
     out[7] = (int32_t)std::min<int64_t>(c->big_fallbacks, 1 << 30);
     out[8] = blocked_eig_coop_aborts(c->blk);      // bonds the persistent tridiagonalisation handed back to the launch-per-step path
     out[9] = blocked_eig_xcd_misplaced(c->blk);    // bonds whose XCD-local attempt found its workgroups on several XCDs (redone across the XCDs)
@@ -2877,7 +2870,7 @@ int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
         Ctx* c4 = (Ctx*)ctx;
         View v4 = make_view(c4, MPST_TRAIN);
         // [18] the bonds of a sweep run the four-launch chain (k_bond_tail); [19] sweeps / bond steps whose tail was redone on the six-launch chain
-        full[18] = (c4->chain4_ok && c4->b2 && !multi(c4) && c4->opt.update_iters == 1 && !c4->opt.track_cost && eig_merged() && bond_tail_supported(v4)) ? 1 : 0;
+        full[18] = bond_uses_tail(c4, v4, c4->opt.track_cost != 0) ? 1 : 0;
         full[19] = c4->tail_redos;
     }
     // bonds the subspace eigensolver attempted / whose result was accepted (the rest went to the exact solver), as of the last sweep,

@@ -206,3 +206,57 @@ def test_three_groups_of_unequal_size_with_a_member_recreated_between_calls():
     finally:
         for e in solo + bat:
             e.close()
+
+
+def test_workspace_rebuilt_on_a_live_context_equals_a_fresh_one():
+    """ensure_workspace tears a training workspace down and builds another on a live context whenever the capacity or the options
+    that size it change.  One engine is taken through (a) capacity 8, d*cap = 64: fused chain, sliced pair, four launches per bond;
+    (b) an MPS of bonds 20, d*cap = 160 > 128: the large-bond solver is created; (c) the first MPS again: the solver is destroyed;
+    (d) rescale = (True, True): the unfused chain.  After every stage one sweep must give the bits - and info() the chain - of a fresh
+    engine that was given only that stage's options and MPS.  Then a -> b -> c in float32 (the element-typed workspace).
+    N = 96, T = 5, d = 8, C = 2, KLD / TSGO: the shape of test_sweep_reads_the_verdict_once_and_redoes_a_failed_sweep."""
+    from tests.helpers import make_problem
+    N, T, d, C, chi = 96, 5, 8, 2, 8
+    ds, W4 = make_problem(N, T, d, 4, C, seed=3)
+    _, W20 = make_problem(N, T, d, 20, C, seed=3)
+    keys = ("fused", "large_bond", "four_launch_chain", "large_bond_verdict_per_sweep", "sliced_bond_gemms")
+    expect = {"a": (True, False, True, False, True), "b": (False, True, False, True, False), "c": (True, False, True, False, True),
+              "d": (False, False, False, False, False)}
+
+    def options(eng, stage):
+        eng.set_options(chi_max=chi, eta=0.05, loss="KLD", bbopt="TSGO", rescale=(stage == "d", True))
+
+    def swept(eng):
+        eng.build_caches()
+        eng.sweep()
+        return eng.get_mps(), eng.get_chi(), {k: eng.info()[k] for k in keys}
+
+    for dt, stages in ((np.dtype("float64"), "abcd"), (np.dtype("float32"), "abc")):
+        live = mt.SweepEngine(0)
+        try:
+            options(live, "a")
+            live.set_dataset(0, ds.phi.astype(dt), ds.label_index, C, dtype=dt)
+            for stage in stages:
+                W = W20 if stage == "b" else W4
+                if stage == "d":
+                    options(live, stage)
+                live.set_mps(W)
+                fresh = mt.SweepEngine(0)
+                try:
+                    options(fresh, stage)
+                    fresh.set_dataset(0, ds.phi.astype(dt), ds.label_index, C, dtype=dt)
+                    fresh.set_mps(W)
+                    (Wf, (chif, lsf), inf), (Wl, (chil, lsl), inl) = swept(fresh), swept(live)
+                finally:
+                    fresh.close()
+                dev = max(float(np.abs(a - b).max()) if a.shape == b.shape else np.inf for a, b in zip(Wf, Wl))
+                print(f"{dt} stage {stage}: chi {chil.tolist()}, largest difference from the fresh engine {dev:.3e}, info {inl}")
+                assert inl == inf, (dt, stage, inl, inf)
+                if dt == np.float64:
+                    assert tuple(inl[k] for k in keys) == expect[stage], (stage, inl)
+                else:                       # the element-typed workspace: no fused chain, the large-bond solver at stage b only
+                    assert tuple(inl[k] for k in keys) == (False, stage == "b", False, stage == "b", False), (stage, inl)
+                assert np.array_equal(chil, chif) and lsl == lsf, (dt, stage)
+                assert all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(Wf, Wl)), (dt, stage, dev)
+        finally:
+            live.close()
