@@ -250,19 +250,6 @@ void dfree(T** p) {
     *p = nullptr;
 }
 
-// A device allocation or an event that lives for one call: released when it goes out of scope, whichever return that is.  Move-only
-// (the move constructor leaves no copy operations).
-template <typename H, typename A, hipError_t (*Release)(A)>
-struct DevOwned {
-    H h = nullptr;
-    DevOwned() = default;
-    DevOwned(DevOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
-    ~DevOwned() { if (h) (void)Release(h); }
-    operator H() const { return h; }
-};
-template <typename T>
-using DevBuf = DevOwned<T*, void*, hipFree>;
-using DevEvent = DevOwned<hipEvent_t, hipEvent_t, hipEventDestroy>;
 template <typename T>
 int dalloc(Ctx* c, DevBuf<T>& b, int64_t n) { return dalloc(c, &b.h, n); }
 

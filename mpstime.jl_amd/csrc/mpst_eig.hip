@@ -1421,11 +1421,11 @@ constexpr int BIGJ_MAX_SWEEPS = 160;     // (graded spectra converge slowly: 67 
 struct BigEig {
     int ncap = 0;
     hipStream_t stream = nullptr;
-    double *W = nullptr;        // [ncap][ncap] working columns (column-major: column p at W + p * ncap)
-    double *A = nullptr;        // [ncap][ncap] eigenvectors, column i = vector of D[i] (ascending), as dsyevd leaves them
-    double *D = nullptr;        // [ncap] eigenvalues, ascending
-    double *nrm = nullptr;      // [ncap] column norms
-    int32_t* info = nullptr;    // [4]: 0 = converged flag (1: stop), 1 = rotations in the current sweep, 2 = sweeps used, 3 = result (0 ok)
+    DevBuf<double> W;           // [ncap][ncap] working columns (column-major: column p at W + p * ncap)
+    DevBuf<double> A;           // [ncap][ncap] eigenvectors, column i = vector of D[i] (ascending), as dsyevd leaves them
+    DevBuf<double> D;           // [ncap] eigenvalues, ascending
+    DevBuf<double> nrm;         // [ncap] column norms
+    DevBuf<int32_t> info;       // [4]: 0 = converged flag (1: stop), 1 = rotations in the current sweep, 2 = sweeps used, 3 = result (0 ok)
 };
 
 __global__ __launch_bounds__(256) void k_big_prep(View v, int lid, int going_left, const double* rawG, int rawn, double* A, int ncap, int32_t* info) {
@@ -1607,22 +1607,14 @@ int big_eig_create(BigEig** out, int ncap, hipStream_t s, std::string* err) {
     };
     b->stream = s;
     const size_t nn = (size_t)b->ncap * b->ncap;
-    if (hipMalloc((void**)&b->W, sizeof(double) * nn) != hipSuccess || hipMalloc((void**)&b->A, sizeof(double) * nn) != hipSuccess ||
-        hipMalloc((void**)&b->D, sizeof(double) * b->ncap) != hipSuccess || hipMalloc((void**)&b->nrm, sizeof(double) * b->ncap) != hipSuccess ||
-        hipMalloc((void**)&b->info, sizeof(int32_t) * 4) != hipSuccess)
+    if (hipMalloc((void**)&b->W.h, sizeof(double) * nn) != hipSuccess || hipMalloc((void**)&b->A.h, sizeof(double) * nn) != hipSuccess ||
+        hipMalloc((void**)&b->D.h, sizeof(double) * b->ncap) != hipSuccess || hipMalloc((void**)&b->nrm.h, sizeof(double) * b->ncap) != hipSuccess ||
+        hipMalloc((void**)&b->info.h, sizeof(int32_t) * 4) != hipSuccess)
         return bail("hipMalloc of the large-bond Jacobi buffers failed");
     *out = b;
     return 0;
 }
-void big_eig_destroy(BigEig* b) {
-    if (!b) return;
-    if (b->W) (void)hipFree(b->W);
-    if (b->A) (void)hipFree(b->A);
-    if (b->D) (void)hipFree(b->D);
-    if (b->nrm) (void)hipFree(b->nrm);
-    if (b->info) (void)hipFree(b->info);
-    delete b;
-}
+void big_eig_destroy(BigEig* b) { delete b; }
 // the iteration proper on b->W (filled by k_big_prep): leaves b->D, b->A, b->info[3]
 static void enqueue_big_jacobi(BigEig* b, hipStream_t s) {
     const int np = b->ncap;

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 namespace mpst {
 
@@ -1793,97 +1794,207 @@ __global__ __launch_bounds__(BT_T) void k_bt_copyback(View v, int lid, int going
 #include "mpst_eig_subspace.inl"
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
+template <typename T>
+using PinnedBuf = DevOwned<T*, void*, hipHostFree>;
+
 struct BlockedEig {
     BtBufs b{};
     BtCoop cp{};
-    int32_t* host_flag = nullptr;      // pinned: [0] verdict, [1] the persistent kernel gave up
+    std::vector<DevBuf<void>> owned;   // every device buffer b, cp, ss and sticky point into: named once, where dev_alloc makes it
+    PinnedBuf<int32_t> host_flag;      // pinned: [0] verdict, [1] the persistent kernel gave up
     int coop_aborts = 0;
     unsigned int seq = 0;              // solve sequence number: part of the key of the XCD-local exchange's entries
     int xcd_misplaced = 0;             // solves whose XCD-local attempt found its workgroups on more than one XCD
     int cooldown = 0;                  // solves left that skip the persistent kernels after one of them gave up waiting
     int32_t* sticky = nullptr;         // device [1]: a solve enqueued by launch_eig_blocked_nosync failed since the last reset
     SsBufs ss{};                       // subspace solver in front of the exact one (mpst_eig_subspace.inl); ss.Mw == nullptr: off
-    int32_t* host_st = nullptr;        // pinned [4]: copy of ss.st
-    BlockedEig* rr = nullptr;          // complex: workspace of the Hermitian Rayleigh-Ritz solve (order 2 pc, pair mode, raw)
+    PinnedBuf<int32_t> host_st;        // pinned [4]: copy of ss.st
+    std::unique_ptr<BlockedEig> rr;    // complex: workspace of the Hermitian Rayleigh-Ritz solve (order 2 pc, pair mode, raw)
 };
-static int coop_threads() {
-    static const int nt = [] { const char* e = getenv("MPST_BT_COOP_T"); return e ? atoi(e) : 512; }();
-    return nt == 256 ? 256 : 512;
-}
-static int coop_grid(int ncap) {
-    static const int gmax = [] { const char* e = getenv("MPST_BT_COOP_G"); return e ? std::max(1, atoi(e)) : 0; }();
-    // measured: 512 threads and one row per wave (8 rows per workgroup): 37 workgroups at n = 296, 64 at n = 512 - fewer
-    // workgroups make the barrier cheaper, more threads keep the row work off the critical path
-    return std::max(1, std::min(gmax ? gmax : 128, (ncap + 7) / 8));
-}
-static size_t coop_lds(int ncap) {
-    const int G = coop_grid(ncap);
-    return (size_t)(3 + (ncap + G - 1) / G) * ncap * sizeof(double);
-}
-// XCD-local variant: one workgroup per CU of one XCD (32), every 8th workgroup of the launch
-constexpr int XCD_G = 32, XCD_STRIDE = 8;
-static size_t xcd_lds(int ncap) { return (size_t)(3 + (ncap + XCD_G - 1) / XCD_G) * ncap * sizeof(double); }
-static bool xcd_usable(int ncap) {
-    static const bool off = getenv("MPST_BT_NO_XCD") != nullptr;
-    return !off && coop_threads() == 512 && xcd_lds(ncap) <= 150 * 1024;
+// n elements on the device, released with the workspace; zero: cleared as well
+template <typename T>
+static bool dev_alloc(BlockedEig* e, T** p, size_t n, bool zero = false) {
+    e->owned.emplace_back();
+    if (hipMalloc(&e->owned.back().h, n * sizeof(T)) != hipSuccess) return false;
+    *p = (T*)e->owned.back().h;
+    return !zero || hipMemset(*p, 0, n * sizeof(T)) == hipSuccess;
 }
 
+// Every runtime switch of this file, each next to its name, meaning and default.  eig_switches() reads them once per process; no_tail
+// and ss_dbg are read again whenever a workspace is created (EigSwitches{} in blocked_eig_create / blocked_eig_enable_subspace).
+struct EigSwitches {
+    enum CXcd { ACROSS, COUNTED, TAGGED };
+    static bool on(const char* name) { return getenv(name) != nullptr; }
+    static int num(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+    static CXcd c_xcd_of(const char* e) { return (e && !strcmp(e, "0")) ? ACROSS : (e && !strcmp(e, "counted")) ? COUNTED : TAGGED; }
+    // =256: 256 threads per workgroup in the real reduction across the XCDs (default 512; the one-XCD reduction exists for 512 only)
+    int coop_threads = num("MPST_BT_COOP_T", 512) == 256 ? 256 : 512;
+    int coop_gmax = std::max(1, num("MPST_BT_COOP_G", 128));   // most workgroups of that reduction
+    int step_grid = std::max(1, num("MPST_BT_G", BT_G));       // most workgroups of a launch-per-step Householder step
+    bool no_xcd = on("MPST_BT_NO_XCD");                        // no reduction confined to one XCD, real or Hermitian
+    // =0|counted|tagged: the Hermitian reduction across the XCDs, or on one XCD with the counting barrier, or with tagged entries (default).
+    // Same box, c64, per bond at n_c = 256 / 512: across the XCDs 1.23 / 3.41 ms, counted 1.10 / 3.32, tagged 1.01 / 3.07
+    CXcd c_xcd = c_xcd_of(getenv("MPST_BT_C_XCD"));
+    bool no_cnative = on("MPST_BT_NO_CNATIVE");                // complex bonds through the embedded real reduction, not the Hermitian one
+    bool no_coop = on("MPST_BT_NO_COOP");                      // one launch per step, no persistent kernel
+    bool no_tail = on("MPST_BT_NO_TAIL");                      // the last BT_TAIL steps stay with the kernels of this file
+    bool no_subspace = on("MPST_NO_SUBSPACE");                 // no subspace solver in front of the exact one
+    bool no_subspace_c = on("MPST_NO_SUBSPACE_C");             // none for complex element types
+    int ss_dbg = num("MPST_SS_DBG", 0);                        // SsBufs::dbg
+    bool ss_debug = on("MPST_SS_DEBUG");                       // the subspace solver's verdict per bond on stderr (launch_eig_blocked only)
+    bool ss_pivot = on("MPST_SS_PIVOT");                       // the pivot-by-pivot elimination instead of the blocked factorisation
+    // the Rayleigh-Ritz problem on ONE workgroup with the exchange through LDS.  Measured and rejected as the default: 95 steps of
+    // barriers instead of L2 round trips, but the row updates of a 96 x 96 complex matrix on one CU take 515 us against the 223 us
+    // of 32 workgroups (c64 at configs[4]'s shape: 1.30 against 1.53 sweeps/s)
+    bool rr_solo = on("MPST_RR_SOLO");
+};
+static const EigSwitches& eig_switches() {
+    static const EigSwitches w;
+    return w;
+}
+
+// ---- how a solve is tridiagonalised ---------------------------------------------------------------------------------------
+enum class Route {
+    PerStep,       // one launch per Householder step (k_bt_prep, k_bt_step ..., k_bt_tail_prep)
+    RealAcross,    // persistent real reduction, workgroups on every XCD, agent-scope exchange
+    RealXcd,       // persistent real reduction confined to one XCD, tagged entries
+    HermAcross,    // persistent Hermitian reduction (pair mode) across the XCDs
+    HermXcd,       // persistent Hermitian reduction on one XCD: see Exchange
+};
+enum class Exchange { Tagged, Counted, Lds };     // HermXcd only: self-validating entries | counting barrier | one workgroup, through LDS
+enum class Solve { Bond, Raw, RayleighRitz };     // the bond's Gram matrix | a caller's matrix | the subspace solver's Hermitian H (on e->rr)
+struct RoutePick {
+    Route route;
+    Exchange xchg = Exchange::Tagged;
+};
+static bool hermitian(Route r) { return r == Route::HermAcross || r == Route::HermXcd; }
+
+// measured: 512 threads and one row per wave (8 rows per workgroup): 37 workgroups at n = 296, 64 at n = 512 - fewer
+// workgroups make the barrier cheaper, more threads keep the row work off the critical path
+static int coop_grid(int n, const EigSwitches& sw) { return std::max(1, std::min(sw.coop_gmax, (n + 7) / 8)); }
+// native Hermitian reduction (pair mode): 8 complex rows per workgroup
+static int coopc_grid(int n) { return std::max(1, std::min(128, (n / 2 + 7) / 8)); }
+// XCD-local variants: one workgroup per CU of one XCD (32), every 8th workgroup of the launch
+constexpr int XCD_G = 32, XCD_STRIDE = 8;
+// LDS of a persistent workgroup: three vectors and its share of the rows of an order-n matrix dealt over G workgroups
+static size_t rows_lds(int n, int G, size_t elem) { return (size_t)(3 + (n + G - 1) / G) * n * elem; }
+static size_t solo_lds(int nc) { return ((size_t)(3 + nc) * nc + 4 * (size_t)nc) * sizeof(double2); }
 static size_t bt_vec_lds() { return (size_t)(6 * BT_NMAX + 16) * sizeof(double); }
-// native Hermitian reduction (pair mode): 8 complex rows per workgroup; MPST_BT_NO_CNATIVE=1 keeps the embedded real reduction
-static int coopc_grid(int ncap) { return std::max(1, std::min(128, (ncap / 2 + 7) / 8)); }
-static size_t coopc_lds(int ncap) {
-    const int nc = ncap / 2, G = coopc_grid(ncap);
-    return (size_t)(3 + (nc + G - 1) / G) * nc * sizeof(double2);
+
+// The one place that decides.  n: order of the matrix the kernels see (pair mode: of the real embedding).  e->cooldown is state
+// and not part of the choice: launch_eig_blocked applies it.
+static RoutePick pick_route(int n, int zw, Solve what, const EigSwitches& sw) {
+    const int nc = n / 2;
+    const bool native = !sw.no_cnative && zw == 2 && (n & 1) == 0 && nc <= BTC_NMAX && rows_lds(nc, coopc_grid(n), sizeof(double2)) <= 150 * 1024;
+    if (what == Solve::RayleighRitz || (what == Solve::Bond && !sw.no_coop && native)) {
+        if (what == Solve::RayleighRitz && sw.rr_solo && solo_lds(nc) <= 158 * 1024) return {Route::HermXcd, Exchange::Lds};
+        if (sw.no_xcd || sw.c_xcd == EigSwitches::ACROSS || rows_lds(nc, XCD_G, sizeof(double2)) > 156 * 1024) return {Route::HermAcross};
+        return {Route::HermXcd, sw.c_xcd == EigSwitches::COUNTED ? Exchange::Counted : Exchange::Tagged};
+    }
+    if (what != Solve::Bond || sw.no_coop) return {Route::PerStep};
+    const bool one_xcd = !sw.no_xcd && sw.coop_threads == 512 && rows_lds(n, XCD_G, sizeof(double)) <= 150 * 1024;
+    return {one_xcd ? Route::RealXcd : Route::RealAcross};
 }
-// XCD-local variants: 32 workgroups on one XCD, ceil(n / 32) complex rows each
-static size_t coopc_xcd_lds(int ncap) {
-    const int nc = ncap / 2;
-    return (size_t)(3 + (nc + XCD_G - 1) / XCD_G) * nc * sizeof(double2);
+
+// A persistent kernel gave up (reason: its abort word): the same bond again - with the exchange across the XCDs if only the
+// placement was wrong (its workgroups were all there); a Hermitian reduction that ran out of patience goes to the embedded real
+// one across the XCDs, a real one to one launch per step (and the caller starts its cooldown).
+struct Retry {
+    Route next;
+    bool misplaced;      // counts as xcd_misplaced, else as coop_aborts
+};
+static Retry after_abort(Route r, int reason) {
+    if (reason == ABORT_PLACEMENT && r == Route::RealXcd) return {Route::RealAcross, true};
+    if (reason == ABORT_PLACEMENT && r == Route::HermXcd) return {Route::HermAcross, true};
+    return {hermitian(r) ? Route::RealAcross : Route::PerStep, false};
 }
-// 0: across the XCDs; 1: one XCD, tagged entries (default where the rows fit); 3: one XCD, counting barrier.  Same box, c64, per bond
-// at n_c = 256 / 512: across the XCDs 1.23 / 3.41 ms, counted 1.10 / 3.32, tagged 1.01 / 3.07 (MPST_BT_C_XCD=0|counted|tagged)
-static int cnative_xcd_mode(int ncap) {
-    static const int pick = [] {
-        if (getenv("MPST_BT_NO_XCD") != nullptr) return 0;
-        const char* e = getenv("MPST_BT_C_XCD");
-        if (e && !strcmp(e, "0")) return 0;
-        return (e && !strcmp(e, "counted")) ? 3 : 1;
-    }();
-    return coopc_xcd_lds(ncap) <= 156 * 1024 ? pick : 0;
+
+// every kernel below that is launched with dynamic LDS has its limit raised here
+static bool raise_lds_limits() {
+    auto raise = [](const void* k, size_t bytes) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess; };
+    return raise((const void*)k_bt_vec, bt_vec_lds()) && raise((const void*)k_bt_coop<256, SC_AGENT>, 150 * 1024) &&
+           raise((const void*)k_bt_coop<512, SC_AGENT>, 150 * 1024) && raise((const void*)k_bt_coop<512, SC_XCD>, 150 * 1024) &&
+           raise((const void*)k_bt_coop_c<0>, 150 * 1024) && raise((const void*)k_bt_coop_c<3>, 156 * 1024) &&
+           raise((const void*)k_bt_coop_c<1>, 156 * 1024) && raise((const void*)k_bt_coop_c<4>, 158 * 1024);
 }
-static bool cnative_xcd_usable(int ncap) { return cnative_xcd_mode(ncap) != 0; }
-static bool cnative_usable(const View& v, int ncap) {
-    static const bool off = getenv("MPST_BT_NO_CNATIVE") != nullptr;
-    return !off && v.zw == 2 && (ncap & 1) == 0 && ncap / 2 <= BTC_NMAX && coopc_lds(ncap) <= 150 * 1024;
+// The tridiagonalisation of one solve by route r on workspace e (its exchange buffers, its sequence number); b: e->b as this solve
+// sees it (solve_bufs).  The only place that names the persistent kernels and that advances seq.  A real reduction ends in
+// k_eig_tail where the workspace uses it (the kernels here stopped at step n - BT_TAIL; nothing to do for n <= BT_TAIL).
+static int enqueue_tridiag(RoutePick r, const View& v, int lid, int going_left, const double* rawG, int rawn, const BtBufs& b, BlockedEig* e,
+                           const EigSwitches& sw, hipStream_t s) {
+    const int n = rawn > 0 ? rawn : b.ncap, nc = n / 2;
+    const BtCoop& cp = e->cp;
+    const dim3 one_xcd(XCD_G * XCD_STRIDE);
+    if (r.route != Route::PerStep && hipMemsetAsync(cp.counter, 0, 16, s) != hipSuccess) return MPST_ERR_DEVICE;
+    switch (r.route) {
+    case Route::PerStep:
+        hipLaunchKernelGGL(k_bt_prep, dim3(256), dim3(BT_T), 0, s, v, lid, going_left, rawG, rawn, b);
+        for (int j = 0; j <= n - 2; ++j) {
+            // fewer workgroups once the trailing matrix is small: the redundant prologue is paid per workgroup
+            const int m = n - 1 - j;
+            const int g = std::max(1, std::min(sw.step_grid, (m + 3) / 4));
+            hipLaunchKernelGGL(k_bt_step, dim3(g), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, j);
+        }
+        if (b.use_tail) hipLaunchKernelGGL(k_bt_tail_prep, dim3(32), dim3(BT_T), 0, s, v, lid, going_left, rawn, b);
+        break;
+    case Route::RealAcross:
+        if (sw.coop_threads == 512)
+            hipLaunchKernelGGL((k_bt_coop<512, SC_AGENT>), dim3(coop_grid(n, sw)), dim3(512), rows_lds(n, coop_grid(n, sw), sizeof(double)), s, v, lid, going_left, b, cp, 1, 0u);
+        else
+            hipLaunchKernelGGL((k_bt_coop<256, SC_AGENT>), dim3(coop_grid(n, sw)), dim3(256), rows_lds(n, coop_grid(n, sw), sizeof(double)), s, v, lid, going_left, b, cp, 1, 0u);
+        break;
+    case Route::RealXcd:
+        hipLaunchKernelGGL((k_bt_coop<512, SC_XCD>), one_xcd, dim3(512), rows_lds(n, XCD_G, sizeof(double)), s, v, lid, going_left, b, cp, XCD_STRIDE, ++e->seq);
+        break;
+    case Route::HermAcross:
+        hipLaunchKernelGGL(k_bt_coop_c<0>, dim3(coopc_grid(n)), dim3(BTC_NT), rows_lds(nc, coopc_grid(n), sizeof(double2)), s, v, lid, going_left, b, cp, 1, 0u, rawG, rawn);
+        break;
+    case Route::HermXcd:
+        if (r.xchg == Exchange::Lds)
+            hipLaunchKernelGGL(k_bt_coop_c<4>, dim3(1), dim3(BTC_NT), solo_lds(nc), s, v, lid, going_left, b, cp, 1, 0u, rawG, rawn);
+        else if (r.xchg == Exchange::Counted)
+            hipLaunchKernelGGL(k_bt_coop_c<3>, one_xcd, dim3(BTC_NT), rows_lds(nc, XCD_G, sizeof(double2)), s, v, lid, going_left, b, cp, XCD_STRIDE, 0u, rawG, rawn);
+        else
+            hipLaunchKernelGGL(k_bt_coop_c<1>, one_xcd, dim3(BTC_NT), rows_lds(nc, XCD_G, sizeof(double2)), s, v, lid, going_left, b, cp, XCD_STRIDE, ++e->seq, rawG, rawn);
+        break;
+    }
+    if (b.use_tail && !hermitian(r.route)) launch_eig_tail(v, lid, going_left, rawn, b.tailG, b.ncap, b.Vall, b.dd, b.ee, b.tau, b.abort, b.skip, s);
+    return 0;
+}
+// e->b as the kernels of one solve see it.  r: whether there is an abort word to watch (when it is set dd / ee / Vall are stale and
+// nothing is published) and whether the reflectors are complex; Route::PerStep also stands for "no tridiagonalisation of its own"
+// (the subspace phase).  gate / ss: the subspace phase; sticky / skip: sweeps that read no verdict per bond.
+static BtBufs solve_bufs(const BlockedEig* e, Route r, const int32_t* gate = nullptr, int ss = 0, int32_t* sticky = nullptr, const int32_t* skip = nullptr) {
+    BtBufs b = e->b;
+    b.abort = r != Route::PerStep ? e->cp.abort_flag : nullptr;
+    b.cnative = hermitian(r) ? 1 : 0;
+    b.gate = gate;
+    b.ss = ss;
+    b.sticky = sticky;
+    b.skip = skip;
+    return b;
 }
 
 int blocked_eig_create(BlockedEig** out, int ncap, std::string* err) {
     BlockedEig* e = new BlockedEig();
-    e->b.ncap = ncap;
-    e->b.use_tail = getenv("MPST_BT_NO_TAIL") == nullptr ? 1 : 0;
-    auto al = [&](double** p, size_t n) { return hipMalloc((void**)p, n * sizeof(double)) == hipSuccess; };
+    BtBufs& b = e->b;
+    b.ncap = ncap;
+    b.use_tail = EigSwitches{}.no_tail ? 0 : 1;
     const size_t n1 = ncap, n2 = (size_t)ncap * ncap;
-    bool ok = al(&e->b.A, n2) && al(&e->b.D, (size_t)CAP_LIMIT * CAP_LIMIT) && al(&e->b.Y, 2 * n1) && al(&e->b.Vall, n2) &&
-              al(&e->b.dd, n1) && al(&e->b.ee, n1) && al(&e->b.tau, n1) && al(&e->b.Z, (size_t)CAP_LIMIT * n1) && al(&e->b.lam, CAP_LIMIT) &&
-              al(&e->b.res, CAP_LIMIT) && al(&e->b.tailG, (size_t)BT_TAIL * BT_TAIL) && al(&e->b.Tfac, (size_t)((ncap + 15) / 16) * 256) && hipMalloc((void**)&e->b.flag, sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&e->b.ctl, 4 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&e->sticky, sizeof(int32_t)) == hipSuccess &&
-              hipHostMalloc((void**)&e->host_flag, 2 * sizeof(int32_t)) == hipSuccess && al(&e->cp.ybuf, 4 * n1) && al(&e->cp.rowbuf, 4 * n1) &&
-              hipMalloc((void**)&e->cp.counter, 16) == hipSuccess;
+    bool ok = dev_alloc(e, &b.A, n2) && dev_alloc(e, &b.D, (size_t)CAP_LIMIT * CAP_LIMIT) && dev_alloc(e, &b.Y, 2 * n1, true) &&
+              dev_alloc(e, &b.Vall, n2, true) && dev_alloc(e, &b.dd, n1) && dev_alloc(e, &b.ee, n1) && dev_alloc(e, &b.tau, n1) &&
+              dev_alloc(e, &b.Z, (size_t)CAP_LIMIT * n1) && dev_alloc(e, &b.lam, CAP_LIMIT) && dev_alloc(e, &b.res, CAP_LIMIT) &&
+              dev_alloc(e, &b.tailG, (size_t)BT_TAIL * BT_TAIL) && dev_alloc(e, &b.Tfac, (size_t)((ncap + 15) / 16) * 256) &&
+              dev_alloc(e, &b.flag, 1) && dev_alloc(e, &b.ctl, 4, true) && dev_alloc(e, &e->sticky, 1, true) &&
+              hipHostMalloc((void**)&e->host_flag.h, 2 * sizeof(int32_t)) == hipSuccess && dev_alloc(e, &e->cp.ybuf, 4 * n1) &&
+              dev_alloc(e, &e->cp.rowbuf, 4 * n1) && dev_alloc(e, &e->cp.counter, 4);
     if (ok) {               // one 16-byte control block, cleared by one memset per solve: counter | abort flag | roll call
         static std::atomic<int> ordinal{0};
         e->cp.abort_flag = (int32_t*)(e->cp.counter + 1);
         e->cp.roll = (unsigned long long*)(e->cp.counter + 2);
         e->cp.xsel = ordinal.fetch_add(1) & 7;
     }
-    if (ok) ok = hipMemset(e->b.Vall, 0, n2 * sizeof(double)) == hipSuccess && hipMemset(e->b.ctl, 0, 4 * sizeof(int32_t)) == hipSuccess && hipMemset(e->sticky, 0, sizeof(int32_t)) == hipSuccess && hipMemset(e->b.Y, 0, 2 * n1 * sizeof(double)) == hipSuccess;
-    if (ok) ok = hipFuncSetAttribute((const void*)k_bt_vec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bt_vec_lds()) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop<256, SC_AGENT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop<512, SC_AGENT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop<512, SC_XCD>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop_c<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop_c<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop_c<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)k_bt_coop_c<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) == hipSuccess;
-    if (!ok) {
+    if (!ok || !raise_lds_limits()) {
         if (err) *err = "allocation of the blocked eigensolver's workspace failed";
         blocked_eig_destroy(e);
         return MPST_ERR_NOMEM;
@@ -1891,41 +2002,17 @@ int blocked_eig_create(BlockedEig** out, int ncap, std::string* err) {
     *out = e;
     return 0;
 }
-void blocked_eig_destroy(BlockedEig* e) {
-    if (!e) return;
-    double* ps[] = {e->b.A, e->b.D, e->b.Y, e->b.Vall, e->b.dd, e->b.ee, e->b.tau, e->b.Z, e->b.lam, e->b.res, e->b.Tfac, e->b.tailG};
-    for (double* p : ps)
-        if (p) (void)hipFree(p);
-    if (e->b.flag) (void)hipFree(e->b.flag);
-    if (e->b.ctl) (void)hipFree(e->b.ctl);
-    if (e->sticky) (void)hipFree(e->sticky);
-    if (e->host_flag) (void)hipHostFree(e->host_flag);
-    if (e->cp.ybuf) (void)hipFree(e->cp.ybuf);
-    if (e->cp.rowbuf) (void)hipFree(e->cp.rowbuf);
-    if (e->cp.counter) (void)hipFree(e->cp.counter);
-    {
-        SsBufs& q = e->ss;
-        double* qs[] = {q.Mw, q.Lb[0], q.Lb[1], q.Rb[0], q.Rb[1], q.Sp, q.Tm, q.H, q.lamH, q.WH, q.wsH, q.part};
-        for (double* p : qs)
-            if (p) (void)hipFree(p);
-        if (q.infoH) (void)hipFree(q.infoH);
-        if (q.st) (void)hipFree(q.st);
-        if (e->host_st) (void)hipHostFree(e->host_st);
-        if (e->rr) blocked_eig_destroy(e->rr);
-    }
-    delete e;
-}
+void blocked_eig_destroy(BlockedEig* e) { delete e; }
 
 // Switch the subspace solver on for this workspace: mcap rows (C * d * cap), kcap = chi_max.  Off (and harmless) when the shape
 // leaves no room for it (block wider than SS_PMAX, or the matrix not at least twice as wide as the block) or MPST_NO_SUBSPACE is set.
 int blocked_eig_enable_subspace(BlockedEig* e, int mcap, int kcap, int C, int cx, std::string* err) {
     if (!e || e->ss.Mw) return 0;
-    static const bool off = getenv("MPST_NO_SUBSPACE") != nullptr;
-    static const bool off_c = getenv("MPST_NO_SUBSPACE_C") != nullptr;
+    const EigSwitches& sw = eig_switches();
     // complex: the workspace of the exact solver holds the 2n embedding; counts below are those of the complex matrix
     const int ncap = cx ? e->b.ncap / 2 : e->b.ncap;
     if (cx) mcap /= 2;
-    if (off || (cx && off_c) || kcap > 64 || C * kcap > SS_PMAX) return 0;      // the block holds rank(M0) <= C chi columns
+    if (sw.no_subspace || (cx && sw.no_subspace_c) || kcap > 64 || C * kcap > SS_PMAX) return 0;      // the block holds rank(M0) <= C chi columns
     const int pc = std::min(SS_PMAX, (C * kcap + SS_EXTRA + 15) & ~15);
     if (ncap < 2 * pc || (cx ? 2 : 1) * ncap <= MAX_DIM) return 0;
     if (cx && pc > 96) return 0;                                                 // the complex elimination keeps a 3 x 12 register tile
@@ -1933,22 +2020,23 @@ int blocked_eig_enable_subspace(BlockedEig* e, int mcap, int kcap, int C, int cx
     q.pc = pc;
     q.capped = (C * kcap + SS_EXTRA > pc) ? 1 : 0;
     q.cx = cx ? 1 : 0;
-    q.dbg = getenv("MPST_SS_DBG") ? atoi(getenv("MPST_SS_DBG")) : 0;
+    q.dbg = EigSwitches{}.ss_dbg;
     q.mcap = mcap;
     q.ncap = ncap;
     const size_t z = cx ? 2 : 1;          // doubles per element
-    auto al = [&](double** p, size_t n) { return hipMalloc((void**)p, n * sizeof(double)) == hipSuccess && hipMemset(*p, 0, n * sizeof(double)) == hipSuccess; };
+    auto al = [&](double** p, size_t n) { return dev_alloc(e, p, n, true); };
     const size_t tn = (size_t)(z * ncap + 15) / 16;
     bool ok = al(&q.Mw, z * mcap * ncap) && al(&q.Lb[0], z * mcap * pc) && al(&q.Lb[1], z * mcap * pc) && al(&q.Rb[0], z * ncap * pc) &&
               al(&q.Rb[1], z * ncap * pc) && al(&q.Sp, z * SS_KS * pc * pc) && al(&q.Tm, z * pc * pc) && al(&q.H, z * z * pc * pc) &&
               al(&q.lamH, SS_PMAX + 16) && al(&q.WH, z * z * pc * pc) && al(&q.wsH, eig_workspace_doubles()) && al(&q.part, tn * CAP_LIMIT + tn + 16) &&
-              hipMalloc((void**)&q.infoH, sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&q.st, 4 * sizeof(int32_t)) == hipSuccess &&
-              hipMemset(q.st, 0, 4 * sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&e->host_st, 4 * sizeof(int32_t)) == hipSuccess;
+              dev_alloc(e, &q.infoH, 1) && dev_alloc(e, &q.st, 4, true) && hipHostMalloc((void**)&e->host_st.h, 4 * sizeof(int32_t)) == hipSuccess;
     if (ok) ok = hipFuncSetAttribute((const void*)k_ss_cholb, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
     if (ok && cx) {
+        BlockedEig* r = nullptr;
         std::string e2;
-        ok = blocked_eig_create(&e->rr, 2 * pc, &e2) == 0;
-        if (ok) q.rrflag = e->rr->b.flag;
+        ok = blocked_eig_create(&r, 2 * pc, &e2) == 0;
+        e->rr.reset(r);
+        if (ok) q.rrflag = r->b.flag;
     }
     if (!ok) {
         if (err) *err = "allocation of the subspace eigensolver's workspace failed";
@@ -1968,14 +2056,44 @@ int blocked_eig_subspace_counts(BlockedEig* e, hipStream_t s, int32_t* attempted
     return 0;
 }
 
-// The subspace phase of a solve: ~30 launches, all leave at once on a bond that is not attempted.  Afterwards ss.st[0] says whether
-// E / lam / chi are published.
+// verification / Loewdin rounds on Z (row k = vector k): Z^T Z - I, verdict, E = Z (I - D/2), the polished vectors as the next round's input
+static void enqueue_rounds(const View& v, int lid, int going_left, const double* rawG, int rawn, double* rawlam, double* rawE, int32_t* rawinfo,
+                           const BtBufs& b, int rounds, hipStream_t s) {
+    const int ncap = rawn > 0 ? rawn : b.ncap;
+    const int kmax = rawn > 0 ? std::min(rawn, CAP_LIMIT) : std::min(v.chi_max, CAP_LIMIT);
+    const int tk = (kmax + 15) / 16, tn = (ncap + 15) / 16;
+    for (int second = 0; second < rounds; ++second) {
+        if (second) hipLaunchKernelGGL(k_bt_copyback, dim3(64), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, (const double*)rawE);
+        hipLaunchKernelGGL(k_bt_gram, dim3(tk * tk), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, second);
+        hipLaunchKernelGGL(k_bt_decide, dim3(1), dim3(512), 0, s, v, lid, going_left, rawG, rawn, b, rawlam, rawinfo, second);
+        hipLaunchKernelGGL(k_bt_polish, dim3(std::max(1, std::min(256, (tn * tk + 3) / 4))), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, rawE, second);
+    }
+}
+// the launches that follow the tridiagonalisation: eigenvectors, verification, publication
 static void enqueue_after_tridiag(const View& v, int lid, int going_left, const double* rawG, int rawn, double* rawlam, double* rawE,
-                                  int32_t* rawinfo, const BtBufs& b, hipStream_t s);
-static int cnative_xcd_mode(int ncap);
-static size_t coopc_xcd_lds(int ncap);
-static size_t coopc_lds(int ncap);
-static int coopc_grid(int ncap);
+                                  int32_t* rawinfo, const BtBufs& b, hipStream_t s) {
+    const int ncap = rawn > 0 ? rawn : b.ncap;
+    const int kmax = rawn > 0 ? std::min(rawn, CAP_LIMIT) : std::min(v.chi_max, CAP_LIMIT);
+    hipLaunchKernelGGL(k_bt_larft, dim3((ncap + BT_NB - 1) / BT_NB), dim3(BT_T), 0, s, v, lid, going_left, rawn, b);
+    hipLaunchKernelGGL(k_bt_vec, dim3(kmax), dim3(BT_T), bt_vec_lds(), s, v, lid, going_left, rawn, b);
+    if (b.cnative) hipLaunchKernelGGL(k_bt_back_c, dim3((kmax / 2 + 3) / 4), dim3(256), 0, s, v, lid, going_left, rawn, b);
+    enqueue_rounds(v, lid, going_left, rawG, rawn, rawlam, rawE, rawinfo, b, 2, s);
+}
+
+// The subspace phase of a solve: ~30 launches, all leave at once on a bond that is not attempted.  Afterwards ss.st[0] says whether
+// E / lam / chi are published.  Both element kinds end alike, from the Ritz vectors to the verdict: ritz(b) launches k_ss_ritz or
+// k_ss_ritz_c, resid_grid covers the rows of the residual (ncap, or 2 ncap of the embedding) by the wanted pairs.
+template <typename Ritz>
+static void enqueue_subspace_tail(const View& v, int lid, int going_left, BlockedEig* e, Ritz ritz, int resid_grid, hipStream_t s) {
+    const SsBufs& q = e->ss;
+    const BtBufs b = solve_bufs(e, Route::PerStep, q.st + 1, 1);
+    ritz(b);
+    hipLaunchKernelGGL(k_ss_resid, dim3(resid_grid), dim3(256), 0, s, v, lid, going_left, q, b);
+    hipLaunchKernelGGL(k_ss_collect, dim3(1), dim3(1024), 0, s, v, lid, going_left, q, b);
+    // one round for fp32 tensors (k_bt_decide fails the bond on a deviation from orthonormality above 1e-8), two for fp64
+    enqueue_rounds(v, lid, going_left, nullptr, 0, nullptr, nullptr, nullptr, b, v.ss_f32 ? 1 : 2, s);
+    hipLaunchKernelGGL(k_ss_verdict, dim3(1), dim3(64), 0, s, q, b);
+}
 
 // complex element types: the same sequence with the complex kernels; the Hermitian Rayleigh-Ritz problem goes through the native
 // pair-mode chain (k_bt_coop_c ...) on the small workspace e->rr, raw mode, gated by st[1]
@@ -2006,52 +2124,16 @@ static void enqueue_subspace_c(const View& v, int lid, int going_left, BlockedEi
     hipLaunchKernelGGL(k_ss_gram_c, dim3(tp * tp * SS_KS), dim3(256), 0, s, v, lid, going_left, q, (const double2*)R0, 0);
     hipLaunchKernelGGL(k_ss_chol_c<1>, dim3((pc * pc + CH_T - 1) / CH_T), dim3(CH_T), 0, s, v, lid, going_left, q);
     {   // Hermitian Rayleigh-Ritz: eigenpairs of the 2 pc x 2 pc embedding in pair mode -> lamH (each value twice), WH (vector k in column 2k)
-        BlockedEig* r = e->rr;
+        BlockedEig* r = e->rr.get();
         const int rn = 2 * pc;
-        (void)hipMemsetAsync(r->cp.counter, 0, 16, s);
-        BtBufs bt = r->b;
-        bt.abort = r->cp.abort_flag;
-        bt.sticky = nullptr;
-        bt.skip = nullptr;
-        bt.gate = q.st + 1;
-        bt.ss = 0;
-        bt.cnative = 1;
-        const int xm = cnative_xcd_mode(rn);
-        // MPST_RR_SOLO=1: ONE workgroup with the exchange through LDS (XMODE 4).  Measured and rejected as the default: 95 steps of
-        // barriers instead of L2 round trips, but the row updates of a 96 x 96 complex matrix on one CU take 515 us against the 223 us
-        // of 32 workgroups (c64 at configs[4]'s shape: 1.30 against 1.53 sweeps/s)
-        static const bool solo = getenv("MPST_RR_SOLO") != nullptr;
-        const size_t solo_lds = ((size_t)(3 + pc) * pc + 4 * (size_t)pc) * sizeof(double2);
-        if (solo && solo_lds <= 158 * 1024)
-            hipLaunchKernelGGL(k_bt_coop_c<4>, dim3(1), dim3(BTC_NT), solo_lds, s, v, 0, 0, bt, r->cp, 1, 0u, (const double*)q.H, rn);
-        else if (xm == 3)
-            hipLaunchKernelGGL(k_bt_coop_c<3>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(rn), s, v, 0, 0, bt, r->cp, XCD_STRIDE, 0u, (const double*)q.H, rn);
-        else if (xm == 1)
-            hipLaunchKernelGGL(k_bt_coop_c<1>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(rn), s, v, 0, 0, bt, r->cp, XCD_STRIDE, ++r->seq, (const double*)q.H, rn);
-        else
-            hipLaunchKernelGGL(k_bt_coop_c<0>, dim3(coopc_grid(rn)), dim3(BTC_NT), coopc_lds(rn), s, v, 0, 0, bt, r->cp, 1, 0u, (const double*)q.H, rn);
+        const RoutePick pick = pick_route(rn, 2, Solve::RayleighRitz, eig_switches());
+        const BtBufs bt = solve_bufs(r, pick.route, q.st + 1);
+        (void)enqueue_tridiag(pick, v, 0, 0, q.H, rn, bt, r, eig_switches(), s);
         enqueue_after_tridiag(v, 0, 0, q.H, rn, q.lamH, q.WH, q.infoH, bt, s);
     }
-    BtBufs b = e->b;
-    b.abort = nullptr;
-    b.sticky = nullptr;
-    b.skip = nullptr;
-    b.gate = q.st + 1;
-    b.ss = 1;
-    b.cnative = 0;
-    hipLaunchKernelGGL(k_ss_ritz_c, dim3((tn * tk + 3) / 4), dim3(256), 0, s, v, lid, going_left, q, b, (const double2*)R0, 0);
-    const int tne = (2 * q.ncap + 15) / 16;
-    hipLaunchKernelGGL(k_ss_resid, dim3(tne * tk), dim3(256), 0, s, v, lid, going_left, q, b);
-    hipLaunchKernelGGL(k_ss_collect, dim3(1), dim3(1024), 0, s, v, lid, going_left, q, b);
-    const int ncap = b.ncap, tkk = (std::min(v.chi_max, CAP_LIMIT) + 15) / 16, tnn = (ncap + 15) / 16;
-    // verification / Loewdin rounds: one for fp32 tensors (k_bt_decide fails the bond on a deviation from orthonormality above 1e-8), two for fp64
-    for (int second = 0; second < (v.ss_f32 ? 1 : 2); ++second) {
-        if (second) hipLaunchKernelGGL(k_bt_copyback, dim3(64), dim3(BT_T), 0, s, v, lid, going_left, 0, b, (const double*)nullptr);
-        hipLaunchKernelGGL(k_bt_gram, dim3(tkk * tkk), dim3(BT_T), 0, s, v, lid, going_left, 0, b, second);
-        hipLaunchKernelGGL(k_bt_decide, dim3(1), dim3(512), 0, s, v, lid, going_left, (const double*)nullptr, 0, b, (double*)nullptr, (int32_t*)nullptr, second);
-        hipLaunchKernelGGL(k_bt_polish, dim3(std::max(1, std::min(256, (tnn * tkk + 3) / 4))), dim3(BT_T), 0, s, v, lid, going_left, 0, b, (double*)nullptr, second);
-    }
-    hipLaunchKernelGGL(k_ss_verdict, dim3(1), dim3(64), 0, s, q, b);
+    enqueue_subspace_tail(v, lid, going_left, e, [&](const BtBufs& b) {
+        hipLaunchKernelGGL(k_ss_ritz_c, dim3((tn * tk + 3) / 4), dim3(256), 0, s, v, lid, going_left, q, b, (const double2*)R0, 0);
+    }, (2 * q.ncap + 15) / 16 * tk, s);
 }
 
 static void enqueue_subspace(const View& v, int lid, int going_left, BlockedEig* e, hipStream_t s) {
@@ -2062,17 +2144,16 @@ static void enqueue_subspace(const View& v, int lid, int going_left, BlockedEig*
     const SsBufs& q = e->ss;
     const int pc = q.pc, tp = pc / 16;
     const int tm = (q.mcap + 15) / 16, tn = (q.ncap + 15) / 16;
-    const size_t chol_lds = 0;
     const int kmax = std::min(v.chi_max, 64), tk = (kmax + 15) / 16;
     const int short_start = v.ss_f32 ? 1 : 0;
     hipLaunchKernelGGL(k_ss_load, dim3(256), dim3(256), 0, s, v, lid, going_left, q, short_start);
-    static const bool pivotwise = getenv("MPST_SS_PIVOT") != nullptr;     // the pivot-by-pivot elimination instead of the blocked factorisation
+    const bool pivotwise = eig_switches().ss_pivot;
     const size_t cb_lds = ((size_t)pc * (pc + CB_LDPAD) + pc + (size_t)(pc / 16) * 256) * sizeof(double);
     auto orth = [&](double* raw, double* out, int left) {          // out = cholqr(raw)
         hipLaunchKernelGGL(k_ss_gram, dim3(tp * tp * SS_KS), dim3(256), 0, s, v, lid, going_left, q, (const double*)raw, left);
         if (!pivotwise) hipLaunchKernelGGL(k_ss_cholb, dim3(1), dim3(CB_T), cb_lds, s, v, lid, going_left, q);
-        else if (pc <= 96) hipLaunchKernelGGL(k_ss_chol<2>, dim3(1), dim3(CH_T), chol_lds, s, v, lid, going_left, q);
-        else hipLaunchKernelGGL(k_ss_chol<0>, dim3(1), dim3(CH_T), chol_lds, s, v, lid, going_left, q);
+        else if (pc <= 96) hipLaunchKernelGGL(k_ss_chol<2>, dim3(1), dim3(CH_T), 0, s, v, lid, going_left, q);
+        else hipLaunchKernelGGL(k_ss_chol<0>, dim3(1), dim3(CH_T), 0, s, v, lid, going_left, q);
         hipLaunchKernelGGL(k_ss_apply, dim3(((left ? tm : tn) * tp + 3) / 4), dim3(256), 0, s, v, lid, going_left, q, (const double*)raw, out, left);
     };
     // X = cholqr(M^T Omega)  (fp32: X = Omega / sqrt(n), written by k_ss_load)
@@ -2094,55 +2175,44 @@ static void enqueue_subspace(const View& v, int lid, int going_left, BlockedEig*
     // Z = M^T Q; H = Z^T Z; Rayleigh-Ritz
     hipLaunchKernelGGL(k_ss_mm<1>, dim3(tn * tp), dim3(256), 0, s, v, lid, going_left, q, (const double*)q.Lb[1], q.Rb[0]);
     hipLaunchKernelGGL(k_ss_gram, dim3(tp * tp * SS_KS), dim3(256), 0, s, v, lid, going_left, q, (const double*)q.Rb[0], 0);
-    hipLaunchKernelGGL(k_ss_chol<1>, dim3((pc * pc + CH_T - 1) / CH_T), dim3(CH_T), chol_lds, s, v, lid, going_left, q);
+    hipLaunchKernelGGL(k_ss_chol<1>, dim3((pc * pc + CH_T - 1) / CH_T), dim3(CH_T), 0, s, v, lid, going_left, q);
     launch_eig_raw_gated(q.H, pc, q.lamH, q.WH, q.infoH, q.wsH, q.st + 1, s);
-    BtBufs b = e->b;
-    b.abort = nullptr;
-    b.sticky = nullptr;
-    b.skip = nullptr;
-    b.gate = q.st + 1;
-    b.ss = 1;
-    b.cnative = 0;
-    hipLaunchKernelGGL(k_ss_ritz, dim3((tn * tk + 3) / 4), dim3(256), 0, s, v, lid, going_left, q, b, (const double*)q.Rb[0]);
-    hipLaunchKernelGGL(k_ss_resid, dim3(tn * tk), dim3(256), 0, s, v, lid, going_left, q, b);
-    hipLaunchKernelGGL(k_ss_collect, dim3(1), dim3(1024), 0, s, v, lid, going_left, q, b);
-    const int ncap = b.ncap, tkk = (std::min(v.chi_max, CAP_LIMIT) + 15) / 16, tnn = (ncap + 15) / 16;
-    // verification / Loewdin rounds: one for fp32 tensors (k_bt_decide fails the bond on a deviation from orthonormality above 1e-8), two for fp64
-    for (int second = 0; second < (v.ss_f32 ? 1 : 2); ++second) {
-        if (second) hipLaunchKernelGGL(k_bt_copyback, dim3(64), dim3(BT_T), 0, s, v, lid, going_left, 0, b, (const double*)nullptr);
-        hipLaunchKernelGGL(k_bt_gram, dim3(tkk * tkk), dim3(BT_T), 0, s, v, lid, going_left, 0, b, second);
-        hipLaunchKernelGGL(k_bt_decide, dim3(1), dim3(512), 0, s, v, lid, going_left, (const double*)nullptr, 0, b, (double*)nullptr, (int32_t*)nullptr, second);
-        hipLaunchKernelGGL(k_bt_polish, dim3(std::max(1, std::min(256, (tnn * tkk + 3) / 4))), dim3(BT_T), 0, s, v, lid, going_left, 0, b, (double*)nullptr, second);
-    }
-    hipLaunchKernelGGL(k_ss_verdict, dim3(1), dim3(64), 0, s, q, b);
+    enqueue_subspace_tail(v, lid, going_left, e, [&](const BtBufs& b) {
+        hipLaunchKernelGGL(k_ss_ritz, dim3((tn * tk + 3) / 4), dim3(256), 0, s, v, lid, going_left, q, b, (const double*)q.Rb[0]);
+    }, tn * tk, s);
 }
 
-// the launches that follow the tridiagonalisation: eigenvectors, verification, publication
-static void enqueue_after_tridiag(const View& v, int lid, int going_left, const double* rawG, int rawn, double* rawlam, double* rawE,
-                                  int32_t* rawinfo, const BtBufs& b, hipStream_t s) {
-    const int ncap = rawn > 0 ? rawn : b.ncap;
-    const int kmax = rawn > 0 ? std::min(rawn, CAP_LIMIT) : std::min(v.chi_max, CAP_LIMIT);
-    hipLaunchKernelGGL(k_bt_larft, dim3((ncap + BT_NB - 1) / BT_NB), dim3(BT_T), 0, s, v, lid, going_left, rawn, b);
-    hipLaunchKernelGGL(k_bt_vec, dim3(kmax), dim3(BT_T), bt_vec_lds(), s, v, lid, going_left, rawn, b);
-    if (b.cnative) hipLaunchKernelGGL(k_bt_back_c, dim3((kmax / 2 + 3) / 4), dim3(256), 0, s, v, lid, going_left, rawn, b);
-    const int tk = (kmax + 15) / 16, tn = (ncap + 15) / 16;
-    for (int second = 0; second < 2; ++second) {
-        if (second) hipLaunchKernelGGL(k_bt_copyback, dim3(64), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, (const double*)rawE);
-        hipLaunchKernelGGL(k_bt_gram, dim3(tk * tk), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, second);
-        hipLaunchKernelGGL(k_bt_decide, dim3(1), dim3(512), 0, s, v, lid, going_left, rawG, rawn, b, rawlam, rawinfo, second);
-        hipLaunchKernelGGL(k_bt_polish, dim3(std::max(1, std::min(256, (tn * tk + 3) / 4))), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, rawE, second);
+// MPST_SS_DEBUG: what the subspace solver left on an attempted bond, on stderr
+static void dump_subspace_verdict(const BlockedEig* e, int lid, int going_left) {
+    const BtBufs& b = e->b;
+    double res[CAP_LIMIT], lam[CAP_LIMIT], D[CAP_LIMIT], stamp[8];
+    int32_t ctl[4], flag, info;
+    (void)hipMemcpy(res, b.res, sizeof res, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(lam, b.lam, sizeof lam, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(D, b.D, sizeof D, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(ctl, b.ctl, sizeof ctl, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&flag, b.flag, sizeof flag, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&info, e->ss.infoH, sizeof info, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(stamp, e->ss.lamH + SS_PMAX, sizeof stamp, hipMemcpyDeviceToHost);
+    double r2 = 0, rmax = 0;
+    int bad = -1;
+    for (int i = 0; i < ctl[0] && i < CAP_LIMIT; ++i) {
+        r2 += res[i] * res[i];
+        if (res[i] > rmax) { rmax = res[i]; bad = i; }
     }
+    fprintf(stderr, "[ss] chol phases: load %.2f us, elimination %.2f us | blocked: load %.2f, updates %.2f, diagonal blocks %.2f, panels %.2f, inverse %.2f, store %.2f us\n",
+            stamp[0] * 0.01, stamp[1] * 0.01, stamp[2] * 0.01, stamp[3] * 0.01, stamp[4] * 0.01, stamp[5] * 0.01, stamp[6] * 0.01, stamp[7] * 0.01);
+    fprintf(stderr, "[ss] lid %d gl %d st %d %d ctl %d %d %d %d flag %d eiginfo %d est %.3e rmax %.3e at %d lam0 %.3e lam[k-1] %.3e D00 %.3e D01 %.3e\n", lid, going_left,
+            e->host_st[0], e->host_st[1], ctl[0], ctl[1], ctl[2], ctl[3], flag, info, sqrt(r2), rmax, bad, lam[0], lam[ctl[0] > 0 ? ctl[0] - 1 : 0], D[0], D[1]);
 }
 
 // enqueue the whole solve; returns 1 if the on-device verification asks for the library fallback, 0 if E / lam / chi are
 // published, < 0 on a runtime error.  Synchronises the stream once (the verdict is read by the host).  Inside a sweep the
-// tridiagonalisation is the persistent kernel; if its workgroups could not all become resident within its patience it
-// gives up cleanly and the same bond is redone one launch per step.
+// tridiagonalisation is a persistent kernel; if its workgroups could not all become resident within its patience it
+// gives up cleanly and the same bond is redone by the next route of after_abort.
 int launch_eig_blocked(const View& v, int lid, int going_left, const double* rawG, int rawn, double* rawlam, double* rawE,
                        int32_t* rawinfo, BlockedEig* e, hipStream_t s) {
-    const BtBufs& b = e->b;
-    const int ncap = rawn > 0 ? rawn : b.ncap;
-    static const bool no_coop = getenv("MPST_BT_NO_COOP") != nullptr;
+    const EigSwitches& sw = eig_switches();
     if (rawn == 0 && blocked_eig_subspace_on(e)) {
         // the subspace solver first; its verdict is read here (this path synchronises per bond anyway), so the exact solve is
         // enqueued only when it is needed
@@ -2150,93 +2220,31 @@ int launch_eig_blocked(const View& v, int lid, int going_left, const double* raw
         if (hipMemcpyAsync(e->host_st, e->ss.st, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return MPST_ERR_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return MPST_ERR_DEVICE;
         if (hipGetLastError() != hipSuccess) return MPST_ERR_DEVICE;
-        static const bool dbg = getenv("MPST_SS_DEBUG") != nullptr;
-        if (dbg && e->host_st[1]) {
-            double res[CAP_LIMIT], lam[CAP_LIMIT], D[CAP_LIMIT];
-            int32_t ctl[4], flag, info;
-            (void)hipMemcpy(res, b.res, sizeof res, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(lam, b.lam, sizeof lam, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(D, b.D, sizeof D, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ctl, b.ctl, sizeof ctl, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&flag, b.flag, sizeof flag, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&info, e->ss.infoH, sizeof info, hipMemcpyDeviceToHost);
-            double r2 = 0, rmax = 0; int bad = -1;
-            for (int i = 0; i < ctl[0] && i < CAP_LIMIT; ++i) { r2 += res[i] * res[i]; if (res[i] > rmax) { rmax = res[i]; bad = i; } }
-            double stamp[8];
-            (void)hipMemcpy(stamp, e->ss.lamH + SS_PMAX, sizeof stamp, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[ss] chol phases: load %.2f us, elimination %.2f us | blocked: load %.2f, updates %.2f, diagonal blocks %.2f, panels %.2f, inverse %.2f, store %.2f us\n",
-                    stamp[0] * 0.01, stamp[1] * 0.01, stamp[2] * 0.01, stamp[3] * 0.01, stamp[4] * 0.01, stamp[5] * 0.01, stamp[6] * 0.01, stamp[7] * 0.01);
-            fprintf(stderr, "[ss] lid %d gl %d st %d %d ctl %d %d %d %d flag %d eiginfo %d est %.3e rmax %.3e at %d lam0 %.3e lam[k-1] %.3e D00 %.3e D01 %.3e\n", lid, going_left,
-                    e->host_st[0], e->host_st[1], ctl[0], ctl[1], ctl[2], ctl[3], flag, info, sqrt(r2), rmax, bad, lam[0], lam[ctl[0] > 0 ? ctl[0] - 1 : 0], D[0], D[1]);
-        }
+        if (sw.ss_debug && e->host_st[1]) dump_subspace_verdict(e, lid, going_left);
         if (e->host_st[0]) return 0;
     }
-    // mode 2: persistent kernel confined to one XCD; 1: persistent kernel across the XCDs; 0: one launch per step
-    int mode = (rawn == 0 && !no_coop) ? (xcd_usable(ncap) ? 2 : 1) : 0;
-    // pair mode: the Hermitian problem itself (k_bt_coop_c) - 4: confined to one XCD, 3: across the XCDs
-    if (rawn == 0 && !no_coop && cnative_usable(v, ncap)) mode = cnative_xcd_usable(ncap) ? 4 : 3;
+    RoutePick pick = pick_route(rawn > 0 ? rawn : e->b.ncap, v.zw, rawn > 0 ? Solve::Raw : Solve::Bond, sw);
     // after a persistent kernel ran out of patience (its workgroups could not all become resident: the GPU is shared with
     // other work) the next solves go straight to the launch-per-step path instead of each paying the wait again
-    if (mode && e->cooldown > 0) {
+    if (pick.route != Route::PerStep && e->cooldown > 0) {
         e->cooldown--;
-        mode = 0;
+        pick.route = Route::PerStep;
     }
     for (int attempt = 0; attempt < 3; ++attempt) {
-        if (mode) {
-            if (hipMemsetAsync(e->cp.counter, 0, 16, s) != hipSuccess) return MPST_ERR_DEVICE;
-            if (mode == 4 && cnative_xcd_mode(ncap) == 3)
-                hipLaunchKernelGGL(k_bt_coop_c<3>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(ncap), s, v, lid, going_left, b, e->cp, XCD_STRIDE, 0u, (const double*)nullptr, 0);
-            else if (mode == 4)
-                hipLaunchKernelGGL(k_bt_coop_c<1>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(ncap), s, v, lid, going_left, b, e->cp, XCD_STRIDE, ++e->seq, (const double*)nullptr, 0);
-            else if (mode == 3)
-                hipLaunchKernelGGL(k_bt_coop_c<0>, dim3(coopc_grid(ncap)), dim3(BTC_NT), coopc_lds(ncap), s, v, lid, going_left, b, e->cp, 1, 0u, (const double*)nullptr, 0);
-            else if (mode == 2)
-                hipLaunchKernelGGL((k_bt_coop<512, SC_XCD>), dim3(XCD_G * XCD_STRIDE), dim3(512), xcd_lds(ncap), s, v, lid, going_left, b, e->cp, XCD_STRIDE, ++e->seq);
-            else if (coop_threads() == 512)
-                hipLaunchKernelGGL((k_bt_coop<512, SC_AGENT>), dim3(coop_grid(ncap)), dim3(512), coop_lds(ncap), s, v, lid, going_left, b, e->cp, 1, 0u);
-            else
-                hipLaunchKernelGGL((k_bt_coop<256, SC_AGENT>), dim3(coop_grid(ncap)), dim3(256), coop_lds(ncap), s, v, lid, going_left, b, e->cp, 1, 0u);
-        } else {
-            hipLaunchKernelGGL(k_bt_prep, dim3(256), dim3(BT_T), 0, s, v, lid, going_left, rawG, rawn, b);
-            static const int bt_g = [] { const char* e = getenv("MPST_BT_G"); return e ? std::max(1, atoi(e)) : BT_G; }();
-            for (int j = 0; j <= ncap - 2; ++j) {
-                // fewer workgroups once the trailing matrix is small: the redundant prologue is paid per workgroup
-                const int m = ncap - 1 - j;
-                const int g = std::max(1, std::min(bt_g, (m + 3) / 4));
-                hipLaunchKernelGGL(k_bt_step, dim3(g), dim3(BT_T), 0, s, v, lid, going_left, rawn, b, j);
-            }
-        }
-        BtBufs bt = b;
-        bt.abort = mode ? e->cp.abort_flag : nullptr;
-        bt.cnative = mode >= 3 ? 1 : 0;
-        if (b.use_tail && mode < 3) {
-            // the last BT_TAIL steps on one CU (the kernels above stopped at step n - BT_TAIL; nothing to do for n <= BT_TAIL)
-            if (!mode) hipLaunchKernelGGL(k_bt_tail_prep, dim3(32), dim3(BT_T), 0, s, v, lid, going_left, rawn, b);
-            launch_eig_tail(v, lid, going_left, rawn, b.tailG, b.ncap, b.Vall, b.dd, b.ee, b.tau, bt.abort, bt.skip, s);
-        }
+        const bool persistent = pick.route != Route::PerStep;
+        const BtBufs bt = solve_bufs(e, pick.route);
+        if (enqueue_tridiag(pick, v, lid, going_left, rawG, rawn, bt, e, sw, s) != 0) return MPST_ERR_DEVICE;
         enqueue_after_tridiag(v, lid, going_left, rawG, rawn, rawlam, rawE, rawinfo, bt, s);
         e->host_flag[1] = 0;
-        if (hipMemcpyAsync(e->host_flag, b.flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return MPST_ERR_DEVICE;
-        if (mode && hipMemcpyAsync(e->host_flag + 1, e->cp.abort_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return MPST_ERR_DEVICE;
+        if (hipMemcpyAsync(e->host_flag, bt.flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return MPST_ERR_DEVICE;
+        if (persistent && hipMemcpyAsync(e->host_flag + 1, e->cp.abort_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return MPST_ERR_DEVICE;
         if (hipStreamSynchronize(s) != hipSuccess) return MPST_ERR_DEVICE;
         if (hipGetLastError() != hipSuccess) return MPST_ERR_DEVICE;
-        if (!(mode && e->host_flag[1])) break;
-        // the persistent kernel gave up: the same bond again - across the XCDs if only the placement was wrong (its
-        // workgroups were all there), else one launch per step
-        if (mode == 2 && e->host_flag[1] == ABORT_PLACEMENT) {
-            e->xcd_misplaced++;
-            mode = 1;
-        } else if (mode == 4 && e->host_flag[1] == ABORT_PLACEMENT) {
-            e->xcd_misplaced++;
-            mode = 3;           // the same reduction with the cross-XCD exchange
-        } else if (mode >= 3) {
-            e->coop_aborts++;
-            mode = 1;           // the embedded real reduction, across the XCDs
-        } else {
-            e->coop_aborts++;
-            e->cooldown = 32;
-            mode = 0;
-        }
+        if (!(persistent && e->host_flag[1])) break;
+        const Retry again = after_abort(pick.route, e->host_flag[1]);
+        (again.misplaced ? e->xcd_misplaced : e->coop_aborts)++;
+        if (again.next == Route::PerStep) e->cooldown = 32;
+        pick.route = again.next;
     }
     return *e->host_flag ? 1 : 0;
 }
@@ -2245,32 +2253,13 @@ int launch_eig_blocked(const View& v, int lid, int going_left, const double* raw
 // kernel that gave up leaves its mark in e->sticky, and the bonds after it run on whatever the failed one left - the
 // caller discards that sweep.  Returns 0 or a negative error.
 int launch_eig_blocked_nosync(const View& v, int lid, int going_left, BlockedEig* e, hipStream_t s) {
-    const BtBufs& b = e->b;
-    const int ncap = b.ncap;
-    static const bool no_coop = getenv("MPST_BT_NO_COOP") != nullptr;
-    if (no_coop) return MPST_ERR_UNSUPPORTED;
+    const EigSwitches& sw = eig_switches();
+    if (sw.no_coop) return MPST_ERR_UNSUPPORTED;
     const bool ss = blocked_eig_subspace_on(e);
     if (ss) enqueue_subspace(v, lid, going_left, e, s);      // the exact solve below leaves at once where its result stands
-    if (hipMemsetAsync(e->cp.counter, 0, 16, s) != hipSuccess) return MPST_ERR_DEVICE;
-    BtBufs bt = b;
-    bt.abort = e->cp.abort_flag;
-    bt.sticky = e->sticky;
-    bt.skip = ss ? e->ss.st : nullptr;
-    const bool nat = cnative_usable(v, ncap);
-    bt.cnative = nat ? 1 : 0;
-    if (nat && cnative_xcd_mode(ncap) == 3)
-        hipLaunchKernelGGL(k_bt_coop_c<3>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(ncap), s, v, lid, going_left, bt, e->cp, XCD_STRIDE, 0u, (const double*)nullptr, 0);
-    else if (nat && cnative_xcd_mode(ncap) == 1)
-        hipLaunchKernelGGL(k_bt_coop_c<1>, dim3(XCD_G * XCD_STRIDE), dim3(BTC_NT), coopc_xcd_lds(ncap), s, v, lid, going_left, bt, e->cp, XCD_STRIDE, ++e->seq, (const double*)nullptr, 0);
-    else if (nat)
-        hipLaunchKernelGGL(k_bt_coop_c<0>, dim3(coopc_grid(ncap)), dim3(BTC_NT), coopc_lds(ncap), s, v, lid, going_left, bt, e->cp, 1, 0u, (const double*)nullptr, 0);
-    else if (xcd_usable(ncap))
-        hipLaunchKernelGGL((k_bt_coop<512, SC_XCD>), dim3(XCD_G * XCD_STRIDE), dim3(512), xcd_lds(ncap), s, v, lid, going_left, bt, e->cp, XCD_STRIDE, ++e->seq);
-    else if (coop_threads() == 512)
-        hipLaunchKernelGGL((k_bt_coop<512, SC_AGENT>), dim3(coop_grid(ncap)), dim3(512), coop_lds(ncap), s, v, lid, going_left, bt, e->cp, 1, 0u);
-    else
-        hipLaunchKernelGGL((k_bt_coop<256, SC_AGENT>), dim3(coop_grid(ncap)), dim3(256), coop_lds(ncap), s, v, lid, going_left, bt, e->cp, 1, 0u);
-    if (b.use_tail && !nat) launch_eig_tail(v, lid, going_left, 0, b.tailG, b.ncap, b.Vall, b.dd, b.ee, b.tau, bt.abort, bt.skip, s);
+    const RoutePick pick = pick_route(e->b.ncap, v.zw, Solve::Bond, sw);
+    const BtBufs bt = solve_bufs(e, pick.route, nullptr, 0, e->sticky, ss ? e->ss.st : nullptr);
+    if (enqueue_tridiag(pick, v, lid, going_left, nullptr, 0, bt, e, sw, s) != 0) return MPST_ERR_DEVICE;
     enqueue_after_tridiag(v, lid, going_left, nullptr, 0, nullptr, nullptr, nullptr, bt, s);
     return 0;
 }

@@ -634,6 +634,20 @@ void launch_norm2(const View& v, double* out_norm2, double* gscratch /* 3*cap*ca
 void launch_scale_sites(const View& v, const double* norm2, hipStream_t s);
 void launch_selftest_mfma(const double* A, const double* B, int K, double* C, hipStream_t s);
 
+// A device allocation or an event that lives for one call: released when it goes out of scope, whichever return that is.  Move-only
+// (the move constructor leaves no copy operations).
+template <typename H, typename A, hipError_t (*Release)(A)>
+struct DevOwned {
+    H h = nullptr;
+    DevOwned() = default;
+    DevOwned(DevOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    ~DevOwned() { if (h) (void)Release(h); }
+    operator H() const { return h; }
+};
+template <typename T>
+using DevBuf = DevOwned<T*, void*, hipFree>;
+using DevEvent = DevOwned<hipEvent_t, hipEvent_t, hipEventDestroy>;
+
 // hand-written blocked eigensolver for d*chi_max > MAX_DIM (mpst_eig_blocked.hip); returns 1 when its on-device
 // verification asks for the library fallback
 struct BlockedEig;

@@ -241,14 +241,21 @@ def test_blocked_tridiagonalisation_is_deterministic(eng):
     assert info["large_bond"] and info["persistent_tridiag_aborts"] == 0 and info["library_eig_fallbacks"] == 0
 
 
-def test_sweep_reads_the_verdict_once_and_redoes_a_failed_sweep(engine_cls):
+@pytest.mark.parametrize("dtype", ["float64", "complex128"])
+def test_sweep_reads_the_verdict_once_and_redoes_a_failed_sweep(engine_cls, dtype):
     """Large bonds: mpst_sweep no longer synchronises with the host after every bond to read the eigensolver's verdict - it
     reads a sticky word once per sweep and, if any bond failed, redoes the sweep from a snapshot bond by bond (with the
     library fallback).  MPST_BIG_FORCE_FAIL marks one solve as failed: the redone sweep, and the sweep after it, must give
-    the bits of a context that reads the verdict after every bond (MPST_BIG_SYNC=1)."""
+    the bits of a context that reads the verdict after every bond (MPST_BIG_SYNC=1).  float64 goes through the real reduction on
+    one XCD; complex128 (one class, complex order 160, subspace block 64) through the Hermitian reduction from both launchers,
+    the complex subspace sequence and its Rayleigh-Ritz launch."""
     import os
-    N, T, d, chi0, chimax, C = 96, 5, 8, 14, 20, 2          # d*chi = 160 > 128
-    ds, W0 = make_problem(N, T, d, chi0, C, seed=3)
+    N, T, d, chi0, chimax = 96, 5, 8, 14, 20                # d*chi = 160 > 128
+    if dtype == "float64":
+        ds, W0 = make_problem(N, T, d, chi0, 2, seed=3)
+    else:
+        from oracle import ref_complex as RC
+        ds, W0 = RC.make_problem(N, T, d, chi0, 1, seed=3, dtype=np.complex128)
     opts = R.SweepOptions(nsweeps=2, chi_max=chimax, eta=0.05, loss_grad="KLD", bbopt="TSGO")
 
     def run(env):
@@ -391,3 +398,82 @@ def test_subspace_eigensolver_complex_bonds(dtype):
             assert worst[k] < tol[k], (k, worst)
     finally:
         eng.close()
+
+
+# ---- every documented route of the large-bond eigensolver, one child process per setting (the switches are read once per process) ----
+ROUTE_SETTINGS = [
+    # id, complex problem, environment
+    ("real-default", False, {}),
+    ("real-no-xcd", False, {"MPST_BT_NO_XCD": "1"}),
+    ("real-no-tail", False, {"MPST_BT_NO_TAIL": "1"}),
+    ("real-no-subspace", False, {"MPST_NO_SUBSPACE": "1"}),
+    ("complex-default", True, {}),
+    ("complex-no-cnative", True, {"MPST_BT_NO_CNATIVE": "1"}),
+    ("complex-counted", True, {"MPST_BT_C_XCD": "counted"}),
+]
+ROUTE_SWITCHES = sorted({k for _, _, env in ROUTE_SETTINGS for k in env})
+
+
+def _route_problem(cx):
+    if cx:
+        from oracle import ref_complex as RC
+        ds, W0 = RC.make_problem(96, 5, 8, 14, 1, seed=3, dtype=np.complex128)      # the complex shape of the verdict test above
+        return ds, W0, R.SweepOptions(nsweeps=1, chi_max=20, eta=0.05, loss_grad="KLD", bbopt="TSGO")
+    N, T, d, chi0, chimax, C, loss, bbopt = CASES[0]
+    ds, W0 = make_problem(N, T, d, chi0, C, seed=N + d)
+    return ds, W0, R.SweepOptions(nsweeps=1, chi_max=chimax, eta=0.05, loss_grad=loss, bbopt=bbopt)
+
+
+def _route_child(cx, out):
+    """Runs in the child: one sweep (and normalize for the real problem) under the child's environment -> MPS and info() in `out`."""
+    ds, W0, opts = _route_problem(cx)
+    eng = mt.SweepEngine(0)
+    try:
+        load_engine(eng, ds, W0, opts)
+        eng.build_caches()
+        eng.sweep()
+        if not cx:
+            eng.normalize()
+        info = eng.info()
+        W = eng.get_mps()
+    finally:
+        eng.close()
+    np.savez(out, *W, info=np.array([info["large_bond"], info["library_eig_fallbacks"], info["subspace_attempted"],
+                                     info["persistent_tridiag_aborts"], info["xcd_local_misplaced"]], dtype=np.int64))
+
+
+def test_every_documented_route_of_the_large_bond_eigensolver(tmp_path):
+    """Default, MPST_BT_NO_XCD, MPST_BT_NO_TAIL, MPST_NO_SUBSPACE on CASES[0] (real, d*chi = 160, two classes) and default,
+    MPST_BT_NO_CNATIVE, MPST_BT_C_XCD=counted on a complex problem (one class, complex order 160): one sweep each in a child process
+    of its own, one after the other, against the CPU restatement's sweep.  Real: overlaps after normalize within 1e-8 of the largest
+    (the bound of test_big_bond_sweep_bond_by_bond at this shape).  Complex: overlaps within TOL["f64"]["bond"] = 1e-8 of the
+    largest (gauge invariant, unlike the two-site tensors of a free-running chain).  Every setting's deviation is printed before it
+    is asserted; profiles/eig_host_refactor.txt records what was measured."""
+    import os
+    import subprocess
+    import sys
+    from oracle import ref_complex as RC
+    from tests.test_gpu_typed import TOL
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ref = {}
+    for cx in (False, True):
+        ds, W0, opts = _route_problem(cx)
+        Wo = [t.copy() for t in W0]
+        (RC if cx else R).sweep(Wo, ds, opts)
+        ref[cx] = (ds, R.contract_mps(Wo if cx else R.normalize_mps(Wo), ds.phi))
+    base = {k: v for k, v in os.environ.items() if k not in ROUTE_SWITCHES}
+    base["PYTHONPATH"] = root + os.pathsep + os.environ.get("PYTHONPATH", "")
+    for name, cx, env in ROUTE_SETTINGS:
+        out = str(tmp_path / (name + ".npz"))
+        code = "import sys; sys.path.insert(0, %r); from tests.test_gpu_bigbond import _route_child; _route_child(%r, %r)" % (root, cx, out)
+        run = subprocess.run([sys.executable, "-c", code], env=dict(base, **env), capture_output=True, text=True, timeout=120)
+        assert run.returncode == 0, (name, run.stderr[-2000:])
+        with np.load(out) as z:
+            W = [z["arr_%d" % j] for j in range(len(z.files) - 1)]
+            large, fallbacks, attempted, aborts, misplaced = (int(x) for x in z["info"])
+        ds, yo = ref[cx]
+        dev = np.abs(R.contract_mps(W, ds.phi) - yo).max() / np.abs(yo).max()
+        print(f"{name}: deviation {dev:.3e}, subspace_attempted {attempted}, persistent_tridiag_aborts {aborts}, xcd_local_misplaced {misplaced}")
+        assert large and fallbacks == 0, (name, large, fallbacks)
+        assert (attempted == 0) if "MPST_NO_SUBSPACE" in env else (attempted > 0), (name, attempted)
+        assert dev <= (TOL["f64"]["bond"] if cx else 1e-8), (name, dev)
