@@ -196,6 +196,26 @@ int  mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* l
  * eo as for mpst_encode_dataset (fits returned in it); oob_fix [N][2] or NULL. */
 int  mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, void* phi_out,
                         double* oob_fix, double* seconds);
+/* Split bases (src/Encodings/splitbases.jl; histogram_split / uniform_split, basis_structs.jl:247-279): the input range is cut
+ * into nbins bins, every bin carries its own copy of an auxiliary closed-form basis of aux_dim states, d = nbins * aux_dim.  A value
+ * in bin i is encoded as the auxiliary basis at a + (b - a) (x - bins[i]) / (bins[i+1] - bins[i]) in the entries of bin i and zero
+ * elsewhere; a value exactly on an interior edge gives half of the auxiliary state in both neighbours, the outermost edges weight 1
+ * (rect and project_onto_bins, splitbases.jl:96-132, same comparisons on the same expression; an empty bin selects nothing).
+ *   aux_basis  MPST_BASIS_* of the auxiliary basis (Stoudenmire: aux_dim = 2, Sahand: even aux_dim)
+ *   bins       the edges the host fitted (hist_split :56-92 per time point, unif_split :51-54), non-decreasing, in the encoding's
+ *              range: [T][nbins + 1] with per_site = 1 (histogram_split), [nbins + 1] shared by all sites with per_site = 0
+ * mpst_encode_split_dataset / mpst_encode_split_values are mpst_encode_dataset / mpst_encode_values with eo->basis ignored in favour
+ * of sp->aux_basis.  MPST_ERR_INVALID: NULL sp / bins, nbins < 1 or > 512, d != nbins * aux_dim, decreasing edges;
+ * MPST_ERR_UNSUPPORTED: an auxiliary basis outside the six, Stoudenmire with aux_dim != 2, Sahand with odd aux_dim. */
+typedef struct {
+    int32_t aux_basis, aux_dim, nbins, per_site;
+    const double* bins;
+} mpst_split_opts;
+int  mpst_encode_split_dataset(void* ctx, int which, const double* X, const int32_t* label_idx,
+                               int64_t N, int32_t T, int32_t d, int32_t C, mpst_encode_opts* eo, const mpst_split_opts* sp,
+                               const int64_t* n_global_per_class, double* oob_fix, double* seconds);
+int  mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo,
+                              const mpst_split_opts* sp, void* phi_out, double* oob_fix, double* seconds);
 /* Encoded values of data set `which` back to the host, [N][T][d] in the context's element type
  * (EncodedTimeSeriesSet.timeseries). */
 int  mpst_get_encoded(void* ctx, int which, double* phi_out);
@@ -275,7 +295,10 @@ int  mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const
  *   missing[N][T]   1 where the value is to be imputed (row-major, instances in the order of the data set);
  *                   the encoded values the data set holds at those sites are ignored
  *   grid_x[ngrid]   the candidate values x_k (range(guess_range...; step = dx), imputation.jl:90) and
- *   grid_phi[ngrid][d]  their encoded states (time-independent encodings, :100-106)
+ *   grid_phi[ngrid][d]  their encoded states (time-independent encodings, :100-106); with o->grid_per_site = 1
+ *                   grid_phi[T][ngrid][d], one table per site (time-dependent encodings, :92-99): the state of grid value k at
+ *                   site t is row t * ngrid + k.  A per-site table is never recognised as a closed-form grid: the call evaluates
+ *                   the densities from the table, one instance per workgroup.  MPST_IMPUTE_MEAN with it: MPST_ERR_UNSUPPORTED
  *   o->method       MPST_IMPUTE_MEDIAN (+ weighted median absolute deviation when get_err), MPST_IMPUTE_MODE,
  *                   MPST_IMPUTE_QUANTILE: inverse-transform sampling with the caller's uniform numbers (impute_ITS with
  *                   rejection_threshold = :none; the reference draws them from a MersenneTwister),
@@ -301,7 +324,7 @@ typedef struct {
     int32_t get_err;                /* get_wmad (median) / get_std (mean) */
     int32_t max_trials;             /* ITS_REJECT only (reference default 10) */
     int32_t mean_basis;             /* MEAN only */
-    int32_t reserved;
+    int32_t grid_per_site;          /* 0: grid_phi[ngrid][d] shared by all sites, 1: grid_phi[T][ngrid][d]; else MPST_ERR_INVALID */
     double  rejection_threshold;    /* ITS_REJECT only */
 } mpst_impute_opts;
 int  mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,

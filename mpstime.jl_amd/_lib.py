@@ -47,13 +47,18 @@ class mpst_encode_opts(C.Structure):
                 ("data_lb", C.c_double), ("data_ub", C.c_double), ("range_a", C.c_double), ("range_b", C.c_double)]
 
 
+class mpst_split_opts(C.Structure):
+    _fields_ = [("aux_basis", C.c_int32), ("aux_dim", C.c_int32), ("nbins", C.c_int32), ("per_site", C.c_int32),
+                ("bins", C.POINTER(C.c_double))]
+
+
 BASIS = {"Legendre_Norm": 0, "Legendre_No_Norm": 1, "Fourier": 2, "Stoudenmire": 3, "Sahand": 4, "Uniform": 5}      # canonical names (options.jl:243-279; :Legendre == :Legendre_No_Norm)
 
 # every symbol include/mpstime_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dp = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double)
 class ImputeOpts(C.Structure):          # mpst_impute_opts
     _fields_ = [("method", C.c_int32), ("order", C.c_int32), ("get_err", C.c_int32), ("max_trials", C.c_int32),
-                ("mean_basis", C.c_int32), ("reserved", C.c_int32), ("rejection_threshold", C.c_double)]
+                ("mean_basis", C.c_int32), ("grid_per_site", C.c_int32), ("rejection_threshold", C.c_double)]
 
 
 class ImputeModel(C.Structure):         # mpst_impute_model
@@ -78,6 +83,9 @@ SYMBOLS = {
     "mpst_encode_dataset": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(_i32), _i64, _i32, _i32, _i32, C.POINTER(mpst_encode_opts),
                                       C.POINTER(_i64), _dp, _dp]),
     "mpst_encode_values": (C.c_int, [_vp, _dp, _i64, _i32, _i32, C.POINTER(mpst_encode_opts), _vp, _dp, _dp]),
+    "mpst_encode_split_dataset": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(_i32), _i64, _i32, _i32, _i32, C.POINTER(mpst_encode_opts),
+                                            C.POINTER(mpst_split_opts), C.POINTER(_i64), _dp, _dp]),
+    "mpst_encode_split_values": (C.c_int, [_vp, _dp, _i64, _i32, _i32, C.POINTER(mpst_encode_opts), C.POINTER(mpst_split_opts), _vp, _dp, _dp]),
     "mpst_get_encoded": (C.c_int, [_vp, C.c_int, _dp]),
     "mpst_set_options": (C.c_int, [_vp, C.POINTER(mpst_options)]),
     "mpst_set_mps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i32), _i32, _i32]),

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .encodings import model_encoding, transform_test_data, transform_train_data
+from .encodings import fit_encoding_from_training_data, transform_test_data, transform_train_data
 from .engine import SweepEngine, _site_to_abi
 from .options import safe_options
 
@@ -114,10 +114,10 @@ def see_variation(W, measure_series, cls: int = 0, engine: Optional[SweepEngine]
     if X.shape[0] == 0:
         return np.zeros((0, T, T))
     opts = safe_options(W.opts)
-    enc = model_encoding(opts.encoding)
+    enc, _, encoder = fit_encoding_from_training_data(opts, W.train_data.original_data, W.train_data.labels)
     _, norms = transform_train_data(W.train_data.original_data, opts, enc.range)
     scaled, _ = transform_test_data(X, norms, opts, enc.range)
-    phi = enc.encode(scaled, opts.d)
+    phi = encoder(scaled)
     if np.iscomplexobj(phi):
         raise ValueError(f"entanglement analysis with the complex encoding {enc.name} is not supported (Float64 only)")
     m = _Model(W, phi)

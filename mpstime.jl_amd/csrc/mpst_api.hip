@@ -1360,10 +1360,17 @@ int mpst_set_dataset(void* ctx, int which, const void* phi_, const int32_t* labe
 
 // preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
 // mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
-static int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, double* dphi, double* oob_fix,
-                       double* seconds) {
+// sp: a split basis over eo->basis (its edges are uploaded for the call), or null
+static int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp, double* dphi,
+                       double* oob_fix, double* seconds) {
     int rc;
     if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
+    DevBuf<double> dbins;
+    if (sp) {
+        const size_t nedge = (size_t)(sp->per_site ? T : 1) * (size_t)(sp->nbins + 1);
+        if ((rc = dalloc(c, dbins, (int64_t)nedge))) return rc;
+        HIPC(c, hipMemcpy(dbins, sp->bins, nedge * sizeof(double), hipMemcpyHostToDevice));
+    }
     const bool fit_sig = eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test;
     if (eo->fit_sigmoid && eo->is_test) return fail(c, MPST_ERR_INVALID, "fit_sigmoid: the RobustSigmoid is fitted on the training set only");
     if (eo->sigmoid_transform && !fit_sig && !(eo->iqr > 0.0)) return fail(c, MPST_ERR_INVALID, "robust sigmoid needs iqr > 0");
@@ -1413,8 +1420,13 @@ static int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d,
     e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax; e.is_test = test;
     e.med = eo->median; e.s = eo->iqr / 1.35;
     e.lb = eo->data_lb; e.ub = eo->data_ub; e.a = eo->range_a; e.b = eo->range_b;
-    e.nrm = std::sqrt(std::sqrt((2 * d + 1) / 2.0) * d);
+    const int bd = sp ? sp->aux_dim : d;         // the closed-form basis' own dimension
+    e.nrm = std::sqrt(std::sqrt((2 * bd + 1) / 2.0) * bd);
     e.lohi = lohi; e.fix = fix;
+    if (sp) {
+        e.bins = dbins; e.bin_stride = sp->per_site ? sp->nbins + 1 : 0;
+        e.nbins = sp->nbins; e.aux_dim = sp->aux_dim;
+    }
     HIPC(c, hipEventRecord(c->ev_start, c->stream));
     launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
     HIPC(c, hipEventRecord(c->ev_stop, c->stream));
@@ -1433,18 +1445,49 @@ static int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d,
     return 0;
 }
 
-int mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
-                        int32_t C, mpst_encode_opts* eo, const int64_t* n_global_per_class, double* oob_fix, double* seconds) {
+static bool basis_is_complex(int basis) { return basis == MPST_BASIS_FOURIER || basis == MPST_BASIS_STOUDENMIRE || basis == MPST_BASIS_SAHAND; }
+
+// the checks of a split request (include/mpstime_hip.h); on success eo->basis is the auxiliary basis
+static int split_validate(Ctx* c, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp) {
+    if (!sp || !sp->bins) return fail(c, MPST_ERR_INVALID, "NULL split options or bin edges");
+    if (sp->nbins < 1 || sp->nbins > 512) return fail(c, MPST_ERR_INVALID, "nbins must lie in 1 .. 512 (got %d)", (int)sp->nbins);
+    if (sp->aux_dim < 1 || (int64_t)sp->nbins * sp->aux_dim != d)
+        return fail(c, MPST_ERR_INVALID, "The auxilliary basis dimension (%d) must evenly divide the total feature dimension (%d): d = nbins * aux_dim, nbins = %d",
+                    (int)sp->aux_dim, (int)d, (int)sp->nbins);       // get_nbins_safely, splitbases.jl:2-9
+    if (sp->per_site != 0 && sp->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
+    if (sp->aux_basis < MPST_BASIS_LEGENDRE || sp->aux_basis > MPST_BASIS_UNIFORM)
+        return fail(c, MPST_ERR_UNSUPPORTED, "split bases are implemented over the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
+    if (sp->aux_basis == MPST_BASIS_STOUDENMIRE && sp->aux_dim != 2) return fail(c, MPST_ERR_UNSUPPORTED, "Stoudenmire Angle encoding only supports d = 2!");
+    if (sp->aux_basis == MPST_BASIS_SAHAND && sp->aux_dim % 2) return fail(c, MPST_ERR_UNSUPPORTED, "Sahand encoding only supports even dimension");
+    const int64_t nsite = sp->per_site ? T : 1, ne = sp->nbins + 1;
+    for (int64_t t = 0; t < nsite; ++t)
+        for (int64_t k = 0; k + 1 < ne; ++k)
+            if (!(sp->bins[t * ne + k] <= sp->bins[t * ne + k + 1]))
+                return fail(c, MPST_ERR_INVALID, "bin edges must be non-decreasing (site %lld, edges %lld and %lld: %g, %g)", (long long)t, (long long)k,
+                            (long long)(k + 1), sp->bins[t * ne + k], sp->bins[t * ne + k + 1]);
+    eo->basis = sp->aux_basis;
+    return 0;
+}
+
+// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset
+static int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
+                          mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
+                          double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
-        return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-    if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
-    if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
+    if (split) {
+        if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
+        if (int rc = split_validate(c, T, d, eo, sp)) return rc;
+    } else {
+        if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
+            return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
+        if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
+        if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
+    }
     if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
     // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
-    const bool bcx = eo->basis == MPST_BASIS_FOURIER || eo->basis == MPST_BASIS_STOUDENMIRE || eo->basis == MPST_BASIS_SAHAND;
+    const bool bcx = basis_is_complex(eo->basis);
     const int natural = bcx ? MPST_C128 : MPST_F64;
     const int want = c->have_dtype ? c->dtype : natural;
     if (bcx && (want == MPST_F64 || want == MPST_F32))
@@ -1453,32 +1496,48 @@ int mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* la
     if (rc) return rc;
     rc = dataset_common(c, which, label_idx, N, T, d, C, n_global_per_class, X != nullptr);
     if (rc || N == 0) return rc;
-    if (want == natural) return encode_core(c, X, N, T, d, eo, c->ds[which].phi, oob_fix, seconds);
+    if (want == natural) return encode_core(c, X, N, T, d, eo, sp, c->ds[which].phi, oob_fix, seconds);
     double* tmp = nullptr;
     struct T1 {
         double** a;
         ~T1() { dfree(a); }
     } t1{&tmp};
     if ((rc = dalloc(c, &tmp, N * T * d * (bcx ? 2 : 1)))) return rc;
-    if ((rc = encode_core(c, X, N, T, d, eo, tmp, oob_fix, seconds))) return rc;
+    if ((rc = encode_core(c, X, N, T, d, eo, sp, tmp, oob_fix, seconds))) return rc;
     launch_tcast(tmp, bcx ? 1 : 0, c->ds[which].phi, c->zw == 2, want == MPST_F32 || want == MPST_C64, N * T * d, c->stream);
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
-int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, void* phi_out, double* oob_fix,
-                       double* seconds) {
+int mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
+                        int32_t C, mpst_encode_opts* eo, const int64_t* n_global_per_class, double* oob_fix, double* seconds) {
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds);
+}
+
+int mpst_encode_split_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
+                              int32_t C, mpst_encode_opts* eo, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
+                              double* seconds) {
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, true, sp, n_global_per_class, oob_fix, seconds);
+}
+
+// mpst_encode_values and, with split = true, mpst_encode_split_values
+static int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
+                         void* phi_out, double* oob_fix, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-    if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
-        return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-    if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
-    if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
+    if (split) {
+        if (int rc = split_validate(c, T, d, eo, sp)) return rc;
+    } else {
+        if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
+            return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
+        if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
+        if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
+    }
     HIPC(c, hipSetDevice(c->device));
-    const int zw = (eo->basis == MPST_BASIS_FOURIER || eo->basis == MPST_BASIS_STOUDENMIRE || eo->basis == MPST_BASIS_SAHAND) ? 2 : 1;
+    const int zw = basis_is_complex(eo->basis) ? 2 : 1;
     double* dphi = nullptr;
     struct T1 {
         double** a;
@@ -1486,7 +1545,7 @@ int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t
     } t1{&dphi};
     int rc;
     if ((rc = dalloc(c, &dphi, N * T * d * zw))) return rc;
-    if ((rc = encode_core(c, X, N, T, d, eo, dphi, oob_fix, seconds))) return rc;
+    if ((rc = encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds))) return rc;
     std::vector<double> tmp((size_t)N * T * d * zw);
     HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
     double* out = (double*)phi_out;
@@ -1494,6 +1553,16 @@ int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t
     for (int64_t i = 0; i < N; ++i)
         for (int t = 0; t < T; ++t) memcpy(&out[((size_t)i * T + t) * w], &tmp[((size_t)t * N + i) * w], w * sizeof(double));
     return 0;
+}
+
+int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, void* phi_out, double* oob_fix,
+                       double* seconds) {
+    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds);
+}
+
+int mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
+                             void* phi_out, double* oob_fix, double* seconds) {
+    return encode_values(ctx, X, N, T, d, eo, true, sp, phi_out, oob_fix, seconds);
 }
 
 int mpst_get_encoded(void* ctx, int which, double* phi_out) {
@@ -2264,8 +2333,13 @@ struct ImputeRequest {
     int32_t nq = 0, cdf_stride = 0, cdf_rows = 0;
     const double* levels = nullptr;
     double *q_out = nullptr, *cdf_out = nullptr;
+    bool grid_per_site() const { return o && o->grid_per_site == 1; }      // grid_phi is [T][ngrid][d]
 };
 constexpr int IMPUTE_MAX_LEVELS = 16;
+// doubles of the grid table(s) a request hands over
+static int64_t impute_grid_doubles(const ImpModel& m, const ImputeRequest& r) {
+    return (int64_t)(r.grid_per_site() ? m.T : 1) * r.ngrid * m.d * (m.is_complex ? 2 : 1);
+}
 
 // what a valid request comes to, and how its instances are dealt out
 struct ImputePlan {
@@ -2280,6 +2354,7 @@ struct ImputePlan {
 static int impute_validate(Ctx* c, const ImpModel& m, const ImputeRequest& r, ImputePlan* p) {
     const mpst_impute_opts* o = r.o;
     if (!r.missing || !r.grid_x || !r.grid_phi || !r.x_out || !o || r.ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
+    if (o->grid_per_site != 0 && o->grid_per_site != 1) return fail(c, MPST_ERR_INVALID, "grid_per_site must be 0 (grid_phi[ngrid][d]) or 1 (grid_phi[T][ngrid][d]), got %d", (int)o->grid_per_site);
     if (r.dist) {
         // get_cdfs refuses every other method (imputation.jl:594-596)
         if (o->method != MPST_IMPUTE_MEDIAN) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs are read off the median imputer's distribution: method must be MPST_IMPUTE_MEDIAN");
@@ -2306,6 +2381,9 @@ static int impute_validate(Ctx* c, const ImpModel& m, const ImputeRequest& r, Im
         return fail(c, MPST_ERR_UNSUPPORTED, "the device generator's counter holds T <= %d sites and max_trials <= %d (got %d, %d): pass u",
                     IMPUTE_SEED_MAX_SITES, IMPUTE_SEED_MAX_TRIALS, m.T, p->ntrial);
     if (method == MPST_IMPUTE_ITS_REJECT && !(o->rejection_threshold >= 0.0)) return fail(c, MPST_ERR_INVALID, "rejection_threshold must be non-negative");
+    if (method == MPST_IMPUTE_MEAN && o->grid_per_site)
+        return fail(c, MPST_ERR_UNSUPPORTED, "the mean method re-encodes the expectation value with one closed-form basis: not with a per-site grid table "
+                                             "(time-dependent encodings)");
     if (method == MPST_IMPUTE_MEAN) {
         const int mb = o->mean_basis;
         const bool real_ok = mb == MPST_BASIS_LEGENDRE || mb == MPST_BASIS_LEGENDRE_NO_NORM || mb == MPST_BASIS_UNIFORM;
@@ -2369,6 +2447,8 @@ static int impute_plan_chunk(Ctx* c, const ImpModel& m, const ImputeRequest& r, 
         budget = std::max(budget - extra, (double)per_bytes);
     }
     if (r.nq > 0) budget = std::max(budget - (double)(N * T * r.nq) * (double)sizeof(double), (double)per_bytes);
+    // (a per-site table is T times the shared one - 128 MB at configs[4] - and lives for the whole call)
+    if (r.grid_per_site()) budget = std::max(budget - (double)impute_grid_doubles(m, r) * (double)sizeof(double), (double)per_bytes);
     if (r.dist && (double)per_bytes > 0.9 * (double)free_b)       // (the calls without distribution outputs are left as they were)
         return fail(c, MPST_ERR_NOMEM, "one instance needs %.3f GB of device scratch (%d environments, densities%s), %.3f GB are free: "
                     "not even a block of one instance fits", (double)per_bytes / (double)(1ull << 30), p->maxm,
@@ -2390,7 +2470,7 @@ struct ImputeBufs {
 
 static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, ImputeBufs* b) {
     const int64_t N = m.N, K = r.K, chunk = p.chunk;
-    const int T = m.T, d = m.d, zw = m.is_complex ? 2 : 1, ngrid = r.ngrid;
+    const int T = m.T, zw = m.is_complex ? 2 : 1, ngrid = r.ngrid;
     const size_t esz = m.compute_f32 ? 4 : 8, nout = (size_t)N * K * T;
     const bool have_u = p.sampling && !p.seeded;
     int rc;
@@ -2401,7 +2481,7 @@ static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     }
     if (p.cdf_inst > 0 && (rc = dalloc(c, b->cdf, chunk * p.cdf_inst))) return rc;
     if ((rc = dalloc(c, b->miss, N * T)) || (rc = dalloc(c, b->R, (int64_t)(chunk * p.maxm * m.cap * m.cap * zw * esz))) ||
-        (rc = dalloc(c, b->gx, ngrid)) || (rc = dalloc(c, b->gp, (int64_t)ngrid * d * zw)) || (rc = dalloc(c, b->p, chunk * K * ngrid)) ||
+        (rc = dalloc(c, b->gx, ngrid)) || (rc = dalloc(c, b->gp, impute_grid_doubles(m, r))) || (rc = dalloc(c, b->p, chunk * K * ngrid)) ||
         (rc = dalloc(c, b->S, chunk * K * ngrid)) || (rc = dalloc(c, b->x, N * K * T)) || (rc = dalloc(c, b->e, N * K * T))) return rc;
     if (have_u && (rc = dalloc(c, b->u, N * K * T * p.ntrial))) return rc;
     if (p.seeded && r.row_id) {
@@ -2413,7 +2493,7 @@ static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     if (p.welems && (rc = dalloc(c, b->W, (int64_t)(chunk * p.welems * esz)))) return rc;
     HIPC(c, hipMemcpy(b->miss, r.missing, (size_t)N * T, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(b->gx, r.grid_x, (size_t)ngrid * sizeof(double), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(b->gp, r.grid_phi, (size_t)ngrid * d * zw * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(b->gp, r.grid_phi, (size_t)impute_grid_doubles(m, r) * sizeof(double), hipMemcpyHostToDevice));
     if (have_u) HIPC(c, hipMemcpy(b->u, r.u, (size_t)N * K * T * p.ntrial * sizeof(double), hipMemcpyHostToDevice));
     HIPC(c, hipMemset(b->x, 0, nout * sizeof(double)));
     HIPC(c, hipMemset(b->e, 0, nout * sizeof(double)));
@@ -2424,8 +2504,10 @@ static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
 static int impute_params(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, ImputeBufs* b, ImputeParams* q) {
     std::vector<double> lin;
     ImpArgs& g = q->g;
-    q->trig = m.is_complex ? (fourier_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu) ? 1 : 0)
-                           : (legendre_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu, &lin) ? 1 : 0);
+    // (a per-site table is never looked at for a closed form: the call takes the table route, one instance per workgroup)
+    q->trig = r.grid_per_site() ? 0
+              : m.is_complex ? (fourier_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu) ? 1 : 0)
+                             : (legendre_grid(r.grid_x, (const double*)r.grid_phi, r.ngrid, m.d, &g.x0, &g.dxu, &lin) ? 1 : 0);
     c->impute_trig = q->trig;
     if (!lin.empty()) {
         if (int rc = dalloc(c, b->lin, (int64_t)lin.size())) return rc;
@@ -2437,6 +2519,7 @@ static int impute_params(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     g.Rbuf = b->R;
     g.grid_x = b->gx;
     g.grid_phi = b->gp;
+    g.grid_site_stride = r.grid_per_site() ? (int64_t)r.ngrid * m.d * (m.is_complex ? 2 : 1) : 0;
     g.u = b->u;
     g.pbuf = b->p;
     g.sbuf = b->S;

@@ -1,4 +1,4 @@
-// mpst_encode.hip - device-side preprocessing + Legendre encoding.
+// mpst_encode.hip - device-side preprocessing + encoding: the closed-form bases and the split bases over them.
 //
 // Replaces, for the real bases the array sweep can train on, the host pipeline
 //   transform_train_data / transform_test_data  (src/utils.jl:161-275)
@@ -91,70 +91,56 @@ __global__ __launch_bounds__(256) void k_enc_series_fix(EncDev e, const double* 
     }
 }
 
-// one thread per (site, series); consecutive threads = consecutive series, so the d values every
-// thread writes are contiguous across the wave ([T][N][d] site-major, the sweep's layout)
-__global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= e.N * e.T) return;
-    const int64_t t = idx / e.N, i = idx - t * e.N;
-    double x = enc_stage2(e, X[i * e.T + t]);
-    if (e.fix) {
-        const double shift = e.fix[2 * i], scale = e.fix[2 * i + 1];
-        if (shift != 0.0) x -= shift;
-        if (scale != 1.0) x /= scale;
-    }
-    x = (e.b - e.a) * x + e.a;
-    if (e.basis == MPST_BASIS_STOUDENMIRE) {
-        // angle_encode (bases.jl:7-21, periods = 1/4): cispi(3x/2) cospi(x/2), cispi(-3x/2) sinpi(x/2)
-        double* outc = phi + idx * 4;
+// ---- the closed-form bases (src/Encodings/bases.jl), one helper each: k_encode writes the states as they are, k_encode_split
+// (SCALE) writes w times the state - w is rect's 1 or 0.5, so the product is exact ----------------------------------------------
+template <bool SCALE> __device__ __forceinline__ double enc_w(double v, double w) {
+    if constexpr (SCALE) return v * w;
+    else return v;
+}
+// angle_encode (bases.jl:7-21, periods = 1/4): cispi(3x/2) cospi(x/2), cispi(-3x/2) sinpi(x/2)
+template <bool SCALE> __device__ __forceinline__ void enc_stoudenmire(double x, double w, double* outc) {
+    double s3, c3, sh, ch;
+    sincospi(1.5 * x, &s3, &c3);
+    sincospi(0.5 * x, &sh, &ch);
+    outc[0] = enc_w<SCALE>(c3 * ch, w);
+    outc[1] = enc_w<SCALE>(s3 * ch, w);
+    outc[2] = enc_w<SCALE>(c3 * sh, w);
+    outc[3] = enc_w<SCALE>(-s3 * sh, w);
+}
+// sahand_encode (bases.jl:45-68): d/2 intervals of width 2/d, two states each, zero outside their interval
+template <bool SCALE> __device__ __forceinline__ void enc_sahand(double x, int d, double w, double* outc) {
+    const double dxs = 2.0 / d;
+    for (int k = 0; k < d; ++k) {
+        const int interval = k / 2 + 1;
+        const double startx = (interval - 1) * dxs;
+        const bool inside = startx <= x && x <= interval * dxs;
         double s3, c3, sh, ch;
-        sincospi(1.5 * x, &s3, &c3);
-        sincospi(0.5 * x, &sh, &ch);
-        outc[0] = c3 * ch;
-        outc[1] = s3 * ch;
-        outc[2] = c3 * sh;
-        outc[3] = -s3 * sh;
-        return;
+        sincospi(1.5 * x / dxs, &s3, &c3);
+        sincospi(0.5 * (x - startx) / dxs, &sh, &ch);
+        const bool odd = (k & 1) == 0;
+        outc[2 * k] = inside ? enc_w<SCALE>(odd ? c3 * ch : c3 * sh, w) : 0.0;
+        outc[2 * k + 1] = inside ? enc_w<SCALE>(odd ? s3 * ch : -s3 * sh, w) : 0.0;
     }
-    if (e.basis == MPST_BASIS_SAHAND) {
-        // sahand_encode (bases.jl:45-68): d/2 intervals of width 2/d, two states each, zero outside their interval
-        double* outc = phi + idx * e.d * 2;
-        const double dxs = 2.0 / e.d;
-        for (int k = 0; k < e.d; ++k) {
-            const int interval = k / 2 + 1;
-            const double startx = (interval - 1) * dxs;
-            const bool inside = startx <= x && x <= interval * dxs;
-            double s3, c3, sh, ch;
-            sincospi(1.5 * x / dxs, &s3, &c3);
-            sincospi(0.5 * (x - startx) / dxs, &sh, &ch);
-            const bool odd = (k & 1) == 0;
-            outc[2 * k] = inside ? (odd ? c3 * ch : c3 * sh) : 0.0;
-            outc[2 * k + 1] = inside ? (odd ? s3 * ch : -s3 * sh) : 0.0;
-        }
-        return;
+}
+// uniform_encode (bases.jl:2-4)
+template <bool SCALE> __device__ __forceinline__ void enc_uniform(int d, double w, double* outu) {
+    for (int k = 0; k < d; ++k) outu[k] = enc_w<SCALE>(1.0 / d, w);
+}
+// fourier_encode (bases.jl:23-42): cispi(f x) / sqrt(d) with f = 0, 1, -1, 2, -2, ...
+template <bool SCALE> __device__ __forceinline__ void enc_fourier(double x, int d, double w, double* outc) {
+    const double inv = 1.0 / sqrt((double)d);
+    for (int k = 0; k < d; ++k) {
+        const int f = (k + 1) / 2 * ((k & 1) ? 1 : -1);
+        double sn, cs;
+        sincospi((double)f * x, &sn, &cs);
+        outc[2 * k] = enc_w<SCALE>(cs * inv, w);
+        outc[2 * k + 1] = enc_w<SCALE>(sn * inv, w);
     }
-    if (e.basis == MPST_BASIS_UNIFORM) {
-        double* outu = phi + idx * e.d;
-        for (int k = 0; k < e.d; ++k) outu[k] = 1.0 / e.d;        // uniform_encode (bases.jl:2-4)
-        return;
-    }
-    if (e.fourier) {
-        // fourier_encode (bases.jl:23-42): cispi(f x) / sqrt(d) with f = 0, 1, -1, 2, -2, ...
-        double* outc = phi + idx * e.d * 2;
-        const double inv = 1.0 / sqrt((double)e.d);
-        for (int k = 0; k < e.d; ++k) {
-            const int f = (k + 1) / 2 * ((k & 1) ? 1 : -1);
-            double sn, cs;
-            sincospi((double)f * x, &sn, &cs);
-            outc[2 * k] = cs * inv;
-            outc[2 * k + 1] = sn * inv;
-        }
-        return;
-    }
-    double* out = phi + idx * e.d;
-    // Bonnet recursion, then sqrt((2k+1)/2) (normalised Legendre), then the optional 1/nrm (bases.jl:77-92)
+}
+// Bonnet recursion, then sqrt((2k+1)/2) (normalised Legendre), then the optional 1/nrm (bases.jl:77-92)
+template <bool SCALE> __device__ __forceinline__ void enc_legendre(double x, int d, bool norm, double nrm, double w, double* out) {
     double p0 = 1.0, p1 = x;
-    for (int k = 0; k < e.d; ++k) {
+    for (int k = 0; k < d; ++k) {
         double p;
         if (k == 0) p = 1.0;
         else if (k == 1) p = x;
@@ -165,8 +151,66 @@ __global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restri
             p1 = p;
         }
         double v = p * sqrt((2.0 * k + 1.0) / 2.0);
-        if (e.norm) v = v / e.nrm;
-        out[k] = v;
+        if (norm) v = v / nrm;
+        out[k] = enc_w<SCALE>(v, w);
+    }
+}
+// d states of basis `basis` at x: d doubles (real bases) or d (re, im) pairs
+template <bool SCALE> __device__ __forceinline__ void enc_basis(int basis, double x, int d, double nrm, double w, double* out) {
+    if (basis == MPST_BASIS_STOUDENMIRE) enc_stoudenmire<SCALE>(x, w, out);
+    else if (basis == MPST_BASIS_SAHAND) enc_sahand<SCALE>(x, d, w, out);
+    else if (basis == MPST_BASIS_UNIFORM) enc_uniform<SCALE>(d, w, out);
+    else if (basis == MPST_BASIS_FOURIER) enc_fourier<SCALE>(x, d, w, out);
+    else enc_legendre<SCALE>(x, d, basis == MPST_BASIS_LEGENDRE, nrm, w, out);
+}
+
+// the value of (site t, series i) in the encoding's range: stage 2, the per-series out-of-bounds fix, the range map
+__device__ __forceinline__ double enc_value(const EncDev& e, const double* __restrict__ X, int64_t t, int64_t i) {
+    double x = enc_stage2(e, X[i * e.T + t]);
+    if (e.fix) {
+        const double shift = e.fix[2 * i], scale = e.fix[2 * i + 1];
+        if (shift != 0.0) x -= shift;
+        if (scale != 1.0) x /= scale;
+    }
+    return (e.b - e.a) * x + e.a;
+}
+
+// one thread per (site, series); consecutive threads = consecutive series, so the d values every
+// thread writes are contiguous across the wave ([T][N][d] site-major, the sweep's layout)
+__global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= e.N * e.T) return;
+    const int64_t t = idx / e.N, i = idx - t * e.N;
+    const double x = enc_value(e, X, t, i);
+    enc_basis<false>(e.basis, x, e.d, e.nrm, 1.0, phi + idx * e.d * (e.fourier ? 2 : 1));
+}
+
+// Split bases (src/Encodings/splitbases.jl): the same thread mapping and front end; the thread walks its site's edge list
+// (e.bins + t * e.bin_stride, nbins + 1 edges; consecutive threads share it - it stays in the cache) and restates
+// project_onto_bins (:113-132) bin by bin: rect (:96-108) of x_prop / scale - 0.5 selects the bin - or, exactly on an interior
+// edge, both neighbours at 0.5 -, the auxiliary basis is evaluated at a + x_prop in selected bins only, the others are zeroed.
+// An empty bin (dx = 0) gives x_prop = +-inf or NaN, which every comparison rejects, as on the host.
+__global__ __launch_bounds__(256) void k_encode_split(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= e.N * e.T) return;
+    const int64_t t = idx / e.N, i = idx - t * e.N;
+    const double x = enc_value(e, X, t, i);
+    const double* __restrict__ bins = e.bins + t * e.bin_stride;
+    const int nb = e.nbins, w = e.aux_dim * (e.fourier ? 2 : 1);       // doubles per bin
+    double* out = phi + idx * nb * w;
+    const double a = bins[0], scale = bins[nb] - a;
+    for (int k = 0; k < nb; ++k) {
+        const double dx = bins[k + 1] - bins[k];
+        const double x_prop = scale * (x - bins[k]) / dx;
+        const double r = x_prop / scale - 0.5;
+        const double lbound = k == 0 ? 1.0 : 0.5, rbound = k == nb - 1 ? 1.0 : 0.5;
+        const double select = r == -0.5 ? lbound : (r == 0.5 ? rbound : ((-0.5 <= r && r <= 0.5) ? 1.0 : 0.0));
+        double* o = out + k * w;
+        if (select == 0.0) {
+            for (int q = 0; q < w; ++q) o[q] = 0.0;
+        } else {
+            enc_basis<true>(e.basis, a + x_prop, e.aux_dim, e.nrm, select, o);
+        }
     }
 }
 
@@ -209,7 +253,9 @@ void launch_encode(const EncDev& e, const double* X, double* phi, double* part, 
         hipLaunchKernelGGL(k_enc_range_final, dim3(1), dim3(64), 0, s, (const double*)part, nb, lohi);
     }
     if (fix) hipLaunchKernelGGL(k_enc_series_fix, dim3((unsigned)((e.N + 3) / 4)), dim3(256), 0, s, e, X, fix);
-    hipLaunchKernelGGL(k_encode, dim3((unsigned)((e.N * e.T + 255) / 256)), dim3(256), 0, s, e, X, phi);
+    const dim3 grid((unsigned)((e.N * e.T + 255) / 256));
+    if (e.bins) hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi);
+    else hipLaunchKernelGGL(k_encode, grid, dim3(256), 0, s, e, X, phi);
 }
 
 }  // namespace mpst

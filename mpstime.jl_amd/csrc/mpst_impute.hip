@@ -1236,7 +1236,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
             // states: coalesced); then every thread sums its CONTIGUOUS segment for the block-wide scan
             if constexpr (CX) {
                 // rho stays in LDS (every lane reads the same entry: broadcast), two grid values per round trip
-                const double2* gp = reinterpret_cast<const double2*>(g.grid_phi);
+                const double2* gp = reinterpret_cast<const double2*>(g.grid_phi + (int64_t)j * g.grid_site_stride);      // site j's table (stride 0: the shared one)
                 auto evalc = [&](auto DD) {
                     constexpr int D = decltype(DD)::value;
                     for (int kb = tid; kb < n; kb += 2 * IMP_T) {
@@ -1321,11 +1321,12 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #pragma unroll
                     for (int e = 0; e < DR * DR; ++e) rr[e] = rho[(e / DR) * IMP_MAXD + (e % DR)];
                     double fa[Q][D], fb[Q][D];                             // two batches: one in flight while the other is consumed
+                    const double* gphi = g.grid_phi + (int64_t)j * g.grid_site_stride;      // site j's table (stride 0: the shared one)
                     auto loadf = [&](double (&f)[Q][D], int kb) {
 #pragma unroll
                         for (int q = 0; q < Q; ++q) {
                             const int k = kb + q * IMP_T;
-                            const double* ph = g.grid_phi + (int64_t)(k < n ? k : 0) * D;
+                            const double* ph = gphi + (int64_t)(k < n ? k : 0) * D;
 #pragma unroll
                             for (int s2 = 0; s2 < D; ++s2) f[q][s2] = ph[s2];
                         }
@@ -1378,7 +1379,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
                     case 16: eval(std::integral_constant<int, 16>{}); break;
                     default:
                         for (int k = tid; k < n; k += IMP_T) {
-                            const double* ph = g.grid_phi + (int64_t)k * d;
+                            const double* ph = g.grid_phi + (int64_t)j * g.grid_site_stride + (int64_t)k * d;
                             double pk = 0.0;
                             for (int s_ = 0; s_ < d; ++s_) {
                                 double q = 0.0;
@@ -1687,8 +1688,9 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
             if (state_from_grid) {
                 xsel = g.grid_x[ksel];
                 if (tid < d) {
-                    ms.r[tid] = (R)g.grid_phi[((int64_t)ksel * d + tid) * ZW];
-                    if constexpr (CX) ms.i[tid] = (R)g.grid_phi[((int64_t)ksel * d + tid) * ZW + 1];
+                    const double* gsel = g.grid_phi + (int64_t)j * g.grid_site_stride;
+                    ms.r[tid] = (R)gsel[((int64_t)ksel * d + tid) * ZW];
+                    if constexpr (CX) ms.i[tid] = (R)gsel[((int64_t)ksel * d + tid) * ZW + 1];
                 }
             }
             if (tid == 0) {

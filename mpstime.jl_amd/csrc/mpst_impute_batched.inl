@@ -790,8 +790,9 @@ __global__ __launch_bounds__(IMB_T, 1) void k_imp_leftb(ImpModel v, ImpArgs g, i
                 if (state_from_grid) {
                     xsel = g.grid_x[ksel];
                     if (lane < d) {
-                        msr[lane] = (double)(R)g.grid_phi[((int64_t)ksel * d + lane) * ZW];
-                        msi[lane] = CX ? (double)(R)g.grid_phi[((int64_t)ksel * d + lane) * ZW + (ZW - 1)] : 0.0;
+                        const double* gsel = g.grid_phi + (int64_t)j * g.grid_site_stride;      // (0 here: only closed-form grids, which are shared, run batched)
+                        msr[lane] = (double)(R)gsel[((int64_t)ksel * d + lane) * ZW];
+                        msi[lane] = CX ? (double)(R)gsel[((int64_t)ksel * d + lane) * ZW + (ZW - 1)] : 0.0;
                     }
                 }
                 if (lane == 0) {

@@ -620,6 +620,10 @@ struct EncDev {
     double nrm;             // legendre: sqrt(Pl(1, d; normalized) * d)
     const double* lohi;     // device [2] min, max of the (sigmoid-transformed) training data
     const double* fix;      // device [N][2] per-series (shift, scale) of the out-of-bounds rescale, or null
+    // split bases (k_encode_split; bins == null: k_encode): `basis` is the auxiliary basis, nrm its Legendre norm, d = nbins * aux_dim
+    const double* bins;     // device [T][nbins + 1] edges (bin_stride = nbins + 1) or [nbins + 1] shared by all sites (bin_stride = 0)
+    int64_t bin_stride;
+    int32_t nbins, aux_dim;
 };
 size_t order_stats_temp_bytes(int64_t n);
 hipError_t launch_order_stats(const double* X, double* sorted, void* temp, size_t temp_bytes, int64_t n, double* out3, hipStream_t s);
@@ -683,7 +687,8 @@ struct ImpArgs {
     const uint8_t* missing;     // [N][T]
     const void* Rbuf;           // [chunk][max_missing][cap*cap] elements of the chain type
     const double* grid_x;       // [ngrid]
-    const double* grid_phi;     // [ngrid][d] doubles (real model) or (re, im) pairs (complex model)
+    const double* grid_phi;     // [ngrid][d] doubles (real model) or (re, im) pairs (complex model); per site: [T][ngrid][d]
+    int64_t grid_site_stride;   // doubles between the tables of consecutive sites: ngrid * d (* 2, complex), 0 for the one shared table
     const double* u;            // [N][T][ntrial] uniform numbers (quantile / ITS) or null
     double* pbuf;               // [chunk][ngrid] scratch: p_k
     double* sbuf;               // [chunk][ngrid] scratch: prefix sums S_k

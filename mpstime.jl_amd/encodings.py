@@ -2,13 +2,16 @@
 
 Mirrors src/utils.jl:161-295 (RobustSigmoid + MinMax) and src/Encodings (encode_dataset,
 Encodings/encodings.jl:33-156; bases, Encodings/bases.jl).  These run once per fit on the
-host in the reference as well; the data-driven bases (SLTD, Sahand-Legendre, split bases,
-projected bases) are out of scope of the sweep engine and raise.
+host in the reference as well.  Encodings whose basis differs from site to site (Encodings/splitbases.jl,
+basis_structs.jl) are fitted once by ``fit_encoding`` and applied through the encoder it returns; SLTD,
+Sahand-Legendre and projected bases (they need a kernel density estimator) raise.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from dataclasses import dataclass
+from fractions import Fraction
 from typing import Optional
 
 import numpy as np
@@ -128,25 +131,202 @@ def uniform_encode(x, d):
     return np.full(x.shape + (d,), 1.0 / d)
 
 
+def no_init(X_norm=None, y=None, opts=None, range=None):
+    """no_init (bases.jl): a closed-form basis has no arguments to fit."""
+    return []
+
+
 @dataclass(frozen=True)
 class Encoding:
-    """Basis (src/Encodings/basis_structs.jl): name, encode(x, d), complex flag, input range."""
+    """Basis / SplitBasis (src/Encodings/basis_structs.jl:49-92): name, complex flag, input range, encode and - for bases
+    that are fitted to the training data or differ from site to site - init and the two flags.
+
+    ``encode(x, d, *init_args)`` takes an array of values of any shape and returns shape + (d,); a time-dependent basis is
+    called as ``encode(x, d, ti, *init_args)`` with ``ti`` the site COUNTED FROM 0 (the reference's ``j`` of encode_TS,
+    encodings.jl:18-24, counts from 1).  ``init(X_norm, y, opts=opts)`` returns ``init_args``; X_norm is the (N, T)
+    training matrix in the encoding's range, rows = series (the reference passes its transpose)."""
 
     name: str
     iscomplex: bool
     range: tuple
     encode: object = None
+    istimedependent: bool = False
+    isdatadriven: bool = False
+    init: object = None                 # None: no_init
+    splitmethod: object = None          # SplitBasis only
+    aux_enc: object = None              # SplitBasis only
 
 
-def model_encoding(symbol, custom: Optional[Encoding] = None) -> Encoding:
+_CLOSED_FORM = ("Legendre_No_Norm", "Legendre_Norm", "Fourier", "Stoudenmire", "Sahand", "Uniform")
+
+
+# ---------------------------------------------------------------------------------------
+# split bases (src/Encodings/splitbases.jl)
+# ---------------------------------------------------------------------------------------
+def get_nbins_safely(opts) -> int:
+    """splitbases.jl:2-9."""
+    if opts.d % opts.aux_basis_dim != 0:
+        raise ValueError(f"The auxilliary basis dimension ({opts.aux_basis_dim}) must evenly divide the total feature "
+                         f"dimension ({opts.d})")
+    return opts.d // opts.aux_basis_dim
+
+
+def unif_split(data, nbins, a, b):
+    """splitbases.jl:51-54: ``collect(a:dx:b)`` with dx = (b - a) / nbins.  Julia builds a float range from the
+    rationals behind its end points (twice-precision arithmetic), so edge i is the double nearest to a + i (b - a) / nbins
+    and the last one is b: restated with exact fractions."""
+    fa, fb = Fraction(float(a)), Fraction(float(b))
+    return np.array([float(fa + (fb - fa) * i / nbins) for i in range(nbins + 1)])
+
+
+def hist_split(samples, nbins, a, b):
+    """splitbases.jl:56-92.  A vector: the bin edges that put round(npts / nbins) of the sorted samples inside [a, b]
+    into every bin; a matrix (N, T): one edge list per time point, (T, nbins + 1)."""
+    samples = np.asarray(samples, dtype=np.float64)
+    if samples.ndim == 2:                                                      # :90-92 (columns here: rows = series)
+        return np.stack([hist_split(samples[:, t], nbins, a, b) for t in range(samples.shape[1])])
+    npts = len(samples)
+    bin_pts = int(round(npts / nbins))                                         # round half to even, as Julia's
+    if bin_pts == 0:
+        warnings.warn("Less than one data point per bin! Putting the extra bins at x=1 and hoping for the best")
+        bin_pts = 1
+    bins = np.full(nbins + 1, float(a))
+    ds = np.sort(samples[(a <= samples) & (samples <= b)])                     # :69
+    # every bin_pts-th sorted sample (1-based i, i < npts) closes a bin until nbins - 1 interior edges are set (:70-80)
+    take = [i for i in range(bin_pts, len(ds) + 1, bin_pts) if i < npts][:nbins - 1]
+    for j, i in enumerate(take, start=1):
+        if i >= len(ds):                                                       # ds[i+1] of :77 is past the end
+            raise IndexError(f"hist_split: sample {i + 1} of {len(ds)} inside [{a}, {b}]")
+        bins[j] = (ds[i - 1] + ds[i]) / 2
+    if len(take) + 2 <= nbins:                                                 # :81-84 (j <= nbins)
+        bins[bins == a] = b
+        bins[0] = a
+    bins[-1] = b
+    return bins
+
+
+def rect(x, lbound=0.5, rbound=0.5):
+    """splitbases.jl:96-108, elementwise: lbound at -0.5, rbound at 0.5, 1 inside, 0 outside (and for NaN)."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x == -0.5, lbound, np.where(x == 0.5, rbound, np.where((-0.5 <= x) & (x <= 0.5), 1.0, 0.0)))
+
+
+def _project(x, aux_dim, aux_encoder, bins, iscomplex, norm=True):
+    """project_onto_bins(x, aux_dim, aux_encoder, bins) (splitbases.jl:113-132) for an array of values: the auxiliary
+    encoder is evaluated in the selected bin(s) only, at a + scale (x - bins[i]) / dx."""
+    x = np.asarray(x, dtype=np.float64)
+    bins = np.asarray(bins, dtype=np.float64)
+    widths = np.diff(bins)
+    a, b = bins[0], bins[-1]
+    scale = b - a
+    nb = len(widths)
+    out = np.zeros(x.shape + (nb * aux_dim,), dtype=np.complex128 if iscomplex else np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):                       # an empty bin (dx = 0) selects nothing
+        for i in range(nb):
+            dx = widths[i]
+            y = 1.0 if norm else 1.0 / dx
+            x_prop = scale * (x - bins[i]) / dx
+            select = y * rect(x_prop / scale - 0.5, 1.0 if i == 0 else 0.5, 1.0 if i == nb - 1 else 0.5)
+            hit = select != 0
+            if hit.any():
+                out[hit, i * aux_dim:(i + 1) * aux_dim] = select[hit][:, None] * aux_encoder(a + x_prop[hit], i)
+    return out
+
+
+def project_onto_bins(x, d, aux_enc_args, split_args, norm=True):
+    """splitbases.jl:135-142: the time-independent form, one edge list for all sites."""
+    bins, aux_dim, aux_enc = split_args
+    return _project(x, aux_dim, lambda xx, i: aux_enc.encode(xx, aux_dim, *aux_enc_args[i]), bins, aux_enc.iscomplex, norm)
+
+
+def project_onto_bins_td(x, d, ti, all_aux_enc_args, split_args, norm=True):
+    """splitbases.jl:144-163: the time-dependent form; ``ti`` (from 0) picks the site's edge list when there is one per site.
+    (The auxiliary basis is never time-dependent here: the SplitBasis constructor refuses it.)"""
+    all_bins, aux_dim, aux_enc = split_args
+    bins = all_bins[ti] if np.ndim(all_bins) == 2 else all_bins
+    return _project(x, aux_dim, lambda xx, i: aux_enc.encode(xx, aux_dim, *all_aux_enc_args[i]), bins, aux_enc.iscomplex, norm)
+
+
+def split_init(X_norm, y, opts, range=None):
+    """splitbases.jl:12-48: [aux_enc_args, [bins, aux_dim, aux_enc]]."""
+    enc = opts_encoding(opts)
+    nbins = get_nbins_safely(opts)
+    a, b = enc.range if range is None else range
+    bins = enc.splitmethod(np.asarray(X_norm, dtype=np.float64), nbins, a, b)
+    aux = enc.aux_enc
+    if aux.aux_enc is not None:
+        raise NotImplementedError("nested split bases are not implemented")
+    enc_arg = [] if aux.init is None else aux.init(X_norm, y, opts=opts.set(d=opts.aux_basis_dim))       # :30, :42
+    return [[enc_arg] * nbins, [bins, int(opts.aux_basis_dim), aux]]
+
+
+def SplitBasis(name, init, splitmethod, aux_enc, encode, iscomplex, istimedependent, isdatadriven, range) -> Encoding:
+    """The SplitBasis constructor's consistency checks (basis_structs.jl:75-91), same texts."""
+    if aux_enc.iscomplex != iscomplex:
+        raise ValueError("The SplitBasis and its auxilliary basis must agree on whether they are complex!")
+    if tuple(aux_enc.range) != tuple(range):
+        raise ValueError("The SplitBasis and its auxilliary basis must agree on the normalised timeseries range!")
+    if aux_enc.isdatadriven or aux_enc.istimedependent:
+        raise ValueError("Splitting up a data-driven encoding is not yet supported, sorry")
+    if aux_enc.aux_enc is not None:
+        raise NotImplementedError("nested split bases are not implemented")
+    return Encoding(name, iscomplex, tuple(range), encode, istimedependent, isdatadriven, init, splitmethod, aux_enc)
+
+
+def _aux(enc_or_name) -> Encoding:
+    return enc_or_name if isinstance(enc_or_name, Encoding) else model_encoding(enc_or_name)
+
+
+def histogram_split(enc_or_name="uniform") -> Encoding:
+    """histogram_split (basis_structs.jl:247-260, :278): per-site bins holding equal shares of the training values."""
+    aux = _aux(enc_or_name)
+    return SplitBasis(f"Hist Split {aux.name}", split_init, hist_split, aux, project_onto_bins_td, aux.iscomplex, True, True, aux.range)
+
+
+def uniform_split(enc_or_name="uniform") -> Encoding:
+    """uniform_split (basis_structs.jl:262-276, :279): equal-width bins, time-independent over a closed-form basis."""
+    aux = _aux(enc_or_name)
+    return SplitBasis(f"Unif Split {aux.name}", split_init, unif_split, aux, project_onto_bins, aux.iscomplex, aux.istimedependent,
+                      aux.isdatadriven, aux.range)
+
+
+def function_basis(fn, is_complex, range, is_time_dependent=False, is_data_driven=False, init=None, name="Custom") -> Encoding:
+    """function_basis (basis_structs.jl:235-244).  ``fn(x, d, *init_args)`` - or, with ``is_time_dependent``,
+    ``fn(x, d, ti, *init_args)`` - takes ONE value and returns its d coefficients.  ``ti`` counts sites from 0 here; the
+    reference passes Julia's 1-based index, so a function ported from Julia uses ``ti + 1`` where it used ``ti``."""
+    dt = np.complex128 if is_complex else np.float64
+
+    def encode(x, d, *args):
+        x = np.asarray(x, dtype=np.float64)
+        out = np.empty((x.size, d), dtype=dt)
+        for k, v in enumerate(x.ravel().tolist()):
+            out[k] = fn(v, d, *args)
+        return out.reshape(x.shape + (d,))
+
+    return Encoding(name, bool(is_complex), tuple(range), encode, bool(is_time_dependent), bool(is_data_driven), init)
+
+
+_SPLIT_PREFIXES = (("hist_split_", "hist._split_", "histogram_split_"), ("unif_split_", "unif._split_", "uniform_split_"))
+
+
+def model_encoding(symbol, custom: Optional[Encoding] = None, project: bool = False) -> Encoding:
     """options.jl:243-279."""
+    if project:
+        raise NotImplementedError("projected_basis=True (projected Legendre / Fourier bases) is not implemented")
+    if isinstance(symbol, Encoding):
+        return symbol
+    s = str(symbol).lstrip(":").lower()
+    for kind, prefixes in enumerate(_SPLIT_PREFIXES):                          # :261-272
+        if s.startswith(prefixes):
+            aux = model_encoding(s[s.index("split_") + 6:])
+            return uniform_split(aux) if kind else histogram_split(aux)
     canon, iscomplex, rng, data_driven = encoding_info(symbol)
     if canon == "Custom":
         if custom is None:
             raise ValueError("To use a custom encoding, pass custom_encoding")
         return custom
     if data_driven:
-        raise NotImplementedError(f"encoding {canon} is data-driven (host-side, one-off) and outside the sweep engine's scope")
+        raise NotImplementedError(f"encoding {canon} is data-driven through a kernel density estimate, which this package does not ship")
     fn = {"Legendre_No_Norm": legendre_encode_no_norm, "Legendre_Norm": legendre_encode, "Fourier": fourier_encode,
           "Stoudenmire": angle_encode, "Sahand": sahand_encode, "Uniform": uniform_encode}[canon]
     return Encoding(canon, iscomplex, rng, fn)
@@ -154,7 +334,62 @@ def model_encoding(symbol, custom: Optional[Encoding] = None) -> Encoding:
 
 def symbolic_encoding(enc: Encoding) -> str:
     """Inverse of model_encoding (options.jl:281-296); basis_tests.jl:8 pins the round trip."""
-    return enc.name
+    return enc.name.replace(" ", "_").replace("-", "_")
+
+
+def opts_encoding(opts, custom: Optional[Encoding] = None) -> Encoding:
+    """opts.encoding as an Encoding (the reference's Options holds the object, MPSOptions here its name)."""
+    return model_encoding(opts.encoding, custom, opts.projected_basis)
+
+
+# ---------------------------------------------------------------------------------------
+# the fit step: opts.encoding.init(X_norm, y; opts) (encodings.jl:129-138) and encode_TS (:1-31) bound to its result
+# ---------------------------------------------------------------------------------------
+class FittedEncoder:
+    """encode_TS with the encoding arguments bound: ``enc(X)`` maps an (N, T) matrix of values in the encoding's range to
+    (N, T, d), column t through site t's basis; ``enc.table(xvals, T)`` tabulates candidate values - (ngrid, d), or
+    (T, ngrid, d) for a time-dependent encoding (imputation.jl:92-107)."""
+
+    def __init__(self, enc: Encoding, d: int, args):
+        self.enc, self.d, self.args = enc, int(d), args
+
+    def __call__(self, X):
+        X = np.asarray(X, dtype=np.float64)
+        if not self.enc.istimedependent:
+            return self.enc.encode(X, self.d, *self.args)
+        return np.stack([self.enc.encode(X[:, t], self.d, t, *self.args) for t in range(X.shape[1])], axis=1)
+
+    def table(self, xvals, T):
+        if not self.enc.istimedependent:
+            return self.enc.encode(xvals, self.d, *self.args)
+        return np.stack([self.enc.encode(xvals, self.d, t, *self.args) for t in range(T)])
+
+    @property
+    def bins(self):
+        """the split bases' edges: (nbins + 1,) shared by all sites or (T, nbins + 1); None for any other encoding"""
+        return np.asarray(self.args[1][0]) if self.enc.aux_enc is not None else None
+
+
+def fit_encoding(enc: Encoding, X_norm, y, opts: MPSOptions):
+    """The fit step of encode_safe_dataset (encodings.jl:129-132): ``(encoding_args, encoder)``.  ``X_norm`` is the training
+    matrix (N, T) after transform_train_data, ``encoder`` a FittedEncoder.  Closed-form encodings have nothing to fit: their
+    encoder is ``enc.encode(X, d)`` itself."""
+    if enc.isdatadriven and opts.encode_classes_separately:
+        raise NotImplementedError("encode_classes_separately=True together with a data-driven encoding is not implemented")
+    args = [] if enc.init is None else enc.init(X_norm, y, opts=opts)
+    return args, FittedEncoder(enc, opts.d, args)
+
+
+def fit_encoding_from_training_data(opts: MPSOptions, X_train, y_train=None, custom: Optional[Encoding] = None):
+    """get_enc_args_from_opts (imputation.jl:23-45): re-derive the encoding arguments from the raw training data a
+    TrainedMPS carries.  Returns (enc, norms, encoder)."""
+    enc = opts_encoding(opts, custom)
+    if enc.init is None:
+        return enc, None, FittedEncoder(enc, opts.d, [])
+    X_norm, norms = transform_train_data(X_train, opts, enc.range)
+    if y_train is not None:
+        X_norm = X_norm[np.argsort(np.asarray(y_train), kind="stable")]        # :39-40
+    return enc, norms, fit_encoding(enc, X_norm, y_train, opts)[1]
 
 
 # ---------------------------------------------------------------------------------------
@@ -232,9 +467,14 @@ def transform_data(X_train, X_test, opts: MPSOptions, enc_range):
 # ---------------------------------------------------------------------------------------
 # encode_dataset (Encodings/encodings.jl:33-156)
 # ---------------------------------------------------------------------------------------
-def encode_dataset(X_orig, X_scaled, y, enc: Encoding, d, class_keys) -> EncodedTimeSeriesSet:
+def encode_dataset(X_orig, X_scaled, y, enc: Encoding, d, class_keys, encoder=None) -> EncodedTimeSeriesSet:
     """Stable sort by class (:43), range check (:115-119), encode every value, class
-    distribution in class-key order (:151-152)."""
+    distribution in class-key order (:151-152).  ``encoder``: the FittedEncoder of the training set (``fit_encoding``),
+    required for an encoding with an init step (:133-138)."""
+    if encoder is None:
+        if enc.init is not None:
+            raise ValueError("Can't encode a test or val set without training encoding arguments!")
+        encoder = FittedEncoder(enc, d, [])
     y = np.asarray(y)
     if X_scaled.shape[0] == 0:
         return EncodedTimeSeriesSet.empty()
@@ -243,7 +483,7 @@ def encode_dataset(X_orig, X_scaled, y, enc: Encoding, d, class_keys) -> Encoded
     a, b = enc.range
     if not np.all((a <= Xs) & (Xs <= b)):
         raise ValueError(f"Data must be rescaled between {a} and {b} before a {enc.name} encoding.")
-    phi = enc.encode(Xs, d)
+    phi = encoder(Xs)
     label_index = np.array([class_keys[v] for v in ys.tolist()], dtype=np.int32)
     _, counts = np.unique(ys, return_counts=True)
     return EncodedTimeSeriesSet(phi, ys, label_index, np.array(Xo, dtype=np.float64), counts.astype(np.int64))

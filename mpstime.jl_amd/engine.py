@@ -67,6 +67,36 @@ def _dtype_of(x):
     return dt if dt in DTYPES else np.dtype(np.float64)
 
 
+def _device_basis(basis):
+    """(closed-form basis name - of the auxiliary basis for a split encoding -, its input range, is split) of what encode_dataset /
+    encode_values were handed: a name or an Encoding.  Raises MPSTError(UNSUPPORTED) for what the device does not encode."""
+    from .encodings import Encoding, model_encoding
+    rng, split = (-1.0, 1.0), False
+    try:
+        enc = basis if isinstance(basis, Encoding) else model_encoding(basis)
+        split = enc.aux_enc is not None
+        # canonical name; :Legendre is :Legendre_No_Norm (options.jl:245-246)
+        basis, rng = (enc.aux_enc.name if split else enc.name), (enc.range or rng)
+    except Exception:
+        pass
+    if basis not in L.BASIS:
+        raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)} and split bases over them, not {basis!r}")
+    return basis, rng, split
+
+
+def _split_opts(aux_basis, d, T, bins):
+    """mpst_split_opts of a split encoding over ``aux_basis`` with the fitted edges ``bins`` - (nbins + 1,) shared by all sites or
+    (T, nbins + 1) - and the array the struct points into (keep it alive over the call)."""
+    if bins is None:
+        raise ValueError("a split encoding is encoded with the bin edges its fit produced: pass bins (fit_encoding(...)[1].bins)")
+    b = np.ascontiguousarray(bins, dtype=np.float64)
+    if b.ndim not in (1, 2) or b.shape[-1] < 2 or (b.ndim == 2 and b.shape[0] != T):
+        raise ValueError(f"bins must be (nbins + 1,) or ({T}, nbins + 1), got {b.shape}")
+    nbins = b.shape[-1] - 1
+    sp = L.mpst_split_opts(L.BASIS[aux_basis], int(d) // nbins, nbins, int(b.ndim == 2), b.ctypes.data_as(C.POINTER(C.c_double)))
+    return sp, b
+
+
 class SweepEngine:
     def __init__(self, device: int = 0):
         self.lib = L.load()
@@ -140,18 +170,15 @@ class SweepEngine:
 
     def encode_dataset(self, which, X_sorted, label_index, C_classes, basis="Legendre_No_Norm", d=None, sigmoid_transform=True,
                        minmax=True, data_bounds=(0.0, 1.0), enc_range=(-1.0, 1.0), norms=None, rescale_out_of_bounds=True,
-                       global_counts=None, sigmoid_fit=None):
+                       global_counts=None, sigmoid_fit=None, bins=None):
         """Preprocess + encode the raw (N, T) matrix on the device (mpst_encode_dataset).  ``X_sorted`` must already be
         sorted by class.  ``norms=None`` fits a training set (median/IQR on the host, min/max on the device) and
         returns ``(norms, seconds)``; with ``norms`` from the training fit the data is treated as a test set and
-        ``(oob, seconds)`` comes back, ``oob`` in the format of transform_test_data (utils.jl:243-266)."""
-        from .encodings import Norms, model_encoding
-        try:
-            basis = model_encoding(basis).name           # canonical name; :Legendre is :Legendre_No_Norm (options.jl:245-246)
-        except Exception:
-            pass
-        if basis not in L.BASIS:
-            raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, not {basis!r}")
+        ``(oob, seconds)`` comes back, ``oob`` in the format of transform_test_data (utils.jl:243-266).
+        A split encoding (name or Encoding) goes through mpst_encode_split_dataset with ``bins``, the edges its fit produced
+        (``fit_encoding(...)[1].bins``: (nbins + 1,) or (T, nbins + 1))."""
+        from .encodings import Norms
+        basis, _, split = _device_basis(basis)
         X = np.ascontiguousarray(X_sorted, dtype=np.float64)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
         N, T = X.shape
@@ -177,10 +204,14 @@ class SweepEngine:
         fix = np.zeros((N, 2)) if norms is not None else None
         sec = C.c_double()
         dp = C.POINTER(C.c_double)
-        self._chk(self.lib.mpst_encode_dataset(
-            self.ctx, which, X.ctypes.data_as(dp), lab.ctypes.data_as(C.POINTER(C.c_int32)), N, T, d, int(C_classes), C.byref(eo),
-            gc.ctypes.data_as(C.POINTER(C.c_int64)) if gc is not None else None,
-            fix.ctypes.data_as(dp) if fix is not None else None, C.byref(sec)))
+        head = (self.ctx, which, X.ctypes.data_as(dp), lab.ctypes.data_as(C.POINTER(C.c_int32)), N, T, d, int(C_classes), C.byref(eo))
+        tail = (gc.ctypes.data_as(C.POINTER(C.c_int64)) if gc is not None else None, fix.ctypes.data_as(dp) if fix is not None else None,
+                C.byref(sec))
+        if split:
+            sp, _keep = _split_opts(basis, d, T, bins)
+            self._chk(self.lib.mpst_encode_split_dataset(*head, C.byref(sp), *tail))
+        else:
+            self._chk(self.lib.mpst_encode_dataset(*head, *tail))
         self.T, self.d, self.C = T, d, int(C_classes)
         self.N[which] = N
         self.dtype = self._ctx_dtype(basis)
@@ -191,20 +222,13 @@ class SweepEngine:
         return oob, sec.value
 
     def encode_values(self, X, basis="Legendre_No_Norm", d=4, sigmoid_transform=False, minmax=False, data_bounds=(0.0, 1.0),
-                      enc_range=None, norms=None, rescale_out_of_bounds=False):
+                      enc_range=None, norms=None, rescale_out_of_bounds=False, bins=None):
         """mpst_encode_values: the device preprocessing + encoding kernels on a raw (N, T) matrix, states back to the host -
         (N, T, d) float64 for the Legendre / Uniform bases, complex128 for "Fourier", "Stoudenmire", "Sahand".  Defaults: X is already in the encoding's
         domain (no transforms, identity range map); with transforms the [0, 1] data is mapped onto ``enc_range``
-        (default: the basis' own range, (-1, 1) for Legendre / Fourier, (0, 1) for Stoudenmire / Sahand / Uniform).  ``norms`` as for encode_dataset (a test set) or None."""
-        from .encodings import model_encoding
-        basis_range = (-1.0, 1.0)
-        try:
-            enc_ = model_encoding(basis)
-            basis, basis_range = enc_.name, (enc_.range or basis_range)
-        except Exception:
-            pass
-        if basis not in L.BASIS:
-            raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, not {basis!r}")
+        (default: the basis' own range, (-1, 1) for Legendre / Fourier, (0, 1) for Stoudenmire / Sahand / Uniform).  ``norms`` as for encode_dataset (a test set) or None.
+        A split encoding with its fitted ``bins`` goes through mpst_encode_split_values, as in encode_dataset."""
+        basis, basis_range, split = _device_basis(basis)
         X = np.ascontiguousarray(X, dtype=np.float64)
         N, T = X.shape
         eo = L.mpst_encode_opts()
@@ -225,8 +249,12 @@ class SweepEngine:
         cx = basis in ("Fourier", "Stoudenmire", "Sahand")
         out = np.zeros((N, T, int(d)), dtype=np.complex128 if cx else np.float64)
         sec = C.c_double()
-        self._chk(self.lib.mpst_encode_values(self.ctx, X.ctypes.data_as(C.POINTER(C.c_double)), N, T, int(d), C.byref(eo),
-                                              out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
+        head = (self.ctx, X.ctypes.data_as(C.POINTER(C.c_double)), N, T, int(d), C.byref(eo))
+        if split:
+            sp, _keep = _split_opts(basis, int(d), T, bins)
+            self._chk(self.lib.mpst_encode_split_values(*head, C.byref(sp), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
+        else:
+            self._chk(self.lib.mpst_encode_values(*head, out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
         return out, sec.value
 
     def _ctx_dtype(self, basis):
@@ -367,8 +395,8 @@ class SweepEngine:
             if uu is not None:
                 assert uu.size == N * T * (int(a["max_trials"]) if int(a["method"]) == 4 else 1)
             mid = (ptr(uu),)
-        o = L.ImputeOpts(int(a["method"]), int(a["order"]), int(bool(a["get_wmad"])), int(a["max_trials"]), int(a["mean_basis"]), 0,
-                         float(a["rejection_threshold"]))
+        o = L.ImputeOpts(int(a["method"]), int(a["order"]), int(bool(a["get_wmad"])), int(a["max_trials"]), int(a["mean_basis"]),
+                         int(gp.ndim == 3), float(a["rejection_threshold"]))          # a (T, ngrid, d) table: one per site
         x, err, sec = np.zeros(shape), np.zeros(shape), C.c_double()
         self._chk(getattr(self.lib, name)(self.ctx, *head, ptr(m, C.POINTER(C.c_uint8)), ptr(gx), C.cast(gp.ctypes.data, dp), len(gx),
                                           C.byref(o), *mid, ptr(x), ptr(err), C.byref(sec), *tail))
@@ -384,11 +412,13 @@ class SweepEngine:
         With ``levels`` (up to 16 numbers inside (0, 1)) and / or ``cdf_stride`` >= 1 (mpst_impute_dist, median only) the return value is
         (x, err, seconds, q, cdf): q (N, T, nq) the grid value at every level of every missing site's conditional cdf (0 at known
         sites) or None, cdf (N, cdf_rows, ncdf) that cdf at the grid indices 0, s, 2s, ... and ngrid - 1, row r = the r-th missing
-        site of the instance in ascending order, cdf_rows = the largest missing count, or None."""
+        site of the instance in ascending order, cdf_rows = the largest missing count, or None.
+        ``grid_phi`` (ngrid, d) is one table for all sites; (T, ngrid, d) holds one per site (time-dependent encodings; grid_per_site
+        of mpst_impute_opts): the densities are then read from the table, one instance per workgroup; method 3 (mean) is refused."""
         m = np.ascontiguousarray(missing, dtype=np.uint8)
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=np.complex128 if self.dtype.kind == "c" else np.float64)   # grid states: fp64 (pairs)
-        assert gp.shape == (len(gx), self.d) and m.shape == (self.N[which], self.T)
+        assert gp.shape in ((len(gx), self.d), (self.T, len(gx), self.d)) and m.shape == (self.N[which], self.T)
         args = dict(method=method, order=order, get_wmad=get_wmad, max_trials=max_trials, mean_basis=mean_basis,
                     rejection_threshold=rejection_threshold, u=u, num_trajectories=num_trajectories, seed=seed, row_id=row_id, levels=levels,
                     cdf_stride=cdf_stride)
@@ -423,7 +453,7 @@ class SweepEngine:
         assert ph.shape == (N, T, d) and m.shape == (N, T) and lab.shape == (N,)
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=dt)
-        assert gp.shape == (len(gx), d)
+        assert gp.shape in ((len(gx), d), (T, len(gx), d))
         if u is not None and num_trajectories is None:         # (also where levels / cdf_stride leave u unused)
             assert np.size(u) == N * T * (int(max_trials) if int(method) == 4 else 1)
         if mean_basis is None:

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .encodings import model_encoding, transform_test_data, transform_train_data
+from .encodings import fit_encoding_from_training_data, opts_encoding, transform_test_data, transform_train_data
 from .engine import SweepEngine, check_levels
 from .options import MPSOptions, engine_options, safe_options
 
@@ -66,7 +66,7 @@ class EncodedDataRange:                 # imputation.jl:2-8
     dx: float
     guess_range: tuple
     xvals: np.ndarray
-    xvals_enc: np.ndarray               # (ngrid, d): time-independent encodings share one table (:100-106)
+    xvals_enc: np.ndarray               # (ngrid, d): time-independent encodings share one table (:100-106); (T, ngrid, d): one per site (:92-99)
 
 
 @dataclass
@@ -79,35 +79,40 @@ class ImputationProblem:                # imputation.jl:10-20
     opts: MPSOptions
     x_guess_range: EncodedDataRange
     class_map: dict
+    encoder: object = None              # FittedEncoder: the reference's enc_args (:88), bound
 
 
 def init_imputation_problem(W, X_test, y_test=None, dx: float = 1e-4, guess_range=None, verbosity: int = 1):
     """init_imputation_problem(W::TrainedMPS, X_test, y_test; dx, guess_range) (imputation.jl:143-190): the candidate
     values ``range(guess_range...; step=dx)`` and their encoded states are tabulated once."""
     opts = safe_options(W.opts)
-    enc = model_encoding(opts.encoding)
+    td = W.train_data
+    enc, _, encoder = fit_encoding_from_training_data(opts, td.original_data, td.labels)          # :88
     if guess_range is None:
         guess_range = tuple(enc.range)
     X_test = np.asarray(X_test, dtype=np.float64)
     y_test = np.zeros(X_test.shape[0], dtype=np.int64) if y_test is None else np.asarray(y_test)
     n = int(np.floor((guess_range[1] - guess_range[0]) / dx + 1e-9)) + 1
     xvals = guess_range[0] + dx * np.arange(n)
-    td = W.train_data
     classes = np.unique(td.labels)
-    states = enc.encode(xvals, opts.d)
+    # a time-dependent encoding is tabulated per site (:92-99), here on the host: the grid hits bin edges exactly, where one
+    # tabulation must decide for every consumer
+    states = encoder.table(xvals, X_test.shape[1])
     rng = EncodedDataRange(dx, guess_range, xvals, np.ascontiguousarray(states, dtype=np.complex128 if np.iscomplexobj(states) else np.float64))
     if verbosity > 0:
         print(f" - Dataset has {td.original_data.shape[0]} training samples and {X_test.shape[0]} testing samples.")
         print(f" - {len(classes)} class(es) were detected.")
     return ImputationProblem(W.mps, td.original_data, np.asarray(td.labels), X_test, y_test, opts, rng,
-                             {c: i for i, c in enumerate(classes.tolist())})
+                             {c: i for i, c in enumerate(classes.tolist())}, encoder)
 
 
 def _scaled_instances(imp: ImputationProblem, rows, masks, fill=None):
     """get_predictions' pre-processing (imputation.jl:283-297) for several instances at once: the missing region is
     overwritten with ``fill`` (default: the training mean) BEFORE the test transform (its per-series out-of-bounds rescale sees
     the masked series), the full series is transformed separately as the target in the encoding's domain."""
-    enc = model_encoding(imp.opts.encoding)
+    enc = opts_encoding(imp.opts)
+    if imp.encoder is None:
+        imp.encoder = fit_encoding_from_training_data(imp.opts, imp.X_train, imp.y_train)[2]
     _, norms = transform_train_data(imp.X_train, imp.opts, enc.range)
     raw = imp.X_test[rows]
     full, _ = transform_test_data(raw, norms, imp.opts, enc.range)
@@ -210,7 +215,7 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
     enc, norms, raw, full, scaled, oob = _scaled_instances(imp, rows, mask)
     lab = np.array([imp.class_map[c] for c in np.asarray(imp.y_test)[rows].tolist()], dtype=np.int32)
     order = np.argsort(lab, kind="stable")                      # the engine wants class-sorted data sets
-    phi = enc.encode(scaled[order], imp.opts.d)
+    phi = imp.encoder(scaled[order])
     m8 = np.ascontiguousarray(mask[order], dtype=np.uint8)
     N, T = m8.shape
     u = None
@@ -222,7 +227,7 @@ def impute_dataset(imp: ImputationProblem, missing_mask, method: str = "median",
             u = _draw_uniforms(rng, N, T, trials, K)
     if method == "mean":
         codes = {"Legendre_Norm": 0, "Legendre_No_Norm": 1, "Fourier": 2, "Stoudenmire": 3, "Sahand": 4, "Uniform": 5}    # MPST_BASIS_*
-        if enc.name not in codes:
+        if enc.name not in codes:                   # (split and time-dependent encodings included)
             raise NotImplementedError("method 'mean' re-encodes the expectation value on the device: closed-form bases only "
                                       f"({', '.join(codes)}), not {enc.name}")
         basis = codes[enc.name]
@@ -335,7 +340,7 @@ def get_cdfs(imp: ImputationProblem, class_, instance: int, missing_sites, metho
     mask[0, missing_sites] = True
     enc, _, _, full, scaled, _ = _scaled_instances(imp, [row], mask, fill=np.mean(imp.X_test))
     lab = np.array([imp.class_map[class_]], dtype=np.int32)
-    data = (enc.encode(scaled, imp.opts.d), lab, np.ascontiguousarray(mask, dtype=np.uint8))
+    data = (imp.encoder(scaled), lab, np.ascontiguousarray(mask, dtype=np.uint8))
     kw = dict(method=0, get_wmad=get_wmad, order=ORDERS[impute_order], cdf_stride=int(stride))
     x, err, _, _, cdf = _run_engine(imp, data, kw, engine=engine, device=device, compute="f64")
     nmiss = int(mask.sum())

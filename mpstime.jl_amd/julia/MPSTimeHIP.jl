@@ -233,7 +233,7 @@ struct MpstImputeOpts            # mpst_impute_opts
     get_err::Int32               # get_wmad / get_std
     max_trials::Int32
     mean_basis::Int32            # 0 :Legendre_Norm, 1 :Legendre_No_Norm, 2 :Fourier
-    reserved::Int32
+    grid_per_site::Int32         # 0: xvals_enc (d, ngrid) shared by all sites, 1: (d, ngrid, T), one table per site
     rejection_threshold::Float64
 end
 struct MpstImputeModel           # mpst_impute_model

@@ -16,6 +16,7 @@ def _sym(x) -> str:
 
 # model_encoding (options.jl:243-279): name -> (canonical name, is complex, range, time dependent / data driven)
 _ENCODINGS = {
+    # (the names model_encoding builds for split bases - "Hist Split Legendre_No_Norm" - are accepted with "_" for " ")
     "legendre": ("Legendre_No_Norm", False, (-1.0, 1.0), False),          # :Legendre == :Legendre_No_Norm (:245-246)
     "legendre_no_norm": ("Legendre_No_Norm", False, (-1.0, 1.0), False),
     "legendre_norm": ("Legendre_Norm", False, (-1.0, 1.0), False),
@@ -30,8 +31,18 @@ _ENCODINGS = {
 }
 
 
+_SPLIT_PREFIXES = {"hist_split_": "Hist Split ", "hist._split_": "Hist Split ", "histogram_split_": "Hist Split ",
+                   "unif_split_": "Unif Split ", "unif._split_": "Unif Split ", "uniform_split_": "Unif Split "}
+
+
 def encoding_info(name):
+    """(canonical name, is complex, range, data driven) of an encoding's symbol.  A split basis (options.jl:261-272) takes the
+    complex flag and the range of its auxiliary basis; ``histogram_split`` is data-driven."""
     key = _sym(name).lower()
+    for prefix, label in _SPLIT_PREFIXES.items():
+        if key.startswith(prefix):
+            canon, iscomplex, rng, dd = encoding_info(key[len(prefix):])
+            return label + canon, iscomplex, rng, dd or label == "Hist Split "
     if key not in _ENCODINGS:
         raise ValueError(f"Unknown encoding {name!r}")
     return _ENCODINGS[key]

@@ -14,7 +14,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, model_encoding, transform_data)
+from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, fit_encoding, fit_encoding_from_training_data, opts_encoding,
+                        transform_data, transform_train_data)
 from .engine import SweepEngine
 from .options import MPSOptions, engine_options, numpy_dtype, safe_options
 
@@ -185,7 +186,8 @@ def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = M
     overloads without test data / labels (:413,:416).  X_* are (N, T) matrices, rows = series.
     Returns (TrainedMPS, training_information, encoded_test_states).
 
-    ``device_encode=True`` (the closed-form bases: Legendre, Fourier, Stoudenmire, Sahand, Uniform) preprocesses and encodes on the GPU
+    ``device_encode=True`` (the closed-form bases - Legendre, Fourier, Stoudenmire, Sahand, Uniform - and histogram_split /
+    uniform_split over them, whose bins are fitted on the host first) preprocesses and encodes on the GPU
     (mpst_encode_dataset): the raw matrices are uploaded, the product states are downloaded once for the
     returned EncodedTimeSeriesSets."""
     W, X_train, y_train, X_test, y_test, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding, W)
@@ -211,7 +213,7 @@ def _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding=None, W=
         raise AssertionError("Size of testing dataset and number of testing labels are different!")     # :461
     if X_test.size and X_test.shape[1] != T:
         raise AssertionError("The number of sites supported by the MPS, training, and testing data do not match! ")
-    enc = model_encoding(opts.encoding, custom_encoding)
+    enc = opts_encoding(opts, custom_encoding)
     if enc.iscomplex and opts.dtype == "Float64":
         raise RuntimeError("Using a complex valued encoding but the MPS is real. If using a complex-valued custom "
                            "encoding, set 'dtype <: Complex' in MPSOptions")                              # :466-468
@@ -230,8 +232,10 @@ def _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding=None, W=
 def _encode_fit(X_train, y_train, X_test, y_test, opts, enc, class_keys):
     """transform_data + encode_dataset of fitMPS (:445, :489) on the host"""
     Xtr_s, Xte_s, norms, oob = transform_data(X_train, X_test, opts, enc.range)                          # :445
-    train_states = encode_dataset(X_train, Xtr_s, y_train, enc, opts.d, class_keys)                      # :489
-    test_states = encode_dataset(X_test, Xte_s, y_test, enc, opts.d, class_keys) if X_test.size else \
+    order = np.argsort(np.asarray(y_train), kind="stable")                                               # encodings.jl:43
+    _, encoder = fit_encoding(enc, Xtr_s[order], np.asarray(y_train)[order], opts)                       # encodings.jl:130-131
+    train_states = encode_dataset(X_train, Xtr_s, y_train, enc, opts.d, class_keys, encoder)             # :489
+    test_states = encode_dataset(X_test, Xte_s, y_test, enc, opts.d, class_keys, encoder) if X_test.size else \
         EncodedTimeSeriesSet.empty()
     return train_states, test_states
 
@@ -256,6 +260,13 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
         eng.set_dtype(numpy_dtype(opts.dtype))
         common = dict(basis=enc.name, d=opts.d, sigmoid_transform=opts.sigmoid_transform, minmax=opts.minmax,
                       data_bounds=opts.data_bounds, enc_range=enc.range)
+        if enc.init is not None:
+            # the one fit of the encoding's arguments: on the host, from the training matrix through the host transform
+            # (encodings.jl:130-131); the device encodes both data sets with these bins
+            _, encoder = fit_encoding(enc, transform_train_data(Xs, opts, enc.range)[0], ys, opts)
+            if encoder.bins is None:
+                raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases are encoded on the device")
+            common.update(basis=enc, bins=encoder.bins)
         norms, _ = eng.encode_dataset(0, Xs, li, C, **common)
         train_states = EncodedTimeSeriesSet(eng.get_encoded(0), ys, li, Xs, counts)
         test_states = EncodedTimeSeriesSet.empty()
@@ -276,10 +287,11 @@ def classify_states(mps: TrainedMPS, X_or_states) -> EncodedTimeSeriesSet:
         return X_or_states
     opts = safe_options(mps.opts)
     X_test = np.asarray(X_or_states, dtype=np.float64)
-    enc = model_encoding(opts.encoding)
+    enc = opts_encoding(opts)
     _, Xte_s, _, _ = transform_data(mps.train_data.original_data, X_test, opts, enc.range)          # :160
+    _, _, encoder = fit_encoding_from_training_data(opts, mps.train_data.original_data, mps.train_data.labels)
     n = X_test.shape[0]
-    return encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0})                     # :175 (unsorted: all one label)
+    return encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0}, encoder)            # :175 (unsorted: all one label)
 
 
 def classify(mps: TrainedMPS, X_or_states, engine: Optional[SweepEngine] = None, device: int = 0):
