@@ -147,7 +147,10 @@ int  mpst_comm_select(void* ctx, int oneshot);
 
 /* EncodedTimeSeriesSet -> device (src/Structs/structs.jl:12-33).  `n_global_per_class`
  * may be NULL on a single GPU; with sharding it carries the global class counts that
- * the loss normalisation uses (loss_functions.jl:367,371,423-424). */
+ * the loss normalisation uses (loss_functions.jl:367,371,423-424).
+ * A rejected call of this function or of mpst_encode_[split_]dataset leaves the context
+ * exactly as it was, the old set included; one that fails later (allocation, copy, sigmoid
+ * fit) leaves set `which` empty (N = 0). */
 int  mpst_set_dataset(void* ctx, int which, const void* phi, const int32_t* label_idx,
                       int64_t N, int32_t T, int32_t d, int32_t C, int32_t dtype,
                       const int64_t* n_global_per_class);

@@ -256,12 +256,6 @@ int dalloc(Ctx* c, DevBuf<T>& b, int64_t n) { return dalloc(c, &b.h, n); }
 // (E) buffers: `n` elements of c->esz bytes behind a double* name
 int dalloc_e(struct Ctx* c, double** p, int64_t n);
 
-void free_dataset(DataSet& s) {
-    dfree(&s.phi); dfree(&s.label); dfree(&s.tiles); dfree(&s.chunks); dfree(&s.cls_chunk_off); dfree(&s.cls_off); dfree(&s.inv_count);
-    for (int k = 0; k < 2; ++k) { dfree(&s.parts[k]); dfree(&s.part_off[k]); }
-    s = DataSet();
-}
-
 View make_view(Ctx* c, int which) {
     View v{};
     const DataSet& s = c->ds[which];
@@ -291,7 +285,7 @@ View make_view(Ctx* c, int which) {
             v.kcls_tile[k] = to;
             if (k < (int)s.counts.size()) {
                 so += (int32_t)s.counts[k];
-                to += (int32_t)((s.counts[k] + TILE_S - 1) / TILE_S);
+                to += (int32_t)tiles_of(s.counts[k]);
             }
         }
     }
@@ -1002,6 +996,289 @@ int enqueue_eval(Ctx* c, int which) {
     return 0;
 }
 
+// ---- data sets: validate, plan (mpst_dataset_plan.h), commit ----------------------------------------------------------------
+// mpst_set_dataset and mpst_encode_[split_]dataset run every check that can reject the call before they touch the context: a
+// rejected call leaves it exactly as it was.  The commit releases the old set, builds the new one aside and moves it in complete; an
+// allocation or a copy that fails in between leaves the set empty (N = 0, no buffers), never N > 0 over missing buffers.
+bool basis_is_complex(int basis) { return basis == MPST_BASIS_FOURIER || basis == MPST_BASIS_STOUDENMIRE || basis == MPST_BASIS_SAHAND; }
+bool dtype_is_f32(int dtype) { return dtype == MPST_F32 || dtype == MPST_C64; }
+
+// dst[b][a] = src[a][b] over rows of `row` bytes: series-major [N][T][row] <-> site-major [T][N][row]
+void transpose_rows(void* dst, const void* src, int64_t A, int64_t B, size_t row) {
+    for (int64_t a = 0; a < A; ++a)
+        for (int64_t b = 0; b < B; ++b) memcpy((char*)dst + ((size_t)b * A + a) * row, (const char*)src + ((size_t)a * B + b) * row, row);
+}
+
+// the element type of a context is fixed by its first data set (or mpst_set_dtype) and can only change once both are gone
+int dtype_validate(Ctx* c, int which, int dtype) {
+    if (dtype != MPST_F64 && dtype != MPST_F32 && dtype != MPST_C128 && dtype != MPST_C64) return fail(c, MPST_ERR_INVALID, "unknown dtype %d", dtype);
+    const bool other = c->ds[which ^ 1].N > 0 || c->have_mps;
+    if (c->have_dtype && dtype != c->dtype && other)
+        return fail(c, MPST_ERR_INVALID, "dtype %d disagrees with the context's element type %d (data sets and MPS share one element type, opts.dtype)", dtype, c->dtype);
+    return 0;
+}
+void set_ctx_dtype(Ctx* c, int dtype) {
+    if (!c->have_dtype || dtype != c->dtype) c->ws_ready = c->eval_ready = false;
+    c->dtype = dtype;
+    c->have_dtype = true;
+    c->zw = (dtype == MPST_C128 || dtype == MPST_C64) ? 2 : 1;
+    c->esz = (size_t)(dtype_is_f32(dtype) ? 4 : 8) * c->zw;
+    c->typed = dtype != MPST_F64 || getenv("MPST_TYPED") != nullptr;
+}
+
+// a closed-form basis of dimension d: on its own (mpst_encode_dataset / _values) or as the auxiliary basis of a split one
+int basis_validate(Ctx* c, int basis, int d, bool split) {
+    if (basis < MPST_BASIS_LEGENDRE || basis > MPST_BASIS_UNIFORM)
+        return fail(c, MPST_ERR_UNSUPPORTED, split ? "split bases are implemented over the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)"
+                                                   : "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
+    const int odd = split ? MPST_ERR_UNSUPPORTED : MPST_ERR_INVALID;
+    if (basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, odd, "Stoudenmire Angle encoding only supports d = 2!");
+    if (basis == MPST_BASIS_SAHAND && d % 2) return fail(c, odd, "Sahand encoding only supports even dimension");
+    return 0;
+}
+
+// the checks of a split request (include/mpstime_hip.h); on success eo->basis is the auxiliary basis
+int split_validate(Ctx* c, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp) {
+    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
+    if (!sp || !sp->bins) return fail(c, MPST_ERR_INVALID, "NULL split options or bin edges");
+    if (sp->nbins < 1 || sp->nbins > 512) return fail(c, MPST_ERR_INVALID, "nbins must lie in 1 .. 512 (got %d)", (int)sp->nbins);
+    if (sp->aux_dim < 1 || (int64_t)sp->nbins * sp->aux_dim != d)
+        return fail(c, MPST_ERR_INVALID, "The auxilliary basis dimension (%d) must evenly divide the total feature dimension (%d): d = nbins * aux_dim, nbins = %d",
+                    (int)sp->aux_dim, (int)d, (int)sp->nbins);       // get_nbins_safely, splitbases.jl:2-9
+    if (sp->per_site != 0 && sp->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
+    if (int rc = basis_validate(c, sp->aux_basis, sp->aux_dim, true)) return rc;
+    const int64_t nsite = sp->per_site ? T : 1, ne = sp->nbins + 1;
+    for (int64_t t = 0; t < nsite; ++t)
+        for (int64_t k = 0; k + 1 < ne; ++k)
+            if (!(sp->bins[t * ne + k] <= sp->bins[t * ne + k + 1]))
+                return fail(c, MPST_ERR_INVALID, "bin edges must be non-decreasing (site %lld, edges %lld and %lld: %g, %g)", (long long)t, (long long)k,
+                            (long long)(k + 1), sp->bins[t * ne + k], sp->bins[t * ne + k + 1]);
+    eo->basis = sp->aux_basis;
+    return 0;
+}
+
+bool fits_sigmoid(const mpst_encode_opts* eo) { return eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test; }
+int preprocess_validate(Ctx* c, const mpst_encode_opts* eo, int64_t N, int32_t T) {
+    if (eo->fit_sigmoid && eo->is_test) return fail(c, MPST_ERR_INVALID, "fit_sigmoid: the RobustSigmoid is fitted on the training set only");
+    if (eo->sigmoid_transform && !fits_sigmoid(eo) && !(eo->iqr > 0.0)) return fail(c, MPST_ERR_INVALID, "robust sigmoid needs iqr > 0");
+    if (fits_sigmoid(eo) && N * (int64_t)T > 0x7fffffffll) return fail(c, MPST_ERR_UNSUPPORTED, "fit_sigmoid sorts at most 2^31 - 1 values");
+    return 0;
+}
+
+// What mpst_set_dataset (encoded values of the given dtype) and, with eo set, mpst_encode_[split_]dataset (raw values through eo,
+// split: over sp; dtype from the context or the basis) ask for
+struct DataSetRequest {
+    int which;
+    const int32_t* label_idx;
+    int64_t N;
+    int32_t T, d, C;
+    int dtype;
+    const int64_t* n_global_per_class;
+    bool have_values;
+    mpst_encode_opts* eo = nullptr;
+    bool split = false;
+    const mpst_split_opts* sp = nullptr;
+};
+
+// Every check that can reject the call, in the order the entry points report them; fills r.dtype of an encode call and the plan.
+// Reads the context, changes nothing of it.
+int dataset_validate(Ctx* c, DataSetRequest& r, DataSetPlan* plan) {
+    if (r.eo) {
+        if (int rc = r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false)) return rc;
+    }
+    if (r.which != MPST_TRAIN && r.which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
+    if (r.eo) {
+        // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
+        const bool bcx = basis_is_complex(r.eo->basis);
+        r.dtype = c->have_dtype ? c->dtype : (bcx ? MPST_C128 : MPST_F64);
+        if (bcx && (r.dtype == MPST_F64 || r.dtype == MPST_F32))
+            return fail(c, MPST_ERR_INVALID, "Using a complex valued encoding but the MPS is real. If using a complex-valued custom encoding, set 'dtype <: Complex' in MPSOptions");   // RealRealHighDimension.jl:462-464
+    }
+    if (int rc = dtype_validate(c, r.which, r.dtype)) return rc;
+    if (r.N < 0 || r.T < 2 || r.d < 1 || r.C < 1) return fail(c, MPST_ERR_INVALID, "bad data set dimensions");
+    if ((c->T && c->T != r.T) || (c->d && c->d != r.d) || (c->C && c->C != r.C)) {
+        if (c->have_mps || c->ds[r.which ^ 1].N > 0)
+            return fail(c, MPST_ERR_INVALID, "data set dimensions (T=%d,d=%d,C=%d) disagree with the context (T=%d,d=%d,C=%d)", r.T, r.d, r.C, c->T, c->d, c->C);
+    }
+    plan->counts.assign(r.C, 0);
+    if (r.N == 0) return 0;         // an empty set: no pointer is read
+    if (!r.have_values || !r.label_idx) return fail(c, MPST_ERR_INVALID, "NULL data pointer");
+    const char* e = getenv("MPST_PARTS");
+    const LabelVerdict v = plan_dataset(r.label_idx, r.N, r.C, r.n_global_per_class, e ? std::max(1, atoi(e)) : 0, plan);
+    if (v.what == LabelVerdict::OUT_OF_RANGE) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] = %d out of range", (long long)v.index, v.label);
+    if (v.what == LabelVerdict::UNSORTED) return fail(c, MPST_ERR_INVALID, "Training data must be sorted by class!");  // :624
+    return r.eo ? preprocess_validate(c, r.eo, r.N, r.T) : 0;
+}
+
+template <typename T>
+int upload(Ctx* c, DevBuf<T>& dst, const std::vector<T>& src) {
+    if (int rc = dalloc(c, dst, (int64_t)src.size())) return rc;
+    if (!src.empty()) HIPC(c, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The commit of a validated request: the context takes its element type and dimensions and forgets the old set `which` (released
+// before anything is allocated: the peak is one set, not two); *n receives the plan's tables, the labels and room for the states.
+int dataset_commit(Ctx* c, const DataSetRequest& r, const DataSetPlan& p, DataSet* n) {
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    set_ctx_dtype(c, r.dtype);
+    c->T = r.T; c->d = r.d; c->C = r.C;
+    c->ds[r.which] = DataSet();
+    if (r.which == MPST_TRAIN) c->ws_ready = c->caches_valid = false;       // caches, yhat, partials are sized by the training set
+    c->eval_ready = false;
+    c->epoch++;
+    n->N = r.N;
+    n->counts = p.counts;
+    if (r.N == 0) return 0;
+    n->Nglobal = p.Nglobal;
+    n->ntiles = (int32_t)p.tiles.size();
+    n->nchunks = (int32_t)p.chunks.size();
+    int rc;
+    if ((rc = dalloc_e(c, &n->phi.h, r.N * r.T * r.d)) || (rc = dalloc(c, n->label, r.N))) return rc;
+    HIPC(c, hipMemcpy(n->label, r.label_idx, (size_t)r.N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = upload(c, n->tiles, p.tiles)) || (rc = upload(c, n->chunks, p.chunks)) || (rc = upload(c, n->cls_chunk_off, p.cls_chunk_off)) ||
+        (rc = upload(c, n->cls_off, p.cls_off)) || (rc = upload(c, n->inv_count, p.inv_count)))
+        return rc;
+    for (int pk = 0; pk < 2; ++pk) {
+        n->nparts[pk] = (int32_t)p.parts[pk].size();
+        if ((rc = upload(c, n->parts[pk], p.parts[pk])) || (rc = upload(c, n->part_off[pk], p.part_off[pk]))) return rc;
+    }
+    return 0;
+}
+
+// The one front end of the three entry points.  fill(phi) writes the states ([T][N][d] elements of the context's type) of a non-empty
+// set; the set enters the context once it is complete.
+template <typename Fill>
+int dataset_set(Ctx* c, DataSetRequest& r, Fill fill) {
+    DataSetPlan plan;
+    if (int rc = dataset_validate(c, r, &plan)) return rc;
+    DataSet n;
+    if (int rc = dataset_commit(c, r, plan, &n)) return rc;
+    if (int rc = r.N > 0 ? fill((double*)n.phi) : 0) return rc;
+    c->ds[r.which] = std::move(n);
+    return 0;
+}
+
+// `launch` between the context's two events, waited for: its device time is added to *seconds
+template <typename Launch>
+int timed_launch(Ctx* c, double* seconds, Launch launch) {
+    HIPC(c, hipEventRecord(c->ev_start, c->stream));
+    HIPC(c, launch());
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    *seconds += 1e-3 * ms;
+    return 0;
+}
+
+// preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
+// mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
+// sp: a split basis over eo->basis (its edges are uploaded for the call), or null.  eo has passed preprocess_validate.
+int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp, double* dphi,
+                       double* oob_fix, double* seconds) {
+    int rc;
+    DevBuf<double> dbins, dX, part, lohi, fix;      // released on every exit path, the HIPC early returns included
+    if (sp) {
+        const size_t nedge = (size_t)(sp->per_site ? T : 1) * (size_t)(sp->nbins + 1);
+        if ((rc = dalloc(c, dbins, (int64_t)nedge))) return rc;
+        HIPC(c, hipMemcpy(dbins, sp->bins, nedge * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = dalloc(c, dX, N * T)) || (rc = dalloc(c, part, 512)) || (rc = dalloc(c, lohi, 2))) return rc;
+    const bool test = eo->is_test != 0;
+    if (test && eo->rescale_out_of_bounds && (rc = dalloc(c, fix, 2 * N))) return rc;
+    HIPC(c, hipMemcpy(dX, X, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice));
+    double secs = 0.0;
+    if (fits_sigmoid(eo)) {
+        // Normalization.fit(RobustSigmoid, X_train) (utils.jl:174): median and quartiles of all values from a device sort
+        DevBuf<double> sorted, q3;
+        DevBuf<uint8_t> tmp;
+        const size_t tb = order_stats_temp_bytes(N * T);
+        if ((rc = dalloc(c, sorted, N * T)) || (rc = dalloc(c, q3, 3)) || (rc = dalloc(c, tmp, (int64_t)tb))) return rc;
+        if ((rc = timed_launch(c, &secs, [&] { return launch_order_stats(dX, sorted, tmp, tb, N * T, q3, c->stream); }))) return rc;
+        double h3[3];
+        HIPC(c, hipMemcpy(h3, q3, sizeof h3, hipMemcpyDeviceToHost));
+        eo->median = h3[0];
+        eo->iqr = h3[2] - h3[1];
+        if (!(eo->iqr > 0.0)) return fail(c, MPST_ERR_INVALID, "robust sigmoid needs iqr > 0 (the training data has iqr = %g)", eo->iqr);
+    }
+    if (test || !eo->minmax) {
+        const double h[2] = {eo->lo, eo->hi};
+        HIPC(c, hipMemcpy(lohi, h, sizeof h, hipMemcpyHostToDevice));
+    }
+    EncDev e{};
+    e.N = N; e.T = T; e.d = d;
+    e.norm = eo->basis == MPST_BASIS_LEGENDRE;
+    e.fourier = basis_is_complex(eo->basis);
+    e.basis = eo->basis;
+    e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax; e.is_test = test;
+    e.med = eo->median; e.s = eo->iqr / 1.35;
+    e.lb = eo->data_lb; e.ub = eo->data_ub; e.a = eo->range_a; e.b = eo->range_b;
+    const int bd = sp ? sp->aux_dim : d;         // the closed-form basis' own dimension
+    e.nrm = std::sqrt(std::sqrt((2 * bd + 1) / 2.0) * bd);
+    e.lohi = lohi; e.fix = fix;
+    if (sp) {
+        e.bins = dbins; e.bin_stride = sp->per_site ? sp->nbins + 1 : 0;
+        e.nbins = sp->nbins; e.aux_dim = sp->aux_dim;
+    }
+    if ((rc = timed_launch(c, &secs, [&] {
+            launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
+            return hipGetLastError();
+        })))
+        return rc;
+    if (seconds) *seconds = secs;
+    if (!test && eo->minmax) {
+        double h[2];
+        HIPC(c, hipMemcpy(h, lohi, sizeof h, hipMemcpyDeviceToHost));
+        eo->lo = h[0];
+        eo->hi = h[1];
+    }
+    if (fix && oob_fix) HIPC(c, hipMemcpy(oob_fix, fix, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset
+int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
+                          mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
+                          double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
+    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp};
+    return dataset_set(c, r, [&](double* dphi) {
+        const bool bcx = basis_is_complex(eo->basis);
+        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds);
+        // the basis' own type (fp64, real or pairs) aside, then cast to the context's
+        DevBuf<double> tmp;
+        int rc;
+        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, tmp, oob_fix, seconds))) return rc;
+        launch_tcast(tmp, bcx ? 1 : 0, dphi, c->zw == 2, dtype_is_f32(r.dtype), N * T * d, c->stream);
+        HIPC(c, hipGetLastError());
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+
+// mpst_encode_values and, with split = true, mpst_encode_split_values
+int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
+                         void* phi_out, double* oob_fix, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
+    int rc;
+    if ((rc = split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) || (rc = preprocess_validate(c, eo, N, T))) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    const size_t w = (size_t)d * (basis_is_complex(eo->basis) ? 2 : 1);
+    DevBuf<double> dphi;
+    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds))) return rc;
+    std::vector<double> tmp((size_t)N * T * w);
+    HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    transpose_rows(phi_out, tmp.data(), T, N, w * sizeof(double));
+    return 0;
+}
+
 }  // namespace
 
 // ===========================================================================================
@@ -1043,7 +1320,7 @@ void mpst_destroy(void* ctx) {
     dfree(&c->score_buf);
     if (c->comm && rccl_ready(nullptr)) rccl_ready(nullptr)->CommDestroy(c->comm);
     ipc_release(c);
-    free_dataset(c->ds[0]); free_dataset(c->ds[1]);
+    c->ds[0] = DataSet(); c->ds[1] = DataSet();
     dfree(&c->sites); dfree(&c->chi); dfree(&c->label_site); dfree(&c->LE); dfree(&c->RE); dfree(&c->bt);
     dfree(&c->yhat); dfree(&c->tile_loss); dfree(&c->partial); dfree(&c->gradbuf); dfree(&c->gram); dfree(&c->lam);
     if (c->big) big_eig_destroy(c->big);
@@ -1191,143 +1468,6 @@ int mpst_set_options(void* ctx, const mpst_options* o) {
     return 0;
 }
 
-// Everything of a data set except the encoded values: validation, class counts, class-pure spans.
-static int dataset_common(Ctx* c, int which, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
-                          const int64_t* n_global_per_class, bool have_values) {
-    if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
-    if (N < 0 || T < 2 || d < 1 || C < 1) return fail(c, MPST_ERR_INVALID, "bad data set dimensions");
-    if ((c->T && c->T != T) || (c->d && c->d != d) || (c->C && c->C != C)) {
-        if (c->have_mps || c->ds[which ^ 1].N > 0)
-            return fail(c, MPST_ERR_INVALID, "data set dimensions (T=%d,d=%d,C=%d) disagree with the context (T=%d,d=%d,C=%d)", T, d, C, c->T, c->d, c->C);
-    }
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->T = T; c->d = d; c->C = C;
-    DataSet& s = c->ds[which];
-    free_dataset(s);
-    if (which == MPST_TRAIN) {
-        c->ws_ready = false;        // caches, yhat, partials are sized by the training set
-        c->caches_valid = false;
-    }
-    c->eval_ready = false;
-    c->epoch++;
-    s.N = N;
-    s.counts.assign(C, 0);
-    if (N == 0) return 0;
-    if (!have_values || !label_idx) return fail(c, MPST_ERR_INVALID, "NULL data pointer");
-    for (int64_t i = 0; i < N; ++i) {
-        const int32_t l = label_idx[i];
-        if (l < 0 || l >= C) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] = %d out of range", (long long)i, l);
-        if (i && l < label_idx[i - 1]) return fail(c, MPST_ERR_INVALID, "Training data must be sorted by class!");  // :624
-        s.counts[l]++;
-    }
-    s.gcounts.assign(C, 0);
-    s.Nglobal = 0;
-    for (int k = 0; k < C; ++k) {
-        s.gcounts[k] = n_global_per_class ? n_global_per_class[k] : s.counts[k];
-        s.Nglobal += s.gcounts[k];
-    }
-    int rc;
-    if ((rc = dalloc_e(c, &s.phi, N * T * d))) return rc;
-    if ((rc = dalloc(c, &s.label, N))) return rc;
-    HIPC(c, hipMemcpy(s.label, label_idx, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-    // class-pure spans
-    std::vector<Span> tiles, chunks;
-    std::vector<int32_t> coff(C + 1, 0);
-    int64_t start = 0;
-    for (int k = 0; k < C; ++k) {
-        coff[k] = (int32_t)chunks.size();
-        for (int64_t o = 0; o < s.counts[k]; o += TILE_S)
-            tiles.push_back({(int32_t)(start + o), (int32_t)std::min<int64_t>(TILE_S, s.counts[k] - o), k, 0});
-        for (int64_t o = 0; o < s.counts[k]; o += CHUNK_S)
-            chunks.push_back({(int32_t)(start + o), (int32_t)std::min<int64_t>(CHUNK_S, s.counts[k] - o), k, 0});
-        start += s.counts[k];
-    }
-    coff[C] = (int32_t)chunks.size();
-    s.ntiles = (int32_t)tiles.size();
-    s.nchunks = (int32_t)chunks.size();
-    if ((rc = dalloc(c, &s.tiles, (int64_t)tiles.size()))) return rc;
-    HIPC(c, hipMemcpy(s.tiles, tiles.data(), tiles.size() * sizeof(Span), hipMemcpyHostToDevice));
-    if ((rc = dalloc(c, &s.chunks, (int64_t)chunks.size()))) return rc;
-    HIPC(c, hipMemcpy(s.chunks, chunks.data(), chunks.size() * sizeof(Span), hipMemcpyHostToDevice));
-    if ((rc = dalloc(c, &s.cls_chunk_off, C + 1))) return rc;
-    HIPC(c, hipMemcpy(s.cls_chunk_off, coff.data(), (size_t)(C + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    {
-        std::vector<int32_t> soff(C + 1, 0);
-        for (int k = 0; k < C; ++k) soff[k + 1] = soff[k] + (int32_t)s.counts[k];
-        if ((rc = dalloc(c, &s.cls_off, C + 1))) return rc;
-        HIPC(c, hipMemcpy(s.cls_off, soff.data(), (size_t)(C + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    // parts of the fused gradient kernel: class-pure runs of whole 16-series tiles, about PARTS_TARGET of them
-    {
-        int64_t tiles_total = 0;
-        for (int k = 0; k < C; ++k) tiles_total += (s.counts[k] + TILE_S - 1) / TILE_S;
-        int target = tiles_total >= 4 * PARTS_TARGET ? 2 * PARTS_TARGET : PARTS_TARGET;
-        if (const char* e = getenv("MPST_PARTS")) target = std::max(1, atoi(e));
-        for (int pk = 0; pk < 2; ++pk) {
-            const int tgt = pk ? std::max(1, target / C) : target;      // MSE: every run is walked once per class
-            std::vector<Part> runs;
-            int64_t st = 0;
-            for (int k = 0; k < C; ++k) {
-                const int64_t tk = (s.counts[k] + TILE_S - 1) / TILE_S;
-                if (tk > 0) {
-                    int64_t pkn = (tgt * tk + tiles_total / 2) / std::max<int64_t>(tiles_total, 1);
-                    pkn = std::max<int64_t>(1, std::min(pkn, tk));
-                    for (int64_t q = 0; q < pkn; ++q) {
-                        const int64_t t0 = tk * q / pkn, t1 = tk * (q + 1) / pkn;
-                        const int64_t a = st + t0 * TILE_S, bnd = std::min(st + t1 * TILE_S, st + s.counts[k]);
-                        runs.push_back({(int32_t)a, (int32_t)(bnd - a), k, k, 0, 0, 0, 0});
-                    }
-                }
-                st += s.counts[k];
-            }
-            std::vector<Part> parts;
-            std::vector<int32_t> poff(C + 1, 0);
-            for (int cc = 0; cc < C; ++cc) {
-                poff[cc] = (int32_t)parts.size();
-                bool first = true;
-                for (const Part& r : runs) {
-                    if (!pk && r.own != cc) continue;
-                    Part q = r;
-                    q.cls = cc;
-                    q.first_of_cls = first ? 1 : 0;
-                    first = false;
-                    parts.push_back(q);
-                }
-            }
-            poff[C] = (int32_t)parts.size();
-            s.nparts[pk] = (int32_t)parts.size();
-            if ((rc = dalloc(c, &s.parts[pk], (int64_t)parts.size()))) return rc;
-            if (!parts.empty()) HIPC(c, hipMemcpy(s.parts[pk], parts.data(), parts.size() * sizeof(Part), hipMemcpyHostToDevice));
-            if ((rc = dalloc(c, &s.part_off[pk], C + 1))) return rc;
-            HIPC(c, hipMemcpy(s.part_off[pk], poff.data(), (size_t)(C + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
-    std::vector<double> inv(C);
-    for (int k = 0; k < C; ++k) inv[k] = s.gcounts[k] > 0 ? 1.0 / (double)s.gcounts[k] : 0.0;
-    if ((rc = dalloc(c, &s.inv_count, C))) return rc;
-    HIPC(c, hipMemcpy(s.inv_count, inv.data(), (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// the element type of a context is fixed by its first data set (or mpst_set_dtype) and can only change once both are gone
-static int set_ctx_dtype(Ctx* c, int which, int dtype) {
-    if (dtype != MPST_F64 && dtype != MPST_F32 && dtype != MPST_C128 && dtype != MPST_C64) return fail(c, MPST_ERR_INVALID, "unknown dtype %d", dtype);
-    const bool other = c->ds[which ^ 1].N > 0 || c->have_mps;
-    if (c->have_dtype && dtype != c->dtype && other)
-        return fail(c, MPST_ERR_INVALID, "dtype %d disagrees with the context's element type %d (data sets and MPS share one element type, opts.dtype)", dtype, c->dtype);
-    if (!c->have_dtype || dtype != c->dtype) {
-        c->ws_ready = false;
-        c->eval_ready = false;
-    }
-    c->dtype = dtype;
-    c->have_dtype = true;
-    c->zw = (dtype == MPST_C128 || dtype == MPST_C64) ? 2 : 1;
-    c->esz = (size_t)((dtype == MPST_F32 || dtype == MPST_C64) ? 4 : 8) * c->zw;
-    c->typed = dtype != MPST_F64 || getenv("MPST_TYPED") != nullptr;
-    return 0;
-}
-
 int mpst_set_dtype(void* ctx, int32_t dtype) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
@@ -1335,179 +1475,23 @@ int mpst_set_dtype(void* ctx, int32_t dtype) {
         if (c->have_dtype && dtype == c->dtype) return 0;
         return fail(c, MPST_ERR_INVALID, "mpst_set_dtype must precede the data sets and the MPS");
     }
-    return set_ctx_dtype(c, 0, dtype);
+    const int rc = dtype_validate(c, 0, dtype);
+    if (!rc) set_ctx_dtype(c, dtype);
+    return rc;
 }
 
-int mpst_set_dataset(void* ctx, int which, const void* phi_, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
+int mpst_set_dataset(void* ctx, int which, const void* phi, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                      int32_t C, int32_t dtype, const int64_t* n_global_per_class) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
-    int rc = set_ctx_dtype(c, which, dtype);
-    if (rc) return rc;
-    rc = dataset_common(c, which, label_idx, N, T, d, C, n_global_per_class, phi_ != nullptr);
-    if (rc || N == 0) return rc;
-    DataSet& s = c->ds[which];
-    // site-major copy [T][N][d]
-    const size_t row = (size_t)d * c->esz;
-    const char* phi = (const char*)phi_;
-    std::vector<char> tmp((size_t)N * T * row);
-    for (int64_t i = 0; i < N; ++i)
-        for (int t = 0; t < T; ++t) memcpy(&tmp[((size_t)t * N + i) * row], &phi[((size_t)i * T + t) * row], row);
-    HIPC(c, hipMemcpy(s.phi, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
-// mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
-// sp: a split basis over eo->basis (its edges are uploaded for the call), or null
-static int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp, double* dphi,
-                       double* oob_fix, double* seconds) {
-    int rc;
-    if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    DevBuf<double> dbins;
-    if (sp) {
-        const size_t nedge = (size_t)(sp->per_site ? T : 1) * (size_t)(sp->nbins + 1);
-        if ((rc = dalloc(c, dbins, (int64_t)nedge))) return rc;
-        HIPC(c, hipMemcpy(dbins, sp->bins, nedge * sizeof(double), hipMemcpyHostToDevice));
-    }
-    const bool fit_sig = eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test;
-    if (eo->fit_sigmoid && eo->is_test) return fail(c, MPST_ERR_INVALID, "fit_sigmoid: the RobustSigmoid is fitted on the training set only");
-    if (eo->sigmoid_transform && !fit_sig && !(eo->iqr > 0.0)) return fail(c, MPST_ERR_INVALID, "robust sigmoid needs iqr > 0");
-    if (fit_sig && N * (int64_t)T > 0x7fffffffll) return fail(c, MPST_ERR_UNSUPPORTED, "fit_sigmoid sorts at most 2^31 - 1 values");
-    double *dX = nullptr, *part = nullptr, *lohi = nullptr, *fix = nullptr;
-    struct Temps {      // released on every exit path, the HIPC early returns included
-        double **a, **b, **cc, **d;
-        ~Temps() { dfree(a); dfree(b); dfree(cc); dfree(d); }
-    } temps{&dX, &part, &lohi, &fix};
-    if ((rc = dalloc(c, &dX, N * T)) || (rc = dalloc(c, &part, 512)) || (rc = dalloc(c, &lohi, 2))) return rc;
-    const bool test = eo->is_test != 0;
-    if (test && eo->rescale_out_of_bounds && (rc = dalloc(c, &fix, 2 * N))) return rc;
-    HIPC(c, hipMemcpy(dX, X, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice));
-    double fit_seconds = 0.0;
-    if (fit_sig) {
-        // Normalization.fit(RobustSigmoid, X_train) (utils.jl:174): median and quartiles of all values from a device sort
-        double *sorted = nullptr, *q3 = nullptr;
-        uint8_t* tmp = nullptr;
-        struct T2 {
-            double **a, **b; uint8_t** t;
-            ~T2() { dfree(a); dfree(b); dfree(t); }
-        } t2{&sorted, &q3, &tmp};
-        const size_t tb = order_stats_temp_bytes(N * T);
-        if ((rc = dalloc(c, &sorted, N * T)) || (rc = dalloc(c, &q3, 3)) || (rc = dalloc(c, &tmp, (int64_t)tb))) return rc;
-        HIPC(c, hipEventRecord(c->ev_start, c->stream));
-        HIPC(c, launch_order_stats(dX, sorted, tmp, tb, N * T, q3, c->stream));
-        HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-        HIPC(c, hipEventSynchronize(c->ev_stop));
-        float fms = 0.f;
-        HIPC(c, hipEventElapsedTime(&fms, c->ev_start, c->ev_stop));
-        fit_seconds = 1e-3 * fms;
-        double h3[3];
-        HIPC(c, hipMemcpy(h3, q3, sizeof h3, hipMemcpyDeviceToHost));
-        eo->median = h3[0];
-        eo->iqr = h3[2] - h3[1];
-        if (!(eo->iqr > 0.0)) return fail(c, MPST_ERR_INVALID, "robust sigmoid needs iqr > 0 (the training data has iqr = %g)", eo->iqr);
-    }
-    if (test || !eo->minmax) {
-        const double h[2] = {eo->lo, eo->hi};
-        HIPC(c, hipMemcpy(lohi, h, sizeof h, hipMemcpyHostToDevice));
-    }
-    EncDev e{};
-    e.N = N; e.T = T; e.d = d;
-    e.norm = eo->basis == MPST_BASIS_LEGENDRE;
-    e.fourier = eo->basis == MPST_BASIS_FOURIER || eo->basis == MPST_BASIS_STOUDENMIRE || eo->basis == MPST_BASIS_SAHAND;
-    e.basis = eo->basis;
-    e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax; e.is_test = test;
-    e.med = eo->median; e.s = eo->iqr / 1.35;
-    e.lb = eo->data_lb; e.ub = eo->data_ub; e.a = eo->range_a; e.b = eo->range_b;
-    const int bd = sp ? sp->aux_dim : d;         // the closed-form basis' own dimension
-    e.nrm = std::sqrt(std::sqrt((2 * bd + 1) / 2.0) * bd);
-    e.lohi = lohi; e.fix = fix;
-    if (sp) {
-        e.bins = dbins; e.bin_stride = sp->per_site ? sp->nbins + 1 : 0;
-        e.nbins = sp->nbins; e.aux_dim = sp->aux_dim;
-    }
-    HIPC(c, hipEventRecord(c->ev_start, c->stream));
-    launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_stop));
-    HIPC(c, hipGetLastError());
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    if (seconds) *seconds = 1e-3 * ms + fit_seconds;
-    if (!test && eo->minmax) {
-        double h[2];
-        HIPC(c, hipMemcpy(h, lohi, sizeof h, hipMemcpyDeviceToHost));
-        eo->lo = h[0];
-        eo->hi = h[1];
-    }
-    if (fix && oob_fix) HIPC(c, hipMemcpy(oob_fix, fix, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-static bool basis_is_complex(int basis) { return basis == MPST_BASIS_FOURIER || basis == MPST_BASIS_STOUDENMIRE || basis == MPST_BASIS_SAHAND; }
-
-// the checks of a split request (include/mpstime_hip.h); on success eo->basis is the auxiliary basis
-static int split_validate(Ctx* c, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp) {
-    if (!sp || !sp->bins) return fail(c, MPST_ERR_INVALID, "NULL split options or bin edges");
-    if (sp->nbins < 1 || sp->nbins > 512) return fail(c, MPST_ERR_INVALID, "nbins must lie in 1 .. 512 (got %d)", (int)sp->nbins);
-    if (sp->aux_dim < 1 || (int64_t)sp->nbins * sp->aux_dim != d)
-        return fail(c, MPST_ERR_INVALID, "The auxilliary basis dimension (%d) must evenly divide the total feature dimension (%d): d = nbins * aux_dim, nbins = %d",
-                    (int)sp->aux_dim, (int)d, (int)sp->nbins);       // get_nbins_safely, splitbases.jl:2-9
-    if (sp->per_site != 0 && sp->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
-    if (sp->aux_basis < MPST_BASIS_LEGENDRE || sp->aux_basis > MPST_BASIS_UNIFORM)
-        return fail(c, MPST_ERR_UNSUPPORTED, "split bases are implemented over the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-    if (sp->aux_basis == MPST_BASIS_STOUDENMIRE && sp->aux_dim != 2) return fail(c, MPST_ERR_UNSUPPORTED, "Stoudenmire Angle encoding only supports d = 2!");
-    if (sp->aux_basis == MPST_BASIS_SAHAND && sp->aux_dim % 2) return fail(c, MPST_ERR_UNSUPPORTED, "Sahand encoding only supports even dimension");
-    const int64_t nsite = sp->per_site ? T : 1, ne = sp->nbins + 1;
-    for (int64_t t = 0; t < nsite; ++t)
-        for (int64_t k = 0; k + 1 < ne; ++k)
-            if (!(sp->bins[t * ne + k] <= sp->bins[t * ne + k + 1]))
-                return fail(c, MPST_ERR_INVALID, "bin edges must be non-decreasing (site %lld, edges %lld and %lld: %g, %g)", (long long)t, (long long)k,
-                            (long long)(k + 1), sp->bins[t * ne + k], sp->bins[t * ne + k + 1]);
-    eo->basis = sp->aux_basis;
-    return 0;
-}
-
-// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset
-static int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
-                          mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
-                          double* seconds) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return MPST_ERR_INVALID;
-    if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    if (split) {
-        if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-        if (int rc = split_validate(c, T, d, eo, sp)) return rc;
-    } else {
-        if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
-            return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-        if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
-        if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
-    }
-    if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
-    // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
-    const bool bcx = basis_is_complex(eo->basis);
-    const int natural = bcx ? MPST_C128 : MPST_F64;
-    const int want = c->have_dtype ? c->dtype : natural;
-    if (bcx && (want == MPST_F64 || want == MPST_F32))
-        return fail(c, MPST_ERR_INVALID, "Using a complex valued encoding but the MPS is real. If using a complex-valued custom encoding, set 'dtype <: Complex' in MPSOptions");   // RealRealHighDimension.jl:462-464
-    int rc = set_ctx_dtype(c, which, want);
-    if (rc) return rc;
-    rc = dataset_common(c, which, label_idx, N, T, d, C, n_global_per_class, X != nullptr);
-    if (rc || N == 0) return rc;
-    if (want == natural) return encode_core(c, X, N, T, d, eo, sp, c->ds[which].phi, oob_fix, seconds);
-    double* tmp = nullptr;
-    struct T1 {
-        double** a;
-        ~T1() { dfree(a); }
-    } t1{&tmp};
-    if ((rc = dalloc(c, &tmp, N * T * d * (bcx ? 2 : 1)))) return rc;
-    if ((rc = encode_core(c, X, N, T, d, eo, sp, tmp, oob_fix, seconds))) return rc;
-    launch_tcast(tmp, bcx ? 1 : 0, c->ds[which].phi, c->zw == 2, want == MPST_F32 || want == MPST_C64, N * T * d, c->stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return 0;
+    DataSetRequest r{which, label_idx, N, T, d, C, dtype, n_global_per_class, phi != nullptr};
+    return dataset_set(c, r, [&](double* dphi) {
+        const size_t row = (size_t)d * c->esz;
+        std::vector<char> tmp((size_t)N * T * row);
+        transpose_rows(tmp.data(), phi, N, T, row);
+        HIPC(c, hipMemcpy(dphi, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+        return 0;
+    });
 }
 
 int mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
@@ -1519,40 +1503,6 @@ int mpst_encode_split_dataset(void* ctx, int which, const double* X, const int32
                               int32_t C, mpst_encode_opts* eo, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
                               double* seconds) {
     return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, true, sp, n_global_per_class, oob_fix, seconds);
-}
-
-// mpst_encode_values and, with split = true, mpst_encode_split_values
-static int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
-                         void* phi_out, double* oob_fix, double* seconds) {
-    Ctx* c = (Ctx*)ctx;
-    if (!c) return MPST_ERR_INVALID;
-    if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
-    if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-    if (split) {
-        if (int rc = split_validate(c, T, d, eo, sp)) return rc;
-    } else {
-        if (eo->basis < MPST_BASIS_LEGENDRE || eo->basis > MPST_BASIS_UNIFORM)
-            return fail(c, MPST_ERR_UNSUPPORTED, "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-        if (eo->basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, MPST_ERR_INVALID, "Stoudenmire Angle encoding only supports d = 2!");
-        if (eo->basis == MPST_BASIS_SAHAND && d % 2) return fail(c, MPST_ERR_INVALID, "Sahand encoding only supports even dimension");
-    }
-    HIPC(c, hipSetDevice(c->device));
-    const int zw = basis_is_complex(eo->basis) ? 2 : 1;
-    double* dphi = nullptr;
-    struct T1 {
-        double** a;
-        ~T1() { dfree(a); }
-    } t1{&dphi};
-    int rc;
-    if ((rc = dalloc(c, &dphi, N * T * d * zw))) return rc;
-    if ((rc = encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds))) return rc;
-    std::vector<double> tmp((size_t)N * T * d * zw);
-    HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    double* out = (double*)phi_out;
-    const size_t w = (size_t)d * zw;
-    for (int64_t i = 0; i < N; ++i)
-        for (int t = 0; t < T; ++t) memcpy(&out[((size_t)i * T + t) * w], &tmp[((size_t)t * N + i) * w], w * sizeof(double));
-    return 0;
 }
 
 int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, void* phi_out, double* oob_fix,
@@ -1573,14 +1523,10 @@ int mpst_get_encoded(void* ctx, int which, double* phi_out) {
     if (s.N == 0) return 0;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    const int64_t N = s.N;
-    const int T = c->T;
     const size_t row = (size_t)c->d * c->esz;             // phi_out holds elements of the context's type
-    std::vector<char> tmp((size_t)N * T * row);
+    std::vector<char> tmp((size_t)s.N * c->T * row);
     HIPC(c, hipMemcpy(tmp.data(), s.phi, tmp.size(), hipMemcpyDeviceToHost));
-    char* out = (char*)phi_out;
-    for (int64_t i = 0; i < N; ++i)
-        for (int t = 0; t < T; ++t) memcpy(&out[((size_t)i * T + t) * row], &tmp[((size_t)t * N + i) * row], row);
+    transpose_rows(phi_out, tmp.data(), c->T, s.N, row);
     return 0;
 }
 

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/mpstime_hip.h"
+#include "mpst_dataset_plan.h"
 
 namespace mpst {
 
@@ -283,25 +284,7 @@ __device__ __forceinline__ double wave_max(double x) {
     return fmax(fmax(readlane_f64(x, 0), readlane_f64(x, 16)), fmax(readlane_f64(x, 32), readlane_f64(x, 48)));
 }
 
-// A class-pure run of consecutive series (<= 16 for tiles, <= 64 for chunks).
-struct Span {
-    int32_t start;
-    int32_t count;
-    int32_t cls;
-    int32_t pad;
-};
-
-// A part = the series one persistent workgroup of k_bond_fused walks: a class-pure run [start, start+count) of class
-// `own`, contracted with the bond tensor of class `cls` (KLD: cls == own; MSE: every class).  Parts are ordered by
-// `cls`, so the partial gradients of one class are consecutive.
-struct Part {
-    int32_t start, count, own, cls;
-    int32_t first_of_cls, pad0, pad1, pad2;
-};
-constexpr int PARTS_TARGET = 128;   // persistent workgroups of the fused gradient kernel (256 for >= 512 tiles of 16 series)
-
-constexpr int TILE_S = 16;    // series per yhat/env tile (one MFMA M-tile)
-constexpr int CHUNK_S = 64;   // series per gradient chunk (the GEMM K extent of one partial)
+// Span, Part, TILE_S, CHUNK_S, PARTS_TARGET: mpst_dataset_plan.h
 constexpr int GB = 64;        // gradient output block edge per workgroup
 // k_grad (unfused path): workgroups that share the chunks of one (class, output block); each walks its share with the
 // accumulators in registers and writes one partial block.  Enough workgroups to fill the chip (GRAD_WG_TARGET over all
@@ -336,23 +319,44 @@ struct DevScalars {
     unsigned long long eig_stamps[64];  // s_memrealtime (100 MHz) at the phase boundaries of the last eigensolve
 };
 
-// One encoded data set on the device.
+// A device allocation or an event with one owner: released when the owner goes out of scope, whichever return that is, or is assigned
+// another.  Move-only (the move operations leave no copy operations).
+template <typename H, typename A, hipError_t (*Release)(A)>
+struct DevOwned {
+    H h = nullptr;
+    DevOwned() = default;
+    DevOwned(DevOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    DevOwned& operator=(DevOwned&& o) noexcept {
+        if (this != &o) {
+            if (h) (void)Release(h);
+            h = o.h;
+            o.h = nullptr;
+        }
+        return *this;
+    }
+    ~DevOwned() { if (h) (void)Release(h); }
+    operator H() const { return h; }
+};
+template <typename T>
+using DevBuf = DevOwned<T*, void*, hipFree>;
+using DevEvent = DevOwned<hipEvent_t, hipEvent_t, hipEventDestroy>;
+
+// One encoded data set on the device: the uploaded DataSetPlan, the labels and the states.  Owns its buffers; an empty set is DataSet().
 struct DataSet {
     int64_t N = 0;
-    double* phi = nullptr;       // [T][N][d] site-major
-    int32_t* label = nullptr;    // [N]
-    Span* tiles = nullptr;       // class-pure tiles of <= TILE_S series
+    DevBuf<double> phi;          // [T][N][d] site-major
+    DevBuf<int32_t> label;       // [N]
+    DevBuf<Span> tiles;          // class-pure tiles of <= TILE_S series
     int32_t ntiles = 0;
-    Span* chunks = nullptr;      // class-pure chunks of <= CHUNK_S series
+    DevBuf<Span> chunks;         // class-pure chunks of <= CHUNK_S series
     int32_t nchunks = 0;
-    int32_t* cls_chunk_off = nullptr;  // [C+1] first chunk of each class
-    int32_t* cls_off = nullptr;        // [C+1] first series of each class
-    double* inv_count = nullptr;       // [C] 1 / (global series count of the class)
-    Part* parts[2] = {nullptr, nullptr};          // [0] KLD, [1] MSE
+    DevBuf<int32_t> cls_chunk_off;     // [C+1] first chunk of each class
+    DevBuf<int32_t> cls_off;           // [C+1] first series of each class
+    DevBuf<double> inv_count;          // [C] 1 / (global series count of the class)
+    DevBuf<Part> parts[2];             // [0] KLD, [1] MSE
     int32_t nparts[2] = {0, 0};
-    int32_t* part_off[2] = {nullptr, nullptr};    // [C+1] first part of each bond-tensor class
+    DevBuf<int32_t> part_off[2];       // [C+1] first part of each bond-tensor class
     std::vector<int64_t> counts;       // local per-class counts
-    std::vector<int64_t> gcounts;      // global per-class counts
     int64_t Nglobal = 0;
 };
 
@@ -637,20 +641,6 @@ void launch_eval_reduce(const View& v, const double* yhat_in, double* out3, int6
 void launch_norm2(const View& v, double* out_norm2, double* gscratch /* 3*cap*cap doubles */, hipStream_t s);
 void launch_scale_sites(const View& v, const double* norm2, hipStream_t s);
 void launch_selftest_mfma(const double* A, const double* B, int K, double* C, hipStream_t s);
-
-// A device allocation or an event that lives for one call: released when it goes out of scope, whichever return that is.  Move-only
-// (the move constructor leaves no copy operations).
-template <typename H, typename A, hipError_t (*Release)(A)>
-struct DevOwned {
-    H h = nullptr;
-    DevOwned() = default;
-    DevOwned(DevOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
-    ~DevOwned() { if (h) (void)Release(h); }
-    operator H() const { return h; }
-};
-template <typename T>
-using DevBuf = DevOwned<T*, void*, hipFree>;
-using DevEvent = DevOwned<hipEvent_t, hipEvent_t, hipEventDestroy>;
 
 // hand-written blocked eigensolver for d*chi_max > MAX_DIM (mpst_eig_blocked.hip); returns 1 when its on-device
 // verification asks for the library fallback

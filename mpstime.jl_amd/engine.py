@@ -84,6 +84,23 @@ def _device_basis(basis):
     return basis, rng, split
 
 
+def _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds):
+    """mpst_encode_opts of a training set (``norms`` None: nothing fitted yet, fit_sigmoid left to the caller) or of a test set with
+    the training fit's ``norms``."""
+    eo = L.mpst_encode_opts()
+    eo.basis, eo.sigmoid_transform, eo.minmax = L.BASIS[basis], int(bool(sigmoid_transform)), int(bool(minmax))
+    eo.is_test, eo.rescale_out_of_bounds = int(norms is not None), int(bool(rescale_out_of_bounds))
+    eo.data_lb, eo.data_ub = map(float, data_bounds)
+    eo.range_a, eo.range_b = map(float, enc_range)
+    if norms is not None:
+        if norms.sigmoid is not None:
+            eo.median, eo.iqr = norms.sigmoid
+        eo.sigmoid_transform = int(norms.sigmoid is not None)
+        if norms.minmax is not None:
+            eo.lo, eo.hi = norms.minmax
+    return eo
+
+
 def _split_opts(aux_basis, d, T, bins):
     """mpst_split_opts of a split encoding over ``aux_basis`` with the fitted edges ``bins`` - (nbins + 1,) shared by all sites or
     (T, nbins + 1) - and the array the struct points into (keep it alive over the call)."""
@@ -183,23 +200,12 @@ class SweepEngine:
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
         N, T = X.shape
         d = int(d if d is not None else self.d)
-        eo = L.mpst_encode_opts()
-        eo.basis, eo.sigmoid_transform, eo.minmax = L.BASIS[basis], int(bool(sigmoid_transform)), int(bool(minmax))
-        eo.is_test, eo.rescale_out_of_bounds = int(norms is not None), int(bool(rescale_out_of_bounds))
-        eo.data_lb, eo.data_ub = map(float, data_bounds)
-        eo.range_a, eo.range_b = map(float, enc_range)
-        if norms is None:
-            if sigmoid_transform:
-                if sigmoid_fit is not None:             # (median, iqr) fitted elsewhere, e.g. over all shards
-                    eo.median, eo.iqr = map(float, sigmoid_fit)
-                else:
-                    eo.fit_sigmoid = 1                  # median / quartiles from a device sort of the values
-        else:
-            if norms.sigmoid is not None:
-                eo.median, eo.iqr = norms.sigmoid
-            eo.sigmoid_transform = int(norms.sigmoid is not None)
-            if norms.minmax is not None:
-                eo.lo, eo.hi = norms.minmax
+        eo = _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds)
+        if norms is None and sigmoid_transform:
+            if sigmoid_fit is not None:                 # (median, iqr) fitted elsewhere, e.g. over all shards
+                eo.median, eo.iqr = map(float, sigmoid_fit)
+            else:
+                eo.fit_sigmoid = 1                      # median / quartiles from a device sort of the values
         gc = np.ascontiguousarray(global_counts, dtype=np.int64) if global_counts is not None else None
         fix = np.zeros((N, 2)) if norms is not None else None
         sec = C.c_double()
@@ -231,21 +237,11 @@ class SweepEngine:
         basis, basis_range, split = _device_basis(basis)
         X = np.ascontiguousarray(X, dtype=np.float64)
         N, T = X.shape
-        eo = L.mpst_encode_opts()
-        eo.basis, eo.sigmoid_transform, eo.minmax = L.BASIS[basis], int(bool(sigmoid_transform)), int(bool(minmax))
-        eo.is_test, eo.rescale_out_of_bounds = int(norms is not None), int(bool(rescale_out_of_bounds))
-        eo.data_lb, eo.data_ub = map(float, data_bounds)
         if enc_range is None:
             enc_range = basis_range if (sigmoid_transform or minmax or norms is not None) else (0.0, 1.0)
-        eo.range_a, eo.range_b = map(float, enc_range)
+        eo = _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds)
         if norms is None:
             eo.fit_sigmoid = int(bool(sigmoid_transform))
-        else:
-            if norms.sigmoid is not None:
-                eo.median, eo.iqr = norms.sigmoid
-            eo.sigmoid_transform = int(norms.sigmoid is not None)
-            if norms.minmax is not None:
-                eo.lo, eo.hi = norms.minmax
         cx = basis in ("Fourier", "Stoudenmire", "Sahand")
         out = np.zeros((N, T, int(d)), dtype=np.complex128 if cx else np.float64)
         sec = C.c_double()

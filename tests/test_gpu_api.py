@@ -61,6 +61,79 @@ def test_abi_error_paths(engine_cls):
         e.close()
 
 
+def _state(e):
+    return e.get_encoded(0), e.eval(0), e.info()
+
+
+def _assert_untouched(e, W, phi0, rejected_calls):
+    """Every call of ``rejected_calls`` raises and leaves the context as it was recorded just before - states, evaluation, get_info,
+    bit for bit - with its caches still valid: a bond step runs without build_caches.  The MPS is reset after it."""
+    first = None
+    for match, call in rejected_calls:
+        rec = _state(e)
+        first = first or rec
+        assert np.array_equal(rec[0], phi0) and rec[1][:3] == first[1][:3]
+        with pytest.raises(mt.MPSTError, match=match):
+            call()
+        phi, (mse, kld, acc, conf), info = _state(e)
+        assert np.array_equal(phi, rec[0]) and phi.dtype == rec[0].dtype, match
+        assert (mse, kld, acc) == rec[1][:3] and np.array_equal(conf, rec[1][3]), match
+        assert info == rec[2], match
+        e.bond_step(2, True)
+        e.set_mps(W)
+        e.build_caches()
+
+
+def test_rejected_set_dataset_leaves_the_context_as_it_was(engine_cls):
+    e = engine_cls(0)
+    try:
+        e.set_options(chi_max=4)
+        phi = np.random.default_rng(0).uniform(-1, 1, (8, 4, 2))
+        lab = np.array([0, 0, 0, 0, 1, 1, 1, 1])
+        e.set_dataset(0, phi, lab, 2)
+        W = mt.generate_startingMPS(2, 4, 2, 2, 0)
+        e.set_mps(W)
+        e.build_caches()
+        _assert_untouched(e, W, phi, [
+            ("sorted by class", lambda: e.set_dataset(0, phi, lab[::-1], 2)),
+            ("out of range", lambda: e.set_dataset(0, phi, np.array([0, 0, 0, 0, 1, 1, 1, 2]), 2)),
+            ("disagrees with the context's element type", lambda: e.set_dataset(0, phi, lab, 2, dtype=np.float32)),
+            ("disagree with the context", lambda: e.set_dataset(0, np.zeros((8, 5, 2)), lab, 2)),
+        ])
+        assert e.dtype == np.float64 and (e.T, e.d, e.C, e.N[0]) == (4, 2, 2, 8)
+    finally:
+        e.close()
+
+
+def test_rejected_encode_dataset_leaves_the_context_as_it_was(engine_cls):
+    e = engine_cls(0)
+    try:
+        e.set_options(chi_max=4)
+        e.set_dtype(np.float64)
+        X = np.random.default_rng(1).normal(size=(8, 4))
+        lab = np.array([0, 0, 0, 0, 1, 1, 1, 1])
+        edges = np.array([-1.0, 0.0, 1.0])
+        e.encode_dataset(0, X, lab, 2, d=2)
+        W = mt.generate_startingMPS(2, 4, 2, 2, 0)
+        e.set_mps(W)
+        e.build_caches()
+        phi = e.get_encoded(0)
+        assert phi.dtype == np.float64 and np.abs(phi).max() > 0
+        _assert_untouched(e, W, phi, [
+            ("sorted by class", lambda: e.encode_dataset(0, X, lab[::-1], 2, d=2)),
+            ("out of range", lambda: e.encode_dataset(0, X, np.array([0, 0, 0, 0, 1, 1, 1, 2]), 2, d=2)),
+            ("disagree with the context", lambda: e.encode_dataset(0, np.zeros((8, 5)), lab, 2, d=2)),
+            ("the MPS is real", lambda: e.encode_dataset(0, X, lab, 2, basis="Fourier", d=2)),
+            ("sorted by class", lambda: e.encode_dataset(0, X, lab[::-1], 2, basis="unif_split_legendre", d=2, bins=edges)),
+            ("out of range", lambda: e.encode_dataset(0, X, np.array([2, 0, 0, 0, 1, 1, 1, 1]), 2, basis="unif_split_legendre", d=2, bins=edges)),
+            ("non-decreasing", lambda: e.encode_dataset(0, X, lab, 2, basis="unif_split_legendre", d=2, bins=edges[::-1])),
+            ("the MPS is real", lambda: e.encode_dataset(0, X, lab, 2, basis="unif_split_fourier", d=2, bins=edges)),
+        ])
+        assert e.dtype == np.float64 and (e.T, e.d, e.C, e.N[0]) == (4, 2, 2, 8)
+    finally:
+        e.close()
+
+
 def test_rccl_single_rank_communicator_is_a_no_op(engine_cls):
     """The all-reduce leg of the sharded sweep (mpst_comm_init + ncclAllReduce on the engine's stream)
     with a 1-rank communicator must give the same bits as the engine without a communicator."""
