@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -408,6 +408,25 @@ int  mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double
 int  mpst_impute_model_dist(void* ctx, const mpst_impute_model* m, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                             int32_t ngrid, const mpst_impute_opts* o, double* x_out, double* err_out, double* seconds, int32_t nq,
                             const double* levels, double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out);
+
+/* Marginal likelihoods: the natural log of the likelihood of the KNOWN values of every instance under every class, the missing
+ * sites marginalised - what joins mpst_classify (complete series only) and the imputation engine (which conditions on the
+ * known values and drops the scale).  With W_c the label slice of class c of the model AS STORED (not renormalised per class),
+ * phi[i][j] the encoded value of instance i at site j and K_i its known sites,
+ *     l_c(i) = sum over s_j, j not in K_i, of | < (x)_{j in K_i} phi[i][j]  (x)_{j not in K_i} e_{s_j} | W_c > |^2 :
+ * a known site is projected with conj(phi), a missing site is summed over its physical index - the squared norm of what
+ * precondition (src/Imputation/MPS_methods.jl:42-99) leaves behind.  Nothing missing: l_c = |yhat_c|^2, the overlap mpst_classify
+ * maximises; everything missing: l_c = ||W_c||^2.  (The Born rule; not the |rho phi|^2 convention of the imputed densities.)
+ *   m               as in mpst_impute_model_run; m->label_idx is ignored and may be NULL.  phi is not read at missing sites
+ *                   (the host may hold NaN there).
+ *   missing[N][T]   nonzero = missing; NULL = nothing missing (the same bits as an all-zero mask)
+ *   logp_out[N][C]  ln l_c(i), IEEE -inf where l_c is zero; never NaN for finite inputs
+ *   seconds         device time of the call, may be NULL
+ * Real and complex models, MPST_COMPUTE_F64 and _F32; the chain is rescaled at every site and the logarithms of the scales are
+ * accumulated in fp64 on both compute paths, so long chains neither underflow nor lose the scale.
+ * MPST_ERR_INVALID: NULL m or logp_out, non-positive dimensions; MPST_ERR_UNSUPPORTED: chi_max > 128, d > 16 or C > 16. */
+int  mpst_marginal_model(void* ctx, const mpst_impute_model* m, const uint8_t* missing /* [N][T], NULL = nothing missing */,
+                         double* logp_out /* [N][C] */, double* seconds /* may be NULL */);
 
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the

@@ -113,6 +113,7 @@ SYMBOLS = {
                                    _i32, _i32, _dp]),
     "mpst_impute_model_dist": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _vp, _i32, C.POINTER(ImputeOpts), _dp, _dp,
                                          _dp, _i32, _dp, _dp, _i32, _i32, _dp]),
+    "mpst_marginal_model": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _dp]),
     "mpst_entanglement": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
     "mpst_see_variation": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
     "mpst_get_impute_phases": (C.c_int, [_vp, _dp]),

@@ -2279,6 +2279,8 @@ struct ImputeRequest {
     int32_t nq = 0, cdf_stride = 0, cdf_rows = 0;
     const double* levels = nullptr;
     double *q_out = nullptr, *cdf_out = nullptr;
+    bool marginal = false;      // mpst_marginal_model: no grid, no options; missing may be NULL; logp_out[N][C]
+    double* logp_out = nullptr;
     bool grid_per_site() const { return o && o->grid_per_site == 1; }      // grid_phi is [T][ngrid][d]
 };
 constexpr int IMPUTE_MAX_LEVELS = 16;
@@ -2579,6 +2581,50 @@ static int run_impute(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
     return 0;
 }
 
+// The marginal likelihoods of a request (mpst_marginal_model) on the same plan, buffers and route: no grid, no environments kept, one
+// kernel per chunk of instances; beyond the LDS limit a chunk is what its global scratch lets fit.
+constexpr int MARGINAL_MAX_CLASSES = 16;
+static int run_marginal(Ctx* c, const ImpModel& m, const ImputeRequest& r, int C) {
+    const int64_t N = m.N;
+    const size_t esz = m.compute_f32 ? 4 : 8;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    ImputePlan p;
+    p.order.resize((size_t)N);
+    for (int64_t i = 0; i < N; ++i) p.order[i] = (int32_t)i;
+    p.welems = marginal_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
+    p.chunk = std::min<int64_t>(N, (int64_t)1 << 30);
+    if (p.welems) {
+        size_t free_b = 0, total_b = 0;
+        HIPC(c, hipMemGetInfo(&free_b, &total_b));
+        const double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b), per_bytes = (double)p.welems * (double)esz;
+        p.chunk = std::max<int64_t>(1, std::min<int64_t>(p.chunk, (int64_t)(budget / per_bytes)));
+    }
+    ImputeBufs b;
+    ImputeParams q{};
+    int rc;
+    if ((rc = dalloc(c, b.ord, N)) || (rc = dalloc(c, b.x, N * C)) || (r.missing && (rc = dalloc(c, b.miss, N * m.T))) ||
+        (p.welems && (rc = dalloc(c, b.W, (int64_t)(p.chunk * p.welems * esz))))) return rc;
+    HIPC(c, hipMemcpy(b.ord, p.order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (r.missing) HIPC(c, hipMemcpy(b.miss, r.missing, (size_t)N * m.T, hipMemcpyHostToDevice));
+    q.g.missing = b.miss;
+    q.g.x_out = b.x;
+    q.work = b.W;
+    q.order = b.ord;
+    q.nclass = C;
+    HIPC(c, hipEventRecord(c->ev_start, c->stream));
+    for (int64_t i0 = 0; i0 < N; i0 += p.chunk)
+        if (launch_marginal(m, q, i0, std::min(p.chunk, N - i0), c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the marginal-likelihood kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    HIPC(c, hipGetLastError());
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    if (r.seconds) *r.seconds = 1e-3 * ms;
+    HIPC(c, hipMemcpy(r.logp_out, b.x, (size_t)N * C * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int mpst_get_impute_phases(void* ctx, double* seconds_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !seconds_out) return MPST_ERR_INVALID;
@@ -2682,8 +2728,13 @@ static void pack_model(const mpst_impute_model* h, int cap, int64_t stride, bool
 
 // the model from host arrays: packed, uploaded for the call, freed after it
 static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest& r) {
-    if (!h || !h->site || !h->chi || !h->phi || !h->label_idx) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (!h || !h->site || !h->chi || !h->phi || (!r.marginal && !h->label_idx)) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (h->N <= 0 || h->T < 1 || h->d < 1 || h->C < 1) return fail(c, MPST_ERR_INVALID, "empty model or data");
+    if (r.marginal) {
+        if (!r.logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+        if (h->d > 16 || h->C > MARGINAL_MAX_CLASSES)
+            return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold d <= 16 and C <= %d (got %d, %d)", MARGINAL_MAX_CLASSES, h->d, h->C);
+    }
     if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
     if (h->compute != MPST_COMPUTE_F64 && h->compute != MPST_COMPUTE_F32) return fail(c, MPST_ERR_INVALID, "compute must be MPST_COMPUTE_F64 or MPST_COMPUTE_F32");
     if (h->label_site < 0 || h->label_site >= h->T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
@@ -2695,9 +2746,11 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest&
     }
     for (int j = 0; j < h->T; ++j)
         if (!h->site[j]) return fail(c, MPST_ERR_INVALID, "site[%d] is NULL", j);
-    for (int64_t i = 0; i < h->N; ++i)
+    for (int64_t i = 0; i < h->N && !r.marginal; ++i)
         if (h->label_idx[i] < 0 || h->label_idx[i] >= h->C) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] out of range", (long long)i);
     const bool cx = h->dtype == MPST_DTYPE_C64, f32 = h->compute == MPST_COMPUTE_F32;
+    if (r.marginal && cap > impute_chi_limit(cx, f32))
+        return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold chi_max <= %d (got %d)", impute_chi_limit(cx, f32), cap);
     HIPC(c, hipSetDevice(c->device));
     const int64_t stride = (int64_t)h->C * cap * h->d * cap;
     const size_t esz = (f32 ? 4 : 8) * (cx ? 2 : 1);
@@ -2705,7 +2758,7 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest&
     DevBuf<int32_t> dchi, dls, dlab;
     int rc;
     if ((rc = dalloc(c, dsites, (int64_t)(stride * h->T * esz))) || (rc = dalloc(c, dphi, (int64_t)(h->N * h->T * h->d * esz))) ||
-        (rc = dalloc(c, dchi, h->T + 1)) || (rc = dalloc(c, dls, 1)) || (rc = dalloc(c, dlab, h->N))) return rc;
+        (rc = dalloc(c, dchi, h->T + 1)) || (rc = dalloc(c, dls, 1)) || (!r.marginal && (rc = dalloc(c, dlab, h->N)))) return rc;
     if (f32) {
         std::vector<float> hs, hp;
         pack_model<float>(h, cap, stride, cx, hs, hp);
@@ -2719,9 +2772,9 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest&
     }
     HIPC(c, hipMemcpy(dchi, h->chi, (size_t)(h->T + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!r.marginal) HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
     const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return run_impute(c, m, r);
+    return r.marginal ? run_marginal(c, m, r, h->C) : run_impute(c, m, r);
 }
 
 int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2756,6 +2809,15 @@ int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t*
     r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
     r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
     r.K = K, r.seeded = u == nullptr, r.seed = (uint64_t)seed, r.row_id = row_id;
+    return impute_model(c, h, r);
+}
+
+int mpst_marginal_model(void* ctx, const mpst_impute_model* h, const uint8_t* missing, double* logp_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    ImputeRequest r;
+    r.missing = missing, r.seconds = seconds, r.marginal = true, r.logp_out = logp_out;
     return impute_model(c, h, r);
 }
 

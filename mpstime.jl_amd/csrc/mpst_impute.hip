@@ -1734,6 +1734,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 }
 
 #include "mpst_impute_batched.inl"
+#include "mpst_marginal.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1749,6 +1750,7 @@ static int impute_lds_chi_limit(bool cx, bool f32) {
 }
 int impute_chi_limit(bool, bool) { return CAP_LIMIT; }
 int64_t impute_work_elems(int cap, bool cx, bool f32) { return cap > impute_lds_chi_limit(cx, f32) ? 4ll * cap * cap * (cx ? 2 : 1) : 0; }
+int64_t marginal_work_elems(int cap, bool cx, bool f32) { return cap > impute_lds_chi_limit(cx, f32) ? (int64_t)MRG_BIG_MATS * cap * cap * (cx ? 2 : 1) : 0; }
 
 // ---- the route of a call: which kernels, at which block size / occupancy / dynamic LDS -----------------------------------
 struct ImputeSwitches {
@@ -1842,6 +1844,7 @@ static hipError_t imp_raise_lds() {
 #define X(WHEN, EMB, DIST) if constexpr (WHEN) { RAISE((k_imp_leftb<R, CX, EMB, DIST>), IMB_LDS_MAX) }
     IMP_LEFTB_LIST(X)
 #undef X
+    RAISE((k_marginal<R, CX, false>), right_max)      // the environment pass's matrices and limit
 #undef RAISE
     return hipSuccess;
 }
@@ -1925,5 +1928,24 @@ int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t 
     const hipError_t e = v.is_complex ? (v.compute_f32 ? imp_run<float, true>(rt, v, q, ch) : imp_run<double, true>(rt, v, q, ch))
                                       : (v.compute_f32 ? imp_run<float, false>(rt, v, q, ch) : imp_run<double, false>(rt, v, q, ch));
     return e == hipSuccess ? (rt.batched ? 1 : 0) : -1;
+}
+
+// the marginal likelihoods of the instances order[i0 .. i0 + count): the environment pass's route (LDS or global scratch), one kernel
+template <typename R, bool CX>
+static hipError_t marg_run(const ImputeRoute& rt, const ImpModel& v, const ImputeParams& q, const ImputeChunk& ch) {
+    ImpArgs g = q.g;
+    g.ord = q.order + ch.i0;
+    const dim3 grid((unsigned)ch.count);
+    if (rt.env_big) hipLaunchKernelGGL((k_marginal<R, CX, true>), grid, dim3(IMP_T), 0, ch.s, v, g, q.nclass, (R*)q.work);
+    else hipLaunchKernelGGL((k_marginal<R, CX, false>), grid, dim3(IMP_T), rt.env_lds, ch.s, v, g, q.nclass, (R*)nullptr);
+    return hipGetLastError();
+}
+
+int launch_marginal(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s) {
+    const ImputeRoute rt = impute_route(v, q, impute_switches());
+    const ImputeChunk ch{i0, count, s, nullptr};
+    const hipError_t e = v.is_complex ? (v.compute_f32 ? marg_run<float, true>(rt, v, q, ch) : marg_run<double, true>(rt, v, q, ch))
+                                      : (v.compute_f32 ? marg_run<float, false>(rt, v, q, ch) : marg_run<double, false>(rt, v, q, ch));
+    return e == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

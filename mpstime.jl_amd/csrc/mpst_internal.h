@@ -709,11 +709,16 @@ struct ImputeParams {
     void* work;                 // device [chunk][4][cap*cap] elements when the bond dimension exceeds the LDS kernel's, else null
     int trig;                   // the grid states are the Fourier / Legendre basis on the uniform grid x0 + k dxu: densities in closed form
     const int32_t* order;       // device [N]: the order in which the instances are dealt out to workgroups
+    int nclass;                 // marginal likelihoods (k_marginal): the classes of the label site; g.x_out is then logp[N][C]
 };
 int impute_chi_limit(bool cx, bool f32);
 int64_t impute_work_elems(int cap, bool cx, bool f32);     // per-instance scratch elements of the large-chi environment kernel
 // environment pass for the instances order[i0 .. i0 + count), the sweep for their count * ntraj chains
 int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s, hipEvent_t mid = nullptr);   // 1: the sweep ran sixteen chains per workgroup (k_imp_leftb), 0: one each, -1: the route names no built kernel
+// marginal likelihoods (k_marginal): per-instance scratch elements beyond the LDS limit; the launch (0, or -1 on a launch error).
+// q.g.missing may be null (nothing missing), q.g.x_out is logp[N][q.nclass], q.work the scratch, v.label is not read
+int64_t marginal_work_elems(int cap, bool cx, bool f32);
+int launch_marginal(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin

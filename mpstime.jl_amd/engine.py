@@ -463,6 +463,12 @@ class SweepEngine:
         return self._impute(("mpst_impute_model_run", "mpst_impute_model_traj", "mpst_impute_model_dist"), (C.byref(model),), (m, gx, gp),
                             args, dist)
 
+    def marginal_model(self, W, phi, missing, compute="f64", label_site=None):
+        """mpst_marginal_model: (logp (N, C), seconds), the log likelihood of the known values of every instance under every class
+        with the sites where ``missing`` (N, T; None: none) is set marginalised; see ``marginal.marginal_model``."""
+        from .marginal import marginal_model
+        return marginal_model(self, W, phi, missing, compute=compute, label_site=label_site)
+
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call."""
         out = np.zeros(2)

@@ -294,9 +294,13 @@ def classify_states(mps: TrainedMPS, X_or_states) -> EncodedTimeSeriesSet:
     return encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0}, encoder)            # :175 (unsorted: all one label)
 
 
-def classify(mps: TrainedMPS, X_or_states, engine: Optional[SweepEngine] = None, device: int = 0):
+def classify(mps: TrainedMPS, X_or_states, engine: Optional[SweepEngine] = None, device: int = 0, missing_mask=None):
     """classify(mps, test_states) (summary.jl:116-136) and classify(mps, X_test) (:155-177):
-    predicted labels (original label values) by maximum overlap |yhat|^2."""
+    predicted labels (original label values) by maximum overlap |yhat|^2.  With a ``missing_mask`` (N, T) the series may be
+    incomplete: the label of the largest marginal likelihood of the known values (``marginal.log_marginals``)."""
+    if missing_mask is not None:
+        from .marginal import classify_incomplete
+        return classify_incomplete(mps, X_or_states, missing_mask, engine=engine, device=device)
     opts = safe_options(mps.opts)
     labels = np.unique(mps.train_data.labels)
     states = classify_states(mps, X_or_states)
