@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include "mpst_internal.h"
+#include "mpst_batch_groups.h"
 
 using namespace mpst;
 
@@ -96,82 +97,133 @@ Rccl* rccl_ready(std::string* why) {
 
 enum KClass { K_YHAT = 0, K_GRAD, K_UPDATE, K_GRAM, K_EIG_TRI, K_SPLIT, K_ENV, K_BT, K_ALLREDUCE, K_EIG_VEC, K_EIG_FIN, K_NCLASS };
 
+using DevStream = DevOwned<hipStream_t, hipStream_t, hipStreamDestroy>;
+using DevGraphExec = DevOwned<hipGraphExec_t, hipGraphExec_t, hipGraphExecDestroy>;
+inline hipError_t release_big(BigEig* b) { big_eig_destroy(b); return hipSuccess; }
+inline hipError_t release_blocked(BlockedEig* b) { blocked_eig_destroy(b); return hipSuccess; }
+
+struct Ctx;
+
+// ---- the device memory of a context, grouped by the event that replaces it (released first, built aside, moved in complete) ---
+// The MPS: replaced by mpst_set_mps when the capacity changes.
+struct Mps {
+    int cap = 0;              // capacity bond dimension of all device buffers
+    int64_t site_stride = 0;
+    DevBuf<double> sites;     // (E) T slots of site_stride elements
+    DevBuf<int32_t> chi;         // device [T+1]
+    DevBuf<int32_t> label_site;  // device
+};
+
+// Large bonds, sweeps: the state an optimistic sweep starts from, so that a sweep in which any bond failed can be redone bond by bond
+struct Snapshot {
+    DevBuf<double> sites;     // (E)
+    DevBuf<int32_t> chi;      // [T + 2]: chi, label_site
+    DevBuf<DevScalars> sc;
+    explicit operator bool() const { return sites != nullptr; }
+    int copies(Ctx* c, bool restore);
+    int save(Ctx* c) { return copies(c, false); }
+    int restore(Ctx* c) { return copies(c, true); }
+};
+
+// The training workspace: everything ensure_workspace allocates or decides for (training set, options, capacity, element type).
+// Buffers marked (E) hold elements of c->esz bytes behind their double* names.
+struct TrainWs {
+    // caches + workspaces (train set)
+    DevBuf<double> LE, RE;    // (E)
+    int64_t cache_elems = 0;
+    DevBuf<double> bt, partial;      // (E)
+    DevBuf<double> yhat, tile_loss, gradbuf, gram, lam, E, eig_ws, btn, norm_part;
+    // four-launch chain (k_grad_s, k_gram_upd, k_eig_trivec, k_bond_tail): bt_new once more as [c][y][x] for the tail's contraction going
+    // right; a tail whose on-device verification failed marks the sweep (DevScalars::redo) and the rest of it is redone on the six-launch chain
+    DevBuf<double> btnT;
+    DevBuf<unsigned long long> tail_span;    // diagnostics: (start, end) stamps of every workgroup of the stamped k_bond_tail launch
+    bool chain4_ok = false;
+    int tail_force_fail = -1, tail_launches = 0;      // test hook (MPST_TAIL_FORCE_REDO=n): the n-th tail launch of the workspace reports a failed verification
+    // sliced bond GEMMs (k_yhat_s / k_grad_s): slice contributions to yhat, loss pieces, arrival tickets
+    DevBuf<double> b2_ypart, b2_lossp;
+    DevBuf<unsigned int> b2_tick;
+    DevBuf<unsigned long long> b2_dbg;   // bring-up stamps of the sliced kernels (MPST_B2_DEBUG builds)
+    int b2_ksplit = 0, b2_norm_parts = 0;
+    bool b2 = false;            // the fused chain uses k_yhat_s + k_grad_s instead of k_bond_fused + k_fused_reduce
+    DevBuf<double> loss_trace;  // track_cost: [2(T-1)][update_iters + 1]
+    int n_norm_part = 0;
+    bool fused = false;        // bond tensors <= MAX_DIM^2 and no rescale[1]: the 7-launch chain of mpst_fused.hip
+    int64_t partial_elems = 0;
+    DevBuf<DevScalars> sc;
+    DevBuf<double> norm2;
+    DevBuf<double> norm_scratch;    // 3*cap*cap doubles for k_norm2 when they exceed its LDS
+    // element-typed context
+    DevBuf<double> tnorm_scratch;   // typed normalize: three complex cap x cap matrices
+    DevBuf<int32_t> xLE, xRE, yexp; // typed: binary exponents of the environment rows / overlaps
+    DevOwned<BigEig*, BigEig*, release_big> big;          // d*cap > MAX_DIM: library eigensolver at the capacity size (fallback of the blocked one)
+    DevOwned<BlockedEig*, BlockedEig*, release_blocked> blk;    // d*cap > MAX_DIM: hand-written blocked eigensolver
+    // large bonds, sweeps: the verdict of the blocked eigensolver is read once per sweep instead of once per bond (no host
+    // synchronisation inside the sweep); a sweep in which any bond failed is redone from a snapshot, bond by bond
+    bool big_opt = false;
+    Snapshot snap;
+    int big_force_fail = -1, big_solves = 0;          // test hook (MPST_BIG_FORCE_FAIL=n): the n-th solve of the workspace is marked failed
+};
+
+// The evaluation scratch, sized by the larger of the two data sets: replaced by ensure_eval
+struct EvalWs {
+    DevBuf<double> chainL[2], chainR[2];   // (E)
+    DevBuf<int32_t> xchainL[2], xchainR[2];
+    DevBuf<double> yeval, out3;
+    DevBuf<int64_t> conf;
+    DevBuf<int32_t> pred;
+    int64_t eval_N = 0;
+};
+
+// What a context holds as the lead of a batch.  mpst_sweep_batch: the Views of the K fits on the device ([2][K]: plain, and the Gram
+// launch's variant), the captured sweep and what it was captured for; mpst_classify_batch: the jobs and every fit's results in one block
+struct BatchLead {
+    DevBuf<View> batch_views;
+    int batch_cap = 0;
+    DevGraphExec batch_graph;
+    std::vector<std::pair<uint64_t, uint64_t>> batch_key;   // (uid, epoch) per member: an address can be handed out again, a uid cannot
+    DevBuf<uint8_t> score_buf;
+    int64_t score_cap = 0;
+};
+
 struct Ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // session state, the context's lifetime.  Members are destroyed in reverse order: the stream outlives every event, buffer and graph.
+    DevStream stream;
+    DevEvent ev_start, ev_stop;
+    std::vector<DevEvent> ev_pool;
     std::string err;
     mpst_options opt{};
     bool have_opt = false;
     int T = 0, d = 0, C = 0;
-    int cap = 0;              // capacity bond dimension of all device buffers
     // element type of the data sets and of the MPS (mpst_set_dataset's dtype = opts.dtype, RealRealHighDimension.jl:442).
     // typed: everything runs through the element-typed kernels of mpst_typed.hip (always for fp32 / complex; MPST_TYPED=1
-    // sends Float64 through them too - the cross-check of the two implementations); the buffers marked (E) below then hold
+    // sends Float64 through them too - the cross-check of the two implementations); the (E) buffers then hold
     // elements of esz bytes behind their double* names.
     int dtype = MPST_F64;
     bool have_dtype = false, typed = false;
     int zw = 1;               // 2: complex
     size_t esz = 8;           // bytes per element
-    double* tnorm_scratch = nullptr;   // typed normalize: three complex cap x cap matrices
-    int32_t *xLE = nullptr, *xRE = nullptr, *yexp = nullptr;      // typed: binary exponents of the environment rows / overlaps
-    int32_t *xchainL[2] = {nullptr, nullptr}, *xchainR[2] = {nullptr, nullptr};
     DataSet ds[2];
-    // MPS
     bool have_mps = false;
-    double* sites = nullptr;
-    int64_t site_stride = 0;
-    int32_t* chi = nullptr;         // device [T+1]
-    int32_t* label_site = nullptr;  // device
-    // caches + workspaces (train set)
-    double *LE = nullptr, *RE = nullptr;
-    int64_t cache_elems = 0;
-    double *bt = nullptr, *yhat = nullptr, *tile_loss = nullptr, *partial = nullptr, *gradbuf = nullptr;
-    double *gram = nullptr, *lam = nullptr, *E = nullptr, *eig_ws = nullptr;
-    double *btn = nullptr, *norm_part = nullptr;
-    // four-launch chain (k_grad_s, k_gram_upd, k_eig_trivec, k_bond_tail): bt_new once more as [c][y][x] for the tail's contraction going
-    // right; which bond's overlaps the last tail launch left in b2_ypart (valid while nothing else touched the context: bond_seq / epoch);
-    // a tail whose on-device verification failed marks the sweep (DevScalars::redo) and the rest of it is redone on the six-launch chain
-    double* btnT = nullptr;
-    unsigned long long* tail_span = nullptr;    // diagnostics: (start, end) stamps of every workgroup of the stamped k_bond_tail launch
-    bool chain4_ok = false, chain4_hold = false;
+    Mps mps;
+    bool ws_ready = false;      // training workspace (caches, bond tensor, gradient, eigensolver) built for the current sizes
+    TrainWs ws;
+    bool eval_ready = false;    // evaluation scratch (chains, yeval, pred) built for max(N_train, N_test)
+    EvalWs ev;
+    BatchLead lead;
+    bool caches_valid = false;  // LE / RE describe the current MPS: set by mpst_build_caches, cleared by whatever invalidates them
+    int host_label_site = -1;   // host mirror of *label_site (set_mps, bond_step and sweep move it deterministically)
+    // four-launch chain: which bond's overlaps the last tail launch left in b2_ypart (valid while nothing else touched the context:
+    // bond_seq / epoch); held back while a marked sweep / bond is redone
+    bool chain4_hold = false;
     int ynext_lid = -1;
     uint64_t ynext_epoch = 0, ynext_seq = 0, bond_seq = 0;
     int tail_redos = 0;
     int32_t ss_counts[2] = {0, 0};      // subspace eigensolver: bonds attempted / accepted, read where a sweep or a bond step synchronises anyway
-    int tail_force_fail = -1, tail_launches = 0;      // test hook (MPST_TAIL_FORCE_REDO=n): the n-th tail launch of the context reports a failed verification
-    // sliced bond GEMMs (k_yhat_s / k_grad_s): slice contributions to yhat, loss pieces, arrival tickets
-    double *b2_ypart = nullptr, *b2_lossp = nullptr;
-    unsigned int* b2_tick = nullptr;
-    unsigned long long* b2_dbg = nullptr;   // bring-up stamps of the sliced kernels (MPST_B2_DEBUG builds)
-    int b2_ksplit = 0, b2_norm_parts = 0;
-    bool b2 = false;            // the fused chain uses k_yhat_s + k_grad_s instead of k_bond_fused + k_fused_reduce
-    double* loss_trace = nullptr;   // track_cost: [2(T-1)][update_iters + 1]
-    int n_norm_part = 0;
-    bool fused = false;        // bond tensors <= MAX_DIM^2 and no rescale[1]: the 7-launch chain of mpst_fused.hip
-    int64_t partial_elems = 0;
-    DevScalars* sc = nullptr;
-    // eval scratch
-    double *chainL[2] = {nullptr, nullptr}, *chainR[2] = {nullptr, nullptr}, *yeval = nullptr, *out3 = nullptr;
-    int64_t* conf = nullptr;
-    int32_t* pred = nullptr;
-    int64_t eval_N = 0;
-    double* norm2 = nullptr;
-    double* norm_scratch = nullptr;   // 3*cap*cap doubles for k_norm2 when they exceed its LDS
-    BigEig* big = nullptr;            // d*cap > MAX_DIM: library eigensolver at the capacity size (fallback of the blocked one)
-    BlockedEig* blk = nullptr;        // d*cap > MAX_DIM: hand-written blocked eigensolver
     int64_t big_fallbacks = 0;        // bonds on which the blocked solver's verification asked for the library
-    // large bonds, sweeps: the verdict of the blocked eigensolver is read once per sweep instead of once per bond (no host
-    // synchronisation inside the sweep); a sweep in which any bond failed is redone from a snapshot, bond by bond
-    bool big_opt = false, big_opt_active = false;
-    double* snap_sites = nullptr;
-    int32_t* snap_chi = nullptr;      // [T + 2]: chi, label_site
-    DevScalars* snap_sc = nullptr;
-    int big_redos = 0, big_force_fail = -1, big_solves = 0;
+    bool big_opt_active = false;
+    int big_redos = 0;
     int big_cooldown = 0;             // sweeps left that read the verdict per bond after a sweep had to be redone
-    bool ws_ready = false;      // training workspace (caches, bond tensor, gradient, eigensolver) allocated for the current sizes
-    bool eval_ready = false;    // evaluation scratch (chains, yeval, pred) allocated for max(N_train, N_test)
-    bool caches_valid = false;  // LE / RE describe the current MPS: set by mpst_build_caches, cleared by whatever invalidates them
-    int host_label_site = -1;   // host mirror of *label_site (set_mps, bond_step and sweep move it deterministically)
     // multi-GPU
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
@@ -179,8 +231,8 @@ struct Ctx {
     // summed gradient, plain stream) also with ONE rank - the RCCL leg then runs on every 1-GPU CI box (tests/test_gpu_multi.py)
     bool force_coll = false;
     // one-shot direct-write all-reduce (mpst_allreduce.hip): this rank's inbox (fine-grained device memory, exported
-    // over IPC) and the peers' inboxes as mapped here
-    void* ipc_local = nullptr;           // [2][nranks][slot] doubles | 16 flags | 2 counters
+    // over IPC) and the peers' inboxes as mapped here (borrowed: ipc_release closes them)
+    DevBuf<uint8_t> ipc_local;           // [2][nranks][slot] doubles | 16 flags | 2 counters
     void* ipc_peer[AR_MAX_RANKS] = {nullptr};
     int64_t ipc_slot = 0;
     size_t ipc_flag_off = 0, ipc_ctr_off = 0, ipc_bytes = 0;
@@ -189,7 +241,6 @@ struct Ctx {
     unsigned long long ar_epoch = 0;
     // profiling
     unsigned prof_mask = 0;
-    std::vector<hipEvent_t> ev_pool;
     struct Rec { int k; size_t e0, e1; };
     std::vector<Rec> recs;
     size_t ev_used = 0;
@@ -200,22 +251,14 @@ struct Ctx {
     int impute_env_wgs = 0;              // ... the workgroups of its environment pass (one per instance with a missing site or not: the grid)
     int impute_chains = 0;               // ... and the chains (instance, trajectory) its sweep was launched for
     int64_t prof_cnt[16] = {0};
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     // one full sweep captured as a hipGraph (bond dimensions live on the device and every grid is sized
     // for the capacity, so the launch sequence of a sweep never changes between sweeps); `epoch` is
     // bumped by every call that changes what the captured kernels were given
-    hipGraphExec_t sweep_graph = nullptr;
+    DevGraphExec sweep_graph;
     uint64_t epoch = 1, graph_epoch = 0;
-    // mpst_sweep_batch with this context as the lead: the Views of the K fits on the device ([2][K]: plain, and the Gram launch's
-    // variant), the captured sweep and what it was captured for (context pointers and their epochs)
     int batch_hint = 1;            // mpst_set_batch_hint: this context will be advanced in batches of about that many fits
-    View* batch_views = nullptr;
-    uint8_t* score_buf = nullptr;  // mpst_classify_batch with this context as the lead: the jobs and every fit's results in one block
-    int64_t score_cap = 0;
-    int batch_cap = 0;
-    hipGraphExec_t batch_graph = nullptr;
-    std::vector<std::pair<uint64_t, uint64_t>> batch_key;   // (uid, epoch) per member: an address can be handed out again, a uid cannot
     uint64_t uid = 0;              // process-wide, never reused (mpst_create)
+    ~Ctx();                        // the peers' inboxes are unmapped before the members go
 };
 
 int fail(Ctx* c, int code, const char* fmt, ...) {
@@ -237,47 +280,45 @@ int fail(Ctx* c, int code, const char* fmt, ...) {
     } while (0)
 
 template <typename T>
-int dalloc(Ctx* c, T** p, int64_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+int dalloc(Ctx* c, DevBuf<T>& b, int64_t n) {
+    b = DevBuf<T>();
     if (n <= 0) n = 1;
-    hipError_t e = hipMalloc((void**)p, (size_t)n * sizeof(T));
+    hipError_t e = hipMalloc((void**)&b.h, (size_t)n * sizeof(T));
     if (e != hipSuccess) return fail(c, MPST_ERR_NOMEM, "hipMalloc of %lld bytes failed: %s", (long long)(n * sizeof(T)), hipGetErrorString(e));
     return 0;
 }
-template <typename T>
-void dfree(T** p) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-}
-
-template <typename T>
-int dalloc(Ctx* c, DevBuf<T>& b, int64_t n) { return dalloc(c, &b.h, n); }
-
 // (E) buffers: `n` elements of c->esz bytes behind a double* name
-int dalloc_e(struct Ctx* c, double** p, int64_t n);
+int dalloc_e(Ctx* c, DevBuf<double>& b, int64_t n) {
+    b = DevBuf<double>();         // what b held goes first: the peak is one buffer
+    DevBuf<uint8_t> q;
+    const int rc = dalloc(c, q, std::max<int64_t>(n, 1) * (int64_t)c->esz);
+    b.h = (double*)q.h;
+    q.h = nullptr;
+    return rc;
+}
 
 View make_view(Ctx* c, int which) {
     View v{};
     const DataSet& s = c->ds[which];
-    v.T = c->T; v.d = c->d; v.C = c->C; v.chi_max = c->opt.chi_max; v.cap = c->cap;
+    v.T = c->T; v.d = c->d; v.C = c->C; v.chi_max = c->opt.chi_max; v.cap = c->mps.cap;
     v.N = s.N;
     v.invN = s.Nglobal > 0 ? 1.0 / (double)s.Nglobal : 0.0;
     v.phi = s.phi; v.label = s.label; v.tiles = s.tiles; v.chunks = s.chunks;
     v.cls_chunk_off = s.cls_chunk_off; v.inv_count = s.inv_count;
     v.ntiles = s.ntiles; v.nchunks = s.nchunks;
-    v.chi = c->chi; v.label_site = c->label_site; v.sites = c->sites; v.site_stride = c->site_stride;
-    v.LE = c->LE; v.RE = c->RE; v.bt = c->bt; v.yhat = c->yhat; v.tile_loss = c->tile_loss;
-    v.ss_bt = c->bt; v.ss_f32 = 0;
-    v.partial = c->partial; v.gradbuf = c->gradbuf; v.gram = c->gram; v.lam = c->lam; v.E = c->E; v.eig_ws = c->eig_ws; v.sc = c->sc;
+    v.chi = c->mps.chi; v.label_site = c->mps.label_site; v.sites = c->mps.sites; v.site_stride = c->mps.site_stride;
+    v.LE = c->ws.LE; v.RE = c->ws.RE; v.bt = c->ws.bt; v.yhat = c->ws.yhat; v.tile_loss = c->ws.tile_loss;
+    v.ss_bt = c->ws.bt; v.ss_f32 = 0;
+    v.partial = c->ws.partial; v.gradbuf = c->ws.gradbuf; v.gram = c->ws.gram; v.lam = c->ws.lam; v.E = c->ws.E; v.eig_ws = c->ws.eig_ws; v.sc = c->ws.sc;
     v.loss = c->opt.loss; v.optimiser = c->opt.optimiser; v.rescale_before = c->opt.rescale_before;
     v.rescale_after = c->opt.rescale_after; v.train_sep = c->opt.train_classes_separately; v.svd_alg = c->opt.svd_alg;
     v.eta = c->opt.eta; v.cutoff = c->opt.cutoff;
     const int pk = c->opt.loss == MPST_LOSS_MSE ? 1 : 0;
     v.parts = s.parts[pk]; v.part_off = s.part_off[pk]; v.nparts = s.nparts[pk];
-    v.norm_part = c->norm_part; v.n_norm_part = c->n_norm_part; v.btn = c->btn;
-    v.btnT = (which == MPST_TRAIN && c->chain4_ok && !c->chain4_hold) ? c->btnT : nullptr;
+    v.norm_part = c->ws.norm_part; v.n_norm_part = c->ws.n_norm_part; v.btn = c->ws.btn;
+    v.btnT = (which == MPST_TRAIN && c->ws.chain4_ok && !c->chain4_hold) ? c->ws.btnT : nullptr;
     v.trace = nullptr; v.trace_it = 0; v.yhat_scaled = 0;
-    v.cls_off = s.cls_off; v.ypart = c->b2_ypart; v.lossp = c->b2_lossp; v.tick = c->b2_tick; v.b2_ksplit = c->b2_ksplit; v.b2_nw = (c->batch_hint > 1 && c->d == 4) ? 4 : 8; v.dbg = c->b2_dbg;
+    v.cls_off = s.cls_off; v.ypart = c->ws.b2_ypart; v.lossp = c->ws.b2_lossp; v.tick = c->ws.b2_tick; v.b2_ksplit = c->ws.b2_ksplit; v.b2_nw = (c->batch_hint > 1 && c->d == 4) ? 4 : 8; v.dbg = c->ws.b2_dbg;
     {
         int32_t so = 0, to = 0;
         for (int k = 0; k <= MAX_C; ++k) {
@@ -292,29 +333,22 @@ View make_view(Ctx* c, int which) {
     return v;
 }
 
-int dalloc_e(Ctx* c, double** p, int64_t n) {
-    uint8_t* q = (uint8_t*)*p;
-    *p = nullptr;
-    int rc = dalloc(c, &q, std::max<int64_t>(n, 1) * (int64_t)c->esz);
-    *p = (double*)q;
-    return rc;
-}
 inline double* eoff(Ctx* c, double* base, int64_t elems) { return (double*)((char*)base + (size_t)elems * c->esz); }
 
 TView make_tview(Ctx* c, int which) {
     TView t{};
     const DataSet& s = c->ds[which];
-    t.T = c->T; t.d = c->d; t.C = c->C; t.chi_max = c->opt.chi_max; t.cap = c->cap;
+    t.T = c->T; t.d = c->d; t.C = c->C; t.chi_max = c->opt.chi_max; t.cap = c->mps.cap;
     t.cx = c->zw == 2; t.f32 = (c->dtype == MPST_F32 || c->dtype == MPST_C64);
     t.N = s.N;
     t.invN = s.Nglobal > 0 ? 1.0 / (double)s.Nglobal : 0.0;
     t.phi = s.phi; t.label = s.label; t.tiles = s.tiles; t.chunks = s.chunks; t.cls_chunk_off = s.cls_chunk_off; t.inv_count = s.inv_count;
     t.ntiles = s.ntiles; t.nchunks = s.nchunks;
-    t.chi = c->chi; t.label_site = c->label_site; t.sites = c->sites; t.site_stride = c->site_stride;
-    t.LE = c->LE; t.RE = c->RE; t.xLE = c->xLE; t.xRE = c->xRE; t.yexp = c->yexp;
-    t.bt = c->bt; t.yhat = c->yhat; t.tile_loss = c->tile_loss; t.partial = c->partial;
-    t.gradbuf = c->gradbuf; t.norm_part = c->norm_part; t.n_norm_part = c->n_norm_part;
-    t.gram = c->gram; t.E = c->E; t.ldE = c->zw * c->cap; t.sc = c->sc;
+    t.chi = c->mps.chi; t.label_site = c->mps.label_site; t.sites = c->mps.sites; t.site_stride = c->mps.site_stride;
+    t.LE = c->ws.LE; t.RE = c->ws.RE; t.xLE = c->ws.xLE; t.xRE = c->ws.xRE; t.yexp = c->ws.yexp;
+    t.bt = c->ws.bt; t.yhat = c->ws.yhat; t.tile_loss = c->ws.tile_loss; t.partial = c->ws.partial;
+    t.gradbuf = c->ws.gradbuf; t.norm_part = c->ws.norm_part; t.n_norm_part = c->ws.n_norm_part;
+    t.gram = c->ws.gram; t.E = c->ws.E; t.ldE = c->zw * c->mps.cap; t.sc = c->ws.sc;
     t.loss = c->opt.loss; t.optimiser = c->opt.optimiser; t.rescale_before = c->opt.rescale_before; t.rescale_after = c->opt.rescale_after;
     t.train_sep = c->opt.train_classes_separately;
     t.eta = c->opt.eta; t.cutoff = c->opt.cutoff;
@@ -326,12 +360,12 @@ View make_eig_view(Ctx* c) {
     View v{};
     v.T = c->T; v.d = c->d; v.C = c->C;
     v.chi_max = c->zw * c->opt.chi_max;
-    v.cap = c->zw * c->cap;
-    v.chi = c->chi; v.label_site = c->label_site;
-    v.gram = c->gram; v.lam = c->lam; v.E = c->E; v.eig_ws = c->eig_ws; v.sc = c->sc;
+    v.cap = c->zw * c->mps.cap;
+    v.chi = c->mps.chi; v.label_site = c->mps.label_site;
+    v.gram = c->ws.gram; v.lam = c->ws.lam; v.E = c->ws.E; v.eig_ws = c->ws.eig_ws; v.sc = c->ws.sc;
     v.rescale_after = c->opt.rescale_after; v.svd_alg = c->opt.svd_alg; v.cutoff = c->opt.cutoff;
     v.zw = c->zw;
-    v.ss_bt = c->bt;                                             // the subspace eigensolver reads the bond tensor itself
+    v.ss_bt = c->ws.bt;                                             // the subspace eigensolver reads the bond tensor itself
     v.ss_f32 = (c->dtype == MPST_F32 || c->dtype == MPST_C64) ? 1 : 0;
     return v;
 }
@@ -344,71 +378,68 @@ void ipc_release(struct Ctx* c);
 // workspace, so that (re)loading a TEST set never touches the environment caches
 int ensure_eval(Ctx* c) {
     if (c->eval_ready) return 0;
+    c->ev = EvalWs();
+    EvalWs e;
     int rc;
     const int64_t en = std::max<int64_t>(1, std::max(c->ds[0].N, c->ds[1].N));
-    c->eval_N = en;
+    e.eval_N = en;
     for (int k = 0; k < 2; ++k) {
-        if ((rc = dalloc_e(c, &c->chainL[k], en * c->cap))) return rc;
-        if ((rc = dalloc_e(c, &c->chainR[k], en * c->cap))) return rc;
-        if (c->typed && ((rc = dalloc(c, &c->xchainL[k], en)) || (rc = dalloc(c, &c->xchainR[k], en)))) return rc;
+        if ((rc = dalloc_e(c, e.chainL[k], en * c->mps.cap))) return rc;
+        if ((rc = dalloc_e(c, e.chainR[k], en * c->mps.cap))) return rc;
+        if (c->typed && ((rc = dalloc(c, e.xchainL[k], en)) || (rc = dalloc(c, e.xchainR[k], en)))) return rc;
     }
-    if ((rc = dalloc(c, &c->yeval, en * c->C * (c->typed ? 2 : 1)))) return rc;      // typed: (re, im) pairs
-    if ((rc = dalloc(c, &c->out3, 4))) return rc;
-    if ((rc = dalloc(c, &c->conf, (int64_t)MAX_C * MAX_C))) return rc;
-    if ((rc = dalloc(c, &c->pred, en))) return rc;
+    if ((rc = dalloc(c, e.yeval, en * c->C * (c->typed ? 2 : 1)))) return rc;      // typed: (re, im) pairs
+    if ((rc = dalloc(c, e.out3, 4))) return rc;
+    if ((rc = dalloc(c, e.conf, (int64_t)MAX_C * MAX_C))) return rc;
+    if ((rc = dalloc(c, e.pred, en))) return rc;
+    c->ev = std::move(e);
     c->eval_ready = true;
     return 0;
 }
 
 // ---- the training workspace: one builder, parameterised by the element type (c->zw, c->esz) ---------------------------------
-// The eigensolvers of bonds whose (embedded) Gram matrix of dimension n exceeds the LDS-resident solver.  Whatever the previous
-// workspace held goes first: the solvers and the snapshot of the optimistic sweep were sized for the previous MPS.
-int setup_big_eig(Ctx* c, int n, int ss_rows, int ss_cx) {
+// The eigensolvers of bonds whose (embedded) Gram matrix of dimension n exceeds the LDS-resident solver.
+int setup_big_eig(Ctx* c, TrainWs& w, int n, int ss_rows, int ss_cx) {
     int rc;
-    if (c->big) { big_eig_destroy(c->big); c->big = nullptr; }
-    if (c->blk) { blocked_eig_destroy(c->blk); c->blk = nullptr; }
-    dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);
-    c->big_opt = false;
     if (n <= MAX_DIM) return 0;
     std::string e;
-    if ((rc = big_eig_create(&c->big, n, c->stream, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
+    if ((rc = big_eig_create(&w.big.h, n, c->stream, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
     const char* sel = getenv("MPST_BIG_EIG");
-    if (!(sel && (strcmp(sel, "jacobi") == 0 || strcmp(sel, "rocsolver") == 0)) && (rc = blocked_eig_create(&c->blk, n, &e)))
+    if (!(sel && (strcmp(sel, "jacobi") == 0 || strcmp(sel, "rocsolver") == 0)) && (rc = blocked_eig_create(&w.blk.h, n, &e)))
         return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
     // the randomised subspace solver in front of the exact one (complex Gram matrices arrive as embeddings)
-    if (c->blk && (rc = blocked_eig_enable_subspace(c->blk, ss_rows, c->cap, c->C, ss_cx, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
+    if (w.blk && (rc = blocked_eig_enable_subspace(w.blk, ss_rows, c->mps.cap, c->C, ss_cx, &e))) return fail(c, rc, "large-bond eigensolver: %s", e.c_str());
     // MPST_BIG_SYNC=1: read the eigensolver's verdict after every bond (one host synchronisation per bond) instead of once per sweep
-    c->big_opt = c->blk && getenv("MPST_BIG_SYNC") == nullptr && getenv("MPST_BT_NO_COOP") == nullptr;
-    if (const char* ff = getenv("MPST_BIG_FORCE_FAIL")) c->big_force_fail = atoi(ff);       // test hook: the n-th solve of the context is marked failed
+    w.big_opt = w.blk && getenv("MPST_BIG_SYNC") == nullptr && getenv("MPST_BT_NO_COOP") == nullptr;
+    if (const char* ff = getenv("MPST_BIG_FORCE_FAIL")) w.big_force_fail = atoi(ff);       // test hook: the n-th solve of the workspace is marked failed
     return 0;
 }
 
 // What only the element-typed context's workspace holds (mpst_typed.hip): its limits, the binary exponents of the environments,
 // the shares of its gradient and norm kernels.  Everything that decides the truncation stays in fp64.
-int workspace_typed(Ctx* c, int64_t Lmax) {
+int workspace_typed(Ctx* c, TrainWs& w, int64_t Lmax) {
     const DataSet& tr = c->ds[MPST_TRAIN];
-    const int dm = c->d * c->cap, zw = c->zw;
+    const int dm = c->d * c->mps.cap, zw = c->zw;
     int rc;
-    if (zw * dm > DIM_LIMIT || zw * c->cap > CAP_LIMIT)
-        return fail(c, MPST_ERR_UNSUPPORTED, "complex element type: 2*d*chi_max = %d (2*chi_max = %d) exceeds the eigensolver's limits %d, %d", zw * dm, zw * c->cap, DIM_LIMIT, CAP_LIMIT);
+    if (zw * dm > DIM_LIMIT || zw * c->mps.cap > CAP_LIMIT)
+        return fail(c, MPST_ERR_UNSUPPORTED, "complex element type: 2*d*chi_max = %d (2*chi_max = %d) exceeds the eigensolver's limits %d, %d", zw * dm, zw * c->mps.cap, DIM_LIMIT, CAP_LIMIT);
     if (c->d > 32) return fail(c, MPST_ERR_UNSUPPORTED, "the element-typed sweep holds d <= 32");
-    TView tv = make_tview(c, MPST_TRAIN);
-    if (typed_max_lds(tv) > 144 * 1024) return fail(c, MPST_ERR_UNSUPPORTED, "chi_max = %d, d = %d exceed the LDS staging of the element-typed kernels for this element type", c->cap, c->d);
-    c->fused = c->b2 = c->chain4_ok = false;
-    if ((rc = dalloc(c, &c->xLE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, &c->xRE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, &c->yexp, tr.N))) return rc;
-    c->partial_elems = (int64_t)c->C * typed_grad_nsplit(tv, tr.nchunks) * Lmax;
-    c->n_norm_part = typed_norm_parts(tv);
-    if ((rc = dalloc(c, &c->tnorm_scratch, (int64_t)6 * c->cap * c->cap))) return rc;
+    TView tv = make_tview(c, MPST_TRAIN);       // (its shape: the buffers are not there yet)
+    if (typed_max_lds(tv) > 144 * 1024) return fail(c, MPST_ERR_UNSUPPORTED, "chi_max = %d, d = %d exceed the LDS staging of the element-typed kernels for this element type", c->mps.cap, c->d);
+    if ((rc = dalloc(c, w.xLE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, w.xRE, (int64_t)c->T * tr.N)) || (rc = dalloc(c, w.yexp, tr.N))) return rc;
+    w.partial_elems = (int64_t)c->C * typed_grad_nsplit(tv, tr.nchunks) * Lmax;
+    w.n_norm_part = typed_norm_parts(tv);
+    if ((rc = dalloc(c, w.tnorm_scratch, (int64_t)6 * c->mps.cap * c->mps.cap))) return rc;
     return 0;
 }
 
 // What only the Float64 context's workspace holds: which launch chain its bonds run (fused, sliced pair, four launches) and the
 // buffers of that chain.
-int workspace_f64(Ctx* c, int64_t Lmax) {
+int workspace_f64(Ctx* c, TrainWs& w, int64_t Lmax) {
     const DataSet& tr = c->ds[MPST_TRAIN];
-    const int dm = c->d * c->cap;
+    const int dm = c->d * c->mps.cap;
     int rc;
-    c->fused = dm <= MAX_DIM && !c->opt.rescale_before && getenv("MPST_NO_FUSED") == nullptr;
+    w.fused = dm <= MAX_DIM && !c->opt.rescale_before && getenv("MPST_NO_FUSED") == nullptr;
     // Which pair forms the gradient on the fused chain.  The sliced kernels (k_yhat_s + k_grad_s) move tens of KB per workgroup
     // and no partial gradients: 26 us against 31 us per bond at N = 4096, 11.6 MB against 40 MB of HBM traffic.  Their cost per
     // series is higher though (every series is read by 8 slice- and 16 block-workgroups: 2.7 against 1.5 us per 1000 series),
@@ -417,98 +448,106 @@ int workspace_f64(Ctx* c, int64_t Lmax) {
     {
         const char* e = getenv("MPST_B2");
         const bool want = e ? atoi(e) != 0 : (tr.N <= 8192 && getenv("MPST_NO_B2") == nullptr);
-        c->b2 = c->fused && c->d >= 2 && c->d <= 16 && want;
+        w.b2 = w.fused && c->d >= 2 && c->d <= 16 && want;
     }
-    if (c->fused) {
-        c->partial_elems = (int64_t)std::max(tr.nparts[0], tr.nparts[1]) * Lmax;   // independent of N: one partial per persistent workgroup
-        if (c->b2) {
+    if (w.fused) {
+        w.partial_elems = (int64_t)std::max(tr.nparts[0], tr.nparts[1]) * Lmax;   // independent of N: one partial per persistent workgroup
+        if (w.b2) {
             View gv{};
-            gv.C = c->C; gv.d = c->d; gv.cap = c->cap;
+            gv.C = c->C; gv.d = c->d; gv.cap = c->mps.cap;
             const int64_t max_pass = tr.N;                  // MSE walks every series in every pass; KLD at most that
-            c->b2_ksplit = b2_ksplit(gv, max_pass);
+            w.b2_ksplit = b2_ksplit(gv, max_pass);
             // a context that runs in batches of K fits shares the chip with K - 1 others: fewer, longer shares per gradient block
             // (less hand-over per fit; the share count fixes the order of the partial sums, so it belongs to the context, not to the call)
             // (d = 4: the batched launches run k_grad_s with four waves per workgroup, two workgroups per CU - twice the workgroups fill the chip)
             if (c->batch_hint > 1 && getenv("MPST_B2_KSPLIT") == nullptr)
-                c->b2_ksplit = c->d == 4 ? std::max(1, std::min(c->b2_ksplit, 2 * c->b2_ksplit / std::min(c->batch_hint, 16)))
-                                         : std::max(1, c->b2_ksplit / std::min(c->batch_hint, 8));
-            c->b2_norm_parts = c->C * b2_blocks_cap(gv);
-            c->partial_elems = std::max(c->partial_elems, b2_partial_elems(gv, max_pass));
-            if ((rc = dalloc(c, &c->b2_ypart, (int64_t)8 * c->C * tr.N))) return rc;
-            if ((rc = dalloc(c, &c->b2_lossp, (int64_t)c->C * 64))) return rc;     // GS_MAXKS shares per class
-            if ((rc = dalloc(c, &c->b2_tick, (int64_t)c->b2_norm_parts + 1))) return rc;
-            HIPC(c, hipMemset(c->b2_tick, 0, (size_t)(c->b2_norm_parts + 1) * sizeof(unsigned int)));
+                w.b2_ksplit = c->d == 4 ? std::max(1, std::min(w.b2_ksplit, 2 * w.b2_ksplit / std::min(c->batch_hint, 16)))
+                                        : std::max(1, w.b2_ksplit / std::min(c->batch_hint, 8));
+            w.b2_norm_parts = c->C * b2_blocks_cap(gv);
+            w.partial_elems = std::max(w.partial_elems, b2_partial_elems(gv, max_pass));
+            if ((rc = dalloc(c, w.b2_ypart, (int64_t)8 * c->C * tr.N))) return rc;
+            if ((rc = dalloc(c, w.b2_lossp, (int64_t)c->C * 64))) return rc;     // GS_MAXKS shares per class
+            if ((rc = dalloc(c, w.b2_tick, (int64_t)w.b2_norm_parts + 1))) return rc;
+            HIPC(c, hipMemset(w.b2_tick, 0, (size_t)(w.b2_norm_parts + 1) * sizeof(unsigned int)));
 #ifdef MPST_B2_DEBUG
-            if ((rc = dalloc(c, &c->b2_dbg, 8192 * 8))) return rc;
-            HIPC(c, hipMemset(c->b2_dbg, 0, 8192 * 8 * sizeof(unsigned long long)));
+            if ((rc = dalloc(c, w.b2_dbg, 8192 * 8))) return rc;
+            HIPC(c, hipMemset(w.b2_dbg, 0, 8192 * 8 * sizeof(unsigned long long)));
 #endif
         }
     } else {
         const int nbcap = ((dm + GB - 1) / GB) * ((dm + GB - 1) / GB);
-        c->partial_elems = (int64_t)c->C * grad_nsplit(tr.nchunks, nbcap, c->C) * Lmax;    // one partial per k_grad workgroup share, independent of N
+        w.partial_elems = (int64_t)c->C * grad_nsplit(tr.nchunks, nbcap, c->C) * Lmax;    // one partial per k_grad workgroup share, independent of N
     }
-    if ((rc = dalloc(c, &c->btn, c->C * Lmax))) return rc;
+    if ((rc = dalloc(c, w.btn, c->C * Lmax))) return rc;
     {
         const char* e4 = getenv("MPST_CHAIN4");
         // (a context that is advanced in batches keeps the six-launch chain mpst_sweep_batch runs: its solo and its batched sweeps agree bit for bit)
-        c->chain4_ok = c->fused && c->b2 && c->batch_hint <= 1 && !(e4 && e4[0] == '0');
-        c->ynext_lid = -1;
-        c->tail_launches = 0;
-        c->tail_force_fail = -1;
-        if (const char* ff = getenv("MPST_TAIL_FORCE_REDO")) c->tail_force_fail = atoi(ff);
-        dfree(&c->btnT);
-        if (c->chain4_ok && (rc = dalloc(c, &c->btnT, c->C * Lmax))) return rc;
-        if (c->chain4_ok && (rc = dalloc(c, &c->tail_span, 2 * 2048))) return rc;
-        if (c->chain4_ok) HIPC(c, hipMemset(c->tail_span, 0, 2 * 2048 * sizeof(unsigned long long)));
+        w.chain4_ok = w.fused && w.b2 && c->batch_hint <= 1 && !(e4 && e4[0] == '0');
+        if (const char* ff = getenv("MPST_TAIL_FORCE_REDO")) w.tail_force_fail = atoi(ff);
+        if (w.chain4_ok && (rc = dalloc(c, w.btnT, c->C * Lmax))) return rc;
+        if (w.chain4_ok && (rc = dalloc(c, w.tail_span, 2 * 2048))) return rc;
+        if (w.chain4_ok) HIPC(c, hipMemset(w.tail_span, 0, 2 * 2048 * sizeof(unsigned long long)));
     }
-    c->n_norm_part = (int)((c->C * Lmax + 63) / 64);      // RED_E entries per workgroup of k_fused_reduce
-    if ((rc = dalloc(c, &c->norm_scratch, (int64_t)3 * c->cap * c->cap))) return rc;
+    w.n_norm_part = (int)((c->C * Lmax + 63) / 64);      // RED_E entries per workgroup of k_fused_reduce
+    if ((rc = dalloc(c, w.norm_scratch, (int64_t)3 * c->mps.cap * c->mps.cap))) return rc;
     return 0;
 }
 
-// (re)allocate everything whose size depends on (training set, options, capacity).  (E) buffers hold elements of c->esz bytes;
+// everything whose size depends on (training set, options, capacity).  (E) buffers hold elements of c->esz bytes;
 // the Gram matrix, its spectrum and the gradient message are fp64 in every element type (zw doubles per complex entry).
+int build_workspace(Ctx* c, TrainWs& w) {
+    const DataSet& tr = c->ds[MPST_TRAIN];
+    const int dm = c->d * c->mps.cap, zw = c->zw;
+    const int64_t Lmax = (int64_t)dm * dm;
+    int rc;
+    w.cache_elems = (int64_t)c->T * tr.N * c->mps.cap;
+    if ((rc = c->typed ? workspace_typed(c, w, Lmax) : workspace_f64(c, w, Lmax))) return rc;
+    if ((rc = dalloc_e(c, w.LE, w.cache_elems))) return rc;
+    if ((rc = dalloc_e(c, w.RE, w.cache_elems))) return rc;
+    if ((rc = dalloc_e(c, w.bt, c->C * Lmax))) return rc;
+    if ((rc = dalloc(c, w.yhat, (int64_t)(c->typed ? 2 : 1) * c->C * tr.N))) return rc;      // typed: (re, im) pairs
+    if ((rc = dalloc(c, w.tile_loss, std::max<int64_t>((int64_t)c->C * tr.ntiles, c->typed ? 1 : std::max(tr.nparts[0], tr.nparts[1]))))) return rc;
+    if ((rc = dalloc_e(c, w.partial, w.partial_elems))) return rc;
+    if ((rc = dalloc(c, w.norm_part, c->typed ? w.n_norm_part : std::max(w.n_norm_part, w.b2_norm_parts)))) return rc;
+    if ((rc = dalloc(c, w.loss_trace, (int64_t)2 * (c->T - 1) * (c->opt.update_iters + 1)))) return rc;
+    HIPC(c, hipMemset(w.loss_trace, 0, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double)));
+    if ((rc = dalloc(c, w.gradbuf, 2 + c->C * Lmax * zw))) return rc;
+    HIPC(c, hipMemset(w.gradbuf, 0, (size_t)(2 + c->C * Lmax * zw) * sizeof(double)));
+    const int ne = std::max(zw * dm, MAX_DIM);
+    if ((rc = dalloc(c, w.gram, (int64_t)ne * ne))) return rc;
+    if ((rc = dalloc(c, w.lam, ne + 2))) return rc;
+    if ((rc = dalloc(c, w.E, (int64_t)ne * zw * c->mps.cap))) return rc;
+    if ((rc = setup_big_eig(c, w, zw * dm, zw * c->C * dm, zw == 2))) return rc;
+    if ((rc = dalloc(c, w.eig_ws, (int64_t)eig_workspace_doubles()))) return rc;
+    HIPC(c, hipMemset(w.eig_ws, 0, eig_workspace_doubles() * sizeof(double)));
+    if ((rc = dalloc(c, w.sc, 1))) return rc;
+    HIPC(c, hipMemset(w.sc, 0, sizeof(DevScalars)));
+    return dalloc(c, w.norm2, 1);
+}
+
+// The old workspace goes first (the caches alone reach gigabytes), the new one is built aside in `w` and moved in complete: a
+// failure on the way leaves the context without a workspace (ws_ready false), never with half of one beside half of another.
 int ensure_workspace(Ctx* c) {
     if (!c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options must be called first");
     if (!c->have_mps) return fail(c, MPST_ERR_INVALID, "mpst_set_mps must be called first");
     if (c->ws_ready) return ensure_eval(c);
     const DataSet& tr = c->ds[MPST_TRAIN];
     if (tr.N <= 0) return fail(c, MPST_ERR_INVALID, "no training data set (mpst_set_dataset)");
-    const int dm = c->d * c->cap, zw = c->zw;
-    if (dm > DIM_LIMIT || c->cap > CAP_LIMIT)
-        return fail(c, MPST_ERR_UNSUPPORTED, "d*chi_max = %d (chi_max = %d) exceeds the engine's limits d*chi_max <= %d, chi_max <= %d", dm, c->cap, DIM_LIMIT, CAP_LIMIT);
+    const int dm = c->d * c->mps.cap;
+    if (dm > DIM_LIMIT || c->mps.cap > CAP_LIMIT)
+        return fail(c, MPST_ERR_UNSUPPORTED, "d*chi_max = %d (chi_max = %d) exceeds the engine's limits d*chi_max <= %d, chi_max <= %d", dm, c->mps.cap, DIM_LIMIT, CAP_LIMIT);
     if (c->C > MAX_C) return fail(c, MPST_ERR_UNSUPPORTED, "more than %d classes unsupported", MAX_C);
-    const int64_t Lmax = (int64_t)dm * dm;
-    int rc;
-    if (c->ipc_local && 2 + c->C * Lmax * zw > c->ipc_slot) ipc_release(c);   // inbox slots too small for the new capacity: export again
+    if (c->ipc_local && 2 + (int64_t)c->C * dm * dm * c->zw > c->ipc_slot) ipc_release(c);   // inbox slots too small for the new capacity: export again
     c->caches_valid = false;
-    c->cache_elems = (int64_t)c->T * tr.N * c->cap;
-    if ((rc = c->typed ? workspace_typed(c, Lmax) : workspace_f64(c, Lmax))) return rc;
-    if ((rc = dalloc_e(c, &c->LE, c->cache_elems))) return rc;
-    if ((rc = dalloc_e(c, &c->RE, c->cache_elems))) return rc;
-    if ((rc = dalloc_e(c, &c->bt, c->C * Lmax))) return rc;
-    if ((rc = dalloc(c, &c->yhat, (int64_t)(c->typed ? 2 : 1) * c->C * tr.N))) return rc;      // typed: (re, im) pairs
-    if ((rc = dalloc(c, &c->tile_loss, std::max<int64_t>((int64_t)c->C * tr.ntiles, c->typed ? 1 : std::max(tr.nparts[0], tr.nparts[1]))))) return rc;
-    if ((rc = dalloc_e(c, &c->partial, c->partial_elems))) return rc;
-    if ((rc = dalloc(c, &c->norm_part, c->typed ? c->n_norm_part : std::max(c->n_norm_part, c->b2_norm_parts)))) return rc;
-    if ((rc = dalloc(c, &c->loss_trace, (int64_t)2 * (c->T - 1) * (c->opt.update_iters + 1)))) return rc;
-    HIPC(c, hipMemset(c->loss_trace, 0, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double)));
-    if ((rc = dalloc(c, &c->gradbuf, 2 + c->C * Lmax * zw))) return rc;
-    HIPC(c, hipMemset(c->gradbuf, 0, (size_t)(2 + c->C * Lmax * zw) * sizeof(double)));
-    const int ne = std::max(zw * dm, MAX_DIM);
-    if ((rc = dalloc(c, &c->gram, (int64_t)ne * ne))) return rc;
-    if ((rc = dalloc(c, &c->lam, ne + 2))) return rc;
-    if ((rc = dalloc(c, &c->E, (int64_t)ne * zw * c->cap))) return rc;
-    if ((rc = setup_big_eig(c, zw * dm, zw * c->C * dm, zw == 2))) return rc;
-    if ((rc = dalloc(c, &c->eig_ws, (int64_t)eig_workspace_doubles()))) return rc;
-    HIPC(c, hipMemset(c->eig_ws, 0, eig_workspace_doubles() * sizeof(double)));
-    if ((rc = dalloc(c, &c->sc, 1))) return rc;
-    HIPC(c, hipMemset(c->sc, 0, sizeof(DevScalars)));
-    if ((rc = dalloc(c, &c->norm2, 1))) return rc;
+    c->ynext_lid = -1;
+    c->ws = TrainWs();
+    TrainWs w;
+    if (int rc = build_workspace(c, w)) return rc;
     hipError_t ea = init_kernel_attrs(c->device);
     if (ea == hipSuccess) ea = eig_init_attrs(c->device);
     if (ea == hipSuccess) ea = c->typed ? typed_init_attrs(c->device) : b2_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    c->ws = std::move(w);
     c->ws_ready = true;
     c->eval_ready = false;
     c->epoch++;
@@ -521,21 +560,20 @@ int ensure_workspace(Ctx* c) {
 // The subspace eigensolver's counters, read where the stream has just been synchronised (after a sweep, a bond step, a batch): the info
 // query returns these and never touches the stream.
 static void refresh_ss_counts(Ctx* c) {
-    if (c->blk) (void)blocked_eig_subspace_counts(c->blk, c->stream, &c->ss_counts[0], &c->ss_counts[1]);
+    if (c->ws.blk) (void)blocked_eig_subspace_counts(c->ws.blk, c->stream, &c->ss_counts[0], &c->ss_counts[1]);
 }
 int enqueue_reset_status(Ctx* c) {
     static_assert(offsetof(DevScalars, eig_fallbacks) == offsetof(DevScalars, status) + 8, "status / eig_sweeps_total / eig_fallbacks adjacent");
-    HIPC(c, hipMemsetAsync((char*)c->sc + offsetof(DevScalars, status), 0, 12, c->stream));
-    HIPC(c, hipMemsetAsync((char*)c->sc + offsetof(DevScalars, redo), 0, 4, c->stream));
+    HIPC(c, hipMemsetAsync(&c->ws.sc.h->status, 0, 12, c->stream));
+    HIPC(c, hipMemsetAsync(&c->ws.sc.h->redo, 0, 4, c->stream));
     return 0;
 }
 
 // ---- profiling helpers: HIP events on the stream the kernels are launched on -------------
 hipEvent_t pool_event(Ctx* c) {
     if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        c->ev_pool.push_back(e);
+        c->ev_pool.emplace_back();
+        (void)hipEventCreate(&c->ev_pool.back().h);
     }
     return c->ev_pool[c->ev_used++];
 }
@@ -563,13 +601,13 @@ void prof_collect(Ctx* c) {
 // ---- sum over ranks of a device buffer: the one-shot path when the inboxes are attached, else RCCL ---------------
 void ipc_release(struct Ctx* c) {
     for (int r = 0; r < AR_MAX_RANKS; ++r) {
-        if (c->ipc_peer[r] && c->ipc_peer[r] != c->ipc_local) (void)hipIpcCloseMemHandle(c->ipc_peer[r]);
+        if (c->ipc_peer[r] && c->ipc_peer[r] != c->ipc_local.h) (void)hipIpcCloseMemHandle(c->ipc_peer[r]);
         c->ipc_peer[r] = nullptr;
     }
-    if (c->ipc_local) (void)hipFree(c->ipc_local);
-    c->ipc_local = nullptr;
+    c->ipc_local = DevBuf<uint8_t>();
     c->use_ipc = false;
 }
+Ctx::~Ctx() { ipc_release(this); }
 int enqueue_allreduce(Ctx* c, double* buf, int64_t n_fixed, int lid) {
     if (!multi(c)) return 0;
     if (c->use_ipc) {
@@ -579,16 +617,16 @@ int enqueue_allreduce(Ctx* c, double* buf, int64_t n_fixed, int lid) {
             p.flags[r] = (unsigned long long*)((char*)c->ipc_peer[r] + c->ipc_flag_off);
         }
         p.buf = buf;
-        p.status = &c->sc->status;
-        p.dbg = c->sc->pad;
-        p.counter = (unsigned int*)((char*)c->ipc_local + c->ipc_ctr_off);
+        p.status = &c->ws.sc.h->status;
+        p.dbg = c->ws.sc.h->pad;
+        p.counter = (unsigned int*)((char*)c->ipc_local.h + c->ipc_ctr_off);
         p.nranks = c->nranks; p.rank = c->rank; p.slot = c->ipc_slot;
         p.epoch = ++c->ar_epoch;
         {
             static const double secs = [] { const char* e = getenv("MPST_AR_TIMEOUT_S"); const double v = e ? atof(e) : 10.0; return v > 0.0 ? v : 10.0; }();
             p.spin_limit = (long long)(secs * 2.4e9);
         }
-        p.chi = c->chi; p.lid = lid; p.C = c->C * c->zw; p.d = c->d; p.n_fixed = n_fixed;      // complex gradients: (re, im) pairs
+        p.chi = c->mps.chi; p.lid = lid; p.C = c->C * c->zw; p.d = c->d; p.n_fixed = n_fixed;      // complex gradients: (re, im) pairs
         if (lid < 0 && n_fixed > c->ipc_slot) return fail(c, MPST_ERR_INVALID, "all-reduce message exceeds the inbox slot");
         launch_allreduce_oneshot(p, c->stream);
         return 0;
@@ -596,7 +634,7 @@ int enqueue_allreduce(Ctx* c, double* buf, int64_t n_fixed, int lid) {
     if (c->ipc_dead && !c->comm)
         return fail(c, MPST_ERR_DEVICE, "the one-shot all-reduce timed out earlier: export and attach the inboxes again (mpst_comm_ipc_export / _attach)");
     if (!c->comm) return fail(c, MPST_ERR_INVALID, "%d ranks but neither an RCCL communicator nor attached inboxes", c->nranks);
-    const size_t cnt = lid >= 0 ? 2 + (size_t)c->zw * c->C * c->d * c->cap * c->d * c->cap : (size_t)n_fixed;
+    const size_t cnt = lid >= 0 ? 2 + (size_t)c->zw * c->C * c->d * c->mps.cap * c->d * c->mps.cap : (size_t)n_fixed;
     Rccl* nc = rccl_ready(nullptr);
     if (!nc) return fail(c, MPST_ERR_DEVICE, "RCCL is not available");
     ncclResult_t r = nc->AllReduce(buf, buf, cnt, ncclDouble, ncclSum, c->comm, c->stream);
@@ -608,16 +646,16 @@ int enqueue_allreduce(Ctx* c, double* buf, int64_t n_fixed, int lid) {
 int enqueue_big_eig(Ctx* c, const View& v, int lid, int going_left) {
     hipStream_t s = c->stream;
     int need_lib = 1;
-    if (c->blk && c->big_opt_active) {
-        if (launch_eig_blocked_nosync(v, lid, going_left, c->blk, s)) return fail(c, MPST_ERR_DEVICE, "blocked eigensolver failed at bond %d: %s", lid, hipGetErrorString(hipGetLastError()));
-        if (c->big_force_fail >= 0 && c->big_solves++ == c->big_force_fail) blocked_eig_force_sticky(c->blk, s);      // test hook
+    if (c->ws.blk && c->big_opt_active) {
+        if (launch_eig_blocked_nosync(v, lid, going_left, c->ws.blk, s)) return fail(c, MPST_ERR_DEVICE, "blocked eigensolver failed at bond %d: %s", lid, hipGetErrorString(hipGetLastError()));
+        if (c->ws.big_force_fail >= 0 && c->ws.big_solves++ == c->ws.big_force_fail) blocked_eig_force_sticky(c->ws.blk, s);      // test hook
         need_lib = 0;
-    } else if (c->blk) {
-        need_lib = launch_eig_blocked(v, lid, going_left, nullptr, 0, nullptr, nullptr, nullptr, c->blk, s);
+    } else if (c->ws.blk) {
+        need_lib = launch_eig_blocked(v, lid, going_left, nullptr, 0, nullptr, nullptr, nullptr, c->ws.blk, s);
         if (need_lib < 0) return fail(c, MPST_ERR_DEVICE, "blocked eigensolver failed at bond %d: %s", lid, hipGetErrorString(hipGetLastError()));
         if (need_lib) c->big_fallbacks++;
     }
-    if (need_lib && launch_eig_big(v, lid, going_left, c->big, s)) return fail(c, MPST_ERR_DEVICE, "the large-bond Jacobi fallback could not be launched at bond %d", lid);
+    if (need_lib && launch_eig_big(v, lid, going_left, c->ws.big, s)) return fail(c, MPST_ERR_DEVICE, "the large-bond Jacobi fallback could not be launched at bond %d", lid);
     return 0;
 }
 
@@ -626,7 +664,7 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
     hipStream_t s = c->stream;
     TView t = make_tview(c, MPST_TRAIN);
     const int n_it = c->opt.update_iters, rid = lid + 1;
-    if (c->opt.track_cost && trace_row >= 0) t.trace = c->loss_trace + (int64_t)trace_row * (n_it + 1);
+    if (c->opt.track_cost && trace_row >= 0) t.trace = c->ws.loss_trace + (int64_t)trace_row * (n_it + 1);
     { ProfScope p(c, K_BT); launch_tbt_assemble(t, lid, s); }                    // flatten_bt
     if (t.rescale_before) launch_tbt_prescale(t, lid, s);
     for (int it = 0; it < n_it; ++it) {
@@ -635,7 +673,7 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
         { ProfScope p(c, K_UPDATE); launch_tgrad_reduce(t, lid, s); }
         if (multi(c)) {
             ProfScope p(c, K_ALLREDUCE);
-            int rc = enqueue_allreduce(c, c->gradbuf, 0, lid);
+            int rc = enqueue_allreduce(c, c->ws.gradbuf, 0, lid);
             if (rc) return rc;
             launch_tgrad_norm(t, lid, s);
         }
@@ -644,7 +682,7 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
     }
     { ProfScope p(c, K_GRAM); launch_tgram(t, lid, going_left, s); }             // decomposeBT: Gram matrix, fp64
     const View ve = make_eig_view(c);
-    if (c->big) {
+    if (c->ws.big) {
         ProfScope p(c, K_EIG_TRI);
         int rc = enqueue_big_eig(c, ve, lid, going_left);
         if (rc) return rc;
@@ -671,11 +709,11 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
         ProfScope p(c, K_ENV);                                                   // update_caches!: the new site tensor is the map
         const int64_t cs = (int64_t)t.N * t.cap;
         if (going_left)
-            launch_tenv(t, rid, 0, rid < c->T - 1 ? eoff(c, c->RE, (int64_t)(rid + 1) * cs) : nullptr, rid < c->T - 1 ? c->xRE + (int64_t)(rid + 1) * t.N : nullptr, rid + 1,
-                        ENV_M_SITE_T, rid, eoff(c, c->RE, (int64_t)rid * cs), c->xRE + (int64_t)rid * t.N, s);
+            launch_tenv(t, rid, 0, rid < c->T - 1 ? eoff(c, c->ws.RE, (int64_t)(rid + 1) * cs) : nullptr, rid < c->T - 1 ? c->ws.xRE + (int64_t)(rid + 1) * t.N : nullptr, rid + 1,
+                        ENV_M_SITE_T, rid, eoff(c, c->ws.RE, (int64_t)rid * cs), c->ws.xRE + (int64_t)rid * t.N, s);
         else
-            launch_tenv(t, lid, 1, lid > 0 ? eoff(c, c->LE, (int64_t)(lid - 1) * cs) : nullptr, lid > 0 ? c->xLE + (int64_t)(lid - 1) * t.N : nullptr, lid, ENV_M_SITE, lid + 1,
-                        eoff(c, c->LE, (int64_t)lid * cs), c->xLE + (int64_t)lid * t.N, s);
+            launch_tenv(t, lid, 1, lid > 0 ? eoff(c, c->ws.LE, (int64_t)(lid - 1) * cs) : nullptr, lid > 0 ? c->ws.xLE + (int64_t)(lid - 1) * t.N : nullptr, lid, ENV_M_SITE, lid + 1,
+                        eoff(c, c->ws.LE, (int64_t)lid * cs), c->ws.xLE + (int64_t)lid * t.N, s);
     }
     return 0;
 }
@@ -685,11 +723,11 @@ void enqueue_caches_typed(Ctx* c, int left_upto, int right_from) {
     const int64_t cs = (int64_t)t.N * t.cap;
     ProfScope p(c, K_ENV);
     for (int j = 0; j < left_upto && j <= c->T - 2; ++j)
-        launch_tenv(t, j, 1, j > 0 ? eoff(c, c->LE, (int64_t)(j - 1) * cs) : nullptr, j > 0 ? c->xLE + (int64_t)(j - 1) * t.N : nullptr, j, ENV_M_SITE, j + 1,
-                    eoff(c, c->LE, (int64_t)j * cs), c->xLE + (int64_t)j * t.N, c->stream);
+        launch_tenv(t, j, 1, j > 0 ? eoff(c, c->ws.LE, (int64_t)(j - 1) * cs) : nullptr, j > 0 ? c->ws.xLE + (int64_t)(j - 1) * t.N : nullptr, j, ENV_M_SITE, j + 1,
+                    eoff(c, c->ws.LE, (int64_t)j * cs), c->ws.xLE + (int64_t)j * t.N, c->stream);
     for (int j = c->T - 1; j > right_from && j >= 1; --j)
-        launch_tenv(t, j, 0, j < c->T - 1 ? eoff(c, c->RE, (int64_t)(j + 1) * cs) : nullptr, j < c->T - 1 ? c->xRE + (int64_t)(j + 1) * t.N : nullptr, j + 1, ENV_M_SITE_T, j,
-                    eoff(c, c->RE, (int64_t)j * cs), c->xRE + (int64_t)j * t.N, c->stream);
+        launch_tenv(t, j, 0, j < c->T - 1 ? eoff(c, c->ws.RE, (int64_t)(j + 1) * cs) : nullptr, j < c->T - 1 ? c->ws.xRE + (int64_t)(j + 1) * t.N : nullptr, j + 1, ENV_M_SITE_T, j,
+                    eoff(c, c->ws.RE, (int64_t)j * cs), c->ws.xRE + (int64_t)j * t.N, c->stream);
 }
 
 // ---- bond order of one sweep (RealRealHighDimension.jl:731, :776) -------------------------------------------------------
@@ -719,14 +757,14 @@ inline bool assembles_next(const BondSlot& prev, bool fused) { return fused ? pr
 // profiling and the RCCL leg keep the plain stream path.
 // (large bonds stay on the plain stream: replaying their ~8000 launches from a graph was measured to gain nothing - 725.0
 // against 724.5 ms per sweep at (8192, 200, 64, 8) - and a capture must not overlap other threads' legacy-stream copies)
-bool sweep_uses_graph(const Ctx* c) { return !multi(c) && !c->big && c->prof_mask == 0 && getenv("MPST_NO_GRAPH") == nullptr; }
+bool sweep_uses_graph(const Ctx* c) { return !multi(c) && !c->ws.big && c->prof_mask == 0 && getenv("MPST_NO_GRAPH") == nullptr; }
 // four launches per bond: k_eig_fin, k_env_split and the NEXT bond's k_yhat_s in one (k_bond_tail, mpst_fused.hip)
 bool bond_uses_tail(const Ctx* c, const View& v, bool traced) {
-    return c->chain4_ok && !c->chain4_hold && c->b2 && !multi(c) && c->opt.update_iters == 1 && !traced && eig_merged() && bond_tail_supported(v);
+    return c->ws.chain4_ok && !c->chain4_hold && c->ws.b2 && !multi(c) && c->opt.update_iters == 1 && !traced && eig_merged() && bond_tail_supported(v);
 }
 // the context can join a batch (mpst_sweep_batch): the headline chain, six launches per bond
 bool batchable(const Ctx* c) {
-    return c->fused && c->b2 && !c->typed && !multi(c) && eig_merged() && c->opt.update_iters == 1 && !c->opt.track_cost && !c->opt.rebuild_caches &&
+    return c->ws.fused && c->ws.b2 && !c->typed && !multi(c) && eig_merged() && c->opt.update_iters == 1 && !c->opt.track_cost && !c->opt.rebuild_caches &&
            c->prof_mask == 0;
 }
 // the four-launch chain held back while a marked sweep / bond is redone on the six-launch chain: views made meanwhile carry no btnT
@@ -745,7 +783,7 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
     hipStream_t s = c->stream;
     View v = v_in;
     const int n_it = c->opt.update_iters;
-    if (c->opt.track_cost && trace_row >= 0) v.trace = c->loss_trace + (int64_t)trace_row * (n_it + 1);
+    if (c->opt.track_cost && trace_row >= 0) v.trace = c->ws.loss_trace + (int64_t)trace_row * (n_it + 1);
     // track_cost: the loss at the updated (and, with rescale[2], normalised) bond tensor - one more forward pass over the batch
     auto trace_final = [&](const double* bt_new) -> int {
         if (!v.trace) return 0;
@@ -761,7 +799,7 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
     };
     const int rid = lid + 1;
     const uint64_t seq_before = c->bond_seq++;
-    if (c->fused) {
+    if (c->ws.fused) {
         const int iters = c->opt.update_iters;
         // the next bond's tensor is assembled by this bond's last launch when the sweep moves on in the same direction
         const int chain = b.chains_into_next ? 1 : 0;
@@ -771,9 +809,9 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         c->ynext_lid = -1;
         if (!have_bt) { ProfScope p(c, K_BT); launch_bt_assemble(v, lid, s); }   // flatten_bt :733/:777
         View vl = v;                      // after k_grad_s on one rank the loss is still in pieces (bond_loss)
-        vl.n_lossp = c->b2 ? c->b2_ksplit : 0;
+        vl.n_lossp = c->ws.b2 ? c->ws.b2_ksplit : 0;
         for (int it = 0; it < iters; ++it) {                                     // TSGO/custGD :44,:75
-            if (c->b2) {
+            if (c->ws.b2) {
                 if (!(y_ready && it == 0)) { ProfScope p(c, K_YHAT); launch_yhat_s(v, lid, s); }           // yhat, by column slices of B_c
                 { ProfScope p(c, K_GRAD); launch_grad_s(v, lid, s); }           // gradient blocks, reduced by their last arriver
                 if (multi(c)) launch_loss_sum(vl, s);                      // the loss travels in gradbuf[0]
@@ -783,7 +821,7 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             }
             if (multi(c)) {
                 ProfScope p(c, K_ALLREDUCE);
-                int rc = enqueue_allreduce(c, c->gradbuf, 0, lid);
+                int rc = enqueue_allreduce(c, c->ws.gradbuf, 0, lid);
                 if (rc) return rc;
                 launch_grad_norm(v, lid, s);
             }
@@ -791,16 +829,16 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             if (it + 1 < iters) {
                 ProfScope p(c, K_UPDATE);
                 View vu = v;
-                if (c->b2 && !multi(c)) vu.n_lossp = c->b2_ksplit;
+                if (c->ws.b2 && !multi(c)) vu.n_lossp = c->ws.b2_ksplit;
                 launch_update(vu, lid, it == 0, s);
             }
         }
         {
             ProfScope p(c, K_GRAM);                                               // last step + decomposeBT :756/:798
             View vg = v;
-            if (c->b2 && !multi(c)) vg.n_lossp = c->b2_ksplit;
+            if (c->ws.b2 && !multi(c)) vg.n_lossp = c->ws.b2_ksplit;
             // pieces of ||grad||^2: one per gradient block from k_grad_s; after an all-reduce k_grad_norm has rewritten them
-            if (c->b2 && !multi(c)) vg.n_norm_part = c->b2_norm_parts;
+            if (c->ws.b2 && !multi(c)) vg.n_norm_part = c->ws.b2_norm_parts;
             if (!use4) vg.btnT = nullptr;
             launch_gram_upd(vg, lid, going_left, iters == 1, s);
         }
@@ -809,7 +847,7 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             ProfScope p(c, K_ENV);                                                // verification, back-split, update_caches!, next yhat
             const int nxt = going_left ? lid - 1 : lid + 1;
             const int want = (nxt >= 0 && nxt <= c->T - 2) ? 1 : 0;
-            launch_bond_tail(v, lid, going_left, chain, want | (c->tail_launches++ == c->tail_force_fail ? 4 : 0), c->tail_span, s);
+            launch_bond_tail(v, lid, going_left, chain, want | (c->ws.tail_launches++ == c->ws.tail_force_fail ? 4 : 0), c->ws.tail_span, s);
             if (want) {
                 c->ynext_lid = nxt;
                 c->ynext_epoch = c->epoch;
@@ -819,16 +857,16 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         }
         if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(v, lid, going_left, 1, s); }
         { ProfScope p(c, K_EIG_FIN); launch_eig(v, lid, going_left, 2, s); }
-        { int rc = trace_final(c->btn); if (rc) return rc; }
+        { int rc = trace_final(c->ws.btn); if (rc) return rc; }
         {
             ProfScope p(c, K_ENV);                                                // back-split + update_caches! :759/:799
             const int64_t cs = (int64_t)v.N * v.cap;
             if (going_left)
-                launch_env_split(v, lid, 1, rid, 0, rid < c->T - 1 ? c->RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, rid,
-                                 c->RE + (int64_t)rid * cs, chain, s);
+                launch_env_split(v, lid, 1, rid, 0, rid < c->T - 1 ? c->ws.RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, rid,
+                                 c->ws.RE + (int64_t)rid * cs, chain, s);
             else
-                launch_env_split(v, lid, 0, lid, 1, lid > 0 ? c->LE + (int64_t)(lid - 1) * cs : nullptr, lid, lid + 1,
-                                 c->LE + (int64_t)lid * cs, chain, s);
+                launch_env_split(v, lid, 0, lid, 1, lid > 0 ? c->ws.LE + (int64_t)(lid - 1) * cs : nullptr, lid, lid + 1,
+                                 c->ws.LE + (int64_t)lid * cs, chain, s);
         }
         return 0;
     }
@@ -840,14 +878,14 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         { ProfScope p(c, K_UPDATE); launch_grad_reduce(v, lid, s); }
         if (multi(c)) {
             ProfScope p(c, K_ALLREDUCE);
-            int rc = enqueue_allreduce(c, c->gradbuf, 0, lid);
+            int rc = enqueue_allreduce(c, c->ws.gradbuf, 0, lid);
             if (rc) return rc;
         }
         v.trace_it = it;
         { ProfScope p(c, K_UPDATE); launch_update(v, lid, it == 0, s); }
     }
     { ProfScope p(c, K_GRAM); launch_gram(v, lid, going_left, s); }            // decomposeBT :756/:798
-    if (c->big) {
+    if (c->ws.big) {
         ProfScope p(c, K_EIG_TRI);
         int rc = enqueue_big_eig(c, v, lid, going_left);
         if (rc) return rc;
@@ -856,17 +894,17 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(v, lid, going_left, 1, s); }
         { ProfScope p(c, K_EIG_FIN); launch_eig(v, lid, going_left, 2, s); }
     }
-    { int rc = trace_final(c->bt); if (rc) return rc; }
+    { int rc = trace_final(c->ws.bt); if (rc) return rc; }
     { ProfScope p(c, K_SPLIT); launch_split(v, lid, going_left, s); }
     {
         ProfScope p(c, K_ENV);                                                  // update_caches! :759/:799
         const int64_t cs = (int64_t)v.N * v.cap;
         if (going_left)
-            launch_env(v, rid, 0, rid < c->T - 1 ? c->RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, ENV_M_E, rid,
-                       c->RE + (int64_t)rid * cs, s, next_bt_lid);
+            launch_env(v, rid, 0, rid < c->T - 1 ? c->ws.RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, ENV_M_E, rid,
+                       c->ws.RE + (int64_t)rid * cs, s, next_bt_lid);
         else
-            launch_env(v, lid, 1, lid > 0 ? c->LE + (int64_t)(lid - 1) * cs : nullptr, lid, ENV_M_E, lid + 1,
-                       c->LE + (int64_t)lid * cs, s, next_bt_lid);
+            launch_env(v, lid, 1, lid > 0 ? c->ws.LE + (int64_t)(lid - 1) * cs : nullptr, lid, ENV_M_E, lid + 1,
+                       c->ws.LE + (int64_t)lid * cs, s, next_bt_lid);
     }
     return 0;
 }
@@ -877,38 +915,32 @@ bool env_walk_on(const Ctx* c, const View& v) {
     return !c->typed && !(e && e[0] == '0') && env_walk_supported(v);
 }
 
-// construct_caches (RealRealHighDimension.jl:45-103)
-void enqueue_caches(Ctx* c, const View& v, int going_left) {
-    if (c->typed) {
-        if (going_left) enqueue_caches_typed(c, c->T - 1, c->T);
-        else enqueue_caches_typed(c, 0, 0);
-        return;
-    }
+// construct_caches (RealRealHighDimension.jl:45-103) around the label site ls: LE[0 .. ls-1] and RE[T-1 .. ls+1].  ls = T - 1 is
+// construct_caches(W; going_left=true), ls = 0 going_left=false.  One launch per side where every workgroup can walk the chain with
+// its 16 series (k_env_walk: the bits of the per-site launches; a side without sites launches nothing), else one per site.
+void enqueue_caches(Ctx* c, const View& v, int ls) {
+    if (c->typed) return enqueue_caches_typed(c, ls, ls);
     const int64_t cs = (int64_t)v.N * v.cap;
     ProfScope p(c, K_ENV);
-    if (env_walk_on(c, v)) {           // one launch: every workgroup walks the chain with its 16 series (k_env_walk, the bits of the per-site launches)
-        launch_env_walk(v, going_left, c->T - 1, c->stream);
+    if (env_walk_on(c, v)) {
+        launch_env_walk(v, 1, std::min(ls, c->T - 1), c->stream);
+        launch_env_walk(v, 0, c->T - 1 - ls, c->stream);
         return;
     }
-    if (going_left) {
-        for (int j = 0; j <= c->T - 2; ++j)
-            launch_env(v, j, 1, j > 0 ? c->LE + (int64_t)(j - 1) * cs : nullptr, j, ENV_M_SITE, j + 1,
-                       c->LE + (int64_t)j * cs, c->stream);
-    } else {
-        for (int j = c->T - 1; j >= 1; --j)
-            launch_env(v, j, 0, j < c->T - 1 ? c->RE + (int64_t)(j + 1) * cs : nullptr, j + 1, ENV_M_SITE_T, j,
-                       c->RE + (int64_t)j * cs, c->stream);
-    }
+    for (int j = 0; j < ls && j <= c->T - 2; ++j)
+        launch_env(v, j, 1, j > 0 ? v.LE + (int64_t)(j - 1) * cs : nullptr, j, ENV_M_SITE, j + 1, v.LE + (int64_t)j * cs, c->stream);
+    for (int j = c->T - 1; j > ls && j >= 1; --j)
+        launch_env(v, j, 0, j < c->T - 1 ? v.RE + (int64_t)(j + 1) * cs : nullptr, j + 1, ENV_M_SITE_T, j, v.RE + (int64_t)j * cs, c->stream);
 }
 
 // ---- a sweep as a hipGraph, and what it left ----------------------------------------------------------------------------------
 // What `enqueue` puts on the stream, captured (thread-local: other threads' work is none of this capture's) and instantiated into
-// *exec, whose previous graph goes first.  `enqueue` returns 0 or an error it has reported itself; a capture that does not end in a
+// exec, whose previous graph goes first.  `enqueue` returns 0 or an error it has reported itself; a capture that does not end in a
 // graph is reported with `end_text` and the end of capture's error.
 using DevGraph = DevOwned<hipGraph_t, hipGraph_t, hipGraphDestroy>;
 template <typename F>
-int capture_graph(Ctx* c, hipStream_t s, hipGraphExec_t* exec, const char* end_text, F&& enqueue) {
-    if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
+int capture_graph(Ctx* c, hipStream_t s, DevGraphExec& exec, const char* end_text, F&& enqueue) {
+    exec = DevGraphExec();
     HIPC(c, hipStreamSynchronize(s));
     HIPC(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     const int rc = enqueue();
@@ -917,8 +949,8 @@ int capture_graph(Ctx* c, hipStream_t s, hipGraphExec_t* exec, const char* end_t
     if (rc) return rc;
     if (e != hipSuccess || !g) return fail(c, MPST_ERR_DEVICE, end_text, hipGetErrorString(e));
     HIPC(c, hipGetLastError());     // a launch rejected during capture (bad configuration) surfaces here
-    if ((e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0)) != hipSuccess) {
-        *exec = nullptr;
+    if ((e = hipGraphInstantiate(&exec.h, g, nullptr, nullptr, 0)) != hipSuccess) {
+        exec.h = nullptr;
         return fail(c, MPST_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
     }
     return 0;
@@ -928,13 +960,13 @@ int capture_graph(Ctx* c, hipStream_t s, hipGraphExec_t* exec, const char* end_t
 // sweep reads them, redoes its rest and reads them again); read_back: with those, the subspace solver's counters and the bond
 // dimensions (st->seconds is the caller's).  Device errors are reported on `rep` (a batch: its lead).
 int read_scalars(Ctx* c, Ctx* rep, DevScalars* sc) {
-    HIPC(rep, hipMemcpy(sc, c->sc, sizeof *sc, hipMemcpyDeviceToHost));
+    HIPC(rep, hipMemcpy(sc, c->ws.sc, sizeof *sc, hipMemcpyDeviceToHost));
     return 0;
 }
 int read_back(Ctx* c, Ctx* rep, const DevScalars* sc, mpst_sweep_stats* st) {
     refresh_ss_counts(c);
     std::vector<int32_t> chi(c->T + 1);
-    HIPC(rep, hipMemcpy(chi.data(), c->chi, chi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPC(rep, hipMemcpy(chi.data(), c->mps.chi, chi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     st->svd_status = sc->status;
     st->max_chi = *std::max_element(chi.begin(), chi.end());
     st->eig_sweeps_total = sc->eig_sweeps_total;
@@ -952,47 +984,253 @@ int check_ready(Ctx* c) {
 int host_chi(Ctx* c, std::vector<int32_t>& chi, int32_t* ls) {
     chi.resize(c->T + 1);
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipMemcpy(chi.data(), c->chi, (size_t)(c->T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPC(c, hipMemcpy(ls, c->label_site, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(chi.data(), c->mps.chi, (size_t)(c->T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(ls, c->mps.label_site, sizeof(int32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
-// evaluation chain into scratch: returns yhat on device in c->yeval ([N][C])
+// evaluation chain into scratch: yhat on the device in c->ev.yeval ([N][C]).  One walk from each end of the chain to the label site,
+// ping-pong between two scratch rows; in the element-typed context the step is k_tenv and the rows' exponents travel along.
 int enqueue_eval(Ctx* c, int which) {
-    View v = make_view(c, which);
+    const View v = make_view(c, which);
     if (v.N <= 0) return fail(c, MPST_ERR_INVALID, "data set %d is empty", which);
     std::vector<int32_t> chi; int32_t p;
-    int rc = host_chi(c, chi, &p);
+    if (int rc = host_chi(c, chi, &p)) return rc;
+    const TView t = c->typed ? make_tview(c, which) : TView{};
+    EvalWs& e = c->ev;
+    const int T = c->T;
+    const double *Lc = nullptr, *Rc = nullptr;
+    const int32_t *Lx = nullptr, *Rx = nullptr;
+    auto step = [&](int j, int left, DevBuf<double>* row, DevBuf<int32_t>* xrow, int q, bool first, const double** last, const int32_t** xlast) {
+        const double* prev = first ? nullptr : row[q ^ 1].h;
+        const int mode = left ? ENV_M_SITE : ENV_M_SITE_T, prev_bond = left ? j : j + 1, out_bond = left ? j + 1 : j;
+        if (c->typed) launch_tenv(t, j, left, prev, first ? nullptr : xrow[q ^ 1].h, prev_bond, mode, out_bond, row[q], xrow[q], c->stream);
+        else launch_env(v, j, left, prev, prev_bond, mode, out_bond, row[q], c->stream);
+        *last = row[q];
+        *xlast = xrow[q];
+    };
+    for (int j = 0, q = 0; j < p; ++j, q ^= 1) step(j, 1, e.chainL, e.xchainL, q, j == 0, &Lc, &Lx);
+    for (int j = T - 1, q = 0; j > p; --j, q ^= 1) step(j, 0, e.chainR, e.xchainR, q, j == T - 1, &Rc, &Rx);
+    if (c->typed) launch_teval_final(t, Lc, Lx, Rc, Rx, e.yeval, c->stream);
+    else launch_eval_final(v, Lc, Rc, e.yeval, c->stream);
+    return 0;
+}
+
+// mpst_eval and mpst_classify: the chain, then the reduction (sums, confusion counts, predictions), waited for
+int run_eval(Ctx* c, int which) {
+    int rc = check_ready(c);
     if (rc) return rc;
-    if (c->typed) {
-        TView t = make_tview(c, which);
-        const void* Lt = nullptr; const void* Rt = nullptr;
-        const int32_t *Lx = nullptr, *Rx = nullptr;
-        int q = 0;
-        for (int j = 0; j < p; ++j) {
-            launch_tenv(t, j, 1, j > 0 ? c->chainL[q ^ 1] : nullptr, j > 0 ? c->xchainL[q ^ 1] : nullptr, j, ENV_M_SITE, j + 1, c->chainL[q], c->xchainL[q], c->stream);
-            Lt = c->chainL[q]; Lx = c->xchainL[q]; q ^= 1;
-        }
-        q = 0;
-        for (int j = c->T - 1; j > p; --j) {
-            launch_tenv(t, j, 0, j < c->T - 1 ? c->chainR[q ^ 1] : nullptr, j < c->T - 1 ? c->xchainR[q ^ 1] : nullptr, j + 1, ENV_M_SITE_T, j, c->chainR[q], c->xchainR[q], c->stream);
-            Rt = c->chainR[q]; Rx = c->xchainR[q]; q ^= 1;
-        }
-        launch_teval_final(t, Lt, Lx, Rt, Rx, c->yeval, c->stream);
+    if (which != 0 && which != 1) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
+    if ((rc = enqueue_eval(c, which))) return rc;
+    EvalWs& e = c->ev;
+    if (c->typed) launch_teval_reduce(make_tview(c, which), e.yeval, e.out3, e.conf, e.pred, c->stream);
+    else launch_eval_reduce(make_view(c, which), e.yeval, e.out3, e.conf, e.pred, c->stream);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the sweep runner ---------------------------------------------------------------------------------------------------------
+// `body` between the context's two events, waited for: *ms receives its device time.  body returns 0 or an error it has reported.
+template <typename Body>
+int timed(Ctx* c, float* ms, Body&& body) {
+    HIPC(c, hipEventRecord(c->ev_start, c->stream));
+    if (int rc = body()) return rc;
+    HIPC(c, hipGetLastError());         // launch-time failures of the enqueues of body
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    HIPC(c, hipEventElapsedTime(ms, c->ev_start, c->ev_stop));
+    prof_collect(c);
+    return 0;
+}
+
+// the four copies of the snapshot, one list for both directions
+int Snapshot::copies(Ctx* c, bool restore) {
+    const size_t nchi = (size_t)c->T + 1;
+    const struct { void *live, *kept; size_t bytes; } list[4] = {
+        {c->mps.sites.h, sites.h, (size_t)c->mps.site_stride * c->T * c->esz},
+        {c->mps.chi.h, chi.h, nchi * sizeof(int32_t)},
+        {c->mps.label_site.h, chi.h + nchi, sizeof(int32_t)},
+        {c->ws.sc.h, sc.h, sizeof(DevScalars)}};
+    for (const auto& e : list)
+        HIPC(c, hipMemcpyAsync(restore ? e.live : e.kept, restore ? e.kept : e.live, e.bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+int ensure_snapshot(Ctx* c) {
+    if (c->ws.snap) return 0;
+    Snapshot n;
+    int rc;
+    if ((rc = dalloc_e(c, n.sites, c->mps.site_stride * c->T)) || (rc = dalloc(c, n.chi, c->T + 2)) || (rc = dalloc(c, n.sc, 1))) return rc;
+    c->ws.snap = std::move(n);
+    return 0;
+}
+
+// the bonds of a sweep from its k0-th on (k0 > 0: the state is that after bond k0 - 1, the recovery of a marked sweep)
+int enqueue_sweep(Ctx* c, const View& v, int k0 = 0) {
+    if (int rc = enqueue_reset_status(c)) return rc;
+    c->ynext_lid = -1;
+    // unless the tensor is rescaled first or the caches are rebuilt in between, bond k+1's tensor is assembled by bond k's last launch
+    const int nb = c->T - 1;
+    bool have = false;
+    for (int k = k0; k < 2 * nb; ++k) {
+        const bool rebuild_after = c->opt.rebuild_caches && k == nb - 1;
+        const BondSlot b = (v.rescale_before || rebuild_after) ? bond_slot(k, nb).unchained() : bond_slot(k, nb);
+        if (int rc = enqueue_bond(c, v, b, have, k)) return rc;
+        have = assembles_next(b, c->ws.fused);
+        if (rebuild_after) enqueue_caches(c, v, 0);      // :770
+    }
+    if (c->opt.rebuild_caches) enqueue_caches(c, v, c->T - 1);                  // :804
+    return 0;
+}
+
+// Four-launch chain: a tail launch whose verification failed (clustered kept eigenvalues: the case k_eig_fin hands to its Jacobi
+// solver) has marked the sweep or the bond (DevScalars::redo > 0) and left the MPS, the caches and the chained tensor as the bond
+// before it left them; so did every tail launch after it.  What is left to do - `enqueue`, given a fresh View: the rest of the sweep,
+// or the same bond again - runs on the six-launch chain, plain stream; *sc receives what it left.
+template <typename Enqueue>
+int finish_marked(Ctx* c, DevScalars* sc, Enqueue&& enqueue) {
+    c->tail_redos++;
+    const int tail_fallbacks = sc->eig_fallbacks;
+    Chain4Hold hold(c);
+    if (int rc = enqueue(make_view(c, MPST_TRAIN))) return rc;
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (int rc = read_scalars(c, c, sc)) return rc;
+    sc->eig_fallbacks += tail_fallbacks;
+    return 0;
+}
+
+// the error a sweep returns for a non-zero device status
+int sweep_failure(Ctx* c, const DevScalars& sc) {
+    if (sc.status == MPST_ERR_DEVICE && c->use_ipc) {
+        c->use_ipc = false;         // flags / epochs / slots are in an undefined cross-rank state: never reuse them
+        c->ipc_dead = true;
+        return fail(c, MPST_ERR_DEVICE, "the one-shot all-reduce timed out waiting for a peer (MPST_AR_TIMEOUT_S): rank %d of %d saw rank %d's flag at epoch %d while waiting "
+                    "for one of the %llu calls issued so far; the path is retired until the inboxes are exported again", c->rank, c->nranks, sc.pad[0], sc.pad[1],
+                    (unsigned long long)c->ar_epoch);
+    }
+    return fail(c, MPST_ERR_SVD, "bond-tensor decomposition failed (non-finite spectrum or eigensolver did not converge)");
+}
+
+// ---- batches: errors are reported on the lead, ctxs[0] --------------------------------------------------------------------------
+int forward_error(Ctx* lead, const Ctx* member, int rc) {
+    if (member != lead) lead->err = member->err;
+    return rc;
+}
+// What mpst_sweep_batch and mpst_classify_batch ask of every member: there, once, ready (its own error forwarded), on the lead's
+// device and of the caller's shape - shape(c, k) returns 0 or the error it has reported on the lead - and its stream idle.
+template <typename Shape>
+int batch_members(void* const* ctxs, int K, Shape&& shape) {
+    Ctx* c0 = (Ctx*)ctxs[0];
+    for (int k = 0; k < K; ++k) {
+        Ctx* c = (Ctx*)ctxs[k];
+        if (!c) return fail(c0, MPST_ERR_INVALID, "context %d is NULL", k);
+        for (int j = 0; j < k; ++j)
+            if (ctxs[j] == ctxs[k]) return fail(c0, MPST_ERR_INVALID, "context %d appears twice", k);
+        if (int rc = check_ready(c)) return forward_error(c0, c, rc);
+        if (int rc = shape(c, k)) return rc;
+        HIPC(c0, hipStreamSynchronize(c->stream));
+    }
+    HIPC(c0, hipSetDevice(c0->device));
+    return 0;
+}
+
+// K independent fits of one shape advanced by ONE launch chain (hyper-parameter candidates, CV folds, restarts: what the
+// reference farms out with @distributed, tuning.jl).  Every launch of the headline chain carries all K fits (blockIdx.z), so the
+// kernel count per sweep is that of one fit; results are those of K separate mpst_sweep calls, bit for bit.
+// batch_prepare: validation and (if the batch is new) capture of its graph; batch_run: replay and read-back.
+int batch_prepare(void* const* ctxs, int32_t K) {
+    if (!ctxs || K < 1 || K > 64) return fail(nullptr, MPST_ERR_INVALID, "mpst_sweep_batch: 1..64 contexts");
+    Ctx* c0 = (Ctx*)ctxs[0];
+    if (!c0) return MPST_ERR_INVALID;
+    if (hipSetDevice(c0->device) != hipSuccess) return fail(c0, MPST_ERR_DEVICE, "cannot select device %d", c0->device);
+    int rc = batch_members(ctxs, K, [&](Ctx* c, int k) {
+        if (!c->caches_valid) return fail(c0, MPST_ERR_INVALID, "context %d: call mpst_build_caches first", k);
+        if (c->host_label_site != c->T - 1) return fail(c0, MPST_ERR_INVALID, "context %d: a sweep starts with the label index on the last site", k);
+        if (!batchable(c))
+            return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_sweep_batch runs the headline chain only (Float64, d*chi_max <= 128, <= 8192 series, one rank, "
+                                                 "update_iters = 1, no track_cost / rebuild_caches / profiling)", k);
+        // the fits may differ in their series (N, class counts, tiles: every kernel reads those from the fit's own View, the grids are sized
+        // for the largest fit); whatever fixes an order of summation is either the context's (b2_ksplit, b2_nw, b2_norm_parts) or shared
+        const bool same = c->device == c0->device && c->T == c0->T && c->d == c0->d && c->C == c0->C && c->mps.cap == c0->mps.cap &&
+                          c->opt.loss == c0->opt.loss && c->opt.train_classes_separately == c0->opt.train_classes_separately &&
+                          c->opt.chi_max == c0->opt.chi_max && c->ws.b2_ksplit == c0->ws.b2_ksplit && (c->batch_hint > 1) == (c0->batch_hint > 1) && c->ws.b2_norm_parts == c0->ws.b2_norm_parts;
+        if (!same) return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs in shape from context 0 (T, d, C, capacity, chi_max, loss, gradient shares): batch fits of one shape", k);
         return 0;
+    });
+    if (rc) return rc;
+    BatchLead& b = c0->lead;
+    if (b.batch_cap < K) {
+        b.batch_key.clear();
+        b.batch_cap = 0;
+        if ((rc = dalloc(c0, b.batch_views, (int64_t)2 * K))) return rc;
+        b.batch_cap = K;
     }
-    const double* Lc = nullptr; const double* Rc = nullptr;
-    int pp = 0;
-    for (int j = 0; j < p; ++j) {
-        launch_env(v, j, 1, j > 0 ? c->chainL[pp ^ 1] : nullptr, j, ENV_M_SITE, j + 1, c->chainL[pp], c->stream);
-        Lc = c->chainL[pp]; pp ^= 1;
+    std::vector<std::pair<uint64_t, uint64_t>> key;
+    for (int k = 0; k < K; ++k) key.push_back({((Ctx*)ctxs[k])->uid, ((Ctx*)ctxs[k])->epoch});
+    if (b.batch_graph && key == b.batch_key) return 0;
+    View v0 = make_view(c0, MPST_TRAIN);         // the launchers' geometry: the shared shape, and the tiles of the largest fit
+    std::vector<View> hv((size_t)2 * b.batch_cap);
+    for (int k = 0; k < K; ++k) {
+        Ctx* c = (Ctx*)ctxs[k];
+        v0.ntiles = std::max(v0.ntiles, c->ds[MPST_TRAIN].ntiles);
+        hv[k] = make_view(c, MPST_TRAIN);
+        View vg = hv[k];                    // the Gram launch reads the loss pieces and the gradient-norm pieces k_grad_s left
+        vg.n_lossp = c->ws.b2_ksplit;
+        vg.n_norm_part = c->ws.b2_norm_parts;
+        hv[(size_t)b.batch_cap + k] = vg;
     }
-    pp = 0;
-    for (int j = c->T - 1; j > p; --j) {
-        launch_env(v, j, 0, j < c->T - 1 ? c->chainR[pp ^ 1] : nullptr, j + 1, ENV_M_SITE_T, j, c->chainR[pp], c->stream);
-        Rc = c->chainR[pp]; pp ^= 1;
+    b.batch_key.clear();                  // the views the old graph reads are overwritten from here on
+    HIPC(c0, hipMemcpy(b.batch_views, hv.data(), hv.size() * sizeof(View), hipMemcpyHostToDevice));
+    const View* dv = b.batch_views;
+    const View* dvg = b.batch_views + b.batch_cap;
+    hipStream_t s = c0->stream;
+    auto enqueue_batch = [&]() -> int {
+        for (int k = 0; k < K; ++k) {
+            const hipError_t em = hipMemsetAsync(&((Ctx*)ctxs[k])->ws.sc.h->status, 0, 12, s);
+            if (em != hipSuccess) return fail(c0, MPST_ERR_DEVICE, "capture of the batched sweep failed: %s", hipGetErrorString(em));
+        }
+        const int nb = c0->T - 1;
+        bool have = false;
+        for (int q = 0; q < 2 * nb; ++q) {
+            const BondSlot bs = bond_slot(q, nb);
+            const int lid = bs.lid, left = bs.going_left, rid = lid + 1, chain = bs.chains_into_next ? 1 : 0;
+            if (!have) launch_bt_assemble_b(v0, dv, K, lid, s);
+            have = assembles_next(bs, true);
+            launch_yhat_s_b(v0, dv, K, lid, s);
+            launch_grad_s_b(v0, dv, K, lid, s);
+            launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
+            launch_eig_b(v0, dv, K, lid, left, 0, s);
+            launch_eig_b(v0, dv, K, lid, left, 2, s);
+            // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
+            if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
+            else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
+        }
+        return 0;
+    };
+    if ((rc = capture_graph(c0, s, b.batch_graph, "capture of the batched sweep failed: %s", enqueue_batch))) return rc;
+    b.batch_key = key;
+    return 0;
+}
+int batch_run(void* const* ctxs, int32_t K, mpst_sweep_stats* out) {
+    Ctx* c0 = (Ctx*)ctxs[0];
+    HIPC(c0, hipSetDevice(c0->device));
+    float ms = 0.f;
+    int rc = timed(c0, &ms, [&]() -> int {
+        HIPC(c0, hipGraphLaunch(c0->lead.batch_graph, c0->stream));
+        return 0;
+    });
+    if (rc) return rc;
+    int failed = -1;
+    for (int k = 0; k < K; ++k) {
+        DevScalars sc;
+        mpst_sweep_stats st{};
+        if ((rc = read_scalars((Ctx*)ctxs[k], c0, &sc)) || (rc = read_back((Ctx*)ctxs[k], c0, &sc, &st))) return rc;
+        st.seconds = 1e-3 * ms;                    // of the whole batch: the fits advance together
+        if (out) out[k] = st;
+        if (sc.status && failed < 0) failed = k;
     }
-    launch_eval_final(v, Lc, Rc, c->yeval, c->stream);
+    if (failed >= 0) return fail(c0, MPST_ERR_SVD, "bond-tensor decomposition failed in fit %d of the batch (its svd_status is set; the other fits are intact)", failed);
     return 0;
 }
 
@@ -1135,7 +1373,7 @@ int dataset_commit(Ctx* c, const DataSetRequest& r, const DataSetPlan& p, DataSe
     n->ntiles = (int32_t)p.tiles.size();
     n->nchunks = (int32_t)p.chunks.size();
     int rc;
-    if ((rc = dalloc_e(c, &n->phi.h, r.N * r.T * r.d)) || (rc = dalloc(c, n->label, r.N))) return rc;
+    if ((rc = dalloc_e(c, n->phi, r.N * r.T * r.d)) || (rc = dalloc(c, n->label, r.N))) return rc;
     HIPC(c, hipMemcpy(n->label, r.label_idx, (size_t)r.N * sizeof(int32_t), hipMemcpyHostToDevice));
     if ((rc = upload(c, n->tiles, p.tiles)) || (rc = upload(c, n->chunks, p.chunks)) || (rc = upload(c, n->cls_chunk_off, p.cls_chunk_off)) ||
         (rc = upload(c, n->cls_off, p.cls_off)) || (rc = upload(c, n->inv_count, p.inv_count)))
@@ -1160,15 +1398,11 @@ int dataset_set(Ctx* c, DataSetRequest& r, Fill fill) {
     return 0;
 }
 
-// `launch` between the context's two events, waited for: its device time is added to *seconds
+// `launch` (returns a hipError_t) timed: its device time is added to *seconds
 template <typename Launch>
 int timed_launch(Ctx* c, double* seconds, Launch launch) {
-    HIPC(c, hipEventRecord(c->ev_start, c->stream));
-    HIPC(c, launch());
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_stop));
     float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    if (int rc = timed(c, &ms, [&]() -> int { HIPC(c, launch()); return 0; })) return rc;
     *seconds += 1e-3 * ms;
     return 0;
 }
@@ -1299,12 +1533,12 @@ int mpst_create(void** ctx, int device_id) {
     static std::atomic<uint64_t> next_uid{1};
     c->uid = next_uid.fetch_add(1);
     c->device = device_id;
-    if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess) {
+    if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&c->stream.h) != hipSuccess) {
         delete c;
         return fail(nullptr, MPST_ERR_DEVICE, "cannot initialise device %d", device_id);
     }
-    (void)hipEventCreate(&c->ev_start);
-    (void)hipEventCreate(&c->ev_stop);
+    (void)hipEventCreate(&c->ev_start.h);
+    (void)hipEventCreate(&c->ev_stop.h);
     *ctx = c;
     return 0;
 }
@@ -1314,29 +1548,7 @@ void mpst_destroy(void* ctx) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->sweep_graph) (void)hipGraphExecDestroy(c->sweep_graph);
-    if (c->batch_graph) (void)hipGraphExecDestroy(c->batch_graph);
-    dfree(&c->batch_views);
-    dfree(&c->score_buf);
     if (c->comm && rccl_ready(nullptr)) rccl_ready(nullptr)->CommDestroy(c->comm);
-    ipc_release(c);
-    c->ds[0] = DataSet(); c->ds[1] = DataSet();
-    dfree(&c->sites); dfree(&c->chi); dfree(&c->label_site); dfree(&c->LE); dfree(&c->RE); dfree(&c->bt);
-    dfree(&c->yhat); dfree(&c->tile_loss); dfree(&c->partial); dfree(&c->gradbuf); dfree(&c->gram); dfree(&c->lam);
-    if (c->big) big_eig_destroy(c->big);
-    if (c->blk) blocked_eig_destroy(c->blk);
-    dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);
-    dfree(&c->norm_scratch); dfree(&c->tnorm_scratch); dfree(&c->xLE); dfree(&c->xRE); dfree(&c->yexp);
-    for (int k = 0; k < 2; ++k) { dfree(&c->xchainL[k]); dfree(&c->xchainR[k]); }
-    dfree(&c->btn); dfree(&c->norm_part); dfree(&c->loss_trace);
-    dfree(&c->b2_ypart); dfree(&c->b2_lossp); dfree(&c->b2_tick); dfree(&c->b2_dbg);
-    dfree(&c->btnT); dfree(&c->tail_span);
-    dfree(&c->E); dfree(&c->eig_ws); dfree(&c->sc); dfree(&c->norm2); dfree(&c->yeval); dfree(&c->out3); dfree(&c->conf); dfree(&c->pred);
-    for (int k = 0; k < 2; ++k) { dfree(&c->chainL[k]); dfree(&c->chainR[k]); }
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-    if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
-    (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1397,14 +1609,14 @@ int mpst_comm_ipc_export(void* ctx, int nranks, int rank, uint8_t handle_out[64]
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t size");
     ipc_release(c);
     c->nranks = nranks; c->rank = rank;
-    const int64_t dm = (int64_t)c->d * c->cap;
+    const int64_t dm = (int64_t)c->d * c->mps.cap;
     c->ipc_slot = std::max<int64_t>(2 + c->zw * c->C * dm * dm, 4 + (int64_t)c->C * c->C);
     c->ipc_slot = (c->ipc_slot + 15) & ~15ll;
     c->ipc_flag_off = (size_t)2 * nranks * c->ipc_slot * sizeof(double);
     c->ipc_ctr_off = c->ipc_flag_off + 16 * sizeof(unsigned long long);
     c->ipc_bytes = c->ipc_ctr_off + 64;
     // fine-grained device memory: peers write it and this device polls it while kernels run
-    hipError_t e = hipExtMallocWithFlags(&c->ipc_local, c->ipc_bytes, hipDeviceMallocFinegrained);
+    hipError_t e = hipExtMallocWithFlags((void**)&c->ipc_local.h, c->ipc_bytes, hipDeviceMallocFinegrained);
     if (e != hipSuccess) return fail(c, MPST_ERR_NOMEM, "hipExtMallocWithFlags(fine-grained, %zu bytes): %s", c->ipc_bytes, hipGetErrorString(e));
     HIPC(c, hipMemset(c->ipc_local, 0, c->ipc_bytes));
     HIPC(c, hipDeviceSynchronize());
@@ -1422,7 +1634,7 @@ int mpst_comm_ipc_attach(void* ctx, const uint8_t* all_handles) {
     if (!c || !all_handles || !c->ipc_local) return fail(c, MPST_ERR_INVALID, "call mpst_comm_ipc_export first");
     HIPC(c, hipSetDevice(c->device));
     for (int r = 0; r < c->nranks; ++r) {
-        if (r == c->rank) { c->ipc_peer[r] = c->ipc_local; continue; }
+        if (r == c->rank) { c->ipc_peer[r] = c->ipc_local.h; continue; }
         hipIpcMemHandle_t h;
         memcpy(&h, all_handles + (size_t)64 * r, 64);
         hipError_t e = hipIpcOpenMemHandle(&c->ipc_peer[r], h, hipIpcMemLazyEnablePeerAccess);
@@ -1458,8 +1670,8 @@ int mpst_set_options(void* ctx, const mpst_options* o) {
         return fail(c, MPST_ERR_UNSUPPORTED, "Optim/OptimKit based solvers currently unimplemented for this version, set 'use_legacy_ITensor=true' in MPSOptions to enable");
     if (o->loss == MPST_LOSS_MSE && o->train_classes_separately)
         return fail(c, MPST_ERR_UNSUPPORTED, "no Loss_Grad_MSE method for TrainSeparate{true} (loss_functions.jl:561)");
-    if (c->have_mps && o->chi_max > c->cap)
-        return fail(c, MPST_ERR_INVALID, "chi_max %d exceeds the capacity %d fixed when the MPS was set; call mpst_set_options before mpst_set_mps", o->chi_max, c->cap);
+    if (c->have_mps && o->chi_max > c->mps.cap)
+        return fail(c, MPST_ERR_INVALID, "chi_max %d exceeds the capacity %d fixed when the MPS was set; call mpst_set_options before mpst_set_mps", o->chi_max, c->mps.cap);
     const bool resize = !c->have_opt || o->rescale_before != c->opt.rescale_before || o->update_iters != c->opt.update_iters;
     c->opt = *o;
     c->have_opt = true;
@@ -1546,32 +1758,34 @@ int mpst_set_mps(void* ctx, const void* const* site, const int32_t* chi, int32_t
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const int d = c->d, C = c->C;
-    if (cap != c->cap || !c->sites) {
-        c->cap = cap;
-        c->site_stride = (int64_t)C * cap * d * cap;
+    if (cap != c->mps.cap || !c->mps.sites) {
+        // the old MPS goes first, the new one is built aside and moved in complete: a failure leaves the context without one
+        c->have_mps = c->ws_ready = false;
+        c->mps = Mps();
+        Mps m;
+        m.cap = cap;
+        m.site_stride = (int64_t)C * cap * d * cap;
         int rc;
-        if ((rc = dalloc_e(c, &c->sites, c->site_stride * T))) return rc;
-        if ((rc = dalloc(c, &c->chi, T + 1))) return rc;
-        if ((rc = dalloc(c, &c->label_site, 1))) return rc;
-        c->ws_ready = false;
+        if ((rc = dalloc_e(c, m.sites, m.site_stride * T)) || (rc = dalloc(c, m.chi, T + 1)) || (rc = dalloc(c, m.label_site, 1))) return rc;
+        c->mps = std::move(m);
     }
     // boundary layout (s, l, r[, c]) column-major  ->  internal [c][l][s][r]; elements of esz bytes (a pure permutation)
     const size_t esz = c->esz;
-    std::vector<char> buf((size_t)c->site_stride * T * esz, 0);
+    std::vector<char> buf((size_t)c->mps.site_stride * T * esz, 0);
     for (int j = 0; j < T; ++j) {
         const int Dl = chi[j], Dr = chi[j + 1], Cj = (j == label_site) ? C : 1;
         const char* src = (const char*)site[j];
         if (!src) return fail(c, MPST_ERR_INVALID, "site[%d] is NULL", j);
-        char* dst = &buf[(size_t)j * c->site_stride * esz];
+        char* dst = &buf[(size_t)j * c->mps.site_stride * esz];
         for (int cc = 0; cc < Cj; ++cc)
             for (int r = 0; r < Dr; ++r)
                 for (int l = 0; l < Dl; ++l)
                     for (int s = 0; s < d; ++s)
                         memcpy(dst + ((((size_t)cc * Dl + l) * d + s) * Dr + r) * esz, src + (s + (size_t)d * (l + (size_t)Dl * (r + (size_t)Dr * cc))) * esz, esz);
     }
-    HIPC(c, hipMemcpy(c->sites, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->chi, chi, (size_t)(T + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->label_site, &label_site, sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->mps.sites, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->mps.chi, chi, (size_t)(T + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->mps.label_site, &label_site, sizeof(int32_t), hipMemcpyHostToDevice));
     c->have_mps = true;
     c->caches_valid = false;
     c->host_label_site = label_site;
@@ -1599,14 +1813,14 @@ int mpst_get_mps(void* ctx, void* const* site_out) {
     int rc = host_chi(c, chi, &ls);
     if (rc) return rc;
     const size_t esz = c->esz;
-    std::vector<char> buf((size_t)c->site_stride * c->T * esz);
-    HIPC(c, hipMemcpy(buf.data(), c->sites, buf.size(), hipMemcpyDeviceToHost));
+    std::vector<char> buf((size_t)c->mps.site_stride * c->T * esz);
+    HIPC(c, hipMemcpy(buf.data(), c->mps.sites, buf.size(), hipMemcpyDeviceToHost));
     const int d = c->d;
     for (int j = 0; j < c->T; ++j) {
         const int Dl = chi[j], Dr = chi[j + 1], Cj = (j == ls) ? c->C : 1;
         char* dst = (char*)site_out[j];
         if (!dst) return fail(c, MPST_ERR_INVALID, "site_out[%d] is NULL", j);
-        const char* src = &buf[(size_t)j * c->site_stride * esz];
+        const char* src = &buf[(size_t)j * c->mps.site_stride * esz];
         for (int cc = 0; cc < Cj; ++cc)
             for (int r = 0; r < Dr; ++r)
                 for (int l = 0; l < Dl; ++l)
@@ -1623,23 +1837,7 @@ int mpst_build_caches(void* ctx) {
     const int32_t ls = c->host_label_site;
     // environments on both sides of the label site p: LE[0..p-1] and RE[T-1..p+1].  With the label
     // on the last site (the state fitMPS starts from) this is construct_caches(W; going_left=true).
-    View v = make_view(c, MPST_TRAIN);
-    const int64_t cs = (int64_t)v.N * v.cap;
-    if (c->typed) {
-        enqueue_caches_typed(c, ls, ls);
-    } else if (env_walk_on(c, v)) {
-        ProfScope p(c, K_ENV);
-        launch_env_walk(v, 1, std::min(ls, c->T - 1), c->stream);
-        launch_env_walk(v, 0, c->T - 1 - ls, c->stream);
-    } else {
-        ProfScope p(c, K_ENV);
-        for (int j = 0; j < ls && j <= c->T - 2; ++j)
-            launch_env(v, j, 1, j > 0 ? c->LE + (int64_t)(j - 1) * cs : nullptr, j, ENV_M_SITE, j + 1,
-                       c->LE + (int64_t)j * cs, c->stream);
-        for (int j = c->T - 1; j > ls && j >= 1; --j)
-            launch_env(v, j, 0, j < c->T - 1 ? c->RE + (int64_t)(j + 1) * cs : nullptr, j + 1, ENV_M_SITE_T, j,
-                       c->RE + (int64_t)j * cs, c->stream);
-    }
+    enqueue_caches(c, make_view(c, MPST_TRAIN), ls);
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -1656,236 +1854,65 @@ int mpst_sweep(void* ctx, mpst_sweep_stats* out) {
         return fail(c, MPST_ERR_INVALID, "the environment caches do not describe the current MPS / data set: call mpst_build_caches first");
     if (c->host_label_site != c->T - 1)
         return fail(c, MPST_ERR_INVALID, "a sweep starts with the label index on the last site (RealRealHighDimension.jl:19-29), it is on site %d", c->host_label_site);
-    View v = make_view(c, MPST_TRAIN);
-    // k0 > 0: the rest of a sweep from its k0-th bond on (the state is that after bond k0 - 1: mpst_sweep's tail recovery)
-    auto enqueue_sweep = [&](int k0 = 0) -> int {
-        int r0 = enqueue_reset_status(c);
-        if (r0) return r0;
-        c->ynext_lid = -1;
-        // unless the tensor is rescaled first or the caches are rebuilt in between, bond k+1's tensor is assembled by bond k's last launch
-        const int nb = c->T - 1;
-        bool have = false;
-        int r;
-        for (int k = k0; k < 2 * nb; ++k) {
-            const bool rebuild_after = c->opt.rebuild_caches && k == nb - 1;
-            const BondSlot b = (v.rescale_before || rebuild_after) ? bond_slot(k, nb).unchained() : bond_slot(k, nb);
-            if ((r = enqueue_bond(c, v, b, have, k))) return r;
-            have = assembles_next(b, c->fused);
-            if (rebuild_after) enqueue_caches(c, v, 0);      // :770
-        }
-        if (c->opt.rebuild_caches) enqueue_caches(c, v, 1);                         // :804
-        return 0;
-    };
+    const View v = make_view(c, MPST_TRAIN);
     const bool use_graph = sweep_uses_graph(c);
     if (use_graph && (!c->sweep_graph || c->graph_epoch != c->epoch)) {
-        if ((rc = capture_graph(c, c->stream, &c->sweep_graph, "hipStreamEndCapture failed: %s", [&] { return enqueue_sweep(); }))) return rc;
+        if ((rc = capture_graph(c, c->stream, c->sweep_graph, "hipStreamEndCapture failed: %s", [&] { return enqueue_sweep(c, v); }))) return rc;
         c->graph_epoch = c->epoch;
     }
     // large bonds: no verdict is read inside the sweep (launch_eig_blocked_nosync); the state the sweep starts from is kept
     // so that a sweep in which a bond failed can be redone bond by bond
     // (one rank only: a persistent kernel that runs out of patience is a rank-local event, and a rank that redoes its sweep
     // alone would issue all-reduces its peers do not)
-    const bool optimistic = c->big && c->blk && c->big_opt && !multi(c) && c->big_cooldown == 0;
+    const bool optimistic = c->ws.big && c->ws.blk && c->ws.big_opt && !multi(c) && c->big_cooldown == 0;
     if (c->big_cooldown > 0) c->big_cooldown--;
-    const size_t site_bytes = (size_t)c->site_stride * c->T * c->esz, chi_bytes = (size_t)(c->T + 1) * sizeof(int32_t);
     if (optimistic) {
-        if (!c->snap_sites) {
-            // all three or none: a partial failure must not leave a half-allocated snapshot behind
-            if ((rc = dalloc_e(c, &c->snap_sites, c->site_stride * c->T)) || (rc = dalloc(c, &c->snap_chi, c->T + 2)) || (rc = dalloc(c, &c->snap_sc, 1))) {
-                dfree(&c->snap_sites); dfree(&c->snap_chi); dfree(&c->snap_sc);
-                return rc;
-            }
-        }
-        HIPC(c, hipMemcpyAsync(c->snap_sites, c->sites, site_bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(c->snap_chi, c->chi, chi_bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(c->snap_chi + c->T + 1, c->label_site, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(c->snap_sc, c->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = ensure_snapshot(c)) || (rc = c->ws.snap.save(c))) return rc;
         c->big_opt_active = true;
     }
     struct ActiveGuard {        // whatever path leaves this function, the per-bond eigensolver path reads its verdict again
         bool& f;
         ~ActiveGuard() { f = false; }
     } active_guard{c->big_opt_active};
-    HIPC(c, hipEventRecord(c->ev_start, c->stream));
-    if (use_graph) {
-        HIPC(c, hipGraphLaunch(c->sweep_graph, c->stream));
-    } else if ((rc = enqueue_sweep())) {
-        c->big_opt_active = false;
-        return rc;
-    }
-    HIPC(c, hipGetLastError());         // launch-time failures of the ~2000 enqueues above
-    c->ynext_lid = -1;
-    if (optimistic) {
-        c->big_opt_active = false;
-        const int st = blocked_eig_take_sticky(c->blk, c->stream);        // the one synchronisation of the sweep
-        if (st < 0) return fail(c, MPST_ERR_DEVICE, "reading the sweep's eigensolver verdict failed");
-        if (st) {
-            // some bond's verification failed, or a persistent tridiagonalisation gave up: everything after it ran on
-            // unspecified data.  Back to the start of the sweep, caches rebuilt, bond by bond with the verdict read each time.
-            c->big_redos++;
-            c->big_cooldown = 4;        // whatever made the persistent kernels fail (a shared GPU, CU masking) tends to last: the next sweeps take the per-bond path
-            HIPC(c, hipMemcpyAsync(c->sites, c->snap_sites, site_bytes, hipMemcpyDeviceToDevice, c->stream));
-            HIPC(c, hipMemcpyAsync(c->chi, c->snap_chi, chi_bytes, hipMemcpyDeviceToDevice, c->stream));
-            HIPC(c, hipMemcpyAsync(c->label_site, c->snap_chi + c->T + 1, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-            HIPC(c, hipMemcpyAsync(c->sc, c->snap_sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, c->stream));
-            enqueue_caches(c, v, 1);
-            if ((rc = enqueue_sweep())) return rc;
-            HIPC(c, hipGetLastError());
-        }
-    }
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_stop));
     float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    prof_collect(c);
+    rc = timed(c, &ms, [&]() -> int {
+        if (use_graph) HIPC(c, hipGraphLaunch(c->sweep_graph, c->stream));
+        else if (int r = enqueue_sweep(c, v)) return r;
+        c->ynext_lid = -1;
+        if (!optimistic) return 0;
+        HIPC(c, hipGetLastError());
+        c->big_opt_active = false;
+        const int st = blocked_eig_take_sticky(c->ws.blk, c->stream);        // the one synchronisation of the sweep
+        if (st < 0) return fail(c, MPST_ERR_DEVICE, "reading the sweep's eigensolver verdict failed");
+        if (!st) return 0;
+        // some bond's verification failed, or a persistent tridiagonalisation gave up: everything after it ran on
+        // unspecified data.  Back to the start of the sweep, caches rebuilt, bond by bond with the verdict read each time.
+        c->big_redos++;
+        c->big_cooldown = 4;        // whatever made the persistent kernels fail (a shared GPU, CU masking) tends to last: the next sweeps take the per-bond path
+        if (int r = c->ws.snap.restore(c)) return r;
+        enqueue_caches(c, v, c->T - 1);
+        return enqueue_sweep(c, v);
+    });
+    if (rc) return rc;
     DevScalars sc;
     mpst_sweep_stats st{};
     if ((rc = read_scalars(c, c, &sc))) return rc;
     if (sc.redo > 0 && !c->chain4_hold) {
-        // four-launch chain: a tail launch whose verification failed (clustered kept eigenvalues: the case k_eig_fin hands to its Jacobi
-        // solver) has marked the sweep and left the MPS, the caches and the chained tensor as the bond before it left them; so did every
-        // tail launch after it.  The rest of the sweep runs on the six-launch chain, plain stream.
-        c->tail_redos++;
-        const int tail_fallbacks = sc.eig_fallbacks;
-        Chain4Hold hold(c);
-        v = make_view(c, MPST_TRAIN);
-        HIPC(c, hipEventRecord(c->ev_start, c->stream));
-        if ((rc = enqueue_sweep(sc.redo - 1))) return rc;
-        HIPC(c, hipGetLastError());
-        HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-        HIPC(c, hipEventSynchronize(c->ev_stop));
-        float ms2 = 0.f;
-        HIPC(c, hipEventElapsedTime(&ms2, c->ev_start, c->ev_stop));
+        float ms2 = 0.f;          // the rest of the sweep from the marked bond on
+        const int k0 = sc.redo - 1;
+        if ((rc = finish_marked(c, &sc, [&](const View& v6) { return timed(c, &ms2, [&] { return enqueue_sweep(c, v6, k0); }); }))) return rc;
         ms += ms2;
-        prof_collect(c);
-        if ((rc = read_scalars(c, c, &sc))) return rc;
-        sc.eig_fallbacks += tail_fallbacks;
     }
     if ((rc = read_back(c, c, &sc, &st))) return rc;
     st.seconds = 1e-3 * ms;
     if (out) *out = st;
-    if (sc.status) {
-        if (sc.status == MPST_ERR_DEVICE && c->use_ipc) {
-            c->use_ipc = false;         // flags / epochs / slots are in an undefined cross-rank state: never reuse them
-            c->ipc_dead = true;
-            return fail(c, MPST_ERR_DEVICE, "the one-shot all-reduce timed out waiting for a peer (MPST_AR_TIMEOUT_S): rank %d of %d saw rank %d's flag at epoch %d while waiting "
-                        "for one of the %llu calls issued so far; the path is retired until the inboxes are exported again", c->rank, c->nranks, sc.pad[0], sc.pad[1],
-                        (unsigned long long)c->ar_epoch);
-        }
-        return fail(c, MPST_ERR_SVD, "bond-tensor decomposition failed (non-finite spectrum or eigensolver did not converge)");
-    }
-    return 0;
+    return sc.status ? sweep_failure(c, sc) : 0;
 }
 
-// K independent fits of one shape advanced by ONE launch chain (hyper-parameter candidates, CV folds, restarts: what the
-// reference farms out with @distributed, tuning.jl).  Every launch of the headline chain carries all K fits (blockIdx.z), so the
-// kernel count per sweep is that of one fit; results are those of K separate mpst_sweep calls, bit for bit.
-// phase 1: validation and (if the batch is new) capture of its graph; phase 2: replay and read-back; 0: both.  mpst_sweep_batch_multi
-// prepares all its groups on the calling thread before any group runs: a capture in one thread is invalidated by another thread's
-// synchronous copies (the read-back of a group that has finished its sweep) - "operation failed due to a previous error during
-// capture", one run in a dozen when two groups captured side by side.
-static int sweep_batch_impl(void* const* ctxs, int32_t K, mpst_sweep_stats* out, int phase) {
-    if (!ctxs || K < 1 || K > 64) return fail(nullptr, MPST_ERR_INVALID, "mpst_sweep_batch: 1..64 contexts");
-    Ctx* c0 = (Ctx*)ctxs[0];
-    if (!c0) return MPST_ERR_INVALID;
-    if (hipSetDevice(c0->device) != hipSuccess) return fail(c0, MPST_ERR_DEVICE, "cannot select device %d", c0->device);
-    int rc;
-    for (int k = 0; k < K; ++k) {
-        Ctx* c = (Ctx*)ctxs[k];
-        if (!c) return fail(c0, MPST_ERR_INVALID, "context %d is NULL", k);
-        for (int j = 0; j < k; ++j)
-            if (ctxs[j] == ctxs[k]) return fail(c0, MPST_ERR_INVALID, "context %d appears twice", k);
-        if ((rc = check_ready(c))) {
-            if (c != c0) c0->err = c->err;
-            return rc;
-        }
-        if (!c->caches_valid) return fail(c0, MPST_ERR_INVALID, "context %d: call mpst_build_caches first", k);
-        if (c->host_label_site != c->T - 1) return fail(c0, MPST_ERR_INVALID, "context %d: a sweep starts with the label index on the last site", k);
-        if (!batchable(c))
-            return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_sweep_batch runs the headline chain only (Float64, d*chi_max <= 128, <= 8192 series, one rank, "
-                                                 "update_iters = 1, no track_cost / rebuild_caches / profiling)", k);
-        // the fits may differ in their series (N, class counts, tiles: every kernel reads those from the fit's own View, the grids are sized
-        // for the largest fit); whatever fixes an order of summation is either the context's (b2_ksplit, b2_nw, b2_norm_parts) or shared
-        const bool same = c->device == c0->device && c->T == c0->T && c->d == c0->d && c->C == c0->C && c->cap == c0->cap &&
-                          c->opt.loss == c0->opt.loss && c->opt.train_classes_separately == c0->opt.train_classes_separately &&
-                          c->opt.chi_max == c0->opt.chi_max && c->b2_ksplit == c0->b2_ksplit && (c->batch_hint > 1) == (c0->batch_hint > 1) && c->b2_norm_parts == c0->b2_norm_parts;
-        if (!same) return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs in shape from context 0 (T, d, C, capacity, chi_max, loss, gradient shares): batch fits of one shape", k);
-        HIPC(c0, hipStreamSynchronize(c->stream));
-    }
-    HIPC(c0, hipSetDevice(c0->device));
-    if (c0->batch_cap < K) {
-        dfree(&c0->batch_views);
-        if ((rc = dalloc(c0, &c0->batch_views, (int64_t)2 * K))) return rc;
-        c0->batch_cap = K;
-        c0->batch_key.clear();
-    }
-    std::vector<std::pair<uint64_t, uint64_t>> key;
-    for (int k = 0; k < K; ++k) key.push_back({((Ctx*)ctxs[k])->uid, ((Ctx*)ctxs[k])->epoch});
-    View v0 = make_view(c0, MPST_TRAIN);         // the launchers' geometry: the shared shape, and the tiles of the largest fit
-    for (int k = 1; k < K; ++k) v0.ntiles = std::max(v0.ntiles, ((Ctx*)ctxs[k])->ds[MPST_TRAIN].ntiles);
-    if (!c0->batch_graph || key != c0->batch_key) {
-        std::vector<View> hv((size_t)2 * c0->batch_cap);
-        for (int k = 0; k < K; ++k) {
-            Ctx* c = (Ctx*)ctxs[k];
-            hv[k] = make_view(c, MPST_TRAIN);
-            View vg = hv[k];                    // the Gram launch reads the loss pieces and the gradient-norm pieces k_grad_s left
-            vg.n_lossp = c->b2_ksplit;
-            vg.n_norm_part = c->b2_norm_parts;
-            hv[(size_t)c0->batch_cap + k] = vg;
-        }
-        c0->batch_key.clear();                  // the views the old graph reads are overwritten from here on
-        HIPC(c0, hipMemcpy(c0->batch_views, hv.data(), hv.size() * sizeof(View), hipMemcpyHostToDevice));
-        const View* dv = c0->batch_views;
-        const View* dvg = c0->batch_views + c0->batch_cap;
-        hipStream_t s = c0->stream;
-        auto enqueue_batch = [&]() -> int {
-            for (int k = 0; k < K; ++k) {
-                const hipError_t em = hipMemsetAsync((char*)((Ctx*)ctxs[k])->sc + offsetof(DevScalars, status), 0, 12, s);
-                if (em != hipSuccess) return fail(c0, MPST_ERR_DEVICE, "capture of the batched sweep failed: %s", hipGetErrorString(em));
-            }
-            const int nb = c0->T - 1;
-            bool have = false;
-            for (int q = 0; q < 2 * nb; ++q) {
-                const BondSlot b = bond_slot(q, nb);
-                const int lid = b.lid, left = b.going_left, rid = lid + 1, chain = b.chains_into_next ? 1 : 0;
-                if (!have) launch_bt_assemble_b(v0, dv, K, lid, s);
-                have = assembles_next(b, true);
-                launch_yhat_s_b(v0, dv, K, lid, s);
-                launch_grad_s_b(v0, dv, K, lid, s);
-                launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
-                launch_eig_b(v0, dv, K, lid, left, 0, s);
-                launch_eig_b(v0, dv, K, lid, left, 2, s);
-                // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
-                if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
-                else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
-            }
-            return 0;
-        };
-        if ((rc = capture_graph(c0, s, &c0->batch_graph, "capture of the batched sweep failed: %s", enqueue_batch))) return rc;
-        c0->batch_key = key;
-    }
-    if (phase == 1) return 0;
-    HIPC(c0, hipEventRecord(c0->ev_start, c0->stream));
-    HIPC(c0, hipGraphLaunch(c0->batch_graph, c0->stream));
-    HIPC(c0, hipEventRecord(c0->ev_stop, c0->stream));
-    HIPC(c0, hipEventSynchronize(c0->ev_stop));
-    HIPC(c0, hipGetLastError());
-    float ms = 0.f;
-    HIPC(c0, hipEventElapsedTime(&ms, c0->ev_start, c0->ev_stop));
-    int failed = -1;
-    for (int k = 0; k < K; ++k) {
-        DevScalars sc;
-        mpst_sweep_stats st{};
-        if ((rc = read_scalars((Ctx*)ctxs[k], c0, &sc)) || (rc = read_back((Ctx*)ctxs[k], c0, &sc, &st))) return rc;
-        st.seconds = 1e-3 * ms;                    // of the whole batch: the fits advance together
-        if (out) out[k] = st;
-        if (sc.status && failed < 0) failed = k;
-    }
-    if (failed >= 0) return fail(c0, MPST_ERR_SVD, "bond-tensor decomposition failed in fit %d of the batch (its svd_status is set; the other fits are intact)", failed);
-    return 0;
+int mpst_sweep_batch(void* const* ctxs, int32_t K, mpst_sweep_stats* out) {
+    const int rc = batch_prepare(ctxs, K);
+    return rc ? rc : batch_run(ctxs, K, out);
 }
-
-int mpst_sweep_batch(void* const* ctxs, int32_t K, mpst_sweep_stats* out) { return sweep_batch_impl(ctxs, K, out, 0); }
 
 // K fits dealt over several devices (or several groups on one device): every group is one mpst_sweep_batch on its own host
 // thread - no collective, nothing shared between groups.  What scales on a node: the sharded sweep replicates its eigensolver
@@ -1894,61 +1921,45 @@ int mpst_sweep_batch_multi(void* const* ctxs, int32_t K, const int32_t* group, m
     if (!ctxs || K < 1 || K > 512) return fail(nullptr, MPST_ERR_INVALID, "mpst_sweep_batch_multi: 1..512 contexts");
     for (int k = 0; k < K; ++k)
         if (!ctxs[k]) return fail(nullptr, MPST_ERR_INVALID, "context %d is NULL", k);
+    Ctx* c0 = (Ctx*)ctxs[0];
     // groups in order of first appearance; default: one group per device
-    std::vector<int> gid(K), keys;
-    for (int k = 0; k < K; ++k) {
-        const int key = group ? group[k] : ((Ctx*)ctxs[k])->device;
-        int g = -1;
-        for (size_t j = 0; j < keys.size(); ++j)
-            if (keys[j] == key) g = (int)j;
-        if (g < 0) {
-            keys.push_back(key);
-            g = (int)keys.size() - 1;
-        }
-        gid[k] = g;
-    }
-    const int G = (int)keys.size();
+    std::vector<int32_t> keys(K);
+    for (int k = 0; k < K; ++k) keys[k] = group ? group[k] : ((Ctx*)ctxs[k])->device;
+    BatchGroups gr;
+    const int too_large = plan_batch_groups(keys.data(), K, 64, &gr);
+    const int G = (int)gr.keys.size();
     std::vector<std::vector<void*>> members(G);
-    std::vector<std::vector<int>> index(G);
-    for (int k = 0; k < K; ++k) {
-        members[gid[k]].push_back(ctxs[k]);
-        index[gid[k]].push_back(k);
-    }
     for (int g = 0; g < G; ++g) {
-        if (members[g].size() > 64) return fail((Ctx*)ctxs[0], MPST_ERR_INVALID, "group %d holds %zu contexts (at most 64 per group)", keys[g], members[g].size());
+        for (int k : gr.index[g]) members[g].push_back(ctxs[k]);
+        if (g == too_large) return fail(c0, MPST_ERR_INVALID, "group %d holds %zu contexts (at most 64 per group)", gr.keys[g], members[g].size());
         for (void* m : members[g])
             if (((Ctx*)m)->device != ((Ctx*)members[g][0])->device)
-                return fail((Ctx*)ctxs[0], MPST_ERR_INVALID, "group %d mixes devices %d and %d: a group is one launch chain on one device", keys[g],
+                return fail(c0, MPST_ERR_INVALID, "group %d mixes devices %d and %d: a group is one launch chain on one device", gr.keys[g],
                             ((Ctx*)members[g][0])->device, ((Ctx*)m)->device);
     }
     // a context in two groups would be swept by two host threads at once, on one stream and one set of device scalars
     for (int k = 0; k < K; ++k)
         for (int j = 0; j < k; ++j)
-            if (ctxs[j] == ctxs[k]) return fail((Ctx*)ctxs[0], MPST_ERR_INVALID, "context %d appears twice", k);
+            if (ctxs[j] == ctxs[k]) return fail(c0, MPST_ERR_INVALID, "context %d appears twice", k);
+    // Every group's validation and graph capture here, on the calling thread, one after the other; the threads only replay and read
+    // back.  A capture in one thread is invalidated by another thread's synchronous copies (the read-back of a group that has
+    // finished its sweep) - "operation failed due to a previous error during capture", one run in a dozen when two groups captured
+    // side by side.
+    for (int g = 0; g < G; ++g)
+        if (int rc = batch_prepare(members[g].data(), (int32_t)members[g].size())) return forward_error(c0, (Ctx*)members[g][0], rc);
     std::vector<int> rc(G, 0);
     std::vector<std::vector<mpst_sweep_stats>> st(G);
-    // every group's validation and graph capture here, one after the other; the threads only replay
+    std::vector<std::thread> th;
     for (int g = 0; g < G; ++g) {
         st[g].resize(members[g].size());
-        if ((rc[g] = sweep_batch_impl(members[g].data(), (int32_t)members[g].size(), st[g].data(), 1))) {
-            Ctx* lead = (Ctx*)members[g][0];
-            if (lead != (Ctx*)ctxs[0]) ((Ctx*)ctxs[0])->err = lead->err;
-            return rc[g];
-        }
+        th.emplace_back([&, g] { rc[g] = batch_run(members[g].data(), (int32_t)members[g].size(), st[g].data()); });
     }
-    std::vector<std::thread> th;
-    for (int g = 0; g < G; ++g)
-        th.emplace_back([&, g] { rc[g] = sweep_batch_impl(members[g].data(), (int32_t)members[g].size(), st[g].data(), 2); });
     for (auto& t : th) t.join();
     if (out)
         for (int g = 0; g < G; ++g)
-            for (size_t j = 0; j < index[g].size(); ++j) out[index[g][j]] = st[g][j];
+            for (size_t j = 0; j < gr.index[g].size(); ++j) out[gr.index[g][j]] = st[g][j];
     for (int g = 0; g < G; ++g)
-        if (rc[g]) {
-            Ctx* lead = (Ctx*)members[g][0];
-            if (lead != (Ctx*)ctxs[0]) ((Ctx*)ctxs[0])->err = lead->err;      // errors are reported on ctxs[0]
-            return rc[g];
-        }
+        if (rc[g]) return forward_error(c0, (Ctx*)members[g][0], rc[g]);
     return 0;
 }
 
@@ -1969,7 +1980,7 @@ int mpst_get_loss_trace(void* ctx, double* out) {
     int rc = check_ready(c);
     if (rc) return rc;
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipMemcpy(out, c->loss_trace, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(out, c->ws.loss_trace, (size_t)2 * (c->T - 1) * (c->opt.update_iters + 1) * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1990,23 +2001,19 @@ int mpst_bond_step(void* ctx, int32_t lid, int32_t going_left, mpst_bond_debug* 
     HIPC(c, hipStreamSynchronize(c->stream));
     DevScalars sc;
     if ((rc = read_scalars(c, c, &sc))) return rc;
-    if (sc.redo > 0) {
-        // the tail launch of the four-launch chain left the bond alone (its verification failed): once more on the six-launch chain
-        c->tail_redos++;
-        Chain4Hold hold(c);
-        View v6 = make_view(c, MPST_TRAIN);
-        if ((rc = enqueue_reset_status(c))) return rc;
-        if ((rc = enqueue_bond(c, v6, b))) return rc;
-        HIPC(c, hipGetLastError());
-        HIPC(c, hipStreamSynchronize(c->stream));
-        if ((rc = read_scalars(c, c, &sc))) return rc;
+    if (sc.redo > 0) {          // the same bond again
+        rc = finish_marked(c, &sc, [&](const View& v6) {
+            const int r = enqueue_reset_status(c);
+            return r ? r : enqueue_bond(c, v6, b);
+        });
+        if (rc) return rc;
     }
     refresh_ss_counts(c);
     c->host_label_site = going_left ? lid : lid + 1;
     prof_collect(c);
     if (dbg) {
         std::vector<double> lam((size_t)std::max(sc.n_spec, 1));
-        HIPC(c, hipMemcpy(lam.data(), c->lam, lam.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(lam.data(), c->ws.lam, lam.size() * sizeof(double), hipMemcpyDeviceToHost));
         dbg->loss = sc.loss;
         dbg->grad_norm = sc.grad_norm;
         dbg->bt_norm = std::sqrt(sc.bt_norm2);
@@ -2025,28 +2032,22 @@ int mpst_bond_step(void* ctx, int32_t lid, int32_t going_left, mpst_bond_debug* 
 
 int mpst_eval(void* ctx, int which, double* mse, double* kld, double* acc, int64_t* conf) {
     Ctx* c = (Ctx*)ctx;
-    int rc = check_ready(c);
+    int rc = run_eval(c, which);
     if (rc) return rc;
-    if (which != 0 && which != 1) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
-    if ((rc = enqueue_eval(c, which))) return rc;
-    View v = make_view(c, which);
-    if (c->typed) launch_teval_reduce(make_tview(c, which), c->yeval, c->out3, c->conf, c->pred, c->stream);
-    else launch_eval_reduce(v, c->yeval, c->out3, c->conf, c->pred, c->stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipStreamSynchronize(c->stream));
+    const int64_t N = c->ds[which].N;
     double o[3];
-    HIPC(c, hipMemcpy(o, c->out3, sizeof o, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(o, c->ev.out3, sizeof o, hipMemcpyDeviceToHost));
     // multi-GPU: sums over shards
-    double tot[4] = {o[0], o[1], o[2], (double)v.N};
+    double tot[4] = {o[0], o[1], o[2], (double)N};
     std::vector<int64_t> cf((size_t)c->C * c->C);
-    HIPC(c, hipMemcpy(cf.data(), c->conf, cf.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(cf.data(), c->ev.conf, cf.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (multi(c)) {
         // sums over shards: the 4 scalars and the C x C counts (exact in fp64) travel as one message
         std::vector<double> msg(4 + cf.size());
         for (int i = 0; i < 4; ++i) msg[i] = tot[i];
         for (size_t i = 0; i < cf.size(); ++i) msg[4 + i] = (double)cf[i];
-        double* dmsg = c->yeval;                       // scratch of at least N*C >= ... doubles; the message is small
-        if ((int64_t)msg.size() > c->eval_N * c->C) return fail(c, MPST_ERR_INVALID, "evaluation scratch too small for the all-reduce message");
+        double* dmsg = c->ev.yeval;                       // scratch of at least N*C >= ... doubles; the message is small
+        if ((int64_t)msg.size() > c->ev.eval_N * c->C) return fail(c, MPST_ERR_INVALID, "evaluation scratch too small for the all-reduce message");
         HIPC(c, hipMemcpy(dmsg, msg.data(), msg.size() * sizeof(double), hipMemcpyHostToDevice));
         if ((rc = enqueue_allreduce(c, dmsg, (int64_t)msg.size(), -1))) return rc;
         HIPC(c, hipStreamSynchronize(c->stream));
@@ -2063,23 +2064,17 @@ int mpst_eval(void* ctx, int which, double* mse, double* kld, double* acc, int64
 
 int mpst_classify(void* ctx, int which, int32_t* pred, double* yhat) {
     Ctx* c = (Ctx*)ctx;
-    int rc = check_ready(c);
+    int rc = run_eval(c, which);
     if (rc) return rc;
-    if (which != 0 && which != 1) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
-    if ((rc = enqueue_eval(c, which))) return rc;
-    View v = make_view(c, which);
-    if (c->typed) launch_teval_reduce(make_tview(c, which), c->yeval, c->out3, c->conf, c->pred, c->stream);
-    else launch_eval_reduce(v, c->yeval, c->out3, c->conf, c->pred, c->stream);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (pred) HIPC(c, hipMemcpy(pred, c->pred, (size_t)v.N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int64_t N = c->ds[which].N;
+    if (pred) HIPC(c, hipMemcpy(pred, c->ev.pred, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (yhat) {
         if (c->typed && c->zw == 1) {           // the typed kernels keep (re, im) pairs: a real context returns the real parts
-            std::vector<double> tmp((size_t)v.N * c->C * 2);
-            HIPC(c, hipMemcpy(tmp.data(), c->yeval, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < (size_t)v.N * c->C; ++i) yhat[i] = tmp[2 * i];
+            std::vector<double> tmp((size_t)N * c->C * 2);
+            HIPC(c, hipMemcpy(tmp.data(), c->ev.yeval, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < (size_t)N * c->C; ++i) yhat[i] = tmp[2 * i];
         } else {
-            HIPC(c, hipMemcpy(yhat, c->yeval, (size_t)v.N * c->C * c->zw * sizeof(double), hipMemcpyDeviceToHost));
+            HIPC(c, hipMemcpy(yhat, c->ev.yeval, (size_t)N * c->C * c->zw * sizeof(double), hipMemcpyDeviceToHost));
         }
     }
     return 0;
@@ -2094,18 +2089,11 @@ int mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const*
     Ctx* c0 = (Ctx*)ctxs[0];
     if (!c0) return MPST_ERR_INVALID;
     if (which != 0 && which != 1) return fail(c0, MPST_ERR_INVALID, "which must be 0 or 1");
-    int rc;
     int64_t maxN = 0, totN = 0;
-    for (int k = 0; k < K; ++k) {
-        Ctx* c = (Ctx*)ctxs[k];
-        if (!c) return fail(c0, MPST_ERR_INVALID, "context %d is NULL", k);
-        if ((rc = check_ready(c))) {
-            if (c != c0) c0->err = c->err;
-            return rc;
-        }
+    int rc = batch_members(ctxs, K, [&](Ctx* c, int k) {
         if (c->typed || c->zw == 2 || multi(c))
             return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_classify_batch scores Float64 real fits on one rank (use mpst_classify)", k);
-        if (!score_walk_supported(c->T, c->d, c->cap, c->C))
+        if (!score_walk_supported(c->T, c->d, c->mps.cap, c->C))
             return fail(c0, MPST_ERR_UNSUPPORTED, "context %d: mpst_classify_batch needs d * capacity <= 128 and bond dimensions <= 64 (use mpst_classify)", k);
         if (c->device != c0->device || c->T != c0->T || c->d != c0->d || c->C != c0->C)
             return fail(c0, MPST_ERR_UNSUPPORTED, "context %d differs from context 0 in device, T, d or C: score such fits in separate calls", k);
@@ -2113,9 +2101,9 @@ int mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const*
         if (n <= 0) return fail(c0, MPST_ERR_INVALID, "context %d: data set %d is empty", k, which);
         maxN = std::max(maxN, n);
         totN += n;
-        HIPC(c0, hipStreamSynchronize(c->stream));
-    }
-    HIPC(c0, hipSetDevice(c0->device));
+        return 0;
+    });
+    if (rc) return rc;
     HIPC(c0, score_init_attrs());
     // one block: jobs | out3 [K][3] | conf [K][C][C] | yhat of every fit | pred of every fit
     const int C = c0->C;
@@ -2124,9 +2112,10 @@ int mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const*
     const size_t o_yhat = o_conf + (size_t)K * C * C * sizeof(int64_t);
     const size_t o_pred = o_yhat + (size_t)totN * C * sizeof(double);
     const size_t bytes = o_pred + (size_t)totN * sizeof(int32_t);
-    if (c0->score_cap < (int64_t)bytes) {
-        if ((rc = dalloc(c0, &c0->score_buf, (int64_t)bytes))) return rc;
-        c0->score_cap = (int64_t)bytes;
+    if (c0->lead.score_cap < (int64_t)bytes) {
+        c0->lead.score_cap = 0;
+        if ((rc = dalloc(c0, c0->lead.score_buf, (int64_t)bytes))) return rc;
+        c0->lead.score_cap = (int64_t)bytes;
     }
     std::vector<ScoreJob> jobs((size_t)K);
     std::vector<int64_t> first((size_t)K + 1, 0);
@@ -2136,20 +2125,20 @@ int mpst_classify_batch(void* const* ctxs, int32_t K, int which, int32_t* const*
         ScoreJob& j = jobs[k];
         j.T = c->T; j.d = c->d; j.C = c->C; j.pad = 0;
         j.N = s.N;
-        j.phi = s.phi; j.label = s.label; j.chi = c->chi; j.label_site = c->label_site;
-        j.sites = c->sites; j.site_stride = c->site_stride;
-        j.yhat = (double*)(c0->score_buf + o_yhat) + first[k] * C;
-        j.pred = (int32_t*)(c0->score_buf + o_pred) + first[k];
-        j.out3 = (double*)(c0->score_buf + o_out3) + 3 * k;
-        j.conf = (int64_t*)(c0->score_buf + o_conf) + (int64_t)k * C * C;
+        j.phi = s.phi; j.label = s.label; j.chi = c->mps.chi; j.label_site = c->mps.label_site;
+        j.sites = c->mps.sites; j.site_stride = c->mps.site_stride;
+        j.yhat = (double*)(c0->lead.score_buf + o_yhat) + first[k] * C;
+        j.pred = (int32_t*)(c0->lead.score_buf + o_pred) + first[k];
+        j.out3 = (double*)(c0->lead.score_buf + o_out3) + 3 * k;
+        j.conf = (int64_t*)(c0->lead.score_buf + o_conf) + (int64_t)k * C * C;
         first[k + 1] = first[k] + s.N;
     }
-    HIPC(c0, hipMemcpy(c0->score_buf, jobs.data(), jobs.size() * sizeof(ScoreJob), hipMemcpyHostToDevice));
-    launch_score_b((const ScoreJob*)c0->score_buf, K, maxN, c0->stream);
+    HIPC(c0, hipMemcpy(c0->lead.score_buf, jobs.data(), jobs.size() * sizeof(ScoreJob), hipMemcpyHostToDevice));
+    launch_score_b((const ScoreJob*)c0->lead.score_buf.h, K, maxN, c0->stream);
     HIPC(c0, hipGetLastError());
     HIPC(c0, hipStreamSynchronize(c0->stream));
     std::vector<uint8_t> host(bytes - o_out3);
-    HIPC(c0, hipMemcpy(host.data(), c0->score_buf + o_out3, host.size(), hipMemcpyDeviceToHost));
+    HIPC(c0, hipMemcpy(host.data(), c0->lead.score_buf + o_out3, host.size(), hipMemcpyDeviceToHost));
     const double* h3 = (const double*)host.data();
     const int64_t* hc = (const int64_t*)(host.data() + (o_conf - o_out3));
     const double* hy = (const double*)(host.data() + (o_yhat - o_out3));
@@ -2658,7 +2647,7 @@ static int impute_ctx(Ctx* c, int which, const ImputeRequest& r) {
     if (s.N <= 0) return fail(c, MPST_ERR_INVALID, "data set %d is empty", which);
     HIPC(c, hipSetDevice(c->device));
     const View v = make_view(c, which);
-    const ImpModel m{v.sites, v.site_stride, v.chi, v.label_site, v.phi, v.label, s.N, c->T, c->d, c->cap, c->zw == 2 ? 1 : 0,
+    const ImpModel m{v.sites, v.site_stride, v.chi, v.label_site, v.phi, v.label, s.N, c->T, c->d, c->mps.cap, c->zw == 2 ? 1 : 0,
                      (c->dtype == MPST_F32 || c->dtype == MPST_C64) ? 1 : 0};
     return run_impute(c, m, r);
 }
@@ -2883,11 +2872,11 @@ int mpst_normalize(void* ctx) {
     View v = make_view(c, MPST_TRAIN);
     if (c->typed) {
         TView t = make_tview(c, MPST_TRAIN);
-        launch_tnorm2(t, c->norm2, c->tnorm_scratch, c->stream);
-        launch_tscale_sites(t, c->norm2, c->stream);
+        launch_tnorm2(t, c->ws.norm2, c->ws.tnorm_scratch, c->stream);
+        launch_tscale_sites(t, c->ws.norm2, c->stream);
     } else {
-        launch_norm2(v, c->norm2, c->norm_scratch, c->stream);
-        launch_scale_sites(v, c->norm2, c->stream);
+        launch_norm2(v, c->ws.norm2, c->ws.norm_scratch, c->stream);
+        launch_scale_sites(v, c->ws.norm2, c->stream);
     }
     c->ynext_lid = -1;
     HIPC(c, hipGetLastError());
@@ -2920,21 +2909,21 @@ int mpst_get_info(void* ctx, int32_t* out) {
     int rc = check_ready(c);
     if (rc) return rc;
     const int pk = c->opt.loss == MPST_LOSS_MSE ? 1 : 0;
-    out[0] = c->fused ? 1 : 0;
-    out[1] = c->big ? 1 : 0;
+    out[0] = c->ws.fused ? 1 : 0;
+    out[1] = c->ws.big ? 1 : 0;
     out[2] = c->ds[MPST_TRAIN].nparts[pk];
     out[3] = c->ds[MPST_TRAIN].nchunks;
-    out[4] = c->cap;
+    out[4] = c->mps.cap;
     out[5] = c->nranks;
     out[6] = sweep_uses_graph(c) ? 1 : 0;
     out[7] = (int32_t)std::min<int64_t>(c->big_fallbacks, 1 << 30);
-    out[8] = blocked_eig_coop_aborts(c->blk);      // bonds the persistent tridiagonalisation handed back to the launch-per-step path
-    out[9] = blocked_eig_xcd_misplaced(c->blk);    // bonds whose XCD-local attempt found its workgroups on several XCDs (redone across the XCDs)
-    out[10] = c->b2 ? 1 : 0;                        // fused chain with the sliced bond GEMMs (k_yhat_s + k_grad_s)
-    out[11] = c->b2 ? c->b2_ksplit : 0;             // shares per gradient block of k_grad_s
-    out[12] = (!c->big && eig_merged()) ? 1 : 0;    // tridiagonalisation + eigenvectors in one launch (k_eig_trivec)
+    out[8] = blocked_eig_coop_aborts(c->ws.blk);      // bonds the persistent tridiagonalisation handed back to the launch-per-step path
+    out[9] = blocked_eig_xcd_misplaced(c->ws.blk);    // bonds whose XCD-local attempt found its workgroups on several XCDs (redone across the XCDs)
+    out[10] = c->ws.b2 ? 1 : 0;                        // fused chain with the sliced bond GEMMs (k_yhat_s + k_grad_s)
+    out[11] = c->ws.b2 ? c->ws.b2_ksplit : 0;             // shares per gradient block of k_grad_s
+    out[12] = (!c->ws.big && eig_merged()) ? 1 : 0;    // tridiagonalisation + eigenvectors in one launch (k_eig_trivec)
     out[13] = c->big_redos;                          // large-bond sweeps redone bond by bond after a failed verdict
-    out[14] = (c->big_opt && !multi(c)) ? 1 : 0;                   // large bonds: the eigensolver's verdict is read once per sweep
+    out[14] = (c->ws.big_opt && !multi(c)) ? 1 : 0;                   // large bonds: the eigensolver's verdict is read once per sweep
     out[15] = c->typed ? 1 + c->dtype : 0;        // element-typed kernels in use: 1 + dtype
     return 0;
 }
@@ -2961,11 +2950,11 @@ int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
 
 int mpst_get_eig_phases(void* ctx, double* us) {
     Ctx* c = (Ctx*)ctx;
-    if (!c || !c->sc || !us) return MPST_ERR_INVALID;
+    if (!c || !c->ws.sc || !us) return MPST_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     DevScalars sc;
-    HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&sc, c->ws.sc, sizeof sc, hipMemcpyDeviceToHost));
     const unsigned long long* t = sc.eig_stamps;              // 100 MHz ticks
     us[0] = 0.01 * (double)(t[1] - t[0]);                     // k_eig_tri: tridiagonalisation
     us[1] = 0.01 * (double)(t[3] - t[2]);                     // k_eig_vec block 0: staging + bisection
@@ -2980,11 +2969,11 @@ int mpst_get_eig_phases(void* ctx, double* us) {
 // hosts a job of the next bond's tensor when the sweep goes on), us[16..31] the last workgroup (no role) (see include/mpstime_hip.h)
 int mpst_get_tail_phases(void* ctx, double* us) {
     Ctx* c = (Ctx*)ctx;
-    if (!c || !c->sc || !us) return MPST_ERR_INVALID;
+    if (!c || !c->ws.sc || !us) return MPST_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     DevScalars sc;
-    HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&sc, c->ws.sc, sizeof sc, hipMemcpyDeviceToHost));
     const unsigned long long* t = sc.eig_stamps;
     const double t0 = (double)t[16];
     // workgroup 0: slots 16..31; the last workgroup: 32..47
@@ -3000,9 +2989,9 @@ int mpst_get_tail_phases(void* ctx, double* us) {
     us[52] = us[53] = us[54] = 0.0;
     {
         const size_t ng = (size_t)std::min<unsigned long long>(t[60], 2048ull);
-        if (ng > 0 && c->tail_span) {
+        if (ng > 0 && c->ws.tail_span) {
             std::vector<unsigned long long> sp(2 * ng);
-            HIPC(c, hipMemcpy(sp.data(), c->tail_span, sp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            HIPC(c, hipMemcpy(sp.data(), c->ws.tail_span, sp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             unsigned long long s0 = ~0ull, s1 = 0ull, e1 = 0ull;
             for (size_t i = 0; i < ng; ++i) {
                 s0 = std::min(s0, sp[2 * i]);
@@ -3021,10 +3010,10 @@ int mpst_get_tail_phases(void* ctx, double* us) {
 // bring-up builds only (scratch/build_dbg.sh): stamps of the sliced bond kernels, 8192 x 8 slots
 int mpst_debug_b2(void* ctx, unsigned long long* out) {
     Ctx* c = (Ctx*)ctx;
-    if (!c || !c->b2_dbg || !out) return MPST_ERR_INVALID;
+    if (!c || !c->ws.b2_dbg || !out) return MPST_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipMemcpy(out, c->b2_dbg, 8192 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(out, c->ws.b2_dbg, 8192 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -3034,11 +3023,11 @@ int mpst_debug_b2(void* ctx, unsigned long long* out) {
 // bring-up builds only (-DMPST_TRI_DEBUG): raw stamp slots of the eigensolver kernels
 int mpst_debug_stamps(void* ctx, unsigned long long* out64) {
     Ctx* c = (Ctx*)ctx;
-    if (!c || !c->sc || !out64) return MPST_ERR_INVALID;
+    if (!c || !c->ws.sc || !out64) return MPST_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     DevScalars sc;
-    HIPC(c, hipMemcpy(&sc, c->sc, sizeof sc, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&sc, c->ws.sc, sizeof sc, hipMemcpyDeviceToHost));
     for (int i = 0; i < 64; ++i) out64[i] = sc.eig_stamps[i];
     return 0;
 }
@@ -3048,10 +3037,9 @@ int mpst_selftest_mfma(void* ctx, const double* A, const double* B, int32_t K, d
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-    struct Temps { double **a, **b, **cc; ~Temps() { dfree(a); dfree(b); dfree(cc); } } temps{&dA, &dB, &dC};
+    DevBuf<double> dA, dB, dC;
     int rc;
-    if ((rc = dalloc(c, &dA, 16 * K)) || (rc = dalloc(c, &dB, 16 * K)) || (rc = dalloc(c, &dC, 256))) return rc;
+    if ((rc = dalloc(c, dA, 16 * K)) || (rc = dalloc(c, dB, 16 * K)) || (rc = dalloc(c, dC, 256))) return rc;
     HIPC(c, hipMemcpy(dA, A, (size_t)16 * K * sizeof(double), hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(dB, B, (size_t)16 * K * sizeof(double), hipMemcpyHostToDevice));
     launch_selftest_mfma(dA, dB, K, dC, c->stream);
@@ -3066,15 +3054,13 @@ int mpst_selftest_eig(void* ctx, const double* G, int32_t n, int32_t alg, double
     if (!c) return MPST_ERR_INVALID;
     if (n < 1 || n > DIM_LIMIT) return fail(c, MPST_ERR_INVALID, "n must be in 1..%d", DIM_LIMIT);
     HIPC(c, hipSetDevice(c->device));
-    double *dG = nullptr, *dl = nullptr, *dE = nullptr, *dws = nullptr;
-    int32_t* ds = nullptr;
-    struct Temps { double **a, **b, **cc, **d; int32_t** e; ~Temps() { dfree(a); dfree(b); dfree(cc); dfree(d); dfree(e); } }
-        temps{&dG, &dl, &dE, &dws, &ds};
+    DevBuf<double> dG, dl, dE, dws;
+    DevBuf<int32_t> ds;
     hipError_t ea = eig_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
     int rc;
-    if ((rc = dalloc(c, &dG, n * n)) || (rc = dalloc(c, &dl, n)) || (rc = dalloc(c, &dE, n * n)) || (rc = dalloc(c, &ds, 1)) ||
-        (rc = dalloc(c, &dws, (int64_t)eig_workspace_doubles()))) return rc;
+    if ((rc = dalloc(c, dG, n * n)) || (rc = dalloc(c, dl, n)) || (rc = dalloc(c, dE, n * n)) || (rc = dalloc(c, ds, 1)) ||
+        (rc = dalloc(c, dws, (int64_t)eig_workspace_doubles()))) return rc;
     HIPC(c, hipMemcpy(dG, G, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
     HIPC(c, hipMemset(dws, 0, eig_workspace_doubles() * sizeof(double)));
     if (n > MAX_DIM) {

@@ -245,7 +245,8 @@ def test_blocked_tridiagonalisation_is_deterministic(eng):
 def test_sweep_reads_the_verdict_once_and_redoes_a_failed_sweep(engine_cls, dtype):
     """Large bonds: mpst_sweep no longer synchronises with the host after every bond to read the eigensolver's verdict - it
     reads a sticky word once per sweep and, if any bond failed, redoes the sweep from a snapshot bond by bond (with the
-    library fallback).  MPST_BIG_FORCE_FAIL marks one solve as failed: the redone sweep, and the sweep after it, must give
+    library fallback).  MPST_BIG_FORCE_FAIL=n marks the n-th solve of the training workspace as failed (the count restarts, and the variable is read
+    again, whenever the workspace is rebuilt): the redone sweep, and the sweep after it, must give
     the bits of a context that reads the verdict after every bond (MPST_BIG_SYNC=1).  float64 goes through the real reduction on
     one XCD; complex128 (one class, complex order 160, subspace block 64) through the Hermitian reduction from both launchers,
     the complex subspace sequence and its Rayleigh-Ritz launch."""

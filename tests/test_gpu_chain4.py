@@ -37,10 +37,10 @@ class _env:
                 os.environ[k] = v
 
 
-def _fresh(ds, W, chi, eta=0.05, **env):
+def _fresh(ds, W, chi, eta=0.05, options=None, **env):
     with _env(**env):
         eng = mt.SweepEngine(0)
-        eng.set_options(chi_max=chi, eta=eta, cutoff=1e-10)
+        eng.set_options(chi_max=chi, eta=eta, cutoff=1e-10, **(options or {}))
         eng.set_dataset(0, ds.phi, ds.label_index, len(ds.class_distribution))
         eng.set_mps(W)
         eng.build_caches()
@@ -155,6 +155,34 @@ def test_failed_tail_verification_is_recovered_on_the_six_launch_chain():
         assert bad.info()["tail_redos"] == 1
         ya, yb = R.contract_mps(ref.get_mps(), ds.phi), R.contract_mps(bad.get_mps(), ds.phi)
         assert np.abs(ya - yb).max() < 1e-8 * np.abs(ya).max()
+    finally:
+        bad.close()
+        ref.close()
+
+
+@pytest.mark.parametrize("n_fail", [7, 20])
+def test_failed_tail_verification_is_recovered_with_the_caches_rebuilt(n_fail):
+    """The recovery of a marked sweep in the benchmarked configuration, rebuild_caches=True (construct_caches after either half,
+    RealRealHighDimension.jl:770, :804): the rest of the sweep that is redone on the six-launch chain rebuilds the caches where the
+    undisturbed sweep does.  One forced failure in the leftward half (tail launch 7 of 26) and one in the rightward half (20), each
+    against an undisturbed sweep with the same options: bond dimensions, one redo, one fallback, overlaps to 1e-7 of the largest
+    (the bound of the test above: one sweep amplifies the rounding-level difference between the two chains), equal accuracy."""
+    ds, W = make_problem(256, 14, 4, 4, 2, seed=21)
+    ref = _fresh(ds, W, 12, options={"rebuild_caches": True})
+    bad = _fresh(ds, W, 12, options={"rebuild_caches": True}, MPST_TAIL_FORCE_REDO=n_fail)
+    try:
+        assert ref.info()["four_launch_chain"] and bad.info()["four_launch_chain"]
+        ref.sweep()
+        st = bad.sweep()
+        assert ref.info()["tail_redos"] == 0
+        assert bad.info()["tail_redos"] == 1, bad.info()
+        assert st["eig_fallbacks"] == 1
+        assert np.array_equal(ref.get_chi()[0], bad.get_chi()[0])
+        ya, yb = R.contract_mps(ref.get_mps(), ds.phi), R.contract_mps(bad.get_mps(), ds.phi)
+        dev = np.abs(ya - yb).max() / np.abs(ya).max()
+        print(f"forced failure at tail launch {n_fail}: overlaps differ by {dev:.3e} of the largest")
+        assert dev < 1e-7, (n_fail, dev)
+        assert ref.eval(0)[2] == bad.eval(0)[2]
     finally:
         bad.close()
         ref.close()

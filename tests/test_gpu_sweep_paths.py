@@ -212,8 +212,10 @@ def test_workspace_rebuilt_on_a_live_context_equals_a_fresh_one():
     """ensure_workspace tears a training workspace down and builds another on a live context whenever the capacity or the options
     that size it change.  One engine is taken through (a) capacity 8, d*cap = 64: fused chain, sliced pair, four launches per bond;
     (b) an MPS of bonds 20, d*cap = 160 > 128: the large-bond solver is created; (c) the first MPS again: the solver is destroyed;
-    (d) rescale = (True, True): the unfused chain.  After every stage one sweep must give the bits - and info() the chain - of a fresh
-    engine that was given only that stage's options and MPS.  Then a -> b -> c in float32 (the element-typed workspace).
+    (d) rescale = (True, True): the unfused chain; (e) stage a's options again: the sliced, four-launch chain with fresh tickets and
+    tail buffers; (f) set_batch_hint(4): six launches per bond, other gradient shares; (g) hint 1 again.  After every stage one sweep
+    must give the bits - and info() the chain - of a fresh engine that was given only that stage's options, hint and MPS.  Then
+    a -> b -> c in float32 (the element-typed workspace).
     N = 96, T = 5, d = 8, C = 2, KLD / TSGO: the shape of test_sweep_reads_the_verdict_once_and_redoes_a_failed_sweep."""
     from tests.helpers import make_problem
     N, T, d, C, chi = 96, 5, 8, 2, 8
@@ -221,7 +223,9 @@ def test_workspace_rebuilt_on_a_live_context_equals_a_fresh_one():
     _, W20 = make_problem(N, T, d, 20, C, seed=3)
     keys = ("fused", "large_bond", "four_launch_chain", "large_bond_verdict_per_sweep", "sliced_bond_gemms")
     expect = {"a": (True, False, True, False, True), "b": (False, True, False, True, False), "c": (True, False, True, False, True),
-              "d": (False, False, False, False, False)}
+              "d": (False, False, False, False, False), "e": (True, False, True, False, True), "f": (True, False, False, False, True),
+              "g": (True, False, True, False, True)}
+    hint = {"f": 4, "g": 1}
 
     def options(eng, stage):
         eng.set_options(chi_max=chi, eta=0.05, loss="KLD", bbopt="TSGO", rescale=(stage == "d", True))
@@ -231,18 +235,21 @@ def test_workspace_rebuilt_on_a_live_context_equals_a_fresh_one():
         eng.sweep()
         return eng.get_mps(), eng.get_chi(), {k: eng.info()[k] for k in keys}
 
-    for dt, stages in ((np.dtype("float64"), "abcd"), (np.dtype("float32"), "abc")):
+    for dt, stages in ((np.dtype("float64"), "abcdefg"), (np.dtype("float32"), "abc")):
         live = mt.SweepEngine(0)
         try:
             options(live, "a")
             live.set_dataset(0, ds.phi.astype(dt), ds.label_index, C, dtype=dt)
             for stage in stages:
                 W = W20 if stage == "b" else W4
-                if stage == "d":
+                if stage in "de":
                     options(live, stage)
+                if stage in hint:
+                    live.set_batch_hint(hint[stage])
                 live.set_mps(W)
                 fresh = mt.SweepEngine(0)
                 try:
+                    fresh.set_batch_hint(hint.get(stage, 1))
                     options(fresh, stage)
                     fresh.set_dataset(0, ds.phi.astype(dt), ds.label_index, C, dtype=dt)
                     fresh.set_mps(W)

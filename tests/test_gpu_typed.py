@@ -163,6 +163,37 @@ def test_free_running_sweeps_and_evaluation(dtype):
         eng.close()
 
 
+@pytest.mark.parametrize("dtype", ["float64", "float32", "complex128"])
+def test_evaluation_agrees_with_classification(dtype):
+    """mpst_eval and mpst_classify walk one chain and run one reduction: after one sweep, the accuracy and the confusion matrix
+    (truth x prediction) eval(which) returns equal, exactly, the ones recomputed on the host from classify(which)'s predictions and
+    the labels, on either data set; two eval calls return equal bits.  N = 96, T = 5, d = 4, C = 2, capacity 4."""
+    import mpstime_jl_amd as mt
+    N, C = 96, 2
+    ds, W = problem(N, 5, 4, 4, C, 9, DT[dtype])
+    labels = [np.asarray(ds.label_index), np.asarray(ds.label_index[::3])]
+    eng = mt.SweepEngine(0)
+    try:
+        eng.set_options(chi_max=4, eta=0.05)
+        eng.set_dataset(0, ds.phi.astype(DT[dtype]), labels[0], C)
+        eng.set_dataset(1, ds.phi[::3].astype(DT[dtype]), labels[1], C)
+        eng.set_mps([t.astype(DT[dtype]) for t in W])
+        eng.build_caches()
+        eng.sweep()
+        assert eng.info()["cap"] == 4
+        for which in (0, 1):
+            first, second = eng.eval(which), eng.eval(which)
+            assert first[:3] == second[:3] and np.array_equal(first[3], second[3])
+            pred = eng.classify(which)
+            y = labels[which]
+            conf = np.zeros((C, C), dtype=np.int64)
+            np.add.at(conf, (y, pred), 1)
+            assert first[2] == np.count_nonzero(pred == y) / len(y), (which, first[2])
+            assert np.array_equal(first[3], conf), (which, first[3], conf)
+    finally:
+        eng.close()
+
+
 def test_real_encoding_needs_no_complex_type_but_complex_encoding_does():
     import mpstime_jl_amd as mt
     eng = mt.SweepEngine(0)
