@@ -15,6 +15,7 @@
 #include <thread>
 #include "mpst_internal.h"
 #include "mpst_batch_groups.h"
+#include "mpst_bond_plan.h"
 
 using namespace mpst;
 
@@ -332,8 +333,6 @@ View make_view(Ctx* c, int which) {
     }
     return v;
 }
-
-inline double* eoff(Ctx* c, double* base, int64_t elems) { return (double*)((char*)base + (size_t)elems * c->esz); }
 
 TView make_tview(Ctx* c, int which) {
     TView t{};
@@ -658,12 +657,36 @@ int enqueue_big_eig(Ctx* c, const View& v, int lid, int going_left) {
     if (need_lib && launch_eig_big(v, lid, going_left, c->ws.big, s)) return fail(c, MPST_ERR_DEVICE, "the large-bond Jacobi fallback could not be launched at bond %d", lid);
     return 0;
 }
+// the eigensolver of bond lid on the Gram matrix of v: the large-bond route, or stage 0 (tri, or tri + vec merged), 1 (vec), 2 (fin)
+int enqueue_eig(Ctx* c, const View& v, int lid, int going_left) {
+    if (c->ws.big) {
+        ProfScope p(c, K_EIG_TRI);
+        return enqueue_big_eig(c, v, lid, going_left);
+    }
+    { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, c->stream); }
+    if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(v, lid, going_left, 1, c->stream); }
+    { ProfScope p(c, K_EIG_FIN); launch_eig(v, lid, going_left, 2, c->stream); }
+    return 0;
+}
+// one environment step (mpst_bond_plan.h) as a launch: k_tenv (the site tensor is the map, the rows' exponents alongside) or k_env
+void launch_tenv_step(Ctx* c, const TView& t, const EnvStep& e) {
+    const int64_t cs = (int64_t)t.N * t.cap;
+    double* rows = e.left_side ? c->ws.LE : c->ws.RE;
+    int32_t* x = e.left_side ? c->ws.xLE : c->ws.xRE;
+    launch_tenv(t, e.site, e.left_side, env_row_e(rows, e.prev_site, cs, c->esz), env_row(x, e.prev_site, t.N), e.prev_bond,
+                e.left_side ? ENV_M_SITE : ENV_M_SITE_T, e.out_bond, env_row_e(rows, e.out_site, cs, c->esz), env_row(x, e.out_site, t.N), c->stream);
+}
+void launch_env_step(Ctx* c, const View& v, const EnvStep& e, int mode, int bt_lid = -1) {
+    const int64_t cs = (int64_t)v.N * v.cap;
+    double* rows = e.left_side ? v.LE : v.RE;
+    launch_env(v, e.site, e.left_side, env_row(rows, e.prev_site, cs), e.prev_bond, mode, e.out_bond, env_row(rows, e.out_site, cs), c->stream, bt_lid);
+}
 
 // ---- the per-bond chain of the element-typed sweep (mpst_typed.hip) -----------------------------------------------------
 int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
     hipStream_t s = c->stream;
     TView t = make_tview(c, MPST_TRAIN);
-    const int n_it = c->opt.update_iters, rid = lid + 1;
+    const int n_it = c->opt.update_iters;
     if (c->opt.track_cost && trace_row >= 0) t.trace = c->ws.loss_trace + (int64_t)trace_row * (n_it + 1);
     { ProfScope p(c, K_BT); launch_tbt_assemble(t, lid, s); }                    // flatten_bt
     if (t.rescale_before) launch_tbt_prescale(t, lid, s);
@@ -681,16 +704,7 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
         { ProfScope p(c, K_UPDATE); launch_tupdate(t, lid, it == 0, s); }
     }
     { ProfScope p(c, K_GRAM); launch_tgram(t, lid, going_left, s); }             // decomposeBT: Gram matrix, fp64
-    const View ve = make_eig_view(c);
-    if (c->ws.big) {
-        ProfScope p(c, K_EIG_TRI);
-        int rc = enqueue_big_eig(c, ve, lid, going_left);
-        if (rc) return rc;
-    } else {
-        { ProfScope p(c, K_EIG_TRI); launch_eig(ve, lid, going_left, 0, s); }
-        if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(ve, lid, going_left, 1, s); }
-        { ProfScope p(c, K_EIG_FIN); launch_eig(ve, lid, going_left, 2, s); }
-    }
+    if (int rc = enqueue_eig(c, make_eig_view(c), lid, going_left)) return rc;
     if (t.trace) {          // track_cost: the loss at the updated (and, with rescale[2], normalised) bond tensor
         TView ty = t;
         ty.yhat_scaled = t.rescale_after;
@@ -705,50 +719,16 @@ int enqueue_bond_typed(Ctx* c, int lid, int going_left, int trace_row) {
         }
     }
     { ProfScope p(c, K_SPLIT); launch_tsplit(t, lid, going_left, s); }
-    {
-        ProfScope p(c, K_ENV);                                                   // update_caches!: the new site tensor is the map
-        const int64_t cs = (int64_t)t.N * t.cap;
-        if (going_left)
-            launch_tenv(t, rid, 0, rid < c->T - 1 ? eoff(c, c->ws.RE, (int64_t)(rid + 1) * cs) : nullptr, rid < c->T - 1 ? c->ws.xRE + (int64_t)(rid + 1) * t.N : nullptr, rid + 1,
-                        ENV_M_SITE_T, rid, eoff(c, c->ws.RE, (int64_t)rid * cs), c->ws.xRE + (int64_t)rid * t.N, s);
-        else
-            launch_tenv(t, lid, 1, lid > 0 ? eoff(c, c->ws.LE, (int64_t)(lid - 1) * cs) : nullptr, lid > 0 ? c->ws.xLE + (int64_t)(lid - 1) * t.N : nullptr, lid, ENV_M_SITE, lid + 1,
-                        eoff(c, c->ws.LE, (int64_t)lid * cs), c->ws.xLE + (int64_t)lid * t.N, s);
-    }
+    { ProfScope p(c, K_ENV); launch_tenv_step(c, t, env_step_of_bond(lid, going_left, c->T)); }     // update_caches!: the new site tensor is the map
     return 0;
 }
 // construct_caches of the typed context: left environments of sites [0, upto), right environments of sites (from, T-1]
 void enqueue_caches_typed(Ctx* c, int left_upto, int right_from) {
     TView t = make_tview(c, MPST_TRAIN);
-    const int64_t cs = (int64_t)t.N * t.cap;
     ProfScope p(c, K_ENV);
-    for (int j = 0; j < left_upto && j <= c->T - 2; ++j)
-        launch_tenv(t, j, 1, j > 0 ? eoff(c, c->ws.LE, (int64_t)(j - 1) * cs) : nullptr, j > 0 ? c->ws.xLE + (int64_t)(j - 1) * t.N : nullptr, j, ENV_M_SITE, j + 1,
-                    eoff(c, c->ws.LE, (int64_t)j * cs), c->ws.xLE + (int64_t)j * t.N, c->stream);
-    for (int j = c->T - 1; j > right_from && j >= 1; --j)
-        launch_tenv(t, j, 0, j < c->T - 1 ? eoff(c, c->ws.RE, (int64_t)(j + 1) * cs) : nullptr, j < c->T - 1 ? c->ws.xRE + (int64_t)(j + 1) * t.N : nullptr, j + 1, ENV_M_SITE_T, j,
-                    eoff(c, c->ws.RE, (int64_t)j * cs), c->ws.xRE + (int64_t)j * t.N, c->stream);
+    for (int j = 0; j < left_upto && j <= c->T - 2; ++j) launch_tenv_step(c, t, env_step(j, 1, c->T));
+    for (int j = c->T - 1; j > right_from && j >= 1; --j) launch_tenv_step(c, t, env_step(j, 0, c->T));
 }
-
-// ---- bond order of one sweep (RealRealHighDimension.jl:731, :776) -------------------------------------------------------
-// Slot k of a sweep over nb = T - 1 bonds: nb - 1 .. 0 going left, then 0 .. nb - 1 going right.  next_lid: the bond of slot
-// k + 1, whose tensor this bond's last launch may assemble (-1: none, or the caller took it away - `unchained`: the tensor is
-// rescaled first, or the caches are rebuilt in between); chains_into_next: that bond is the neighbour in the direction of travel
-// (everywhere but at the turning point, where the same bond comes again) - the fused chains hand a tensor on only then.
-struct BondSlot {
-    int lid, going_left, next_lid;
-    bool chains_into_next;
-    BondSlot unchained() const { return {lid, going_left, -1, false}; }
-};
-BondSlot bond_slot(int k, int nb) {
-    auto at = [nb](int q) { return q < nb ? nb - 1 - q : q - nb; };
-    BondSlot b{at(k), k < nb, k + 1 < 2 * nb ? at(k + 1) : -1, false};
-    b.chains_into_next = b.next_lid >= 0 && b.next_lid == (b.going_left ? b.lid - 1 : b.lid + 1);
-    return b;
-}
-// have_bt of the slot after `prev` (the caller's: it knows where it started and what it took away): the tensor is there iff the
-// launches enqueued for `prev`, in this call, were told to assemble it
-inline bool assembles_next(const BondSlot& prev, bool fused) { return fused ? prev.chains_into_next : prev.next_lid >= 0; }
 
 // ---- the chain decisions, each taken and reported (mpst_get_info) through one predicate ------------------------------------
 // The 2(T-1) x 11 launches of a sweep are replayed from a hipGraph: nothing in the sequence depends
@@ -797,7 +777,6 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         if (multi(c)) return enqueue_allreduce(c, vy.trace + n_it, 1, -1);
         return 0;
     };
-    const int rid = lid + 1;
     const uint64_t seq_before = c->bond_seq++;
     if (c->ws.fused) {
         const int iters = c->opt.update_iters;
@@ -842,8 +821,8 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             if (!use4) vg.btnT = nullptr;
             launch_gram_upd(vg, lid, going_left, iters == 1, s);
         }
-        { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s); }
         if (use4) {
+            { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s); }
             ProfScope p(c, K_ENV);                                                // verification, back-split, update_caches!, next yhat
             const int nxt = going_left ? lid - 1 : lid + 1;
             const int want = (nxt >= 0 && nxt <= c->T - 2) ? 1 : 0;
@@ -855,19 +834,9 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             }
             return 0;
         }
-        if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(v, lid, going_left, 1, s); }
-        { ProfScope p(c, K_EIG_FIN); launch_eig(v, lid, going_left, 2, s); }
+        if (int rc = enqueue_eig(c, v, lid, going_left)) return rc;
         { int rc = trace_final(c->ws.btn); if (rc) return rc; }
-        {
-            ProfScope p(c, K_ENV);                                                // back-split + update_caches! :759/:799
-            const int64_t cs = (int64_t)v.N * v.cap;
-            if (going_left)
-                launch_env_split(v, lid, 1, rid, 0, rid < c->T - 1 ? c->ws.RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, rid,
-                                 c->ws.RE + (int64_t)rid * cs, chain, s);
-            else
-                launch_env_split(v, lid, 0, lid, 1, lid > 0 ? c->ws.LE + (int64_t)(lid - 1) * cs : nullptr, lid, lid + 1,
-                                 c->ws.LE + (int64_t)lid * cs, chain, s);
-        }
+        { ProfScope p(c, K_ENV); launch_env_split(v, lid, going_left, chain, s); }      // back-split + update_caches! :759/:799
         return 0;
     }
     if (!have_bt) { ProfScope p(c, K_BT); launch_bt_assemble(v, lid, s); }      // flatten_bt :733/:777
@@ -885,27 +854,10 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
         { ProfScope p(c, K_UPDATE); launch_update(v, lid, it == 0, s); }
     }
     { ProfScope p(c, K_GRAM); launch_gram(v, lid, going_left, s); }            // decomposeBT :756/:798
-    if (c->ws.big) {
-        ProfScope p(c, K_EIG_TRI);
-        int rc = enqueue_big_eig(c, v, lid, going_left);
-        if (rc) return rc;
-    } else {
-        { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s); }
-        if (!eig_merged()) { ProfScope p(c, K_EIG_VEC); launch_eig(v, lid, going_left, 1, s); }
-        { ProfScope p(c, K_EIG_FIN); launch_eig(v, lid, going_left, 2, s); }
-    }
+    if (int rc = enqueue_eig(c, v, lid, going_left)) return rc;
     { int rc = trace_final(c->ws.bt); if (rc) return rc; }
     { ProfScope p(c, K_SPLIT); launch_split(v, lid, going_left, s); }
-    {
-        ProfScope p(c, K_ENV);                                                  // update_caches! :759/:799
-        const int64_t cs = (int64_t)v.N * v.cap;
-        if (going_left)
-            launch_env(v, rid, 0, rid < c->T - 1 ? c->ws.RE + (int64_t)(rid + 1) * cs : nullptr, rid + 1, ENV_M_E, rid,
-                       c->ws.RE + (int64_t)rid * cs, s, next_bt_lid);
-        else
-            launch_env(v, lid, 1, lid > 0 ? c->ws.LE + (int64_t)(lid - 1) * cs : nullptr, lid, ENV_M_E, lid + 1,
-                       c->ws.LE + (int64_t)lid * cs, s, next_bt_lid);
-    }
+    { ProfScope p(c, K_ENV); launch_env_step(c, v, env_step_of_bond(lid, going_left, c->T), ENV_M_E, next_bt_lid); }      // update_caches! :759/:799
     return 0;
 }
 
@@ -920,17 +872,14 @@ bool env_walk_on(const Ctx* c, const View& v) {
 // its 16 series (k_env_walk: the bits of the per-site launches; a side without sites launches nothing), else one per site.
 void enqueue_caches(Ctx* c, const View& v, int ls) {
     if (c->typed) return enqueue_caches_typed(c, ls, ls);
-    const int64_t cs = (int64_t)v.N * v.cap;
     ProfScope p(c, K_ENV);
     if (env_walk_on(c, v)) {
         launch_env_walk(v, 1, std::min(ls, c->T - 1), c->stream);
         launch_env_walk(v, 0, c->T - 1 - ls, c->stream);
         return;
     }
-    for (int j = 0; j < ls && j <= c->T - 2; ++j)
-        launch_env(v, j, 1, j > 0 ? v.LE + (int64_t)(j - 1) * cs : nullptr, j, ENV_M_SITE, j + 1, v.LE + (int64_t)j * cs, c->stream);
-    for (int j = c->T - 1; j > ls && j >= 1; --j)
-        launch_env(v, j, 0, j < c->T - 1 ? v.RE + (int64_t)(j + 1) * cs : nullptr, j + 1, ENV_M_SITE_T, j, v.RE + (int64_t)j * cs, c->stream);
+    for (int j = 0; j < ls && j <= c->T - 2; ++j) launch_env_step(c, v, env_step(j, 1, c->T), ENV_M_SITE);
+    for (int j = c->T - 1; j > ls && j >= 1; --j) launch_env_step(c, v, env_step(j, 0, c->T), ENV_M_SITE_T);
 }
 
 // ---- a sweep as a hipGraph, and what it left ----------------------------------------------------------------------------------
@@ -1194,7 +1143,7 @@ int batch_prepare(void* const* ctxs, int32_t K) {
         bool have = false;
         for (int q = 0; q < 2 * nb; ++q) {
             const BondSlot bs = bond_slot(q, nb);
-            const int lid = bs.lid, left = bs.going_left, rid = lid + 1, chain = bs.chains_into_next ? 1 : 0;
+            const int lid = bs.lid, left = bs.going_left, chain = bs.chains_into_next ? 1 : 0;
             if (!have) launch_bt_assemble_b(v0, dv, K, lid, s);
             have = assembles_next(bs, true);
             launch_yhat_s_b(v0, dv, K, lid, s);
@@ -1202,9 +1151,7 @@ int batch_prepare(void* const* ctxs, int32_t K) {
             launch_gram_upd_b(v0, dvg, K, lid, left, 1, s);
             launch_eig_b(v0, dv, K, lid, left, 0, s);
             launch_eig_b(v0, dv, K, lid, left, 2, s);
-            // (environment rows by SITE: a fit's stride between sites, N * cap, is its own)
-            if (left) launch_env_split_b(v0, dv, K, lid, 1, rid, 0, rid < c0->T - 1 ? rid + 1 : -1, rid + 1, rid, rid, chain, s);
-            else launch_env_split_b(v0, dv, K, lid, 0, lid, 1, lid > 0 ? lid - 1 : -1, lid, lid + 1, lid, chain, s);
+            launch_env_split_b(v0, dv, K, lid, left, chain, s);
         }
         return 0;
     };

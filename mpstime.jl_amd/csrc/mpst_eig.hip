@@ -1338,9 +1338,11 @@ bool eig_merged() {
     return m;
 }
 
+// workgroups of the eigenvector kernels (one eigenpair each): the kept dimension n, at least 32, at most the TRI_KMAX they deliver
+static int eig_vec_blocks(int n) { return n < TRI_KMAX ? (n < 32 ? 32 : n) : TRI_KMAX; }
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s) {
     unsigned long long* st = v.sc ? v.sc->eig_stamps : nullptr;
-    const dim3 gvec(v.chi_max < TRI_KMAX ? (v.chi_max < 32 ? 32 : v.chi_max) : TRI_KMAX);
+    const dim3 gvec(eig_vec_blocks(v.chi_max));
     if (stage == 0 && eig_merged())
         hipLaunchKernelGGL(k_eig_trivec, gvec, dim3(TRI_T), vec_lds_bytes(), s, v, lid, going_left, (const double*)nullptr, 0, 0,
                            v.eig_ws, st);
@@ -1357,7 +1359,7 @@ void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s
 
 // the merged chain for K fits of one shape (mpst_sweep_batch): stage 0 k_eig_trivec_b, stage 2 k_eig_fin_b
 void launch_eig_b(const View& v, const View* vs, int K, int lid, int going_left, int stage, hipStream_t s) {
-    const dim3 gvec(v.chi_max < TRI_KMAX ? (v.chi_max < 32 ? 32 : v.chi_max) : TRI_KMAX, 1, K);
+    const dim3 gvec(eig_vec_blocks(v.chi_max), 1, K);
     // more workgroups than CUs (one workgroup per CU: 157 KB of LDS): several eigenpairs per workgroup instead of rounds of workgroups
     // that repeat the reduction (MPST_EIG_BM=0: never)
     static const bool bm_on = [] { const char* e = getenv("MPST_EIG_BM"); return !(e && e[0] == '0'); }();
@@ -1382,8 +1384,7 @@ void launch_eig_raw_gated(const double* G, int n, double* lam, double* E, int32_
     View v{};
     v.label_site = const_cast<int32_t*>(gate);
     const int alg = 8;
-    const int K = n < TRI_KMAX ? (n < 32 ? 32 : n) : TRI_KMAX;
-    hipLaunchKernelGGL(k_eig_trivec_g, dim3(K), dim3(TRI_T), vec_lds_bytes(), s, v, G, n, alg, ws);
+    hipLaunchKernelGGL(k_eig_trivec_g, dim3(eig_vec_blocks(n)), dim3(TRI_T), vec_lds_bytes(), s, v, G, n, alg, ws);
     hipLaunchKernelGGL(k_eig_fin_g, dim3(1), dim3(EIG_THREADS), eig_lds_bytes(), s, v, G, n, alg, ws, lam, E, info);
 }
 

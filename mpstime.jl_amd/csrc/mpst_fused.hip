@@ -12,8 +12,10 @@
 //   k_env_split    update_caches! (:107-144) and the back-split of decomposeBT (:172-176,190-194) in one launch:
 //                  both depend only on the kept eigenvectors E and bt_new
 #include "mpst_internal.h"
+#include "mpst_bond_plan.h"
 #include "mpst_eig_common.inl"
 #include <algorithm>
+#include <cassert>
 #include <cstring>
 
 namespace mpst {
@@ -2345,127 +2347,122 @@ int b2_ksplit(const View& v, int64_t max_pass) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(ks, GS_MAXKS));
 }
 int64_t b2_partial_elems(const View& v, int64_t max_pass) { return (int64_t)v.C * b2_blocks_cap(v) * b2_ksplit(v, max_pass) * 1024; }
-static bool yhat_s_v2(const View& v) { return v.d == 4 && v.cap <= 32 && !(v.cap & 1) && getenv("MPST_YS_V1") == nullptr; }      // 16-byte row loads
-static size_t yhat_s_lds(const View& v) { return (size_t)128 * ((yhat_s_v2(v) ? 2 : 1) * (v.cap + 1 + v.d + 1) + 17) * sizeof(double); }
+// MPST_YS_V1: k_yhat_s without the 16-byte row loads (read once per process, as eig_merged reads its switch)
+static bool yhat_s_v1_forced() { static const bool f = getenv("MPST_YS_V1") != nullptr; return f; }
 static size_t grad_s_lds(const View& v) { return std::max((size_t)GS_KC * (((2 * b2_aw(v) + 2 * v.d + 1) | 1) + 1), (size_t)32 * 256) * sizeof(double); }
 hipError_t b2_init_attrs(int device) {
     static std::atomic<unsigned long long> done{0};
     if (device >= 0 && device < 64 && (done.load(std::memory_order_acquire) >> device) & 1ull) return hipSuccess;
-    hipError_t e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s<2, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s<2, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s<4, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s<1, 1, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s<1, 1, 25, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s<1, 1, 25, 256, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s<2, 1, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s<1, 2, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s_b<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s_b<2, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s_b<2, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_yhat_s_b<4, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s_b<1, 1, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s_b<1, 1, 25, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s_b<1, 1, 25, 256, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s_b<2, 1, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_grad_s_b<1, 2, 0, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_bond_tail<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BT_LDS_DOUBLES * (int)sizeof(double))) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_bond_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BT_LDS_DOUBLES * (int)sizeof(double))) != hipSuccess) return e;
+#define RAISE(KERNEL, BYTES)                                                                                                        \
+    if (hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)); e != hipSuccess) return e;
+#define X(LM, D4, V2) RAISE((k_yhat_s<LM, D4, V2>), 96 * 1024) RAISE((k_yhat_s_b<LM, D4, V2>), 96 * 1024)
+    YHAT_S_LIST(X)
+#undef X
+#define X(AW2, D2, FS, KC, NW, THREADS) RAISE((k_grad_s<AW2, D2, FS, KC, NW>), 96 * 1024) RAISE((k_grad_s_b<AW2, D2, FS, KC, NW>), 96 * 1024)
+    GRAD_S_LIST(X)
+#undef X
+    RAISE(k_bond_tail<true>, BT_LDS_DOUBLES * sizeof(double))
+    RAISE(k_bond_tail<false>, BT_LDS_DOUBLES * sizeof(double))
+#undef RAISE
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
 }
-void launch_yhat_s(const View& v, int lid, hipStream_t s) {
-    const int nslc = cdivf(v.d * v.cap, YS_W);
-    const int ngroups = cdivf(v.ntiles, 8);
-    const int ngw = std::max(1, std::min(ngroups, std::max(1, 512 / nslc)));      // group walkers per slice
-    const dim3 grid(nslc * ngw, v.loss == MPST_LOSS_MSE ? v.C : 1);
-    if (yhat_s_v2(v)) hipLaunchKernelGGL((k_yhat_s<2, true, true>), grid, dim3(YS_T), yhat_s_lds(v), s, v, lid, nslc, ngw);
-    else if (v.cap <= 32 && v.d == 4) hipLaunchKernelGGL((k_yhat_s<2, true, false>), grid, dim3(YS_T), yhat_s_lds(v), s, v, lid, nslc, ngw);
-    else if (v.cap <= 32) hipLaunchKernelGGL((k_yhat_s<2, false, false>), grid, dim3(YS_T), yhat_s_lds(v), s, v, lid, nslc, ngw);
-    else hipLaunchKernelGGL((k_yhat_s<4, false, false>), grid, dim3(YS_T), yhat_s_lds(v), s, v, lid, nslc, ngw);
-}
-void launch_loss_sum(const View& v, hipStream_t s) { hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(64), 0, s, v); }
-
-// ---- batched launchers: v = the shape every fit of the batch shares with ntiles of the LARGEST fit, vs = the K Views on the device.
+// k_yhat_s of one fit (vs null, K = 1) or of the K fits vs: v = the shape every fit of the batch shares with ntiles of the LARGEST fit.
 // The fits may differ in their series: ngw, ntb and tp only deal tiles to workgroups (no sum runs across tiles), a workgroup beyond its
-// fit's own tiles leaves; what orders a sum (b2_ksplit, b2_nw) is the context's own ----
+// fit's own tiles leaves; what orders a sum (b2_ksplit, b2_nw) is the context's own
 void launch_yhat_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s) {
+    assert(vs || K == 1);
     const int nslc = cdivf(v.d * v.cap, YS_W);
     const int ngroups = cdivf(v.ntiles, 8);
     // group walkers per slice: about 512 workgroups over the whole batch - fewer, longer walks per fit amortise a workgroup's
     // start-up and its slice of B_c over more series (the series a walker takes do not change any sum)
     const int ngw = std::max(1, std::min(ngroups, std::max(1, 512 / (nslc * K))));
     const dim3 grid(nslc * ngw, v.loss == MPST_LOSS_MSE ? v.C : 1, K);
-    if (yhat_s_v2(v)) hipLaunchKernelGGL((k_yhat_s_b<2, true, true>), grid, dim3(YS_T), yhat_s_lds(v), s, vs, lid, nslc, ngw);
-    else if (v.cap <= 32 && v.d == 4) hipLaunchKernelGGL((k_yhat_s_b<2, true, false>), grid, dim3(YS_T), yhat_s_lds(v), s, vs, lid, nslc, ngw);
-    else if (v.cap <= 32) hipLaunchKernelGGL((k_yhat_s_b<2, false, false>), grid, dim3(YS_T), yhat_s_lds(v), s, vs, lid, nslc, ngw);
-    else hipLaunchKernelGGL((k_yhat_s_b<4, false, false>), grid, dim3(YS_T), yhat_s_lds(v), s, vs, lid, nslc, ngw);
+    const int row = yhat_s_variant(v.d, v.cap, yhat_s_v1_forced());
+    const size_t lds = (size_t)128 * ((row == 0 ? 2 : 1) * (v.cap + 1 + v.d + 1) + 17) * sizeof(double);      // row 0 stages both environments
+    int r = 0;
+#define X(LM, D4, V2)                                                                                                               \
+    if (r++ == row) {                                                                                                               \
+        if (vs) hipLaunchKernelGGL((k_yhat_s_b<LM, D4, V2>), grid, dim3(YS_T), lds, s, vs, lid, nslc, ngw);                         \
+        else hipLaunchKernelGGL((k_yhat_s<LM, D4, V2>), grid, dim3(YS_T), lds, s, v, lid, nslc, ngw);                               \
+    }
+    YHAT_S_LIST(X)
+#undef X
 }
 void launch_grad_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s) {
-    const int aw = b2_aw(v), nbc = cdivf(v.cap, aw);
+    assert(vs || K == 1);
+    const int nbc = cdivf(v.cap, b2_aw(v));
     const dim3 grid(v.b2_ksplit * nbc * nbc, v.C, K);
-    if (aw > 8) hipLaunchKernelGGL((k_grad_s_b<2, 1, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc);
-    else if (v.d > 8) hipLaunchKernelGGL((k_grad_s_b<1, 2, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc);
-    else if (v.d == 4 && v.b2_nw == 4) hipLaunchKernelGGL((k_grad_s_b<1, 1, 25, 256, 4>), grid, dim3(256), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc);
-    else if (v.d == 4) hipLaunchKernelGGL((k_grad_s_b<1, 1, 25, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc);
-    else hipLaunchKernelGGL((k_grad_s_b<1, 1, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc);
+    const int row = grad_s_variant(v.d, v.b2_nw);
+    int r = 0;
+#define X(AW2, D2, FS, KC, NW, THREADS)                                                                                             \
+    if (r++ == row) {                                                                                                               \
+        static_assert(THREADS == GS_T / 8 * NW, "a row's block is its kernel's launch bound");                                    \
+        if (vs) hipLaunchKernelGGL((k_grad_s_b<AW2, D2, FS, KC, NW>), grid, dim3(THREADS), grad_s_lds(v), s, vs, lid, v.b2_ksplit, nbc); \
+        else hipLaunchKernelGGL((k_grad_s<AW2, D2, FS, KC, NW>), grid, dim3(THREADS), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);  \
+    }
+    GRAD_S_LIST(X)
+#undef X
 }
+void launch_yhat_s(const View& v, int lid, hipStream_t s) { launch_yhat_s_b(v, nullptr, 1, lid, s); }
+void launch_grad_s(const View& v, int lid, hipStream_t s) { launch_grad_s_b(v, nullptr, 1, lid, s); }
+void launch_loss_sum(const View& v, hipStream_t s) { hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(64), 0, s, v); }
+
 void launch_gram_upd_b(const View& v, const View* vs, int K, int lid, int going_left, int first_iter, hipStream_t s) {
     const int dm = v.d * v.cap;
     hipLaunchKernelGGL(k_gram_upd_b, dim3(cdivf(dm, 16) * cdivf(dm, 16), 1, K), dim3(256), 0, s, vs, lid, going_left, first_iter);
 }
-void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int prev_site, int prev_bond,
-                        int out_bond, int out_site, int chain, hipStream_t s) {
-    const int dm = v.d * v.cap;
-    const int nsplit = cdivf(v.C * cdivf(dm, 16) * cdivf(v.cap, 16), 4);
-    const int nchain = chain ? v.C * v.d * cdivf(v.cap, 16) : 0;
-    // tile blocks: about 512 over the whole batch (as one fit of K times the series would get), each walking its fit's tiles
+static int chain_blocks(const View& v, int chain) { return chain ? v.C * v.d * cdivf(v.cap, 16) : 0; }      // assemble the next bond's tensor
+// back-split and environment step of bond lid (env_step_of_bond), of one fit (vs null, K = 1) or of the K fits vs
+void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int chain, hipStream_t s) {
+    assert(vs || K == 1);
+    const EnvStep e = env_step_of_bond(lid, going_left, v.T);
+    const int nsplit = cdivf(v.C * cdivf(v.d * v.cap, 16) * cdivf(v.cap, 16), 4), nchain = chain_blocks(v, chain);
+    // tile blocks: at most two per CU, about 512 over the whole batch (as one fit of K times the series would get); each walks its
+    // fit's tiles with that stride, tp = one or two tiles staged per pass (see the kernel)
     // (K = 8 at the headline shape: 66.9 -> 64.7 ms per batched sweep; walkers of k_yhat_s_b and shares of k_grad_s_b scanned flat)
     constexpr int envb = 512;
-    const int tp = (v.cap <= 32 && v.ntiles * K >= 512 && v.ntiles >= 2 * std::max(1, envb / K)) ? 2 : 1;
-    const size_t lds = std::max((size_t)tp * 16 * FXS, chain ? (size_t)4 * CHAIN_J * 256 : (size_t)0) * sizeof(double);
+    const int tp = (v.cap <= 32 && (vs ? v.ntiles * K >= 512 && v.ntiles >= 2 * std::max(1, envb / K) : v.ntiles >= 512)) ? 2 : 1;
     const int ntb = std::max(1, std::min(v.ntiles, std::max(1, envb / K)));
-    hipLaunchKernelGGL(k_env_split_b, dim3(ntb + nsplit + nchain, 1, K), dim3(256), lds, s, vs, lid, going_left, site, left_side, prev_site, prev_bond,
-                       out_bond, out_site, nsplit, ntb, tp);
+    const size_t lds = std::max((size_t)tp * 16 * FXS, chain ? (size_t)4 * CHAIN_J * 256 : (size_t)0) * sizeof(double);
+    const dim3 grid(ntb + nsplit + nchain, 1, K);
+    const int64_t cs = (int64_t)v.N * v.cap;
+    double* rows = e.left_side ? v.LE : v.RE;
+    // (the batch names its environment rows by SITE: a fit's stride between sites, N * cap, is its own)
+    if (vs) hipLaunchKernelGGL(k_env_split_b, grid, dim3(256), lds, s, vs, lid, going_left, e.site, e.left_side, e.prev_site, e.prev_bond, e.out_bond,
+                               e.out_site, nsplit, ntb, tp);
+    else hipLaunchKernelGGL(k_env_split, grid, dim3(256), lds, s, v, lid, going_left, e.site, e.left_side, env_row(rows, e.prev_site, cs), e.prev_bond,
+                            e.out_bond, env_row(rows, e.out_site, cs), nsplit, ntb, tp);
 }
-void launch_grad_s(const View& v, int lid, hipStream_t s) {
-    const int aw = b2_aw(v), nbc = cdivf(v.cap, aw);
-    const dim3 grid(v.b2_ksplit * nbc * nbc, v.C);
-    if (aw > 8) hipLaunchKernelGGL((k_grad_s<2, 1, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);         // d = 2, 3
-    else if (v.d > 8) hipLaunchKernelGGL((k_grad_s<1, 2, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);   // d = 9..16
-    else if (v.d == 4 && v.b2_nw == 4) hipLaunchKernelGGL((k_grad_s<1, 1, 25, 256, 4>), grid, dim3(256), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);
-    else if (v.d == 4) hipLaunchKernelGGL((k_grad_s<1, 1, 25, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);
-    else hipLaunchKernelGGL((k_grad_s<1, 1, 0, 256, 8>), grid, dim3(GS_T), grad_s_lds(v), s, v, lid, v.b2_ksplit, nbc);
-}
+void launch_env_split(const View& v, int lid, int going_left, int chain, hipStream_t s) { launch_env_split_b(v, nullptr, 1, lid, going_left, chain, s); }
 // the four-launch chain: real fp64, KLD, at most 32 kept vectors (the 32-column layout of the eigenvector block), tridiagonal solver
 bool bond_tail_supported(const View& v) {
     return v.zw != 2 && v.loss == MPST_LOSS_KLD && v.chi_max <= 32 && v.cap <= 32 && v.d * v.cap <= MAX_DIM && v.svd_alg != MPST_SVD_JACOBI && v.d >= 2 && v.d <= 16;
 }
 void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next /* bit 0; bit 2: forced failure (test hook) */, unsigned long long* span, hipStream_t s) {
-    const int dm = v.d * v.cap, rid = lid + 1;
+    const int dm = v.d * v.cap;
     TailArgs ta;
     ta.lid = lid;
     ta.going_left = going_left;
     ta.nsplit = cdivf(v.C * cdivf(dm, 16) * cdivf(v.cap, 16), 2);        // hosts of the back-split: two tiles (of the capacity layout) each
-    ta.nchain = chain ? v.C * v.d * cdivf(v.cap, 16) : 0;
+    ta.nchain = chain_blocks(v, chain);
     ta.flags = (want_next & 1) | (want_next & 4);      // bit 2: test hook - this launch reports a failed verification
     ta.span = span;
+    // S: the side this bond's environment step extends, O: the other side's row next to the bond
     const int64_t cs = (int64_t)v.N * v.cap;
-    const double* LEp = lid > 0 ? v.LE + (int64_t)(lid - 1) * cs : nullptr;
-    const double* REn = rid < v.T - 1 ? v.RE + (int64_t)(rid + 1) * cs : nullptr;
-    const double* phl = v.phi + (int64_t)lid * v.N * v.d;
-    const double* phr = v.phi + (int64_t)rid * v.N * v.d;
-    ta.Sprev = going_left ? REn : LEp;
-    ta.Oprev = going_left ? LEp : REn;
-    ta.phS = going_left ? phr : phl;
-    ta.phO = going_left ? phl : phr;
+    const EnvStep st = env_step_of_bond(lid, going_left, v.T), ot = env_step_of_bond(lid, !going_left, v.T);
+    ta.Sprev = env_row(st.left_side ? v.LE : v.RE, st.prev_site, cs);
+    ta.Oprev = env_row(ot.left_side ? v.LE : v.RE, ot.prev_site, cs);
+    ta.phS = v.phi + (int64_t)st.site * v.N * v.d;
+    ta.phO = v.phi + (int64_t)ot.site * v.N * v.d;
     ta.M = going_left ? v.btn : v.btnT;
-    ta.out = going_left ? v.RE + (int64_t)rid * cs : v.LE + (int64_t)lid * cs;
+    ta.out = env_row(st.left_side ? v.LE : v.RE, st.out_site, cs);
     // which bond's tail leaves its phase stamps (mpst_get_tail_phases): MPST_TAIL_STAMP="lid,going_left", default the middle bond going left
-    static const int stamp_lid = [] { const char* e = getenv("MPST_TAIL_STAMP"); return e ? atoi(e) : -1; }();
-    static const int stamp_dir = [] { const char* e = getenv("MPST_TAIL_STAMP"); const char* q = e ? strchr(e, ',') : nullptr; return q ? atoi(q + 1) : 1; }();
-    if (lid == (stamp_lid >= 0 ? stamp_lid : (v.T - 1) / 2) && (going_left != 0) == (stamp_dir != 0)) ta.flags |= 2;
+    static const std::pair<int, int> stamp = [] {
+        const char *e = getenv("MPST_TAIL_STAMP"), *q = e ? strchr(e, ',') : nullptr;
+        return std::make_pair(e ? atoi(e) : -1, q ? atoi(q + 1) : 1);
+    }();
+    if (lid == (stamp.first >= 0 ? stamp.first : (v.T - 1) / 2) && (going_left != 0) == (stamp.second != 0)) ta.flags |= 2;
     const size_t lds = (size_t)BT_LDS_DOUBLES * sizeof(double);
     const dim3 grid(std::max(v.ntiles, ta.nchain + ta.nsplit));           // one 16-series tile per workgroup; the first ones carry a role as well
     if (v.d == 4) hipLaunchKernelGGL(k_bond_tail<true>, grid, dim3(BT_T), lds, s, v, ta);
@@ -2477,18 +2474,6 @@ void launch_grad_norm(const View& v, int lid, hipStream_t s) {
 void launch_gram_upd(const View& v, int lid, int going_left, int first_iter, hipStream_t s) {
     const int dm = v.d * v.cap;
     hipLaunchKernelGGL(k_gram_upd, dim3(cdivf(dm, 16) * cdivf(dm, 16)), dim3(256), 0, s, v, lid, going_left, first_iter);
-}
-void launch_env_split(const View& v, int lid, int going_left, int site, int left_side, const double* prev, int prev_bond,
-                      int out_bond, double* out, int chain, hipStream_t s) {
-    const int dm = v.d * v.cap;
-    const int nsplit = cdivf(v.C * cdivf(dm, 16) * cdivf(v.cap, 16), 4);
-    const int nchain = chain ? v.C * v.d * cdivf(v.cap, 16) : 0;
-    const int tp = (v.cap <= 32 && v.ntiles >= 512) ? 2 : 1;      // tiles a workgroup stages per pass
-    const size_t lds = std::max((size_t)tp * 16 * FXS, chain ? (size_t)4 * CHAIN_J * 256 : (size_t)0) * sizeof(double);
-    // tile blocks: at most two per CU; each walks the tiles with that stride (one pass covers one or two tiles, see the kernel)
-    const int ntb = std::max(1, std::min(v.ntiles, 512));
-    hipLaunchKernelGGL(k_env_split, dim3(ntb + nsplit + nchain), dim3(256), lds, s, v, lid, going_left,
-                       site, left_side, prev, prev_bond, out_bond, out, nsplit, ntb, tp);
 }
 
 }  // namespace mpst

@@ -542,8 +542,7 @@ int b2_ksplit(const View& v, int64_t max_pass);            // shares per block; 
 int64_t b2_partial_elems(const View& v, int64_t max_pass);
 hipError_t b2_init_attrs(int device);
 void launch_gram_upd(const View& v, int lid, int going_left, int first_iter, hipStream_t s);
-void launch_env_split(const View& v, int lid, int going_left, int site, int left_side, const double* prev, int prev_bond,
-                      int out_bond, double* out, int chain /* also assemble the next bond's tensor */, hipStream_t s);
+void launch_env_split(const View& v, int lid, int going_left, int chain /* also assemble the next bond's tensor */, hipStream_t s);
 // the four-launch chain's last launch (k_bond_tail): k_eig_fin's verification + polish, environment update, back-split, the next
 // bond's tensor (chain) and the next bond's overlaps (want_next) in one
 void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next, unsigned long long* span /* [2 * 2048] or null */, hipStream_t s);
@@ -555,8 +554,7 @@ bool env_walk_supported(const View& v);
 void launch_yhat_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
 void launch_grad_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
 void launch_gram_upd_b(const View& v, const View* vs, int K, int lid, int going_left, int first_iter, hipStream_t s);
-void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int site, int left_side, int prev_site, int prev_bond,
-                        int out_bond, int out_site, int chain, hipStream_t s);
+void launch_env_split_b(const View& v, const View* vs, int K, int lid, int going_left, int chain, hipStream_t s);
 void launch_eig_b(const View& v, const View* vs, int K, int lid, int going_left, int stage, hipStream_t s);
 void launch_bt_assemble_b(const View& v, const View* vs, int K, int lid, hipStream_t s);
 // batched one-launch scoring (mpst_score.hip): one model and one data set per job, blockIdx.z picks the job
