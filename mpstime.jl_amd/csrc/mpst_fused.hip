@@ -1932,7 +1932,10 @@ __device__ __forceinline__ bool tail_polish(double* __restrict__ Z, double* __re
 // lam_k, zero beyond K) instead of an array in LDS every thread walks (1.3 us of dependent reads).  The rule drops values from the small end
 // while the discarded weight stays within cutoff * scale; the weight behind value m is base + sum_{i >= m} P_i (base: what lies beyond the K
 // values, trace - sum), so the answer is the smallest m >= 1 whose tail qualifies - one prefix scan and one ballot.  The sums are taken in
-// another order than truncate_rule()'s loop: the two can differ where a tail equals the threshold to the last bit.
+// another order than truncate_rule()'s loop, but that is not what limits either rule: (kept - pre) + P and scale0 - kept are differences of
+// sums near 1, so a tail carries an absolute error of about 2e-16 of the trace whatever the cutoff.  Both rules decide every state as exact
+// arithmetic would down to a relative cutoff of about 1e-12; below that (simulated at 1e-13 ... 1e-15 against rational arithmetic) both
+// depart from it, equally often, because of the trace - sum base they share ("the cutoff floor").
 __device__ __forceinline__ int truncate_rule_lanes(const double lam_lane, const int K, const int ns, const double tr, const double inv2, const double cutoff) {
     const int lane = threadIdx.x & 63;
     const double scale0 = tr * inv2;

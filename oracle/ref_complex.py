@@ -141,9 +141,10 @@ def apply_update(bt5, LEp, REp, lid, rid, data, opts: SweepOptions, trace=None):
     return bt
 
 
-def decompose_bt(bt5, chi_max, cutoff, going_left=True, svd_double=False):
+def decompose_bt(bt5, chi_max, cutoff, going_left=True, svd_double=False, spectrum=None):
     """decomposeBT_IT, RealRealLegacyITensor.jl:84-142.  ITensors' ``U, S, V = svd(A, rowinds)`` returns A = U*S*V, i.e.
-    the ITensor V holds the conjugated right singular vectors (V^H as a matrix) - scipy's ``Vh``."""
+    the ITensor V holds the conjugated right singular vectors (V^H as a matrix) - scipy's ``Vh``.  ``spectrum`` (a list) receives the
+    spectrum before truncation."""
     d_l, Da, d_r, Db, C = bt5.shape
     dt = bt5.dtype
     if going_left:
@@ -153,6 +154,8 @@ def decompose_bt(bt5, chi_max, cutoff, going_left=True, svd_double=False):
     if svd_double:
         M = M.astype(np.complex128 if np.iscomplexobj(M) else np.float64)
     U, S, Vh = scipy.linalg.svd(M, full_matrices=False, lapack_driver="gesdd")
+    if spectrum is not None:
+        spectrum.append(S)
     n = truncate_spectrum(S, chi_max, cutoff)
     U, S, Vh = U[:, :n], S[:n], Vh[:n]
     if going_left:
@@ -174,11 +177,13 @@ def bond_step(W, LE, RE, lid, data, opts: SweepOptions, going_left, trace=None, 
     LEp = LE[lid - 1] if lid > 0 else None
     REp = RE[rid + 1] if rid < T - 1 else None
     bt_new = apply_update(bt5, LEp, REp, lid, rid, data, opts, trace)
-    lsn, rsn, S = decompose_bt(bt_new, opts.chi_max, opts.cutoff, going_left, svd_double)
+    S_all = []
+    lsn, rsn, S = decompose_bt(bt_new, opts.chi_max, opts.cutoff, going_left, svd_double, S_all)
     update_caches(lsn, rsn, LE, RE, lid, rid, data.phi, going_left)
     W[lid], W[rid] = lsn, rsn
     if trace is not None:
         trace["S"] = np.asarray(S, dtype=np.float64)
+        trace["S_all"] = np.asarray(S_all[0], dtype=np.float64)                # the spectrum before truncation
         trace["bt_new_norm"] = float(np.linalg.norm(bt_new))
         trace["chi"] = len(S)
         trace["bt_new"] = bt_new

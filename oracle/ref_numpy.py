@@ -328,7 +328,7 @@ def truncate_spectrum(S, maxdim, cutoff, mindim=1):
     return n
 
 
-def decompose_bt(bt5, lid, rid, chi_max, cutoff, going_left=True):
+def decompose_bt(bt5, lid, rid, chi_max, cutoff, going_left=True, spectrum=None):
     """decomposeBT, RealRealHighDimension.jl:146-203.
 
     bt5 has axes (s_l, a, s_r, b, c).  LAPACK gesdd (= Julia's
@@ -336,11 +336,13 @@ def decompose_bt(bt5, lid, rid, chi_max, cutoff, going_left=True):
     going_left: rows (a, c, s_l) | cols (s_r, b); left = U*S carries the label,
     right = V (:166-176).  going right: rows (b, c, s_r) | cols (s_l, a);
     right = V*S carries the label, left = U (:185-194).
-    Returns (left_site, right_site, S_kept)."""
+    Returns (left_site, right_site, S_kept); ``spectrum`` (a list) receives the spectrum before truncation."""
     d_l, Da, d_r, Db, C = bt5.shape
     if going_left:
         M = bt5.transpose(1, 4, 0, 2, 3).reshape(Da * C * d_l, d_r * Db)
         U, S, Vh = scipy.linalg.svd(M, full_matrices=False, lapack_driver="gesdd")
+        if spectrum is not None:
+            spectrum.append(S)
         n = truncate_spectrum(S, chi_max, cutoff)
         U, S, Vh = U[:, :n], S[:n], Vh[:n]
         left = (U * S).reshape(Da, C, d_l, n).transpose(0, 2, 3, 1)      # (a, s, k, c)
@@ -348,6 +350,8 @@ def decompose_bt(bt5, lid, rid, chi_max, cutoff, going_left=True):
     else:
         M = bt5.transpose(3, 4, 2, 0, 1).reshape(Db * C * d_r, d_l * Da)
         U, S, Vh = scipy.linalg.svd(M, full_matrices=False, lapack_driver="gesdd")
+        if spectrum is not None:
+            spectrum.append(S)
         n = truncate_spectrum(S, chi_max, cutoff)
         U, S, Vh = U[:, :n], S[:n], Vh[:n]
         right = (U * S).reshape(Db, C, d_r, n).transpose(3, 2, 0, 1)     # (k, s, b, c)
@@ -432,11 +436,13 @@ def bond_step(W, LE, RE, lid, data, opts: SweepOptions, going_left, trace=None):
     bt, shape4 = flatten_bt(W[lid], W[rid])                        # :733 / :777
     bt_new = apply_update(bt, LE, RE, lid, rid, data, opts, trace)  # :736 / :779
     bt5 = unflatten_bt(bt_new, shape4)                             # :753 / :796
-    lsn, rsn, S = decompose_bt(bt5, lid, rid, opts.chi_max, opts.cutoff, going_left)  # :756 / :798
+    S_all = []
+    lsn, rsn, S = decompose_bt(bt5, lid, rid, opts.chi_max, opts.cutoff, going_left, S_all)  # :756 / :798
     update_caches(lsn, rsn, LE, RE, lid, rid, data.phi, going_left)  # :759 / :799
     W[lid], W[rid] = lsn, rsn                                      # :761-762 / :800-801
     if trace is not None:
         trace["S"] = S
+        trace["S_all"] = S_all[0]                                  # the spectrum before truncation
         trace["bt_new_norm"] = float(np.linalg.norm(bt_new))
         trace["chi"] = len(S)
     return trace

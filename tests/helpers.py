@@ -1,7 +1,31 @@
 """Shared builders for parity tests: seeded synthetic inputs in the oracle's conventions."""
+import os
+
 import numpy as np
 
 from oracle import ref_numpy as R
+
+
+class _env:
+    """Environment variables for the engines created inside (the library reads them when a context resolves its launch chain)."""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kv}
+        for k, v in self.kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def make_problem(N, T, d, chi_init, C, seed=0, balanced=True, encoding="legendre"):
@@ -42,7 +66,27 @@ def bond_of(q, T):
     return ((T - 2 - q) if going_left else (q - (T - 1))), going_left
 
 
-def teacher_forced_sweep(eng, co, phi, T, nbonds=None, overlap_every=9, sub=slice(None), first=0):
+def truncation_margin(S_all, chi_max, cutoff, mindim=1):
+    """Decision margin of a bond's truncation (oracle/ref_numpy.py truncate_spectrum): with n the kept dimension, P_i = s_i^2 / sum s^2
+    over the full spectrum S_all and D(k) = sum_{i >= k} P_i the weight discarded when k states are kept,
+
+        margin = min(|D(n) - cutoff|, |D(n - 1) - cutoff|) / cutoff
+
+    over the terms the relative-cutoff rule actually decided: D(n) <= cutoff is its decision only when n lies below the cap
+    min(chi_max, len(S_all)) (otherwise the cap stopped the rule), D(n - 1) > cutoff only when n > mindim.  inf when the rule decided
+    nothing.  Returns (margin, n)."""
+    S = np.asarray(S_all, dtype=float)
+    n = R.truncate_spectrum(S, chi_max, cutoff, mindim)
+    P = S ** 2 / np.sum(S ** 2)
+    terms = []
+    if n < min(chi_max, len(S)):
+        terms.append(abs(P[n:].sum() - cutoff))
+    if n > mindim:
+        terms.append(abs(P[n - 1:].sum() - cutoff))
+    return (min(terms) / cutoff if terms else np.inf), n
+
+
+def teacher_forced_sweep(eng, co, phi, T, nbonds=None, overlap_every=9, sub=slice(None), first=0, cutoff=1e-10):
     """Every bond update of a sweep compared with the C oracle, each starting from the ORACLE's state
     (set_mps + build_caches): free-running trajectories diverge chaotically (oracle/sensitivity_study.py),
     one update from a common state is well conditioned.  Returns the worst relative deviations and the
@@ -65,7 +109,7 @@ def teacher_forced_sweep(eng, co, phi, T, nbonds=None, overlap_every=9, sub=slic
             P = ref["S"] ** 2 / np.sum(ref["S"] ** 2)
             lo, hi = sorted((tr["chi"], ref["chi"]))
             tail = P[lo:].sum()
-            assert hi - lo == 1 and abs(tail - 1e-10) < 1e-3 * 1e-10, (q, lid, tr["chi"], ref["chi"], tail)
+            assert hi - lo == 1 and abs(tail - cutoff) < 1e-3 * cutoff, (q, lid, tr["chi"], ref["chi"], tail)
             chi_flips += 1
         elif q % overlap_every == 0:
             yo = R.contract_mps(co.get_mps(), phi[sub])

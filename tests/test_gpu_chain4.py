@@ -3,44 +3,20 @@
 bond's tensor :221-238) and the NEXT bond's k_yhat_s (loss_functions.jl:248-262) - against the six-launch chain it replaces
 (MPST_CHAIN4=0), against the oracle, and through its recovery path; and k_env_walk (construct_caches :45-103 in one launch) against
 the per-site launches."""
-import os
-
 import numpy as np
 import pytest
 
 import mpstime_jl_amd as mt
 from oracle import ref_numpy as R
-from tests.helpers import bond_of, load_engine, make_problem
+from tests.helpers import _env, bond_of, load_engine, make_problem
 
 pytestmark = pytest.mark.gpu
 
 
-class _env:
-    """Environment variables for the engines created inside (the library reads them when a context resolves its launch chain)."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _fresh(ds, W, chi, eta=0.05, options=None, **env):
+def _fresh(ds, W, chi, eta=0.05, options=None, cutoff=1e-10, **env):
     with _env(**env):
         eng = mt.SweepEngine(0)
-        eng.set_options(chi_max=chi, eta=eta, cutoff=1e-10, **(options or {}))
+        eng.set_options(chi_max=chi, eta=eta, cutoff=cutoff, **(options or {}))
         eng.set_dataset(0, ds.phi, ds.label_index, len(ds.class_distribution))
         eng.set_mps(W)
         eng.build_caches()
@@ -56,9 +32,20 @@ def test_four_launch_chain_agrees_with_six_launch_chain_bond_by_bond(N, T, d, ch
     norm, spectrum and kept dimension agree to rounding, and so does the updated MPS (as overlaps with the data: gauge invariant).  The
     overlaps the tail launch leaves for the next bond are used by the bond that follows in the sweep (same direction, no set_mps in
     between), so the second of every pair of consecutive bonds checks the yhat the tail computed."""
+    _four_against_six(N, T, d, chi, C, 1e-10)
+
+
+def test_four_launch_chain_agrees_with_six_launch_chain_at_the_cutoff_floor():
+    """cutoff = 1e-12, about the smallest relative cutoff the Gram route can honour to the last state ("the cutoff floor"):
+    both chains, whose truncation rules add the discarded weights in different orders (truncate_rule_lanes in the tail launch,
+    truncate_rule in k_eig_fin), keep the same dimension on every bond of two sweeps."""
+    _four_against_six(256, 12, 4, 12, 2, 1e-12)
+
+
+def _four_against_six(N, T, d, chi, C, cutoff):
     ds, W = make_problem(N, T, d, 4, C, seed=11 + N)
-    e6 = _fresh(ds, W, chi, MPST_CHAIN4=0)
-    e4 = _fresh(ds, W, chi, MPST_CHAIN4=None)
+    e6 = _fresh(ds, W, chi, cutoff=cutoff, MPST_CHAIN4=0)
+    e4 = _fresh(ds, W, chi, cutoff=cutoff, MPST_CHAIN4=None)
     try:
         assert not e6.info()["four_launch_chain"] and e4.info()["four_launch_chain"]
         nb = T - 1
