@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -427,6 +427,42 @@ int  mpst_impute_model_dist(void* ctx, const mpst_impute_model* m, const uint8_t
  * MPST_ERR_INVALID: NULL m or logp_out, non-positive dimensions; MPST_ERR_UNSUPPORTED: chi_max > 128, d > 16 or C > 16. */
 int  mpst_marginal_model(void* ctx, const mpst_impute_model* m, const uint8_t* missing /* [N][T], NULL = nothing missing */,
                          double* logp_out /* [N][C] */, double* seconds /* may be NULL */);
+
+/* Leave-one-out site conditionals of COMPLETE series: for every instance i and every site t the distribution of x_t given all the
+ * other values of the series, p(x_t | x_{!=t}), under the label slice c_i = m->label_idx[i] of the model (its scale is irrelevant
+ * to every output).  With M_j = sum_q conj(phi[i][j][q]) W_j[:, q, :] (the projection of precondition), l_{-1} = 1,
+ * l_j = l_{j-1} M_j, r_T = 1, r_j = M_j r_{j+1} (rescaled at every site: long chains do not underflow) and
+ *     a_t[s] = sum_ab l_{t-1}[a] W_t[a, s, b] r_{t+1}[b],
+ * the density on the grid is p_k = |sum_s conj(g_k[s]) a_t[s]|^2, g_k row k of site t's grid table: what mpst_impute_model_dist forms
+ * for an instance whose only missing site is t, up to a constant factor (the conditioned state is pure, so the reference's
+ * |rho phi|^2 and the Born value differ by the constant |a|^2 only).  cdf = cumul_integrate(grid_x, p, TrapezoidalEvenFast()),
+ * Z = cdf[ngrid-1], F = cdf / Z.
+ *   m                 as in mpst_impute_model_run (label_idx required), compute MPST_COMPUTE_F64; all of phi is read
+ *   x[N][T]           the observed values, in the encoding's domain (read for pit_out only)
+ *   grid_x, grid_phi, ngrid   as in mpst_impute_model_run: evenly spaced values and their states, [ngrid][d], or [T][ngrid][d] with
+ *                     o->grid_per_site = 1
+ *   o                 grid_per_site 0 / 1; get_err: compute err_out (else it is 0); nq levels strictly inside (0, 1), 0 <= nq <= 16;
+ *                     reserved: 0
+ * Outputs per (i, t), [N][T]; each may be NULL and is then skipped (at least one must be given):
+ *   nll_out   -ln( |sum_s conj(phi[i][t][s]) a_t[s]|^2 / Z ): the negative log conditional density at the observed value per unit of
+ *             the encoding's domain, at the exact encoded state (not the nearest grid value); +inf where the numerator is zero
+ *   pit_out   F at x[i][t], linear between the two neighbouring grid values; 0 below grid_x[0], 1 above grid_x[ngrid-1]
+ *   med_out   grid_x[argmin_k |F_k - 0.5|] (the median imputer's rule and tie rule)
+ *   err_out   the median imputer's WMAD, weighted_median(|grid_x - med|, p / Z)
+ *   q_out[N][T][nq]   grid_x[argmin_k |F_k - levels[l]|]
+ * A site whose Z is not a positive finite number gives NaN in all its outputs.  seconds (may be NULL): device time of the call;
+ * mpst_get_impute_phases then returns its split into (walk, grid phase).  Results do not depend on how the instances are cut into
+ * blocks (by free device memory) nor on which other instances travel along.
+ * MPST_ERR_INVALID: NULL m / x / grid_x / grid_phi / o, all outputs NULL, ngrid < 2, nq outside 0..16, a level outside (0, 1), q_out
+ * NULL with nq > 0, label_idx NULL or out of range, grid_per_site not 0 / 1; MPST_ERR_UNSUPPORTED: MPST_COMPUTE_F32, chi_max > 128,
+ * d > 16, C > 16.  A rejected call leaves the context as it was. */
+typedef struct {
+    int32_t grid_per_site, get_err, nq, reserved;
+    const double* levels;       /* [nq] */
+} mpst_sitecond_opts;
+int  mpst_site_conditionals(void* ctx, const mpst_impute_model* m, const double* x /* [N][T] */, const double* grid_x, const void* grid_phi,
+                            int32_t ngrid, const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out, double* err_out,
+                            double* q_out /* [N][T][nq] */, double* seconds /* may be NULL */);
 
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the

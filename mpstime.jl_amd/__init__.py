@@ -17,6 +17,7 @@ from .imputation import (ImputationProblem, init_imputation_problem, MPS_impute,
 from .jld2 import JLD2File, read_jld2, load_trained_mps_jld2
 from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
 from .marginal import log_marginals, class_posteriors
+from .conditionals import SiteConditionals, site_conditionals, anomaly_scores
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
                      BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
 from . import options
@@ -29,4 +30,4 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation",
            "classify_batch", "tune", "evaluate", "eval_loss", "fit_batch", "BatchFit", "MPSRandomSearch", "TuningLoss", "ClassificationLoss",
            "MisclassificationRate", "BalancedMisclassificationRate", "ImputationLoss", "make_windows", "make_stratified_cvfolds",
-           "classify_many", "log_marginals", "class_posteriors"]
+           "classify_many", "log_marginals", "class_posteriors", "SiteConditionals", "site_conditionals", "anomaly_scores"]

@@ -67,6 +67,11 @@ class ImputeModel(C.Structure):         # mpst_impute_model
                 ("phi", C.c_void_p), ("label_idx", C.POINTER(C.c_int32))]
 
 
+class SiteCondOpts(C.Structure):        # mpst_sitecond_opts
+    _fields_ = [("grid_per_site", C.c_int32), ("get_err", C.c_int32), ("nq", C.c_int32), ("reserved", C.c_int32),
+                ("levels", C.POINTER(C.c_double))]
+
+
 SYMBOLS = {
     "mpst_version": (C.c_int, []),
     "mpst_last_error": (C.c_char_p, [_vp]),
@@ -114,6 +119,7 @@ SYMBOLS = {
     "mpst_impute_model_dist": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _vp, _i32, C.POINTER(ImputeOpts), _dp, _dp,
                                          _dp, _i32, _dp, _dp, _i32, _i32, _dp]),
     "mpst_marginal_model": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _dp]),
+    "mpst_site_conditionals": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp, _vp, _i32, C.POINTER(SiteCondOpts), _dp, _dp, _dp, _dp, _dp, _dp]),
     "mpst_entanglement": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
     "mpst_see_variation": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
     "mpst_get_impute_phases": (C.c_int, [_vp, _dp]),

@@ -2217,7 +2217,10 @@ struct ImputeRequest {
     double *q_out = nullptr, *cdf_out = nullptr;
     bool marginal = false;      // mpst_marginal_model: no grid, no options; missing may be NULL; logp_out[N][C]
     double* logp_out = nullptr;
-    bool grid_per_site() const { return o && o->grid_per_site == 1; }      // grid_phi is [T][ngrid][d]
+    const mpst_sitecond_opts* sc = nullptr;     // mpst_site_conditionals: x_obs[N][T] and the five outputs, each of which may be NULL
+    const double* x_obs = nullptr;
+    double *nll_out = nullptr, *pit_out = nullptr, *med_out = nullptr;      // (the WMAD goes to err_out, the levels to q_out)
+    bool grid_per_site() const { return (o && o->grid_per_site == 1) || (sc && sc->grid_per_site == 1); }      // grid_phi is [T][ngrid][d]
 };
 constexpr int IMPUTE_MAX_LEVELS = 16;
 // doubles of the grid table(s) a request hands over
@@ -2561,6 +2564,73 @@ static int run_marginal(Ctx* c, const ImpModel& m, const ImputeRequest& r, int C
     return 0;
 }
 
+// The leave-one-out site conditionals of a request (mpst_site_conditionals): the walk's left rows ([T][16][chi] per workgroup of
+// sixteen instances) and the amplitudes are the scratch of a block of instances, cut by free device memory as impute_plan_chunk
+// does; the grid phase keeps ngrid doubles of density and prefix sums per workgroup, whatever the block.
+constexpr int SITECOND_MAX_CLASSES = 16;
+static int run_sitecond(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1, nq = r.sc->nq;
+    size_t free_b = 0, total_b = 0;
+    HIPC(c, hipMemGetInfo(&free_b, &total_b));
+    double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
+    if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
+    const double per_bytes = (double)T * (m.cap + m.d + 1) * zw * sizeof(double);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / per_bytes)));
+    chunk = std::min<int64_t>(chunk, ((int64_t)1 << 30) / T);                                           // (instance, site) pairs in 32 bits
+    if (chunk < N) chunk = std::max<int64_t>(SITECOND_TILE, chunk / SITECOND_TILE * SITECOND_TILE);    // whole workgroups of the walk
+    const int64_t tiles = (chunk + SITECOND_TILE - 1) / SITECOND_TILE, gwgs = sitecond_grid_workgroups(chunk * T);
+    DevBuf<double> dx, gx, gp, lev, nll, pit, med, err, q, amp, lrows, pb, sb;
+    int rc;
+    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, impute_grid_doubles(m, r))) || (rc = dalloc(c, amp, chunk * T * (m.d + 1) * zw)) ||
+        (rc = dalloc(c, lrows, tiles * T * SITECOND_TILE * m.cap * zw)) || (rc = dalloc(c, pb, gwgs * r.ngrid)) || (rc = dalloc(c, sb, gwgs * r.ngrid)) ||
+        (r.pit_out && (rc = dalloc(c, dx, N * T))) || (nq > 0 && ((rc = dalloc(c, lev, nq)) || (rc = dalloc(c, q, N * T * nq)))) ||
+        (r.nll_out && (rc = dalloc(c, nll, N * T))) || (r.pit_out && (rc = dalloc(c, pit, N * T))) || (r.med_out && (rc = dalloc(c, med, N * T))) ||
+        (r.err_out && (rc = dalloc(c, err, N * T)))) return rc;
+    HIPC(c, hipMemcpy(gx, r.grid_x, (size_t)r.ngrid * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)impute_grid_doubles(m, r) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.pit_out) HIPC(c, hipMemcpy(dx, r.x_obs, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+    if (nq > 0) HIPC(c, hipMemcpy(lev, r.sc->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+    ScArgs g{};
+    g.x = dx, g.grid_x = gx, g.grid_phi = gp, g.levels = lev;
+    g.grid_site_stride = r.grid_per_site() ? (int64_t)r.ngrid * m.d * zw : 0;
+    g.nll = nll, g.pit = pit, g.med = med, g.err = err, g.q = q;
+    g.amp = amp, g.lrows = lrows, g.pbuf = pb, g.sbuf = sb;
+    g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.sc->get_err ? 1 : 0;
+    std::vector<DevEvent> evs;
+    auto add_event = [&]() { evs.emplace_back(); return hipEventCreate(&evs.back().h); };
+    HIPC(c, hipEventRecord(c->ev_start, c->stream));
+    for (int64_t i0 = 0; i0 < N; i0 += chunk) {
+        g.first = i0, g.count = std::min(chunk, N - i0);
+        HIPC(c, add_event());
+        const hipEvent_t mid = evs.back();
+        HIPC(c, add_event());
+        if (launch_sitecond(m, g, c->stream, mid) < 0) return fail(c, MPST_ERR_DEVICE, "the site-conditional kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        HIPC(c, hipEventRecord(evs.back(), c->stream));
+    }
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    HIPC(c, hipGetLastError());
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    if (r.seconds) *r.seconds = 1e-3 * ms;
+    c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
+    for (size_t k = 0; k < evs.size(); k += 2) {
+        float a = 0.f, b = 0.f;
+        HIPC(c, hipEventElapsedTime(&a, k == 0 ? c->ev_start : evs[k - 1].h, evs[k]));
+        HIPC(c, hipEventElapsedTime(&b, evs[k], evs[k + 1]));
+        c->impute_phase_s[0] += 1e-3 * a;
+        c->impute_phase_s[1] += 1e-3 * b;
+    }
+    const size_t nb = (size_t)(N * T) * sizeof(double);
+    if (r.nll_out) HIPC(c, hipMemcpy(r.nll_out, nll, nb, hipMemcpyDeviceToHost));
+    if (r.pit_out) HIPC(c, hipMemcpy(r.pit_out, pit, nb, hipMemcpyDeviceToHost));
+    if (r.med_out) HIPC(c, hipMemcpy(r.med_out, med, nb, hipMemcpyDeviceToHost));
+    if (r.err_out) HIPC(c, hipMemcpy(r.err_out, err, nb, hipMemcpyDeviceToHost));
+    if (nq > 0) HIPC(c, hipMemcpy(r.q_out, q, nb * nq, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int mpst_get_impute_phases(void* ctx, double* seconds_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !seconds_out) return MPST_ERR_INVALID;
@@ -2685,6 +2755,12 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest&
     for (int64_t i = 0; i < h->N && !r.marginal; ++i)
         if (h->label_idx[i] < 0 || h->label_idx[i] >= h->C) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] out of range", (long long)i);
     const bool cx = h->dtype == MPST_DTYPE_C64, f32 = h->compute == MPST_COMPUTE_F32;
+    if (r.sc) {
+        if (f32) return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
+        if (cap > CAP_LIMIT || h->d > 16 || h->C > SITECOND_MAX_CLASSES)
+            return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, SITECOND_MAX_CLASSES,
+                        cap, h->d, h->C);
+    }
     if (r.marginal && cap > impute_chi_limit(cx, f32))
         return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold chi_max <= %d (got %d)", impute_chi_limit(cx, f32), cap);
     HIPC(c, hipSetDevice(c->device));
@@ -2710,7 +2786,7 @@ static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest&
     HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
     if (!r.marginal) HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
     const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return r.marginal ? run_marginal(c, m, r, h->C) : run_impute(c, m, r);
+    return r.marginal ? run_marginal(c, m, r, h->C) : (r.sc ? run_sitecond(c, m, r) : run_impute(c, m, r));
 }
 
 int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2754,6 +2830,26 @@ int mpst_marginal_model(void* ctx, const mpst_impute_model* h, const uint8_t* mi
     if (!h || !logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
     ImputeRequest r;
     r.missing = missing, r.seconds = seconds, r.marginal = true, r.logp_out = logp_out;
+    return impute_model(c, h, r);
+}
+
+int mpst_site_conditionals(void* ctx, const mpst_impute_model* h, const double* x, const double* grid_x, const void* grid_phi, int32_t ngrid,
+                           const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out, double* err_out, double* q_out,
+                           double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !x || !grid_x || !grid_phi || !o) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (!nll_out && !pit_out && !med_out && !err_out && !q_out) return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
+    if (ngrid < 2) return fail(c, MPST_ERR_INVALID, "fewer than 2 grid values");
+    if (o->grid_per_site != 0 && o->grid_per_site != 1) return fail(c, MPST_ERR_INVALID, "grid_per_site must be 0 (grid_phi[ngrid][d]) or 1 (grid_phi[T][ngrid][d]), got %d", (int)o->grid_per_site);
+    if (o->nq < 0 || o->nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)o->nq);
+    if (o->nq > 0 && (!o->levels || !q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
+    for (int l = 0; l < o->nq; ++l)
+        if (!(o->levels[l] > 0.0 && o->levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, o->levels[l]);
+    if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is conditioned under its own class");
+    ImputeRequest r;
+    r.sc = o, r.x_obs = x, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.seconds = seconds;
+    r.nll_out = nll_out, r.pit_out = pit_out, r.med_out = med_out, r.err_out = err_out, r.q_out = o->nq > 0 ? q_out : nullptr;
     return impute_model(c, h, r);
 }
 

@@ -810,6 +810,156 @@ enum { IMP_MEDIAN = 0, IMP_MODE = 1, IMP_QUANTILE = 2, IMP_MEAN = 3, IMP_ITS_REJ
 enum { IMP_BASIS_LEGENDRE = 0, IMP_BASIS_LEGENDRE_NO_NORM = 1, IMP_BASIS_FOURIER = 2, IMP_BASIS_STOUDENMIRE = 3, IMP_BASIS_SAHAND = 4,
        IMP_BASIS_UNIFORM = 5 };
 
+// ---- a density on the grid: prefix sums, cumulative trapezoid, selections ----------------------------------------------------------
+// What k_imp_left does with the density of a missing site and k_sc_grid (mpst_sitecond.inl) with a leave-one-out conditional, written
+// once.  Everything here is called by all IMP_T threads of a workgroup; where a prefix sum or a cdf value comes from (the table S_k or
+// a closed form) is the caller's `Sabs` / `cdf_at`.
+//
+// Prefix sums of p[0 .. n): each wave scans a contiguous quarter of the grid, 64 values per row: coalesced loads eight rows ahead, a
+// DPP inclusive scan per row, a wave-uniform carry.  S holds the sums relative to the start of the quarter; the
+// four quarter totals go to wtot and GridSums::at adds the right ones.  No barrier inside the pass.  (The first
+// version gave every thread a contiguous segment: four passes of uncoalesced, latency-bound loads, 64 us per
+// imputed site whatever chi and d - 70 % of the kernel at chi = 32.)
+__device__ __forceinline__ void grid_prefix_sums(const double* p, double* S, int n, int nrow, int rpw, double* wtot) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row0 = wave * rpw, row1 = min(nrow, row0 + rpw);
+    constexpr int PF = 8;
+    double buf[PF], cur[PF];
+#pragma unroll
+    for (int q = 0; q < PF; ++q) {
+        const int k = (row0 + q) * 64 + lane;
+        buf[q] = (row0 + q < row1 && k < n) ? p[k] : 0.0;
+    }
+    double carry = 0.0;
+    for (int rr = row0; rr < row1; rr += PF) {
+#pragma unroll
+        for (int q = 0; q < PF; ++q) {
+            cur[q] = buf[q];
+            const int k = (rr + PF + q) * 64 + lane;
+            buf[q] = (rr + PF + q < row1 && k < n) ? p[k] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < PF; ++q) {
+            if (rr + q < row1) {
+                const double x = wave_incl_scan(cur[q]) + carry;
+                const int k = (rr + q) * 64 + lane;
+                if (k < n) S[k] = x;
+                carry = readlane_f64(x, 63);
+            }
+        }
+    }
+    if (lane == 0) wtot[wave] = carry;
+}
+// the inclusive prefix sum S_k from the table grid_prefix_sums left
+struct GridSums {
+    const double* S;
+    int quarter;
+    double w1, w2, w3;          // the totals of the quarters before the second, third and fourth
+    __device__ __forceinline__ double at(int k) const {
+        const int qd = k / quarter;
+        return S[k] + (qd == 0 ? 0.0 : (qd == 1 ? w1 : (qd == 2 ? w2 : w3)));
+    }
+};
+// cumulative trapezoid at grid index k (cumul_integrate(x, p, TrapezoidalEvenFast()))
+template <typename SF> __device__ __forceinline__ double grid_cdf_at(int k, double dx, double p0, SF Sabs) {
+    if (k == 0) return 0.0;
+    return 0.5 * dx * ((Sabs(k - 1) + Sabs(k)) - p0);
+}
+// first index of the block-wide maximum of p (mode; also the weighted median's "one weight above half" rule) from every thread's
+// own first maximum (pmax, kmax)
+__device__ __forceinline__ int grid_arg_pmax(double pmax, int kmax, int n, double* red, int* isel, double& gmax) {
+    const int tid = threadIdx.x;
+    gmax = blk_max(pmax, red);
+    int cand = (pmax == gmax) ? kmax : n;
+    cand = -(int)wave_max((double)(-cand));
+    __syncthreads();
+    if ((tid & 63) == 0) isel[tid >> 6] = cand;
+    __syncthreads();
+    const int km = min(min(isel[0], isel[1]), min(isel[2], isel[3]));
+    __syncthreads();
+    return km;
+}
+// number of leading rows of 64 whose LAST element satisfies a monotone predicate (true ... true false ... false
+// along the grid): every thread tests the ends of its rows (two gathers in flight), one barrier
+template <typename PF> __device__ __forceinline__ int grid_rows_passing(int n, int nrow, int* isel, PF pred_at) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int c = 0;
+    for (int r = tid; r < nrow; r += IMP_T) c += pred_at(min(n - 1, 64 * r + 63)) ? 1 : 0;
+    int w = 0;
+    for (int it = 0; it < (nrow + IMP_T - 1) / IMP_T; ++it) w += __popcll(__ballot(c > it));
+    __syncthreads();
+    if (lane == 0) isel[wave] = w;
+    __syncthreads();
+    const int tot = isel[0] + isel[1] + isel[2] + isel[3];
+    __syncthreads();
+    return tot;
+}
+// argmin_k |cdf_k / Z - target|: the cdf is non-decreasing, so the minimiser sits at the crossing.  The points
+// with cdf_k <= target * Z form a prefix: first the row of 64 that holds its end (row ends only), then the
+// position inside that row (one coalesced row, every wave for itself) - two memory round trips instead of a pass
+// over the grid - and finally the reference's own expression |cdf_k / Z - target| on the handful of
+// neighbours, first minimum wins (argmin).
+template <typename CF> __device__ __forceinline__ int grid_quantile(double target, double Z, int n, int nrow, int* isel, CF cdf_at) {
+    const int lane = threadIdx.x & 63;
+    const double tz = target * Z;
+    const int rc = grid_rows_passing(n, nrow, isel, [&](int k) { return cdf_at(k) <= tz; });
+    int klo = n - 1;
+    if (rc < nrow) {
+        const int k = 64 * rc + lane;
+        const bool le = k < n && cdf_at(k) <= tz;
+        klo = 64 * rc + __popcll(__ballot(le)) - 1;
+    }
+    if (klo < 0) klo = 0;
+    // (the six candidates on six lanes, then the first minimum in lane order = in grid order)
+    const int kfirst = max(0, klo - 2), klast = min(n - 1, klo + 3);
+    const int kk = kfirst + lane;
+    double a = 1e300;
+    if (lane < 6 && kk <= klast) a = fabs(cdf_at(kk) / Z - target);
+    int ks = klo;
+    double best = 1e300;
+#pragma unroll
+    for (int l = 0; l < 6; ++l) {
+        const double al = readlane_f64(a, l);
+        if (al < best) {
+            best = al;
+            ks = kfirst + l;
+        }
+    }
+    return ks;
+}
+// StatsBase.median(|x - x_c|, pweights(p / Z)): the deviations grow with the distance from kc on the uniform
+// grid; the cumulative weight of the window [kc - jj, kc + jj] comes from the prefix sums and grows with jj: the
+// same two-level search for the first half-width whose window outweighs half the total.  `heaviest(mid, km)`: whether one grid
+// value alone outweighs half the total (then km is its index): the caller knows how to find the maximum of its density.
+// jhit: the half-width at which the window tipped the balance (-1: one value outweighed half the total, or no window did).
+template <typename SF, typename HF>
+__device__ __forceinline__ double grid_wmad(int kc, const double* grid_x, double Stot, double Z, int n, int nrow, int* isel, SF Sabs, HF heaviest,
+                                            int& jtip) {
+    const int lane = threadIdx.x & 63;
+    const double xc = grid_x[kc];
+    const double mid = 0.5 * (Stot / Z);
+    int km = 0;
+    jtip = -1;
+    if (heaviest(mid, km)) return fabs(grid_x[km] - xc);
+    auto light = [&](int jj) {          // the window of half-width jj does NOT yet outweigh half the total
+        const int hi = min(n - 1, kc + jj), lo = kc - jj - 1;
+        const double shi = Sabs(hi), slo = lo >= 0 ? Sabs(lo) : 0.0;
+        return !((shi - slo) / Z > mid);
+    };
+    const int rc = grid_rows_passing(n, nrow, isel, light);
+    int jhit = n;
+    if (rc < nrow) {
+        const int jj = 64 * rc + lane;
+        const unsigned long long bal = __ballot(jj < n && !light(jj));
+        if (bal) jhit = 64 * rc + (__ffsll((long long)bal) - 1);
+    }
+    if (jhit >= n) return 0.0;
+    jtip = jhit;
+    // the element that tips the balance is one of the two at distance jhit (whichever exists)
+    const int lo = kc - jhit, hi = kc + jhit;
+    return (lo >= 0) ? fabs(grid_x[lo] - xc) : fabs(grid_x[min(hi, n - 1)] - xc);
+}
+
 // OCC = workgroups per CU the kernel is compiled for.  Two (256 VGPRs) for real models and for complex ones with d <= 5: the
 // latency-bound loops gain more from the second resident workgroup than the ~300 B of spills cost (45 -> 32 ms at
 // chi = 32); complex models with larger d keep the whole register file (their density loop spills too much at 256).
@@ -871,7 +1021,6 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
     double* p = g.pbuf + (int64_t)blockIdx.x * g.ngrid;
     double* S = g.sbuf + (int64_t)blockIdx.x * g.ngrid;
     const int n = g.ngrid;
-    const int wave = tid >> 6, lane = tid & 63;
     const double dx = g.grid_x[1] - g.grid_x[0];
     if constexpr (DIST) {
         if (tid < g.nq) lev[tid] = g.levels[tid];
@@ -1396,49 +1545,16 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
             }
             __threadfence_block();
             __syncthreads();
-            // ---- prefix sums -------------------------------------------------------------------------------------------
-            // Each wave scans a contiguous quarter of the grid, 64 values per row: coalesced loads eight rows ahead, a
-            // DPP inclusive scan per row, a wave-uniform carry.  S holds the sums relative to the start of the quarter; the
-            // four quarter totals sit in LDS and Sabs() adds the right ones.  No barrier inside the pass.  (The first
-            // version gave every thread a contiguous segment: four passes of uncoalesced, latency-bound loads, 64 us per
-            // imputed site whatever chi and d - 70 % of the kernel at chi = 32.)
-            const int row0 = wave * rpw, row1 = min(nrow, row0 + rpw);
-            {
-                constexpr int PF = 8;
-                double buf[PF], cur[PF];
-#pragma unroll
-                for (int q = 0; q < PF; ++q) {
-                    const int k = (row0 + q) * 64 + lane;
-                    buf[q] = (row0 + q < row1 && k < n) ? p[k] : 0.0;
-                }
-                double carry = 0.0;
-                for (int rr = row0; rr < row1; rr += PF) {
-#pragma unroll
-                    for (int q = 0; q < PF; ++q) {
-                        cur[q] = buf[q];
-                        const int k = (rr + PF + q) * 64 + lane;
-                        buf[q] = (rr + PF + q < row1 && k < n) ? p[k] : 0.0;
-                    }
-#pragma unroll
-                    for (int q = 0; q < PF; ++q) {
-                        if (rr + q < row1) {
-                            const double x = wave_incl_scan(cur[q]) + carry;
-                            const int k = (rr + q) * 64 + lane;
-                            if (k < n) S[k] = x;
-                            carry = readlane_f64(x, 63);
-                        }
-                    }
-                }
-                if (lane == 0) wtot[wave] = carry;
-            }
+            // ---- prefix sums (grid_prefix_sums) --------------------------------------------------------------------------
+            grid_prefix_sums(p, S, n, nrow, rpw, wtot);
             __threadfence_block();
             __syncthreads();
             }
             const double woff1 = wtot[0], woff2 = woff1 + wtot[1], woff3 = woff2 + wtot[2];
+            const GridSums tab{S, quarter, woff1, woff2, woff3};
             auto Sabs = [&](int k) {
                 if constexpr (TRIG) return Strig(k);
-                const int qd = k / quarter;
-                return S[k] + (qd == 0 ? 0.0 : (qd == 1 ? woff1 : (qd == 2 ? woff2 : woff3)));
+                return tab.at(k);
             };
             auto Pat = [&](int k) {
                 if constexpr (TRIG) return Ptrig(g.grid_x[k]);
@@ -1447,102 +1563,30 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
             const double Stot = TRIG ? Strig(n - 1) : woff3 + wtot[3];
             const double p0 = Pat(0);
             auto cdf_at = [&](int k) {                                               // cumulative trapezoid
-                if (k == 0) return 0.0;
                 if constexpr (TRIG && !CX) {
+                    if (k == 0) return 0.0;
                     double pk;
                     const double Sk = Sleg(k, pk);                               // S_{k-1} = S_k - p(x_k)
                     return 0.5 * dx * ((Sk + (Sk - pk)) - p0);
                 }
-                return 0.5 * dx * ((Sabs(k - 1) + Sabs(k)) - p0);
+                return grid_cdf_at(k, dx, p0, Sabs);
             };
             const double Z = cdf_at(n - 1);
-            // first index of the block-wide maximum of p (mode; also the weighted median's "one weight above half" rule)
-            auto arg_pmax = [&](double& gmax) {
-                gmax = blk_max(pmax, red);
-                int cand = (pmax == gmax) ? kmax : n;
-                cand = -(int)wave_max((double)(-cand));
-                __syncthreads();
-                if ((tid & 63) == 0) isel[tid >> 6] = cand;
-                __syncthreads();
-                const int km = min(min(isel[0], isel[1]), min(isel[2], isel[3]));
-                __syncthreads();
-                return km;
-            };
-            // number of leading rows of 64 whose LAST element satisfies a monotone predicate (true ... true false ... false
-            // along the grid): every thread tests the ends of its rows (two gathers in flight), one barrier
-            auto rows_passing = [&](auto pred_at) {
-                int c = 0;
-                for (int r = tid; r < nrow; r += IMP_T) c += pred_at(min(n - 1, 64 * r + 63)) ? 1 : 0;
-                int w = 0;
-                for (int it = 0; it < (nrow + IMP_T - 1) / IMP_T; ++it) w += __popcll(__ballot(c > it));
-                __syncthreads();
-                if (lane == 0) isel[wave] = w;
-                __syncthreads();
-                const int tot = isel[0] + isel[1] + isel[2] + isel[3];
-                __syncthreads();
-                return tot;
-            };
-            // argmin_k |cdf_k / Z - target|: the cdf is non-decreasing, so the minimiser sits at the crossing.  The points
-            // with cdf_k <= target * Z form a prefix: first the row of 64 that holds its end (row ends only), then the
-            // position inside that row (one coalesced row, every wave for itself) - two memory round trips instead of a pass
-            // over the grid - and finally the reference's own expression |cdf_k / Z - target| on the handful of
-            // neighbours, first minimum wins (argmin).
-            auto quantile = [&](double target) {
-                const double tz = target * Z;
-                const int rc = rows_passing([&](int k) { return cdf_at(k) <= tz; });
-                int klo = n - 1;
-                if (rc < nrow) {
-                    const int k = 64 * rc + lane;
-                    const bool le = k < n && cdf_at(k) <= tz;
-                    klo = 64 * rc + __popcll(__ballot(le)) - 1;
-                }
-                if (klo < 0) klo = 0;
-                // (the six candidates on six lanes, then the first minimum in lane order = in grid order)
-                const int kfirst = max(0, klo - 2), klast = min(n - 1, klo + 3);
-                const int kk = kfirst + lane;
-                double a = 1e300;
-                if (lane < 6 && kk <= klast) a = fabs(cdf_at(kk) / Z - target);
-                int ks = klo;
-                double best = 1e300;
-#pragma unroll
-                for (int l = 0; l < 6; ++l) {
-                    const double al = readlane_f64(a, l);
-                    if (al < best) {
-                        best = al;
-                        ks = kfirst + l;
-                    }
-                }
-                return ks;
-            };
-            // StatsBase.median(|x - x_c|, pweights(p / Z)): the deviations grow with the distance from kc on the uniform
-            // grid; the cumulative weight of the window [kc - jj, kc + jj] comes from the prefix sums and grows with jj: the
-            // same two-level search for the first half-width whose window outweighs half the total.
+            // the selections, written once for this kernel and k_sc_grid (grid_arg_pmax, grid_quantile, grid_wmad above)
+            auto arg_pmax = [&](double& gmax) { return grid_arg_pmax(pmax, kmax, n, red, isel, gmax); };
+            auto quantile = [&](double target) { return grid_quantile(target, Z, n, nrow, isel, cdf_at); };
+            int jtip_unused;
             auto wmad = [&](int kc) {
-                const double xc = g.grid_x[kc];
-                const double mid = 0.5 * (Stot / Z);
-                // (TRIG: no grid value can outweigh half the total unless the bound c_0 + sum |c_m| does - never on a fine grid)
-                if (!TRIG || tbound / Z > mid) {
-                    if constexpr (TRIG) scan_pmax();
-                    double gm;
-                    const int km = arg_pmax(gm);
-                    if (gm / Z > mid) return fabs(g.grid_x[km] - xc);
-                }
-                auto light = [&](int jj) {          // the window of half-width jj does NOT yet outweigh half the total
-                    const int hi = min(n - 1, kc + jj), lo = kc - jj - 1;
-                    const double shi = Sabs(hi), slo = lo >= 0 ? Sabs(lo) : 0.0;
-                    return !((shi - slo) / Z > mid);
-                };
-                const int rc = rows_passing(light);
-                int jhit = n;
-                if (rc < nrow) {
-                    const int jj = 64 * rc + lane;
-                    const unsigned long long bal = __ballot(jj < n && !light(jj));
-                    if (bal) jhit = 64 * rc + (__ffsll((long long)bal) - 1);
-                }
-                if (jhit >= n) return 0.0;
-                // the element that tips the balance is one of the two at distance jhit (whichever exists)
-                const int lo = kc - jhit, hi = kc + jhit;
-                return (lo >= 0) ? fabs(g.grid_x[lo] - xc) : fabs(g.grid_x[min(hi, n - 1)] - xc);
+                return grid_wmad(kc, g.grid_x, Stot, Z, n, nrow, isel, Sabs, [&](double mid, int& km) {
+                    // (TRIG: no grid value can outweigh half the total unless the bound c_0 + sum |c_m| does - never on a fine grid)
+                    if (!TRIG || tbound / Z > mid) {
+                        if constexpr (TRIG) scan_pmax();
+                        double gm;
+                        km = arg_pmax(gm);
+                        return gm / Z > mid;
+                    }
+                    return false;
+                }, jtip_unused);
             };
             int ksel = 0;
             double xsel = 0.0, err = 0.0;
@@ -1735,6 +1779,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 
 #include "mpst_impute_batched.inl"
 #include "mpst_marginal.inl"
+#include "mpst_sitecond.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1947,5 +1992,18 @@ int launch_marginal(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_
     const hipError_t e = v.is_complex ? (v.compute_f32 ? marg_run<float, true>(rt, v, q, ch) : marg_run<double, true>(rt, v, q, ch))
                                       : (v.compute_f32 ? marg_run<float, false>(rt, v, q, ch) : marg_run<double, false>(rt, v, q, ch));
     return e == hipSuccess ? 0 : -1;
+}
+// leave-one-out site conditionals of a chunk: the walk, sixteen instances per workgroup, then the grid phase, a workgroup per
+// (instance, site) pair at a time
+int64_t sitecond_grid_workgroups(int64_t pairs) { return std::max<int64_t>(1, std::min<int64_t>(pairs, 4096)); }
+int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_t mid) {
+    const dim3 wgrid((unsigned)((g.count + SC_B - 1) / SC_B)), ggrid((unsigned)sitecond_grid_workgroups(g.count * v.T));
+    if (v.is_complex) hipLaunchKernelGGL((k_sc_walk<true>), wgrid, dim3(SC_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_sc_walk<false>), wgrid, dim3(SC_T), 0, s, v, g);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (mid) (void)hipEventRecord(mid, s);
+    if (v.is_complex) hipLaunchKernelGGL((k_sc_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_sc_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

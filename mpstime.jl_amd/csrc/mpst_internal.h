@@ -717,6 +717,24 @@ int launch_impute(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t 
 // q.g.missing may be null (nothing missing), q.g.x_out is logp[N][q.nclass], q.work the scratch, v.label is not read
 int64_t marginal_work_elems(int cap, bool cx, bool f32);
 int launch_marginal(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_t count, hipStream_t s);
+// leave-one-out site conditionals (k_sc_walk, k_sc_grid; mpst_sitecond.inl): what both kernels take by value, for one chunk of instances
+struct ScArgs {
+    const double* x;            // [N][T] observed values (encoding domain)
+    const double* grid_x;       // [ngrid]
+    const double* grid_phi;     // [ngrid][d] or [T][ngrid][d] (pairs: complex)
+    int64_t grid_site_stride;
+    const double* levels;       // [nq]
+    double *nll, *pit, *med, *err, *q;      // [N][T] ([N][T][nq]); null: skipped
+    double* amp;                // [chunk][T][d + 1] (pairs): a_t[s], then conj(phi_t) . a_t
+    double* lrows;              // [workgroups][T][16][cap] (pairs)
+    double *pbuf, *sbuf;        // [grid workgroups][ngrid]
+    int64_t first, count;       // the instances of this chunk
+    int ngrid, nq, get_err;
+};
+constexpr int SITECOND_TILE = 16;                           // instances per workgroup of the walk
+int64_t sitecond_grid_workgroups(int64_t pairs);            // workgroups of the grid phase (each owns ngrid doubles of pbuf and sbuf)
+// the walk for the instances g.first .. g.first + g.count, an event, the grid phase; v.label is read, v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_t mid);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin

@@ -469,8 +469,15 @@ class SweepEngine:
         from .marginal import marginal_model
         return marginal_model(self, W, phi, missing, compute=compute, label_site=label_site)
 
+    def site_conditionals(self, W, phi, label_index, x, grid_x, grid_phi, levels=None, get_wmad=True, compute="f64", label_site=None):
+        """mpst_site_conditionals: the leave-one-out conditional p(x_t | x_{!=t}) of every site of every COMPLETE series, each under
+        the class ``label_index[i]``; see ``conditionals.site_conditionals_model``.  Returns (nll, pit, median, err, q, seconds)."""
+        from .conditionals import site_conditionals_model
+        return site_conditionals_model(self, W, phi, label_index, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad, compute=compute,
+                                       label_site=label_site)
+
     def impute_phases(self):
-        """(environment pass, density sweep) device seconds of the last imputation call."""
+        """(environment pass, density sweep) device seconds of the last imputation call; after ``site_conditionals``: (walk, grid phase)."""
         out = np.zeros(2)
         self._chk(self.lib.mpst_get_impute_phases(self.ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return float(out[0]), float(out[1])

@@ -338,6 +338,49 @@ function impute_dist(c::Ptr{Cvoid}, which::Integer, missing::Matrix{UInt8}, xval
     return x, err, q, cdf
 end
 
+# ---- leave-one-out site conditionals ----------------------------------------------------------------------------------------
+struct MpstSiteCondOpts          # mpst_sitecond_opts
+    grid_per_site::Int32         # 0: xvals_enc (d, ngrid) shared by all sites, 1: (d, ngrid, T), one table per site
+    get_err::Int32
+    nq::Int32
+    reserved::Int32
+    levels::Ptr{Float64}
+end
+
+"""
+    site_conditionals(sites, chi, label_site, phi, label_idx, x, xvals, xvals_enc; get_err, levels, device)
+
+For every COMPLETE series of `phi` ((d, T, N), its values `x` (T, N) in the encoding's domain) and every site t the distribution of
+x_t given all the other values, under the class MPS of its label (`mpst_site_conditionals`; arguments as `impute_batch` takes them,
+`xvals_enc` (d, ngrid) or (d, ngrid, T)).  Returns `(nll, pit, median, err, q)`: (T, N) arrays - the negative log conditional
+density at the observed value, the PIT, the median imputer's value and its WMAD - and `q` (nq, T, N) the grid value at every level
+(`nothing` without `levels`).
+"""
+function site_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::Integer, phi::Array, label_idx::Vector{Int32},
+                           x::Matrix{Float64}, xvals::Vector{Float64}, xvals_enc::Array;
+                           get_err::Bool=true, levels::Union{Nothing,Vector{Float64}}=nothing, device::Integer=0)
+    d, T, N = size(phi)
+    cx = eltype(phi) <: Complex
+    nq = levels === nothing ? 0 : length(levels)
+    nll = zeros(Float64, T, N); pit = zeros(Float64, T, N); med = zeros(Float64, T, N); err = zeros(Float64, T, N)
+    q = nq > 0 ? zeros(Float64, nq, T, N) : nothing
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        o = Ref(MpstSiteCondOpts(ndims(xvals_enc) == 3 ? 1 : 0, get_err ? 1 : 0, nq, 0, nq > 0 ? pointer(levels) : Ptr{Float64}(C_NULL)))
+        GC.@preserve sites ptrs chi phi label_idx levels o begin
+            model = Ref(MpstImputeModel(N, T, d, maximum(label_idx) + 1, label_site - 1, cx ? 1 : 0, 0,
+                                        pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)), pointer(label_idx)))
+            check(c, ccall((:mpst_site_conditionals, LIB), Cint,
+                           (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Float64},
+                            Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                           c, model, x, xvals, xvals_enc, length(xvals), Base.unsafe_convert(Ptr{Cvoid}, o), nll, pit, med, err,
+                           nq > 0 ? pointer(q) : C_NULL, secs))
+        end
+    end
+    return nll, pit, med, err, q
+end
+
 # ---- entanglement analysis (src/Analysis/analyse.jl) ---------------------------------------------------------------------
 const MPST_ERR_DOMAIN = -6
 
