@@ -478,7 +478,8 @@ int  mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, doub
 
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),
- * [1] the sweep with the densities and selections (k_imp_left). */
+ * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
+ * mpst_marginal_model, which has one kernel: (its device seconds, 0). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid

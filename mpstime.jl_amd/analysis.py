@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib as L
 from .encodings import fit_encoding_from_training_data, transform_test_data, transform_train_data
-from .engine import SweepEngine, _site_to_abi
+from .engine import SweepEngine, label_site_of, model_to_abi
 from .options import safe_options
 
 _LOGS = {"log": 1.0, "log2": 1.0 / math.log(2.0), "log10": 1.0 / math.log(10.0)}
@@ -41,19 +41,8 @@ class _Model:
         mps = W.mps if hasattr(W, "mps") else W
         if any(np.iscomplexobj(t) for t in mps):
             raise ValueError("entanglement analysis of a complex-valued MPS is not supported (the reference computes it in Float64 only)")
-        label = [j for j, t in enumerate(mps) if np.ndim(t) == 4]
-        if len(label) != 1:
-            raise ValueError("exactly one site must carry the label index")
-        self.T, self.label_site = len(mps), label[0]
-        self.C, self.d = int(mps[self.label_site].shape[3]), int(mps[0].shape[1])
-        self.chi = np.array([mps[0].shape[0]] + [t.shape[2] for t in mps], dtype=np.int32)
-        self._bufs = [_site_to_abi(t) for t in mps]
-        self._ptrs = (C.c_void_p * self.T)(*[b.ctypes.data for b in self._bufs])
-        self.phi = None if phi is None else np.ascontiguousarray(phi, dtype=np.float64)
-        N = 0 if self.phi is None else self.phi.shape[0]
-        self.struct = L.ImputeModel(N, self.T, self.d, self.C, self.label_site, 0, 0, C.cast(self._ptrs, C.POINTER(C.c_void_p)),
-                                    self.chi.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    None if self.phi is None else self.phi.ctypes.data_as(C.c_void_p), None)
+        self.struct, self._keep = model_to_abi(mps, phi, label_site=label_site_of(mps, ValueError))
+        self.T, self.C = int(self.struct.T), int(self.struct.C)
 
 
 def _check(lib, ctx, rc):
@@ -106,7 +95,7 @@ def see_variation(W, measure_series, cls: int = 0, engine: Optional[SweepEngine]
     if any(np.iscomplexobj(t) for t in mps):
         raise ValueError("entanglement analysis of a complex-valued MPS is not supported (the reference computes it in Float64 only)")
     T = len(mps)
-    Cn = int([t for t in mps if np.ndim(t) == 4][0].shape[3])
+    Cn = int(mps[label_site_of(mps, ValueError)].shape[3])
     if not 0 <= int(cls) < Cn:
         raise ValueError(f"class {cls} out of range: the model has {Cn} classes (0-based)")
     if X.ndim != 2 or X.shape[1] != T:

@@ -22,8 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .engine import SweepEngine, check_levels
-from .marginal import model_struct
+from .engine import SweepEngine, check_levels, model_to_abi
 
 
 @dataclass
@@ -48,7 +47,7 @@ def site_conditionals_model(eng: SweepEngine, W, phi, label_index, x, grid_x, gr
         raise ValueError('compute must be "f64" or "f32"')
     cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
     dt = np.complex128 if cx else np.float64
-    model, keep = model_struct([np.asarray(t, dtype=dt) for t in W], np.asarray(phi, dtype=dt), compute, label_site)
+    model, keep = model_to_abi([np.asarray(t, dtype=dt) for t in W], np.asarray(phi, dtype=dt), compute, label_site)
     N, T, d = int(model.N), int(model.T), int(model.d)
     lab = np.ascontiguousarray(label_index, dtype=np.int32)
     xs = np.ascontiguousarray(x, dtype=np.float64)

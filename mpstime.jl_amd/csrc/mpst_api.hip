@@ -1689,19 +1689,27 @@ int mpst_get_encoded(void* ctx, int which, double* phi_out) {
     return 0;
 }
 
+// the chain of an MPS handed over from the host: the label site, the ends, every bond dimension at least 1.  *cap: the largest
+static int check_chain(Ctx* c, const int32_t* chi, int32_t T, int32_t label_site, int* cap) {
+    if (label_site < 0 || label_site >= T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
+    if (chi[0] != 1 || chi[T] != 1) return fail(c, MPST_ERR_INVALID, "chi[0] and chi[T] must be 1");
+    *cap = 1;
+    for (int j = 0; j <= T; ++j) {
+        if (chi[j] < 1) return fail(c, MPST_ERR_INVALID, "chi[%d] < 1", j);
+        *cap = std::max(*cap, (int)chi[j]);
+    }
+    return 0;
+}
+
 int mpst_set_mps(void* ctx, const void* const* site, const int32_t* chi, int32_t T, int32_t label_site) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !site || !chi) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (!c->have_opt) return fail(c, MPST_ERR_INVALID, "call mpst_set_options before mpst_set_mps");
     if (c->T == 0) return fail(c, MPST_ERR_INVALID, "call mpst_set_dataset before mpst_set_mps");
     if (T != c->T) return fail(c, MPST_ERR_INVALID, "MPS has %d sites, data has %d", T, c->T);
-    if (label_site < 0 || label_site >= T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
-    if (chi[0] != 1 || chi[T] != 1) return fail(c, MPST_ERR_INVALID, "chi[0] and chi[T] must be 1");
-    int cap = c->opt.chi_max;
-    for (int j = 0; j <= T; ++j) {
-        if (chi[j] < 1) return fail(c, MPST_ERR_INVALID, "chi[%d] < 1", j);
-        cap = std::max(cap, (int)chi[j]);
-    }
+    int cap = 1;
+    if (int rc = check_chain(c, chi, T, label_site, &cap)) return rc;
+    cap = std::max(cap, (int)c->opt.chi_max);
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     const int d = c->d, C = c->C;
@@ -2197,6 +2205,10 @@ static bool legendre_grid(const double* gx, const double* gp, int n, int d, doub
     return true;
 }
 
+// ---- model queries: imputation, marginal likelihoods, site conditionals ------------------------------------------------------
+// Every query is: validate, get the model onto the device (the context's own, or a host model packed and uploaded for the call), plan
+// the blocks (mpst_query_plan.h), run them through run_blocks.
+
 // One imputation call as the six entry points hand it on: the arrays of the caller (host), the trajectories (mpst_impute_traj /
 // mpst_impute_model_traj: K chains per instance, their uniform numbers from the caller's u or, seeded, from the device generator
 // keyed by seed and row_id) and the distribution outputs (mpst_impute_dist / mpst_impute_model_dist).
@@ -2215,18 +2227,105 @@ struct ImputeRequest {
     int32_t nq = 0, cdf_stride = 0, cdf_rows = 0;
     const double* levels = nullptr;
     double *q_out = nullptr, *cdf_out = nullptr;
-    bool marginal = false;      // mpst_marginal_model: no grid, no options; missing may be NULL; logp_out[N][C]
-    double* logp_out = nullptr;
-    const mpst_sitecond_opts* sc = nullptr;     // mpst_site_conditionals: x_obs[N][T] and the five outputs, each of which may be NULL
-    const double* x_obs = nullptr;
-    double *nll_out = nullptr, *pit_out = nullptr, *med_out = nullptr;      // (the WMAD goes to err_out, the levels to q_out)
-    bool grid_per_site() const { return (o && o->grid_per_site == 1) || (sc && sc->grid_per_site == 1); }      // grid_phi is [T][ngrid][d]
+    bool grid_per_site() const { return o && o->grid_per_site == 1; }      // grid_phi is [T][ngrid][d]
+    ImputeRequest& traj(int32_t K_, int64_t seed_, const int64_t* row_id_) {
+        K = K_, seeded = u == nullptr, seed = (uint64_t)seed_, row_id = row_id_;
+        return *this;
+    }
+    ImputeRequest& dist_outputs(int32_t nq_, const double* levels_, double* q_out_, int32_t cdf_stride_, int32_t cdf_rows_, double* cdf_out_) {
+        dist = true, nq = nq_, levels = levels_, q_out = q_out_, cdf_stride = cdf_stride_, cdf_rows = cdf_rows_, cdf_out = cdf_out_;
+        return *this;
+    }
 };
-constexpr int IMPUTE_MAX_LEVELS = 16;
-// doubles of the grid table(s) a request hands over
-static int64_t impute_grid_doubles(const ImpModel& m, const ImputeRequest& r) {
-    return (int64_t)(r.grid_per_site() ? m.T : 1) * r.ngrid * m.d * (m.is_complex ? 2 : 1);
+// what mpst_impute / _traj / _dist and their _model_ twins have in common
+static ImputeRequest impute_request(const uint8_t* missing, const double* grid_x, const void* grid_phi, int32_t ngrid, const mpst_impute_opts* o,
+                                    const double* u, double* x_out, double* err_out, double* seconds) {
+    ImputeRequest r;
+    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
+    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
+    return r;
 }
+constexpr int IMPUTE_MAX_LEVELS = 16;
+// doubles of the grid table(s) a call hands over
+static int64_t grid_doubles(const ImpModel& m, bool per_site, int32_t ngrid) {
+    return (int64_t)(per_site ? m.T : 1) * ngrid * m.d * (m.is_complex ? 2 : 1);
+}
+
+// the two option checks imputation and site conditionals share
+static int check_grid_per_site(Ctx* c, int32_t v) {
+    if (v != 0 && v != 1) return fail(c, MPST_ERR_INVALID, "grid_per_site must be 0 (grid_phi[ngrid][d]) or 1 (grid_phi[T][ngrid][d]), got %d", (int)v);
+    return 0;
+}
+static int check_levels(Ctx* c, int32_t nq, const double* levels, const double* q_out) {
+    if (nq < 0 || nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)nq);
+    if (nq > 0 && (!levels || !q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
+    for (int l = 0; l < nq; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, levels[l]);
+    return 0;
+}
+
+// the switches and the free memory the plans are cut from (mpst_query_plan.h reads neither itself)
+static const char* chunk_gb_override() { return getenv("MPST_IMPUTE_CHUNK_GB"); }
+static int free_device_bytes(Ctx* c, size_t* free_b) {
+    size_t total_b = 0;
+    HIPC(c, hipMemGetInfo(free_b, &total_b));
+    return 0;
+}
+
+// One timed pass over N instances, `chunk` at a time.  enqueue(i0, count, mid) puts the launches of one block on the stream; with
+// `split` it gets an event to record between its two phases, else null.  The runner owns the events, the final synchronise and
+// error check, *seconds (the whole pass) and the context's impute_phase_s: the two phases summed over the blocks, (seconds, 0) without
+// a split.  Hooks: what a caller does around its blocks - prepare() once inside the timed span, before() / after() each block and
+// outside its phases (own_begin(): a block's first phase starts at an event of its own, not where the block before ended).
+struct NoBlockHooks {
+    bool own_begin() const { return false; }
+    int prepare() { return 0; }
+    int before(int64_t, int64_t) { return 0; }
+    int after(int64_t, int64_t) { return 0; }
+};
+extern "C++" {
+template <typename Enqueue, typename Hooks = NoBlockHooks>
+static int run_blocks(Ctx* c, int64_t N, int64_t chunk, bool split, double* seconds, Enqueue&& enqueue, Hooks&& hooks = Hooks()) {
+    const bool own_begin = split && hooks.own_begin();
+    const size_t per = own_begin ? 3 : 2;       // events of a block: [begin,] mid, end
+    std::vector<DevEvent> evs;
+    auto add_event = [&]() { evs.emplace_back(); return hipEventCreate(&evs.back().h); };
+    HIPC(c, hipEventRecord(c->ev_start, c->stream));
+    if (int rc = hooks.prepare()) return rc;
+    const int rc = for_each_block(N, chunk, [&](int64_t i0, int64_t count) -> int {
+        if (int rb = hooks.before(i0, count)) return rb;
+        if (own_begin) {
+            HIPC(c, add_event());
+            HIPC(c, hipEventRecord(evs.back(), c->stream));
+        }
+        if (split) {
+            HIPC(c, add_event());
+            HIPC(c, add_event());
+        }
+        if (int rl = enqueue(i0, count, split ? evs[evs.size() - 2].h : nullptr)) return rl;
+        if (split) HIPC(c, hipEventRecord(evs.back(), c->stream));
+        return hooks.after(i0, count);
+    });
+    if (rc) return rc;
+    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventSynchronize(c->ev_stop));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    if (seconds) *seconds = 1e-3 * ms;
+    c->impute_phase_s[0] = split ? 0.0 : 1e-3 * ms;
+    c->impute_phase_s[1] = 0.0;
+    for (size_t k = 0; k < evs.size(); k += per) {
+        const hipEvent_t from = own_begin ? evs[k].h : (k == 0 ? c->ev_start : evs[k - 1].h), mid = evs[k + per - 2], end = evs[k + per - 1];
+        float a = 0.f, b = 0.f;
+        HIPC(c, hipEventElapsedTime(&a, from, mid));
+        HIPC(c, hipEventElapsedTime(&b, mid, end));
+        c->impute_phase_s[0] += 1e-3 * a;
+        c->impute_phase_s[1] += 1e-3 * b;
+    }
+    return 0;
+}
+}  // extern "C++"
 
 // what a valid request comes to, and how its instances are dealt out
 struct ImputePlan {
@@ -2241,20 +2340,17 @@ struct ImputePlan {
 static int impute_validate(Ctx* c, const ImpModel& m, const ImputeRequest& r, ImputePlan* p) {
     const mpst_impute_opts* o = r.o;
     if (!r.missing || !r.grid_x || !r.grid_phi || !r.x_out || !o || r.ngrid < 2) return fail(c, MPST_ERR_INVALID, "NULL argument or fewer than 2 grid values");
-    if (o->grid_per_site != 0 && o->grid_per_site != 1) return fail(c, MPST_ERR_INVALID, "grid_per_site must be 0 (grid_phi[ngrid][d]) or 1 (grid_phi[T][ngrid][d]), got %d", (int)o->grid_per_site);
+    if (int rc = check_grid_per_site(c, o->grid_per_site)) return rc;
     if (r.dist) {
         // get_cdfs refuses every other method (imputation.jl:594-596)
         if (o->method != MPST_IMPUTE_MEDIAN) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs are read off the median imputer's distribution: method must be MPST_IMPUTE_MEDIAN");
-        if (r.nq < 0 || r.nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)r.nq);
-        if (r.nq > 0 && (!r.levels || !r.q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
-        for (int l = 0; l < r.nq; ++l)
-            if (!(r.levels[l] > 0.0 && r.levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, r.levels[l]);
+        if (int rc = check_levels(c, r.nq, r.levels, r.q_out)) return rc;
         if (r.cdf_stride < 0 || r.cdf_rows < 0) return fail(c, MPST_ERR_INVALID, "cdf_stride and cdf_rows must not be negative");
         if (r.cdf_stride > 0 && !r.cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_stride > 0 needs cdf_out[N][cdf_rows][ncdf]");
         if (r.cdf_stride == 0 && r.cdf_out) return fail(c, MPST_ERR_INVALID, "cdf_out must be NULL when cdf_stride is 0");
         if (r.K != 1) return fail(c, MPST_ERR_UNSUPPORTED, "levels and cdfs belong to the single-series median call");
     }
-    p->ncdf = r.cdf_stride > 0 ? (int64_t)(r.ngrid - 2) / r.cdf_stride + 2 : 0;
+    p->ncdf = cdf_points(r.ngrid, r.cdf_stride);
     p->cdf_inst = (int64_t)r.cdf_rows * p->ncdf;
     const int method = o->method;
     if (method < MPST_IMPUTE_MEDIAN || method > MPST_IMPUTE_ITS_REJECT) return fail(c, MPST_ERR_INVALID, "unknown imputation method");
@@ -2295,55 +2391,21 @@ static int impute_validate(Ctx* c, const ImpModel& m, const ImputeRequest& r, Im
     return 0;
 }
 
-// Instances are dealt out to workgroups in the order of where their missing sites begin (in the direction of the sweep):
-// workgroups that are resident together then walk the chain in step and find the site tensor the first of them fetched
-// still in the L2 (a 262 KB tensor per site at configs[4], re-read by every instance).  Results do not depend on the order.
-static void impute_plan_order(const ImpModel& m, const ImputeRequest& r, ImputePlan* p) {
-    const int64_t N = m.N, T = m.T;
-    p->order.resize((size_t)N);
-    std::vector<int32_t> key((size_t)N, T);
-    const bool backwards = r.o->order == MPST_IMPUTE_BACKWARDS;
-    for (int64_t i = 0; i < N; ++i) {
-        p->order[i] = (int32_t)i;
-        for (int j = 0; j < T; ++j)
-            if (r.missing[i * T + (backwards ? T - 1 - j : j)]) { key[i] = j; break; }
-    }
-    if (getenv("MPST_IMP_NO_ORDER") == nullptr)
-        std::stable_sort(p->order.begin(), p->order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
-}
-
-// instances are processed in chunks so that the per-instance scratch (environments of the missing sites, p_k and
-// its prefix sums) stays below half of the free device memory, at most 48 GB (MPST_IMPUTE_CHUNK_GB overrides): the
-// 27 GB of environments of configs[4] (8192 instances x 100 missing sites x 32 KB) are one chunk on a 288 GB device,
-// 512 workgroups of the batched sweep instead of seven launches of 82
-static int impute_plan_chunk(Ctx* c, const ImpModel& m, const ImputeRequest& r, size_t free_b, ImputePlan* p) {
-    const int64_t N = m.N, K = r.K;
-    const int T = m.T, zw = m.is_complex ? 2 : 1;
-    const size_t esz = m.compute_f32 ? 4 : 8;
+// instances per launch (mpst_query_plan.h: impute_plan_block), or the verdict that not even a block of one fits
+static int impute_block(Ctx* c, const ImpModel& m, const ImputeRequest& r, size_t free_b, ImputePlan* p) {
     p->welems = impute_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
-    // (per instance: its environments once, p_k and S_k for each of its K chains.  A chunk is a run of whole instances, i.e. of
-    // chunk * K chains; the outputs and uniform numbers of the extra trajectories come out of the same budget)
-    // (the cdf rows of an instance are staged with its block - the block's slots, copied out and scattered after its sweep - so
-    // they are part of per_bytes; the levels' q_out is [N][T][nq] for the whole call, like x_out, and comes off the budget)
-    const int64_t per_bytes = ((int64_t)p->maxm * m.cap * m.cap * zw + p->welems) * (int64_t)esz + 2ll * K * r.ngrid * (int64_t)sizeof(double) +
-                              p->cdf_inst * (int64_t)sizeof(double);
-    double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
-    if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
-    if (K > 1) {
-        const double extra = (double)(N * (K - 1) * T) * (double)sizeof(double) * (2.0 + ((p->sampling && !p->seeded) ? (double)p->ntrial : 0.0));
-        budget = std::max(budget - extra, (double)per_bytes);
-    }
-    if (r.nq > 0) budget = std::max(budget - (double)(N * T * r.nq) * (double)sizeof(double), (double)per_bytes);
-    // (a per-site table is T times the shared one - 128 MB at configs[4] - and lives for the whole call)
-    if (r.grid_per_site()) budget = std::max(budget - (double)impute_grid_doubles(m, r) * (double)sizeof(double), (double)per_bytes);
-    if (r.dist && (double)per_bytes > 0.9 * (double)free_b)       // (the calls without distribution outputs are left as they were)
+    ImputeSizes s{};
+    s.N = m.N, s.K = r.K, s.T = m.T, s.cap = m.cap, s.zw = m.is_complex ? 2 : 1, s.esz = m.compute_f32 ? 4 : 8;
+    s.maxm = p->maxm, s.ngrid = r.ngrid, s.welems = p->welems, s.cdf_inst = p->cdf_inst, s.nq = r.nq;
+    s.u_trials = (p->sampling && !p->seeded) ? p->ntrial : 0;
+    s.site_grid_doubles = r.grid_per_site() ? grid_doubles(m, true, r.ngrid) : 0;
+    s.dist = r.dist;
+    const ImputeBlock b = impute_plan_block(s, free_b, chunk_gb_override());
+    if (b.nomem)
         return fail(c, MPST_ERR_NOMEM, "one instance needs %.3f GB of device scratch (%d environments, densities%s), %.3f GB are free: "
-                    "not even a block of one instance fits", (double)per_bytes / (double)(1ull << 30), p->maxm,
+                    "not even a block of one instance fits", (double)b.per_bytes / (double)(1ull << 30), p->maxm,
                     p->cdf_inst ? ", cdf rows: raise cdf_stride" : "", (double)free_b / (double)(1ull << 30));
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / (double)per_bytes)));
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
-    if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
-    p->chunk = chunk;
+    p->chunk = b.chunk;
     return 0;
 }
 
@@ -2368,7 +2430,7 @@ static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     }
     if (p.cdf_inst > 0 && (rc = dalloc(c, b->cdf, chunk * p.cdf_inst))) return rc;
     if ((rc = dalloc(c, b->miss, N * T)) || (rc = dalloc(c, b->R, (int64_t)(chunk * p.maxm * m.cap * m.cap * zw * esz))) ||
-        (rc = dalloc(c, b->gx, ngrid)) || (rc = dalloc(c, b->gp, impute_grid_doubles(m, r))) || (rc = dalloc(c, b->p, chunk * K * ngrid)) ||
+        (rc = dalloc(c, b->gx, ngrid)) || (rc = dalloc(c, b->gp, grid_doubles(m, r.grid_per_site(), r.ngrid))) || (rc = dalloc(c, b->p, chunk * K * ngrid)) ||
         (rc = dalloc(c, b->S, chunk * K * ngrid)) || (rc = dalloc(c, b->x, N * K * T)) || (rc = dalloc(c, b->e, N * K * T))) return rc;
     if (have_u && (rc = dalloc(c, b->u, N * K * T * p.ntrial))) return rc;
     if (p.seeded && r.row_id) {
@@ -2380,7 +2442,7 @@ static int impute_upload(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     if (p.welems && (rc = dalloc(c, b->W, (int64_t)(chunk * p.welems * esz)))) return rc;
     HIPC(c, hipMemcpy(b->miss, r.missing, (size_t)N * T, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(b->gx, r.grid_x, (size_t)ngrid * sizeof(double), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(b->gp, r.grid_phi, (size_t)impute_grid_doubles(m, r) * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(b->gp, r.grid_phi, (size_t)grid_doubles(m, r.grid_per_site(), r.ngrid) * sizeof(double), hipMemcpyHostToDevice));
     if (have_u) HIPC(c, hipMemcpy(b->u, r.u, (size_t)N * K * T * p.ntrial * sizeof(double), hipMemcpyHostToDevice));
     HIPC(c, hipMemset(b->x, 0, nout * sizeof(double)));
     HIPC(c, hipMemset(b->e, 0, nout * sizeof(double)));
@@ -2435,56 +2497,35 @@ static int impute_params(Ctx* c, const ImpModel& m, const ImputeRequest& r, cons
     return 0;
 }
 
-// The launches, a chunk of instances at a time; the cdf rows of a chunk are staged in its slots and scattered to the caller's array after
-// its sweep.  One event between the two kernels of every chunk: the split of the pass into its environment and density halves
-// (mpst_get_impute_phases) costs nothing against kernels of tens of milliseconds
-static int impute_chunks(Ctx* c, const ImpModel& m, const ImputeRequest& r, const ImputePlan& p, const ImputeParams& q) {
-    const int64_t N = m.N, chunk = p.chunk, cdf_inst = p.cdf_inst;
-    std::vector<double> cdf_stage(cdf_inst > 0 ? (size_t)(chunk * cdf_inst) : 0);
-    std::vector<DevEvent> evs, begins;
-    auto add_event = [](std::vector<DevEvent>& v) { v.emplace_back(); return hipEventCreate(&v.back().h); };
-    for (int64_t i0 = 0; i0 < N; i0 += chunk) {
-        if (cdf_inst > 0) {
-            // rows beyond an instance's missing sites stay zero; the block's own start, so that the copy below is in no phase
-            HIPC(c, hipMemsetAsync(q.g.cdf_out, 0, (size_t)(chunk * cdf_inst) * sizeof(double), c->stream));
-            HIPC(c, add_event(begins));
-            HIPC(c, hipEventRecord(begins.back(), c->stream));
-        }
-        HIPC(c, add_event(evs));
-        const hipEvent_t mid = evs.back();
-        HIPC(c, add_event(evs));
-        const int64_t cnt = std::min(chunk, N - i0);
-        c->impute_batched = launch_impute(m, q, i0, cnt, c->stream, mid);
-        if (c->impute_batched < 0) return fail(c, MPST_ERR_DEVICE, "no imputation kernel is built for this call's route");
-        c->impute_env_wgs += (int)cnt;
-        c->impute_chains += (int)(cnt * r.K);
-        HIPC(c, hipEventRecord(evs.back(), c->stream));
-        if (cdf_inst > 0) {
-            // slot s of the block holds the rows of instance order[i0 + s]
-            HIPC(c, hipMemcpyAsync(cdf_stage.data(), q.g.cdf_out, (size_t)(cnt * cdf_inst) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPC(c, hipStreamSynchronize(c->stream));
-            for (int64_t sl = 0; sl < cnt; ++sl)
-                memcpy(r.cdf_out + (size_t)p.order[i0 + sl] * cdf_inst, cdf_stage.data() + (size_t)sl * cdf_inst, (size_t)cdf_inst * sizeof(double));
-        }
+// What an imputation call does around its blocks (run_blocks).  The kernels' arguments are worked out inside the timed span, as they
+// always were.  The cdf rows of a block are staged in its slots and scattered to the caller's array after its sweep; the block then
+// starts at an event of its own, so that neither the copy nor the clearing of the slots is in a phase.
+struct ImputeHooks {
+    Ctx* c; const ImpModel& m; const ImputeRequest& r; const ImputePlan& p;
+    ImputeBufs* b; ImputeParams* q;
+    std::vector<double> stage;          // the block's cdf rows on the host
+    bool own_begin() const { return p.cdf_inst > 0; }
+    int prepare() {
+        stage.resize(p.cdf_inst > 0 ? (size_t)(p.chunk * p.cdf_inst) : 0);
+        return impute_params(c, m, r, p, b, q);
     }
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipEventSynchronize(c->ev_stop));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    if (r.seconds) *r.seconds = 1e-3 * ms;
-    c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
-    for (size_t k = 0; k < evs.size(); k += 2) {
-        float a = 0.f, b = 0.f;
-        HIPC(c, hipEventElapsedTime(&a, !begins.empty() ? begins[k / 2].h : (k == 0 ? c->ev_start : evs[k - 1].h), evs[k]));
-        HIPC(c, hipEventElapsedTime(&b, evs[k], evs[k + 1]));
-        c->impute_phase_s[0] += 1e-3 * a;
-        c->impute_phase_s[1] += 1e-3 * b;
+    int before(int64_t, int64_t) {      // rows beyond an instance's missing sites stay zero
+        if (p.cdf_inst > 0) HIPC(c, hipMemsetAsync(q->g.cdf_out, 0, (size_t)(p.chunk * p.cdf_inst) * sizeof(double), c->stream));
+        return 0;
     }
-    return 0;
-}
+    int after(int64_t i0, int64_t cnt) {        // slot s of the block holds the rows of instance order[i0 + s]
+        if (p.cdf_inst == 0) return 0;
+        HIPC(c, hipMemcpyAsync(stage.data(), q->g.cdf_out, (size_t)(cnt * p.cdf_inst) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        for (int64_t sl = 0; sl < cnt; ++sl)
+            memcpy(r.cdf_out + (size_t)p.order[i0 + sl] * p.cdf_inst, stage.data() + (size_t)sl * p.cdf_inst, (size_t)p.cdf_inst * sizeof(double));
+        return 0;
+    }
+};
 
-// shared tail of the imputation entry points: option checks, plan, scratch, launches, results
+// shared tail of the imputation entry points: option checks, plan, scratch, launches, results.  One event between the two kernels of
+// every block: the split of the pass into its environment and density halves (mpst_get_impute_phases) costs nothing against kernels
+// of tens of milliseconds
 static int run_impute(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
     ImputePlan p;
     if (int rc = impute_validate(c, m, r, &p)) return rc;
@@ -2493,22 +2534,29 @@ static int run_impute(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
     if (r.cdf_stride > 0) memset(r.cdf_out, 0, (size_t)N * r.cdf_rows * (size_t)p.ncdf * sizeof(double));
     std::vector<double> xo((size_t)N * r.K * T, 0.0), eo(xo.size(), 0.0);           // x_out / err_out: [N][K][T]
     c->impute_env_wgs = c->impute_chains = 0;
-    impute_plan_order(m, r, &p);
+    p.order = impute_plan_order(r.missing, N, T, r.o->order == MPST_IMPUTE_BACKWARDS, getenv("MPST_IMP_NO_ORDER") != nullptr);
     if (p.maxm > 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPC(c, hipMemGetInfo(&free_b, &total_b));
+        size_t free_b = 0;
         ImputeBufs b;
         ImputeParams q{};
         int rc;
-        if ((rc = impute_plan_chunk(c, m, r, free_b, &p)) || (rc = impute_upload(c, m, r, p, &b))) return rc;
-        HIPC(c, hipEventRecord(c->ev_start, c->stream));
-        if ((rc = impute_params(c, m, r, p, &b, &q)) || (rc = impute_chunks(c, m, r, p, q))) return rc;
-        if (const char* e = getenv("MPST_IMB_DBG"); e && (atoi(e) & 8)) {   // lab: phase clocks of the batched sweep (k_imp_leftb, workgroup 0 of the last chunk)
+        if ((rc = free_device_bytes(c, &free_b)) || (rc = impute_block(c, m, r, free_b, &p)) || (rc = impute_upload(c, m, r, p, &b))) return rc;
+        auto enqueue = [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+            c->impute_batched = launch_impute(m, q, i0, cnt, c->stream, mid);
+            if (c->impute_batched < 0) return fail(c, MPST_ERR_DEVICE, "no imputation kernel is built for this call's route");
+            c->impute_env_wgs += (int)cnt;
+            c->impute_chains += (int)(cnt * r.K);
+            return 0;
+        };
+        if ((rc = run_blocks(c, N, p.chunk, true, r.seconds, enqueue, ImputeHooks{c, m, r, p, &b, &q, {}}))) return rc;
+#ifdef MPST_LAB
+        if (const char* e = getenv("MPST_IMB_DBG"); e && (atoi(e) & 8)) {   // phase clocks of the batched sweep (k_imp_leftb, workgroup 0 of the last block)
             double ph[6] = {0, 0, 0, 0, 0, 0};
             HIPC(c, hipMemcpy(ph, b.p, sizeof(ph), hipMemcpyDeviceToHost));
             fprintf(stderr, "[imb] phase A %.0f us, barrier %.0f, B1 %.0f, B2 %.0f, barrier %.0f\n", ph[0] * 0.01, ph[1] * 0.01, ph[2] * 0.01,
                     ph[3] * 0.01, ph[4] * 0.01);
         }
+#endif
         HIPC(c, hipMemcpy(xo.data(), b.x, xo.size() * sizeof(double), hipMemcpyDeviceToHost));
         HIPC(c, hipMemcpy(eo.data(), b.e, eo.size() * sizeof(double), hipMemcpyDeviceToHost));
         if (r.nq > 0) HIPC(c, hipMemcpy(r.q_out, b.q, (size_t)N * T * r.nq * sizeof(double), hipMemcpyDeviceToHost));
@@ -2520,108 +2568,85 @@ static int run_impute(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
     return 0;
 }
 
-// The marginal likelihoods of a request (mpst_marginal_model) on the same plan, buffers and route: no grid, no environments kept, one
-// kernel per chunk of instances; beyond the LDS limit a chunk is what its global scratch lets fit.
+// The marginal likelihoods logp_out[N][C] of the instances under every class (mpst_marginal_model), on the imputation engine's buffers
+// and route: no grid, no environments kept, one kernel per block of instances; missing may be NULL (nothing missing).
 constexpr int MARGINAL_MAX_CLASSES = 16;
-static int run_marginal(Ctx* c, const ImpModel& m, const ImputeRequest& r, int C) {
+static int run_marginal(Ctx* c, const ImpModel& m, const uint8_t* missing, int C, double* logp_out, double* seconds) {
     const int64_t N = m.N;
-    const size_t esz = m.compute_f32 ? 4 : 8;
+    const int esz = m.compute_f32 ? 4 : 8;
     hipError_t ea = impute_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
-    ImputePlan p;
-    p.order.resize((size_t)N);
-    for (int64_t i = 0; i < N; ++i) p.order[i] = (int32_t)i;
-    p.welems = marginal_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
-    p.chunk = std::min<int64_t>(N, (int64_t)1 << 30);
-    if (p.welems) {
-        size_t free_b = 0, total_b = 0;
-        HIPC(c, hipMemGetInfo(&free_b, &total_b));
-        const double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b), per_bytes = (double)p.welems * (double)esz;
-        p.chunk = std::max<int64_t>(1, std::min<int64_t>(p.chunk, (int64_t)(budget / per_bytes)));
-    }
+    const int64_t welems = marginal_work_elems(m.cap, m.is_complex != 0, m.compute_f32 != 0);
+    size_t free_b = 0;
+    int rc;
+    if (welems && (rc = free_device_bytes(c, &free_b))) return rc;
+    const int64_t chunk = marginal_plan_block(N, welems, esz, free_b);
+    std::vector<int32_t> order((size_t)N);
+    for (int64_t i = 0; i < N; ++i) order[i] = (int32_t)i;
     ImputeBufs b;
     ImputeParams q{};
-    int rc;
-    if ((rc = dalloc(c, b.ord, N)) || (rc = dalloc(c, b.x, N * C)) || (r.missing && (rc = dalloc(c, b.miss, N * m.T))) ||
-        (p.welems && (rc = dalloc(c, b.W, (int64_t)(p.chunk * p.welems * esz))))) return rc;
-    HIPC(c, hipMemcpy(b.ord, p.order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (r.missing) HIPC(c, hipMemcpy(b.miss, r.missing, (size_t)N * m.T, hipMemcpyHostToDevice));
+    if ((rc = dalloc(c, b.ord, N)) || (rc = dalloc(c, b.x, N * C)) || (missing && (rc = dalloc(c, b.miss, N * m.T))) ||
+        (welems && (rc = dalloc(c, b.W, (int64_t)(chunk * welems * esz))))) return rc;
+    HIPC(c, hipMemcpy(b.ord, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (missing) HIPC(c, hipMemcpy(b.miss, missing, (size_t)N * m.T, hipMemcpyHostToDevice));
     q.g.missing = b.miss;
     q.g.x_out = b.x;
     q.work = b.W;
     q.order = b.ord;
     q.nclass = C;
-    HIPC(c, hipEventRecord(c->ev_start, c->stream));
-    for (int64_t i0 = 0; i0 < N; i0 += p.chunk)
-        if (launch_marginal(m, q, i0, std::min(p.chunk, N - i0), c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the marginal-likelihood kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_stop));
-    HIPC(c, hipGetLastError());
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    if (r.seconds) *r.seconds = 1e-3 * ms;
-    HIPC(c, hipMemcpy(r.logp_out, b.x, (size_t)N * C * sizeof(double), hipMemcpyDeviceToHost));
+    rc = run_blocks(c, N, chunk, false, seconds, [&](int64_t i0, int64_t cnt, hipEvent_t) {
+        if (launch_marginal(m, q, i0, cnt, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the marginal-likelihood kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    });
+    if (rc) return rc;
+    HIPC(c, hipMemcpy(logp_out, b.x, (size_t)N * C * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
-// The leave-one-out site conditionals of a request (mpst_site_conditionals): the walk's left rows ([T][16][chi] per workgroup of
-// sixteen instances) and the amplitudes are the scratch of a block of instances, cut by free device memory as impute_plan_chunk
-// does; the grid phase keeps ngrid doubles of density and prefix sums per workgroup, whatever the block.
+// One mpst_site_conditionals call: the observed values x_obs[N][T], the grid, and the five outputs, each of which may be NULL
+struct SitecondRequest {
+    const mpst_sitecond_opts* o;
+    const double *x_obs, *grid_x;
+    const void* grid_phi;
+    int32_t ngrid;
+    double *nll_out, *pit_out, *med_out, *err_out, *q_out, *seconds;
+};
+// The leave-one-out site conditionals of a request: the walk's left rows and the amplitudes are the scratch of a block of instances
+// (mpst_query_plan.h: sitecond_plan_block); the grid phase keeps ngrid doubles of density and prefix sums per workgroup, whatever the
+// block.  The phases are the walk and the grid phase.
 constexpr int SITECOND_MAX_CLASSES = 16;
-static int run_sitecond(Ctx* c, const ImpModel& m, const ImputeRequest& r) {
+static int run_sitecond(Ctx* c, const ImpModel& m, const SitecondRequest& r) {
     const int64_t N = m.N, T = m.T;
-    const int zw = m.is_complex ? 2 : 1, nq = r.sc->nq;
-    size_t free_b = 0, total_b = 0;
-    HIPC(c, hipMemGetInfo(&free_b, &total_b));
-    double budget = std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
-    if (const char* e = getenv("MPST_IMPUTE_CHUNK_GB")) budget = std::max(0.001, atof(e)) * (double)(1ull << 30);
-    const double per_bytes = (double)T * (m.cap + m.d + 1) * zw * sizeof(double);
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / per_bytes)));
-    chunk = std::min<int64_t>(chunk, ((int64_t)1 << 30) / T);                                           // (instance, site) pairs in 32 bits
-    if (chunk < N) chunk = std::max<int64_t>(SITECOND_TILE, chunk / SITECOND_TILE * SITECOND_TILE);    // whole workgroups of the walk
-    const int64_t tiles = (chunk + SITECOND_TILE - 1) / SITECOND_TILE, gwgs = sitecond_grid_workgroups(chunk * T);
-    DevBuf<double> dx, gx, gp, lev, nll, pit, med, err, q, amp, lrows, pb, sb;
+    const int zw = m.is_complex ? 2 : 1, nq = r.o->nq;
+    const bool per_site = r.o->grid_per_site == 1;
+    size_t free_b = 0;
     int rc;
-    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, impute_grid_doubles(m, r))) || (rc = dalloc(c, amp, chunk * T * (m.d + 1) * zw)) ||
-        (rc = dalloc(c, lrows, tiles * T * SITECOND_TILE * m.cap * zw)) || (rc = dalloc(c, pb, gwgs * r.ngrid)) || (rc = dalloc(c, sb, gwgs * r.ngrid)) ||
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const SitecondBlock blk = sitecond_plan_block(N, m.T, m.cap, m.d, zw, free_b, chunk_gb_override());
+    const int64_t chunk = blk.chunk;
+    DevBuf<double> dx, gx, gp, lev, nll, pit, med, err, q, amp, lrows, pb, sb;
+    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, grid_doubles(m, per_site, r.ngrid))) || (rc = dalloc(c, amp, chunk * T * (m.d + 1) * zw)) ||
+        (rc = dalloc(c, lrows, blk.tiles * T * SITECOND_TILE * m.cap * zw)) || (rc = dalloc(c, pb, blk.grid_wgs * r.ngrid)) ||
+        (rc = dalloc(c, sb, blk.grid_wgs * r.ngrid)) ||
         (r.pit_out && (rc = dalloc(c, dx, N * T))) || (nq > 0 && ((rc = dalloc(c, lev, nq)) || (rc = dalloc(c, q, N * T * nq)))) ||
         (r.nll_out && (rc = dalloc(c, nll, N * T))) || (r.pit_out && (rc = dalloc(c, pit, N * T))) || (r.med_out && (rc = dalloc(c, med, N * T))) ||
         (r.err_out && (rc = dalloc(c, err, N * T)))) return rc;
     HIPC(c, hipMemcpy(gx, r.grid_x, (size_t)r.ngrid * sizeof(double), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)impute_grid_doubles(m, r) * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)grid_doubles(m, per_site, r.ngrid) * sizeof(double), hipMemcpyHostToDevice));
     if (r.pit_out) HIPC(c, hipMemcpy(dx, r.x_obs, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
-    if (nq > 0) HIPC(c, hipMemcpy(lev, r.sc->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+    if (nq > 0) HIPC(c, hipMemcpy(lev, r.o->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
     ScArgs g{};
     g.x = dx, g.grid_x = gx, g.grid_phi = gp, g.levels = lev;
-    g.grid_site_stride = r.grid_per_site() ? (int64_t)r.ngrid * m.d * zw : 0;
+    g.grid_site_stride = per_site ? (int64_t)r.ngrid * m.d * zw : 0;
     g.nll = nll, g.pit = pit, g.med = med, g.err = err, g.q = q;
     g.amp = amp, g.lrows = lrows, g.pbuf = pb, g.sbuf = sb;
-    g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.sc->get_err ? 1 : 0;
-    std::vector<DevEvent> evs;
-    auto add_event = [&]() { evs.emplace_back(); return hipEventCreate(&evs.back().h); };
-    HIPC(c, hipEventRecord(c->ev_start, c->stream));
-    for (int64_t i0 = 0; i0 < N; i0 += chunk) {
-        g.first = i0, g.count = std::min(chunk, N - i0);
-        HIPC(c, add_event());
-        const hipEvent_t mid = evs.back();
-        HIPC(c, add_event());
+    g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.o->get_err ? 1 : 0;
+    rc = run_blocks(c, N, chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
         if (launch_sitecond(m, g, c->stream, mid) < 0) return fail(c, MPST_ERR_DEVICE, "the site-conditional kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
-        HIPC(c, hipEventRecord(evs.back(), c->stream));
-    }
-    HIPC(c, hipEventRecord(c->ev_stop, c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_stop));
-    HIPC(c, hipGetLastError());
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    if (r.seconds) *r.seconds = 1e-3 * ms;
-    c->impute_phase_s[0] = c->impute_phase_s[1] = 0.0;
-    for (size_t k = 0; k < evs.size(); k += 2) {
-        float a = 0.f, b = 0.f;
-        HIPC(c, hipEventElapsedTime(&a, k == 0 ? c->ev_start : evs[k - 1].h, evs[k]));
-        HIPC(c, hipEventElapsedTime(&b, evs[k], evs[k + 1]));
-        c->impute_phase_s[0] += 1e-3 * a;
-        c->impute_phase_s[1] += 1e-3 * b;
-    }
+        return 0;
+    });
+    if (rc) return rc;
     const size_t nb = (size_t)(N * T) * sizeof(double);
     if (r.nll_out) HIPC(c, hipMemcpy(r.nll_out, nll, nb, hipMemcpyDeviceToHost));
     if (r.pit_out) HIPC(c, hipMemcpy(r.pit_out, pit, nb, hipMemcpyDeviceToHost));
@@ -2656,7 +2681,7 @@ static int check_traj(Ctx* c, const mpst_impute_opts* o, int32_t K) {
     return 0;
 }
 
-// the model of a context's data set
+// imputation on the model of a context's data set
 static int impute_ctx(Ctx* c, int which, const ImputeRequest& r) {
     if (which != MPST_TRAIN && which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 or 1");
     if (!c->have_mps || !c->have_opt) return fail(c, MPST_ERR_INVALID, "mpst_set_options / mpst_set_mps must be called first");
@@ -2674,21 +2699,15 @@ int mpst_impute_dist(void* ctx, int which, const uint8_t* missing, const double*
                      double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.x_out = x_out, r.err_out = err_out, r.seconds = seconds, r.dist = true, r.nq = nq, r.levels = levels, r.q_out = q_out;
-    r.cdf_stride = cdf_stride, r.cdf_rows = cdf_rows, r.cdf_out = cdf_out;
-    return impute_ctx(c, which, r);
+    return impute_ctx(c, which, impute_request(missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds)
+                                    .dist_outputs(nq, levels, q_out, cdf_stride, cdf_rows, cdf_out));
 }
 
 int mpst_impute(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
                 const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
-    return impute_ctx(c, which, r);
+    return impute_ctx(c, which, impute_request(missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds));
 }
 
 int mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double* grid_x, const double* grid_phi, int32_t ngrid,
@@ -2697,11 +2716,7 @@ int mpst_impute_traj(void* ctx, int which, const uint8_t* missing, const double*
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (int rc = check_traj(c, o, K)) return rc;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
-    r.K = K, r.seeded = u == nullptr, r.seed = (uint64_t)seed, r.row_id = row_id;
-    return impute_ctx(c, which, r);
+    return impute_ctx(c, which, impute_request(missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds).traj(K, seed, row_id));
 }
 
 // Host arrays of a model in the boundary layouts (site: (s, l, r[, c]) column-major like mpst_set_mps; phi: [N][T][d]) to
@@ -2732,61 +2747,66 @@ static void pack_model(const mpst_impute_model* h, int cap, int64_t stride, bool
 }
 }  // extern "C++"
 
-// the model from host arrays: packed, uploaded for the call, freed after it
-static int impute_model(Ctx* c, const mpst_impute_model* h, const ImputeRequest& r) {
-    if (!h || !h->site || !h->chi || !h->phi || (!r.marginal && !h->label_idx)) return fail(c, MPST_ERR_INVALID, "NULL argument");
-    if (h->N <= 0 || h->T < 1 || h->d < 1 || h->C < 1) return fail(c, MPST_ERR_INVALID, "empty model or data");
-    if (r.marginal) {
-        if (!r.logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
-        if (h->d > 16 || h->C > MARGINAL_MAX_CLASSES)
-            return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold d <= 16 and C <= %d (got %d, %d)", MARGINAL_MAX_CLASSES, h->d, h->C);
-    }
-    if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
-    if (h->compute != MPST_COMPUTE_F64 && h->compute != MPST_COMPUTE_F32) return fail(c, MPST_ERR_INVALID, "compute must be MPST_COMPUTE_F64 or MPST_COMPUTE_F32");
-    if (h->label_site < 0 || h->label_site >= h->T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
-    if (h->chi[0] != 1 || h->chi[h->T] != 1) return fail(c, MPST_ERR_INVALID, "chi[0] and chi[T] must be 1");
-    int cap = 1;
-    for (int j = 0; j <= h->T; ++j) {
-        if (h->chi[j] < 1) return fail(c, MPST_ERR_INVALID, "chi[%d] < 1", j);
-        cap = std::max(cap, (int)h->chi[j]);
-    }
+// The shape of a host model, for every entry point that takes one: pointers (phi and label_idx where the call reads them), sizes, the
+// label site, the chain's ends, every bond dimension at least 1, every site tensor there.  *cap: the largest bond dimension.  What a
+// call holds beyond that (element types, d, class and chi limits, labels in range) stays with the call.
+static int check_model_shape(Ctx* c, const mpst_impute_model* h, bool need_phi, bool need_labels, int* cap) {
+    if (!h || !h->site || !h->chi || (need_phi && !h->phi) || (need_labels && !h->label_idx)) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (h->T < 1 || h->d < 1 || h->C < 1 || (need_phi && h->N <= 0)) return fail(c, MPST_ERR_INVALID, "empty model or data");
+    if (int rc = check_chain(c, h->chi, h->T, h->label_site, cap)) return rc;
     for (int j = 0; j < h->T; ++j)
         if (!h->site[j]) return fail(c, MPST_ERR_INVALID, "site[%d] is NULL", j);
-    for (int64_t i = 0; i < h->N && !r.marginal; ++i)
+    return 0;
+}
+// what the imputation engine's calls hold of a host model's element types and, where they read them, of its labels
+static int check_model_types(Ctx* c, const mpst_impute_model* h, bool labels) {
+    if (h->dtype != MPST_DTYPE_F64 && h->dtype != MPST_DTYPE_C64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64 or MPST_DTYPE_C64");
+    if (h->compute != MPST_COMPUTE_F64 && h->compute != MPST_COMPUTE_F32) return fail(c, MPST_ERR_INVALID, "compute must be MPST_COMPUTE_F64 or MPST_COMPUTE_F32");
+    for (int64_t i = 0; i < h->N && labels; ++i)
         if (h->label_idx[i] < 0 || h->label_idx[i] >= h->C) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] out of range", (long long)i);
+    return 0;
+}
+
+// A host model on the device for the length of a call: sites, phi, chi, label site and (where asked for) labels, and the view of them
+// the engine reads.
+struct DevModel {
+    DevBuf<uint8_t> sites, phi;
+    DevBuf<int32_t> chi, label_site, labels;
+    ImpModel view{};
+};
+// packs a valid model (boundary layouts to the engine's, mpst_impute_model::compute as the element type) and uploads it
+static int upload_model(Ctx* c, const mpst_impute_model* h, int cap, bool labels, DevModel* dm) {
     const bool cx = h->dtype == MPST_DTYPE_C64, f32 = h->compute == MPST_COMPUTE_F32;
-    if (r.sc) {
-        if (f32) return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
-        if (cap > CAP_LIMIT || h->d > 16 || h->C > SITECOND_MAX_CLASSES)
-            return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, SITECOND_MAX_CLASSES,
-                        cap, h->d, h->C);
-    }
-    if (r.marginal && cap > impute_chi_limit(cx, f32))
-        return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold chi_max <= %d (got %d)", impute_chi_limit(cx, f32), cap);
     HIPC(c, hipSetDevice(c->device));
     const int64_t stride = (int64_t)h->C * cap * h->d * cap;
     const size_t esz = (f32 ? 4 : 8) * (cx ? 2 : 1);
-    DevBuf<uint8_t> dsites, dphi;
-    DevBuf<int32_t> dchi, dls, dlab;
     int rc;
-    if ((rc = dalloc(c, dsites, (int64_t)(stride * h->T * esz))) || (rc = dalloc(c, dphi, (int64_t)(h->N * h->T * h->d * esz))) ||
-        (rc = dalloc(c, dchi, h->T + 1)) || (rc = dalloc(c, dls, 1)) || (!r.marginal && (rc = dalloc(c, dlab, h->N)))) return rc;
+    if ((rc = dalloc(c, dm->sites, (int64_t)(stride * h->T * esz))) || (rc = dalloc(c, dm->phi, (int64_t)(h->N * h->T * h->d * esz))) ||
+        (rc = dalloc(c, dm->chi, h->T + 1)) || (rc = dalloc(c, dm->label_site, 1)) || (labels && (rc = dalloc(c, dm->labels, h->N)))) return rc;
     if (f32) {
         std::vector<float> hs, hp;
         pack_model<float>(h, cap, stride, cx, hs, hp);
-        HIPC(c, hipMemcpy(dsites, hs.data(), hs.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(dphi, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dm->sites, hs.data(), hs.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dm->phi, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
     } else {
         std::vector<double> hs, hp;
         pack_model<double>(h, cap, stride, cx, hs, hp);
-        HIPC(c, hipMemcpy(dsites, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(dphi, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dm->sites, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dm->phi, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    HIPC(c, hipMemcpy(dchi, h->chi, (size_t)(h->T + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(dls, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!r.marginal) HIPC(c, hipMemcpy(dlab, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
-    const ImpModel m{dsites, stride, dchi, dls, dphi, dlab, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
-    return r.marginal ? run_marginal(c, m, r, h->C) : (r.sc ? run_sitecond(c, m, r) : run_impute(c, m, r));
+    HIPC(c, hipMemcpy(dm->chi, h->chi, (size_t)(h->T + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(dm->label_site, &h->label_site, sizeof(int32_t), hipMemcpyHostToDevice));
+    if (labels) HIPC(c, hipMemcpy(dm->labels, h->label_idx, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice));
+    dm->view = ImpModel{dm->sites, stride, dm->chi, dm->label_site, dm->phi, dm->labels, h->N, h->T, h->d, cap, cx ? 1 : 0, f32 ? 1 : 0};
+    return 0;
+}
+
+// imputation on a model from host arrays
+static int impute_host(Ctx* c, const mpst_impute_model* h, const ImputeRequest& r) {
+    int cap = 0, rc;
+    DevModel dm;
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, true)) || (rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_impute(c, dm.view, r);
 }
 
 int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2794,21 +2814,15 @@ int mpst_impute_model_dist(void* ctx, const mpst_impute_model* h, const uint8_t*
                            const double* levels, double* q_out, int32_t cdf_stride, int32_t cdf_rows, double* cdf_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.x_out = x_out, r.err_out = err_out, r.seconds = seconds, r.dist = true, r.nq = nq, r.levels = levels, r.q_out = q_out;
-    r.cdf_stride = cdf_stride, r.cdf_rows = cdf_rows, r.cdf_out = cdf_out;
-    return impute_model(c, h, r);
+    return impute_host(c, h, impute_request(missing, grid_x, grid_phi, ngrid, o, nullptr, x_out, err_out, seconds)
+                                 .dist_outputs(nq, levels, q_out, cdf_stride, cdf_rows, cdf_out));
 }
 
 int mpst_impute_model_run(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
                           int32_t ngrid, const mpst_impute_opts* o, const double* u, double* x_out, double* err_out, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
-    return impute_model(c, h, r);
+    return impute_host(c, h, impute_request(missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds));
 }
 
 int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* grid_x, const void* grid_phi,
@@ -2817,20 +2831,23 @@ int mpst_impute_model_traj(void* ctx, const mpst_impute_model* h, const uint8_t*
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (int rc = check_traj(c, o, K)) return rc;
-    ImputeRequest r;
-    r.missing = missing, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.o = o;
-    r.u = u, r.x_out = x_out, r.err_out = err_out, r.seconds = seconds;
-    r.K = K, r.seeded = u == nullptr, r.seed = (uint64_t)seed, r.row_id = row_id;
-    return impute_model(c, h, r);
+    return impute_host(c, h, impute_request(missing, grid_x, grid_phi, ngrid, o, u, x_out, err_out, seconds).traj(K, seed, row_id));
 }
 
 int mpst_marginal_model(void* ctx, const mpst_impute_model* h, const uint8_t* missing, double* logp_out, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!h || !logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
-    ImputeRequest r;
-    r.missing = missing, r.seconds = seconds, r.marginal = true, r.logp_out = logp_out;
-    return impute_model(c, h, r);
+    int cap = 0, rc;
+    if ((rc = check_model_shape(c, h, true, false, &cap))) return rc;
+    if (h->d > 16 || h->C > MARGINAL_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold d <= 16 and C <= %d (got %d, %d)", MARGINAL_MAX_CLASSES, h->d, h->C);
+    if ((rc = check_model_types(c, h, false))) return rc;
+    const int lim = impute_chi_limit(h->dtype == MPST_DTYPE_C64, h->compute == MPST_COMPUTE_F32);
+    if (cap > lim) return fail(c, MPST_ERR_UNSUPPORTED, "marginal likelihoods hold chi_max <= %d (got %d)", lim, cap);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, false, &dm))) return rc;
+    return run_marginal(c, dm.view, missing, h->C, logp_out, seconds);
 }
 
 int mpst_site_conditionals(void* ctx, const mpst_impute_model* h, const double* x, const double* grid_x, const void* grid_phi, int32_t ngrid,
@@ -2841,35 +2858,30 @@ int mpst_site_conditionals(void* ctx, const mpst_impute_model* h, const double* 
     if (!h || !x || !grid_x || !grid_phi || !o) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (!nll_out && !pit_out && !med_out && !err_out && !q_out) return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
     if (ngrid < 2) return fail(c, MPST_ERR_INVALID, "fewer than 2 grid values");
-    if (o->grid_per_site != 0 && o->grid_per_site != 1) return fail(c, MPST_ERR_INVALID, "grid_per_site must be 0 (grid_phi[ngrid][d]) or 1 (grid_phi[T][ngrid][d]), got %d", (int)o->grid_per_site);
-    if (o->nq < 0 || o->nq > IMPUTE_MAX_LEVELS) return fail(c, MPST_ERR_INVALID, "nq must lie in 0 .. %d (got %d)", IMPUTE_MAX_LEVELS, (int)o->nq);
-    if (o->nq > 0 && (!o->levels || !q_out)) return fail(c, MPST_ERR_INVALID, "nq > 0 needs levels[nq] and q_out[N][T][nq]");
-    for (int l = 0; l < o->nq; ++l)
-        if (!(o->levels[l] > 0.0 && o->levels[l] < 1.0)) return fail(c, MPST_ERR_INVALID, "levels[%d] = %g is not inside (0, 1)", l, o->levels[l]);
+    int cap = 0, rc;
+    if ((rc = check_grid_per_site(c, o->grid_per_site)) || (rc = check_levels(c, o->nq, o->levels, q_out))) return rc;
     if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is conditioned under its own class");
-    ImputeRequest r;
-    r.sc = o, r.x_obs = x, r.grid_x = grid_x, r.grid_phi = grid_phi, r.ngrid = ngrid, r.seconds = seconds;
-    r.nll_out = nll_out, r.pit_out = pit_out, r.med_out = med_out, r.err_out = err_out, r.q_out = o->nq > 0 ? q_out : nullptr;
-    return impute_model(c, h, r);
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, true))) return rc;
+    if (h->compute == MPST_COMPUTE_F32) return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > SITECOND_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "site conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, SITECOND_MAX_CLASSES,
+                    cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_sitecond(c, dm.view, SitecondRequest{o, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out, o->nq > 0 ? q_out : nullptr, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------
 static int analysis_model(Ctx* c, const mpst_impute_model* h, bool need_phi, AnalysisHost* out) {
-    if (!h || !h->site || !h->chi || (need_phi && !h->phi)) return fail(c, MPST_ERR_INVALID, "NULL argument");
-    if (h->T < 1 || h->d < 1 || h->C < 1 || (need_phi && h->N <= 0)) return fail(c, MPST_ERR_INVALID, "empty model or data");
+    int cap = 0;
+    if (int rc = check_model_shape(c, h, need_phi, false, &cap)) return rc;
     if (h->dtype == MPST_DTYPE_C64)
         return fail(c, MPST_ERR_UNSUPPORTED, "entanglement analysis of a complex model: the reference computes it in Float64 only");
     if (h->dtype != MPST_DTYPE_F64) return fail(c, MPST_ERR_INVALID, "dtype must be MPST_DTYPE_F64");
     if (h->compute != MPST_COMPUTE_F64) return fail(c, MPST_ERR_UNSUPPORTED, "entanglement analysis runs in fp64 only (compute = MPST_COMPUTE_F64)");
     if (h->d > 16) return fail(c, MPST_ERR_UNSUPPORTED, "d = %d > 16", h->d);
-    if (h->label_site < 0 || h->label_site >= h->T) return fail(c, MPST_ERR_INVALID, "label_site out of range");
-    if (h->chi[0] != 1 || h->chi[h->T] != 1) return fail(c, MPST_ERR_INVALID, "chi[0] and chi[T] must be 1");
-    for (int j = 0; j <= h->T; ++j) {
-        if (h->chi[j] < 1) return fail(c, MPST_ERR_INVALID, "chi[%d] < 1", j);
+    for (int j = 0; j <= h->T; ++j)
         if (h->chi[j] > 128) return fail(c, MPST_ERR_UNSUPPORTED, "chi[%d] = %d > 128", j, h->chi[j]);
-    }
-    for (int j = 0; j < h->T; ++j)
-        if (!h->site[j]) return fail(c, MPST_ERR_INVALID, "site[%d] is NULL", j);
     *out = AnalysisHost{h->T, h->d, h->C, h->label_site, h->chi, (const double* const*)h->site};
     return 0;
 }

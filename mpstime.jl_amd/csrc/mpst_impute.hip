@@ -1995,7 +1995,6 @@ int launch_marginal(const ImpModel& v, const ImputeParams& q, int64_t i0, int64_
 }
 // leave-one-out site conditionals of a chunk: the walk, sixteen instances per workgroup, then the grid phase, a workgroup per
 // (instance, site) pair at a time
-int64_t sitecond_grid_workgroups(int64_t pairs) { return std::max<int64_t>(1, std::min<int64_t>(pairs, 4096)); }
 int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_t mid) {
     const dim3 wgrid((unsigned)((g.count + SC_B - 1) / SC_B)), ggrid((unsigned)sitecond_grid_workgroups(g.count * v.T));
     if (v.is_complex) hipLaunchKernelGGL((k_sc_walk<true>), wgrid, dim3(SC_T), 0, s, v, g);

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/mpstime_hip.h"
 #include "mpst_dataset_plan.h"
+#include "mpst_query_plan.h"
 
 namespace mpst {
 
@@ -731,8 +732,7 @@ struct ScArgs {
     int64_t first, count;       // the instances of this chunk
     int ngrid, nq, get_err;
 };
-constexpr int SITECOND_TILE = 16;                           // instances per workgroup of the walk
-int64_t sitecond_grid_workgroups(int64_t pairs);            // workgroups of the grid phase (each owns ngrid doubles of pbuf and sbuf)
+// SITECOND_TILE (instances per workgroup of the walk), sitecond_grid_workgroups (workgroups of the grid phase): mpst_query_plan.h
 // the walk for the instances g.first .. g.first + g.count, an event, the grid phase; v.label is read, v.compute_f32 must be 0.  0, or -1 on a launch error
 int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_t mid);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word

@@ -1,0 +1,117 @@
+// The host-side arithmetic of a model query (imputation, marginal likelihoods, site conditionals): the scratch budget, the order in
+// which instances are dealt out, and how many instances one launch takes.  Pure functions in plain C++17, no HIP and no environment:
+// free device memory and the MPST_IMPUTE_CHUNK_GB / MPST_IMP_NO_ORDER switches come in as arguments, which the caller reads.
+// tests/test_query_plan.py compiles it alone; mpst_internal.h includes it for everything else.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <vector>
+
+namespace mpst {
+
+constexpr int SITECOND_TILE = 16;       // instances per workgroup of the site conditionals' walk
+
+// Bytes of per-instance scratch a query may keep on the device at a time: half of the free memory, at most 48 GB; chunk_gb (the text
+// of MPST_IMPUTE_CHUNK_GB, or null) replaces it, with a floor of 0.001 GB.  The 27 GB of environments of configs[4] (8192 instances
+// x 100 missing sites x 32 KB) are one block on a 288 GB device, 512 workgroups of the batched sweep instead of seven launches of 82.
+inline double query_budget(size_t free_b, const char* chunk_gb) {
+    if (chunk_gb) return std::max(0.001, atof(chunk_gb)) * (double)(1ull << 30);
+    return std::min(48.0 * (double)(1ull << 30), 0.5 * (double)free_b);
+}
+
+// cdf points stored per missing site: the grid indices 0, stride, 2 stride, ... and always ngrid - 1 (0: no cdfs asked for)
+inline int64_t cdf_points(int32_t ngrid, int32_t stride) { return stride > 0 ? (int64_t)(ngrid - 2) / stride + 2 : 0; }
+
+// Instances are dealt out to workgroups in the order of where their missing sites begin (in the direction of the sweep):
+// workgroups that are resident together then walk the chain in step and find the site tensor the first of them fetched
+// still in the L2 (a 262 KB tensor per site at configs[4], re-read by every instance).  The key of an instance with nothing
+// missing is T; ties keep the caller's order, and so does everything with keep_caller_order (MPST_IMP_NO_ORDER).  Results do
+// not depend on the order.
+inline std::vector<int32_t> impute_plan_order(const uint8_t* missing, int64_t N, int64_t T, bool backwards, bool keep_caller_order) {
+    std::vector<int32_t> order((size_t)N), key((size_t)N, (int32_t)T);
+    for (int64_t i = 0; i < N; ++i) {
+        order[i] = (int32_t)i;
+        for (int64_t j = 0; j < T; ++j)
+            if (missing[i * T + (backwards ? T - 1 - j : j)]) { key[i] = (int32_t)j; break; }
+    }
+    if (!keep_caller_order) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+    return order;
+}
+
+// what the block of an imputation call is cut from
+struct ImputeSizes {
+    int64_t N, K;               // instances; trajectories per instance
+    int32_t T, cap, zw, esz;    // sites; largest bond dimension; 2 for complex models; bytes of a chain element (4 or 8)
+    int32_t maxm, ngrid;        // most missing sites of an instance; grid values
+    int64_t welems;             // scratch elements per instance of the large-chi environment kernel (mpst_impute.hip: impute_work_elems)
+    int64_t cdf_inst;           // doubles of cdf rows per instance
+    int32_t nq, u_trials;       // levels; uniform numbers per (chain, site) the caller hands over (0: none, or drawn on the device)
+    int64_t site_grid_doubles;  // doubles of a per-site grid table, 0 for the one shared table
+    bool dist;                  // a *_dist call
+};
+struct ImputeBlock {
+    int64_t chunk, per_bytes;   // instances per launch; scratch bytes of one instance
+    bool nomem;                 // a *_dist call of which not even one instance fits: chunk is not set
+};
+// Per instance: its environments once, p_k and S_k for each of its K chains, its cdf rows (staged with its block, copied out and
+// scattered after its sweep).  A block is a run of whole instances, i.e. of chunk * K chains.  What lives for the whole call comes
+// off the budget, never below one instance: the outputs and uniform numbers of the extra trajectories, the levels' q_out [N][T][nq],
+// a per-site table (T times the shared one - 128 MB at configs[4]).
+inline ImputeBlock impute_plan_block(const ImputeSizes& s, size_t free_b, const char* chunk_gb) {
+    const int64_t N = s.N, K = s.K;
+    const double dbl = (double)sizeof(double);
+    ImputeBlock b{0, 0, false};
+    b.per_bytes = ((int64_t)s.maxm * s.cap * s.cap * s.zw + s.welems) * (int64_t)s.esz + 2ll * K * s.ngrid * (int64_t)sizeof(double) +
+                  s.cdf_inst * (int64_t)sizeof(double);
+    const double per = (double)b.per_bytes;
+    double budget = query_budget(free_b, chunk_gb);
+    if (K > 1) budget = std::max(budget - (double)(N * (K - 1) * s.T) * dbl * (2.0 + (double)s.u_trials), per);
+    if (s.nq > 0) budget = std::max(budget - (double)(N * s.T * s.nq) * dbl, per);
+    if (s.site_grid_doubles > 0) budget = std::max(budget - (double)s.site_grid_doubles * dbl, per);
+    if (s.dist && per > 0.9 * (double)free_b) {         // (the calls without distribution outputs are left as they were)
+        b.nomem = true;
+        return b;
+    }
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / per)));
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(1ll << 30) / K));      // the sweep's grid counts chains in 32 bits
+    if (chunk < N && chunk > 4096) chunk &= ~(int64_t)4095;      // whole rounds of 16-instance workgroups on 256 CUs
+    b.chunk = chunk;
+    return b;
+}
+
+// Marginal likelihoods keep no environments: a block is all N instances (at most 2^30) unless the kernel works in global scratch
+// (welems > 0, mpst_impute.hip: marginal_work_elems), which is cut from half of the free memory, at most 48 GB.  MPST_IMPUTE_CHUNK_GB
+// has never applied to this call, and still does not.
+inline int64_t marginal_plan_block(int64_t N, int64_t welems, int32_t esz, size_t free_b) {
+    int64_t chunk = std::min<int64_t>(N, (int64_t)1 << 30);
+    if (welems) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(query_budget(free_b, nullptr) / ((double)welems * (double)esz))));
+    return chunk;
+}
+
+// workgroups of the site conditionals' grid phase (each owns ngrid doubles of pbuf and sbuf), an (instance, site) pair at a time
+inline int64_t sitecond_grid_workgroups(int64_t pairs) { return std::max<int64_t>(1, std::min<int64_t>(pairs, 4096)); }
+
+struct SitecondBlock {
+    int64_t chunk, tiles, grid_wgs;     // instances per launch; workgroups of its walk; workgroups of its grid phase
+};
+// Site conditionals: the walk's left rows ([T][16][chi] per workgroup of sixteen instances) and the amplitudes are the scratch of a
+// block; a block smaller than N is whole workgroups of the walk, at least one.
+inline SitecondBlock sitecond_plan_block(int64_t N, int32_t T, int32_t cap, int32_t d, int32_t zw, size_t free_b, const char* chunk_gb) {
+    const double per_bytes = (double)T * (cap + d + 1) * zw * sizeof(double);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(query_budget(free_b, chunk_gb) / per_bytes)));
+    chunk = std::min<int64_t>(chunk, ((int64_t)1 << 30) / T);                                           // (instance, site) pairs in 32 bits
+    if (chunk < N) chunk = std::max<int64_t>(SITECOND_TILE, chunk / SITECOND_TILE * SITECOND_TILE);
+    return {chunk, (chunk + SITECOND_TILE - 1) / SITECOND_TILE, sitecond_grid_workgroups(chunk * T)};
+}
+
+// the blocks [i0, i0 + count) of N instances, `chunk` at a time; stops at the first non-zero result of f and returns it
+template <typename F>
+inline int for_each_block(int64_t N, int64_t chunk, F&& f) {
+    for (int64_t i0 = 0; i0 < N; i0 += chunk)
+        if (int rc = f(i0, std::min(chunk, N - i0))) return rc;
+    return 0;
+}
+
+}  // namespace mpst

@@ -22,6 +22,36 @@ def _site_to_abi(t, dtype=np.float64):
     return np.asfortranarray(a)
 
 
+def label_site_of(W, error=AssertionError):
+    """index of the one site tensor (Dl, d, Dr, C) that carries the label index"""
+    ls = [j for j, t in enumerate(W) if np.ndim(t) == 4]
+    if len(ls) != 1:
+        raise error("exactly one site must carry the label index")
+    return ls[0]
+
+
+def model_to_abi(W, phi, compute="f64", label_site=None):
+    """(mpst_impute_model, the arrays it points into) of site tensors ``W`` (Dl, d, Dr), the label site (Dl, d, Dr, C), and encoded
+    values ``phi`` (N, T, d), or None for a model without data (N = 0); complex if any of them is.  label_idx is NULL: the callers
+    that have labels set it."""
+    cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi)
+    dt = np.complex128 if cx else np.float64
+    T = len(W)
+    if label_site is None:
+        label_site = label_site_of(W)
+    Cn, d = int(W[label_site].shape[3]), int(W[0].shape[1])
+    chi = np.array([W[0].shape[0]] + [t.shape[2] for t in W], dtype=np.int32)
+    bufs = [_site_to_abi(t, dt) for t in W]
+    ptrs = (C.c_void_p * T)(*[b.ctypes.data for b in bufs])
+    ph = None if phi is None else np.ascontiguousarray(phi, dtype=dt)
+    N = 0 if ph is None else ph.shape[0]
+    assert ph is None or ph.shape == (N, T, d)
+    model = L.ImputeModel(N, T, d, Cn, int(label_site), 1 if cx else 0, {"f64": 0, "f32": 1}[compute],
+                          C.cast(ptrs, C.POINTER(C.c_void_p)), chi.ctypes.data_as(C.POINTER(C.c_int32)),
+                          None if ph is None else ph.ctypes.data_as(C.c_void_p), None)
+    return model, (bufs, ptrs, chi, ph)
+
+
 def _site_from_abi(buf, Dl, d, Dr, Cj):
     shape = (d, Dl, Dr) + ((Cj,) if Cj else ())
     a = np.reshape(buf, shape, order="F")
@@ -268,9 +298,7 @@ class SweepEngine:
     def set_mps(self, W, label_site=None):
         T = len(W)
         if label_site is None:
-            label_site = [j for j, t in enumerate(W) if np.ndim(t) == 4]
-            assert len(label_site) == 1, "exactly one site must carry the label index"
-            label_site = label_site[0]
+            label_site = label_site_of(W)
         chi = np.array([W[0].shape[0]] + [t.shape[2] for t in W], dtype=np.int32)
         bufs = [_site_to_abi(t, self.dtype) for t in W]       # in the context's element type
         ptrs = (C.c_void_p * T)(*[b.ctypes.data for b in bufs])
@@ -433,20 +461,11 @@ class SweepEngine:
         dist = self._dist_args(m, len(grid_x), method, levels, cdf_stride, num_trajectories) if levels is not None or cdf_stride else None
         cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
         dt = np.complex128 if cx else np.float64
-        T = len(W)
-        if label_site is None:
-            label_site = [j for j, t in enumerate(W) if np.ndim(t) == 4]
-            assert len(label_site) == 1, "exactly one site must carry the label index"
-            label_site = label_site[0]
-        Cn = int(W[label_site].shape[3])
-        d = int(W[0].shape[1])
-        chi = np.array([W[0].shape[0]] + [t.shape[2] for t in W], dtype=np.int32)
-        bufs = [_site_to_abi(t, dt) for t in W]
-        ptrs = (C.c_void_p * T)(*[b.ctypes.data for b in bufs])
-        ph = np.ascontiguousarray(phi, dtype=dt)
+        model, keep = model_to_abi(W, np.asarray(phi, dtype=dt), compute, label_site)
+        N, T, d = int(model.N), int(model.T), int(model.d)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
-        N = ph.shape[0]
-        assert ph.shape == (N, T, d) and m.shape == (N, T) and lab.shape == (N,)
+        assert m.shape == (N, T) and lab.shape == (N,)
+        model.label_idx = lab.ctypes.data_as(C.POINTER(C.c_int32))
         gx = np.ascontiguousarray(grid_x, dtype=np.float64)
         gp = np.ascontiguousarray(grid_phi, dtype=dt)
         assert gp.shape in ((len(gx), d), (T, len(gx), d))
@@ -454,9 +473,6 @@ class SweepEngine:
             assert np.size(u) == N * T * (int(max_trials) if int(method) == 4 else 1)
         if mean_basis is None:
             mean_basis = 2 if cx else 1
-        model = L.ImputeModel(N, T, d, Cn, int(label_site), 1 if cx else 0, {"f64": 0, "f32": 1}[compute],
-                              C.cast(ptrs, C.POINTER(C.c_void_p)), chi.ctypes.data_as(C.POINTER(C.c_int32)),
-                              ph.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.POINTER(C.c_int32)))
         args = dict(method=method, order=order, get_wmad=get_wmad, max_trials=max_trials, mean_basis=mean_basis,
                     rejection_threshold=rejection_threshold, u=u, num_trajectories=num_trajectories, seed=seed, row_id=row_id, levels=levels,
                     cdf_stride=cdf_stride)

@@ -242,6 +242,10 @@ struct MpstImputeModel           # mpst_impute_model
     compute::Int32               # 0 fp64, 1 fp32 chain contractions (densities stay fp64)
     site::Ptr{Ptr{Cvoid}}; chi::Ptr{Int32}; phi::Ptr{Cvoid}; label_idx::Ptr{Int32}
 end
+# the mpst_impute_model of packed sites (label_site 0-based; phi / label_idx may be nothing); the caller GC.@preserve's what it points into
+impute_model_ref(ptrs, chi, N, T, d, C, label_site, cx, compute, phi, label_idx) =
+    Ref(MpstImputeModel(N, T, d, C, label_site, cx ? 1 : 0, compute, pointer(ptrs), pointer(chi),
+                        phi === nothing ? C_NULL : Ptr{Cvoid}(pointer(phi)), label_idx === nothing ? Ptr{Int32}(C_NULL) : pointer(label_idx)))
 
 """
     impute_batch(sites, chi, label_site, phi, label_idx, missing, xvals, xvals_enc; method, order, ...)
@@ -279,8 +283,7 @@ function impute_batch(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::In
         x = num_trajectories === nothing ? zeros(Float64, T, N) : zeros(Float64, T, K, N)
         err = zeros(Float64, size(x)...); secs = Ref(0.0)
         GC.@preserve sites ptrs chi phi label_idx begin
-            model = Ref(MpstImputeModel(N, T, d, maximum(label_idx) + 1, label_site - 1, cx ? 1 : 0, compute,
-                                        pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)), pointer(label_idx)))
+            model = impute_model_ref(ptrs, chi, N, T, d, maximum(label_idx) + 1, label_site - 1, cx, compute, phi, label_idx)
             o = Ref(MpstImputeOpts(method, order, get_err ? 1 : 0, max_trials, cx ? 2 : 1, 0, rejection_threshold))
             if levels !== nothing || cdf_stride > 0
                 nq = levels === nothing ? 0 : length(levels)
@@ -369,8 +372,7 @@ function site_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_sit
         ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
         o = Ref(MpstSiteCondOpts(ndims(xvals_enc) == 3 ? 1 : 0, get_err ? 1 : 0, nq, 0, nq > 0 ? pointer(levels) : Ptr{Float64}(C_NULL)))
         GC.@preserve sites ptrs chi phi label_idx levels o begin
-            model = Ref(MpstImputeModel(N, T, d, maximum(label_idx) + 1, label_site - 1, cx ? 1 : 0, 0,
-                                        pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)), pointer(label_idx)))
+            model = impute_model_ref(ptrs, chi, N, T, d, maximum(label_idx) + 1, label_site - 1, cx, 0, phi, label_idx)
             check(c, ccall((:mpst_site_conditionals, LIB), Cint,
                            (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Float64},
                             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
@@ -407,7 +409,7 @@ function entanglement(tm::TrainedMPS; device::Integer=0)
     with_context(device) do c
         ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
         GC.@preserve sites ptrs chi begin
-            model = Ref(MpstImputeModel(0, T, d, C, label_site, 0, 0, pointer(ptrs), pointer(chi), C_NULL, Ptr{Int32}(C_NULL)))
+            model = impute_model_ref(ptrs, chi, 0, T, d, C, label_site, false, 0, nothing, nothing)
             check_analysis(c, ccall((:mpst_entanglement, LIB), Cint, (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{Float64}, Ptr{Float64}),
                                     c, model, bee, see))
         end
@@ -447,8 +449,7 @@ function see_variation(tm::TrainedMPS, measure_series::Matrix, class::Int=0; dev
     with_context(device) do c
         ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
         GC.@preserve sites ptrs chi phi begin
-            model = Ref(MpstImputeModel(N, T, d, C, label_site, 0, 0, pointer(ptrs), pointer(chi), Ptr{Cvoid}(pointer(phi)),
-                                        Ptr{Int32}(C_NULL)))
+            model = impute_model_ref(ptrs, chi, N, T, d, C, label_site, false, 0, phi, nothing)
             check_analysis(c, ccall((:mpst_see_variation, LIB), Cint, (Ptr{Cvoid}, Ref{MpstImputeModel}, Int32, Ptr{Float64}, Ref{Float64}),
                                     c, model, Int32(class), out, secs))
         end

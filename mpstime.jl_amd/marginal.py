@@ -17,33 +17,12 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib as L
 from .encodings import EncodedTimeSeriesSet
-from .engine import SweepEngine, _site_to_abi
+from .engine import SweepEngine, model_to_abi
 from .options import safe_options
 
 
-def model_struct(W, phi, compute="f64", label_site=None):
-    """(mpst_impute_model without label_idx, the arrays it points into) of site tensors ``W`` and encoded values ``phi`` (N, T, d)."""
-    cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi)
-    dt = np.complex128 if cx else np.float64
-    T = len(W)
-    if label_site is None:
-        label_site = [j for j, t in enumerate(W) if np.ndim(t) == 4]
-        assert len(label_site) == 1, "exactly one site must carry the label index"
-        label_site = label_site[0]
-    Cn = int(W[label_site].shape[3])
-    d = int(W[0].shape[1])
-    chi = np.array([W[0].shape[0]] + [t.shape[2] for t in W], dtype=np.int32)
-    bufs = [_site_to_abi(t, dt) for t in W]
-    ptrs = (C.c_void_p * T)(*[b.ctypes.data for b in bufs])
-    ph = np.ascontiguousarray(phi, dtype=dt)
-    N = ph.shape[0]
-    assert ph.shape == (N, T, d)
-    model = L.ImputeModel(N, T, d, Cn, int(label_site), 1 if cx else 0, {"f64": 0, "f32": 1}[compute],
-                          C.cast(ptrs, C.POINTER(C.c_void_p)), chi.ctypes.data_as(C.POINTER(C.c_int32)),
-                          ph.ctypes.data_as(C.c_void_p), None)
-    return model, (bufs, ptrs, chi, ph)
+model_struct = model_to_abi       # (mpst_impute_model without label_idx, the arrays it points into) of (W, phi, compute, label_site)
 
 
 def marginal_model(eng: SweepEngine, W, phi, missing, compute="f64", label_site=None):
