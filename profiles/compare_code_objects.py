@@ -32,7 +32,7 @@ def load(path):
     syms = {}
     for ln in subprocess.check_output([f"{LLVM}/llvm-readelf", "-sW", path], text=True).splitlines():
         f = ln.split()
-        if len(f) == 8 and f[3] in ("FUNC", "OBJECT") and f[6].isdigit():
+        if len(f) == 8 and f[3] in ("FUNC", "OBJECT") and f[6].isdigit() and not f[7].startswith("__hip_cuid_"):   # (named after a hash of the build path)
             name, addr, size, (sec, saddr, soff) = f[7], int(f[1], 16), int(f[2]), secs[int(f[6])]
             off = addr - saddr + soff
             syms[name] = (f[3], b"" if sec == ".bss" else data[off:off + size])
@@ -44,6 +44,13 @@ def load(path):
     return data, syms, kernels
 
 
+def demangle(name):
+    try:
+        return subprocess.check_output(["c++filt", name], text=True).strip()
+    except OSError:
+        return name
+
+
 def main(a_obj, b_obj):
     with tempfile.TemporaryDirectory() as tmp:
         (da, a, ka), (db, b, kb) = load(extract(a_obj, tmp, "a")), load(extract(b_obj, tmp, "b"))
@@ -51,6 +58,12 @@ def main(a_obj, b_obj):
     print(f"symbols: {len(a)} / {len(b)}, same names: {set(a) == set(b)}")
     funcs = [n for n in a if a[n][0] == "FUNC"]
     print(f"functions: {len(funcs)}, with identical code bytes: {sum(1 for n in funcs if n in b and a[n][1] == b[n][1])}")
+    for n in funcs:          # which ones differ, and what of their metadata moved
+        if n in b and a[n][1] != b[n][1]:
+            moved = ", ".join(f"{k} {ka[n].get(k)} -> {kb[n].get(k)}" for k in ka.get(n, {}) if n in kb and ka[n].get(k) != kb[n].get(k))
+            print(f"  differs: {demangle(n)}: {len(a[n][1])} -> {len(b[n][1])} code bytes" + (f"; {moved}" if moved else ""))
+    for n in sorted(set(a) ^ set(b)):
+        print(f"  only in {'the first' if n in a else 'the second'}: {demangle(n)}")
     ok = set(a) == set(b) and all(a[n][1] == b[n][1] for n in funcs)
     for n in a:
         if n in b and a[n][0] == "OBJECT" and a[n][1] != b[n][1]:
