@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -475,11 +475,26 @@ int  mpst_entanglement(void* ctx, const mpst_impute_model* m, double* bee_out, d
  * sites < k; NaN rows where the measured state vanishes).  m->label_idx is ignored.  seconds (may be NULL) = device time.
  * MPST_ERR_DOMAIN names the class, instance, k, site and offending value in mpst_last_error. */
 int  mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, double* out, double* seconds);
+/* Pair analysis of every class MPS (m->N, m->phi, m->label_idx unused): the two-site reduced density matrix rho_ij of every pair of
+ * sites i < j, the physical index of every other site summed out (the convention of mpst_marginal_model; the model's distribution for
+ * encodings orthonormal on the domain).  Entropies S(rho) = -sum over eigenvalues lam > 0 of lam ln lam (of (rho + rho^T) / 2; no
+ * rho_correct, no threshold, no MPST_ERR_DOMAIN).  Each output may be NULL:
+ *   mi_out[C][T][T]   symmetric; [i][j] = S(rho_i) + S(rho_j) - S(rho_ij) off the diagonal, S(rho_i) on it;
+ *   mean_out[C][T]    tr(rho_i O_i), O a real symmetric observable: obs[d][d] (obs_per_site 0) or obs[T][d][d] (1), row-major;
+ *   cov_out[C][T][T]  symmetric; tr(rho_ij (O_i (x) O_j)) - mean_i mean_j off the diagonal, tr(rho_i O_i O_i) - mean_i^2 on it.
+ * A class whose state is zero gives NaN in its slices.  seconds (may be NULL) = device time; mpst_get_impute_phases then gives
+ * (the pair walk k_an_pair, the entropy kernel k_an_pair_ent).  Results do not depend on the free device memory or MPST_IMPUTE_CHUNK_GB.
+ * MPST_ERR_INVALID: all three outputs NULL, mean_out or cov_out with obs NULL, obs_per_site not 0 / 1; MPST_ERR_UNSUPPORTED: a complex
+ * model, MPST_COMPUTE_F32, chi_max > 128, d > 16, mi_out with d > 11 (the pair matrix is d^2 x d^2 and the in-workgroup Jacobi holds
+ * n <= 128; the moments have no such limit).  A rejected call leaves the context as it was. */
+int  mpst_pair_analysis(void* ctx, const mpst_impute_model* m, const double* obs /* [d][d] or [T][d][d]; NULL: no moments */,
+                        int32_t obs_per_site, double* mi_out /* [C][T][T] */, double* mean_out /* [C][T] */,
+                        double* cov_out /* [C][T][T] */, double* seconds /* may be NULL */);
 
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),
  * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
- * mpst_marginal_model, which has one kernel: (its device seconds, 0). */
+ * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid

@@ -16,6 +16,7 @@ from .imputation import (ImputationProblem, init_imputation_problem, MPS_impute,
                          invert_test_transform, get_cdfs)
 from .jld2 import JLD2File, read_jld2, load_trained_mps_jld2
 from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
+from .analysis import PairAnalysis, pair_analysis, position_operator, mutual_information, model_correlations
 from .marginal import log_marginals, class_posteriors
 from .conditionals import SiteConditionals, site_conditionals, anomaly_scores
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
@@ -28,6 +29,7 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "init_imputation_problem", "save_trained_mps", "load_trained_mps", "mps_content_digest", "MPS_impute", "impute_dataset", "kNN_impute", "mar", "invert_test_transform", "get_cdfs",
            "JLD2File", "read_jld2", "load_trained_mps_jld2",
            "DomainError", "bipartite_spectrum", "single_site_spectrum", "see_variation",
+           "PairAnalysis", "pair_analysis", "position_operator", "mutual_information", "model_correlations",
            "classify_batch", "tune", "evaluate", "eval_loss", "fit_batch", "BatchFit", "MPSRandomSearch", "TuningLoss", "ClassificationLoss",
            "MisclassificationRate", "BalancedMisclassificationRate", "ImputationLoss", "make_windows", "make_stratified_cvfolds",
            "classify_many", "log_marginals", "class_posteriors", "SiteConditionals", "site_conditionals", "anomaly_scores"]

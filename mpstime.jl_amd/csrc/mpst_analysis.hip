@@ -15,6 +15,9 @@
 //   4. k_an_see    one thread per rho: cyclic Jacobi (eigenvalues only), rho_correct (:69-91), -sum lambda log lambda.
 //   5. k_an_bee    eigenvalues of L_j (the Schmidt weights across bond j in this gauge: no SVD), one workgroup per bond,
 //                  parallel-ordered Jacobi, -sum p log p over p > 1e-12 (:37-43).
+//   6. k_an_pair   pair analysis, no counterpart in the reference: from the canonical tensors and the L_j of the k = 0
+//                  walk, the two-site reduced density matrix of every pair of sites on the fp64 matrix pipe, its moments under an
+//                  observable as they appear, and (k_an_pair_ent, on the Jacobi sweep k_an_bee uses) its entropy.
 // Real fp64 only, chi <= 128, d <= 16.  No trap or abort on the device: a DomainError of rho_correct is reported through a
 // status word (the smallest failing flat index, atomicMin) and the offending value stored in place of the entropy.
 #include <algorithm>
@@ -26,6 +29,8 @@ namespace mpst {
 namespace {
 
 constexpr int AN_THREADS = 256;
+// k_an_pair: eight waves up to four column tiles (two waves per SIMD, 256 registers each: no scratch), four beyond
+constexpr int pair_threads(int nt) { return nt <= 4 ? 512 : AN_THREADS; }
 constexpr int AN_LDS_LD = 48;                  // leading dimension up to which the walk keeps L, X, L' in LDS (3 ld^2 doubles)
 constexpr double AN_EIGTOL = 1.4901161193847656e-8;     // sqrt(eps()), rho_correct's default
 constexpr int64_t AN_BLOCK_BYTES = 512ll << 20;         // densities + boundary vectors of one block of instances
@@ -318,16 +323,12 @@ __global__ __launch_bounds__(AN_THREADS) void k_an_see(const double* rho, int64_
     see_one<D>(rho + e * D * D, out, e, status);
 }
 
-// eig(L_j), j = 1 + blockIdx.x, by parallel-ordered (round-robin) Jacobi in place; bee[j - 1] = -sum_{p > 1e-12} p log p.
-__global__ __launch_bounds__(AN_THREADS) void k_an_bee(double* Lall, const int32_t* chi, int ld, double* bee) {
-    const int j = 1 + blockIdx.x, tid = threadIdx.x;
-    const int n = chi[j], n2 = n + (n & 1), np = n2 / 2;
-    double* A = Lall + (int64_t)j * ld * ld;
-    __shared__ double cs[64][2];
-    __shared__ int pq[64][2];
-    __shared__ int any;
+// Parallel-ordered (round-robin) Jacobi of the symmetric n x n matrix A (leading dimension ld, n <= 128) in place, by the whole
+// workgroup; the eigenvalues are left on the diagonal.
+__device__ void jacobi_diag(double* A, int n, int ld, double (*cs)[2], int (*pq)[2], int* any) {
+    const int tid = threadIdx.x, n2 = n + (n & 1), np = n2 / 2;
     for (int sweep = 0; sweep < 60 && n > 1; ++sweep) {
-        if (tid == 0) any = 0;
+        if (tid == 0) *any = 0;
         __syncthreads();
         for (int r = 0; r < n2 - 1; ++r) {
             if (tid < np) {
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(AN_THREADS) void k_an_bee(double* Lall, const int32
                         const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
                         c = 1.0 / sqrt(t * t + 1.0);
                         s = t * c;
-                        any = 1;
+                        *any = 1;
                     }
                 }
                 pq[tid][0] = p; pq[tid][1] = q; cs[tid][0] = c; cs[tid][1] = s;
@@ -373,10 +374,21 @@ __global__ __launch_bounds__(AN_THREADS) void k_an_bee(double* Lall, const int32
             }
             __syncthreads();
         }
-        const bool more = any != 0;
+        const bool more = *any != 0;
         __syncthreads();
         if (!more) break;
     }
+}
+
+// eig(L_j), j = 1 + blockIdx.x, in place; bee[j - 1] = -sum_{p > 1e-12} p log p.
+__global__ __launch_bounds__(AN_THREADS) void k_an_bee(double* Lall, const int32_t* chi, int ld, double* bee) {
+    const int j = 1 + blockIdx.x, tid = threadIdx.x;
+    const int n = chi[j];
+    double* A = Lall + (int64_t)j * ld * ld;
+    __shared__ double cs[64][2];
+    __shared__ int pq[64][2];
+    __shared__ int any;
+    jacobi_diag(A, n, ld, cs, pq, &any);
     if (tid == 0) {
         double h = 0.0;
         for (int i = 0; i < n; ++i) {
@@ -385,6 +397,236 @@ __global__ __launch_bounds__(AN_THREADS) void k_an_bee(double* Lall, const int32
             else if (p != p) h = p;
         }
         bee[j - 1] = h;
+    }
+}
+
+// ---- pair analysis: the two-site reduced density matrix of every pair of sites -------------------------------------
+// S of the n x n matrices at M + m n n (m = blockIdx.x; overwritten): (rho + rho^T) / 2, Jacobi, -sum over lam > 0 of lam ln lam.
+// No rho_correct and no threshold: x ln x is continuous at 0.  A NaN eigenvalue gives NaN.
+__global__ __launch_bounds__(AN_THREADS) void k_an_pair_ent(double* M, int n, double* S) {
+    const int tid = threadIdx.x;
+    double* A = M + (int64_t)blockIdx.x * n * n;
+    __shared__ double cs[64][2];
+    __shared__ int pq[64][2];
+    __shared__ int any;
+    for (int e = tid; e < n * n; e += AN_THREADS) {
+        const int r = e / n, c = e % n;
+        if (r < c) {
+            const double v = 0.5 * (A[r * n + c] + A[c * n + r]);
+            A[r * n + c] = v;
+            A[c * n + r] = v;
+        }
+    }
+    __syncthreads();
+    jacobi_diag(A, n, n, cs, pq, &any);
+    if (tid == 0) {
+        double h = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double p = A[(int64_t)i * n + i];
+            if (p > 0.0) h -= p * log(p);
+            else if (p != p) h = p;
+        }
+        S[blockIdx.x] = h;
+    }
+}
+
+// Bp[c][j][s] (ldp x ldp, row l, column r): site tensor j of class c after k_an_canon, zero beyond its bonds
+__global__ __launch_bounds__(AN_THREADS) void k_an_pair_pack(const double* sites, const int32_t* chi, int T, int d, int64_t S, int ldp, double* Bp) {
+    const int j = blockIdx.x, c = blockIdx.y;
+    const int32_t* ch = chi + (int64_t)c * (T + 1);
+    const int cl = ch[j], cr = ch[j + 1];
+    const double* src = sites + ((int64_t)c * T + j) * S;
+    double* dst = Bp + ((int64_t)c * T + j) * d * ldp * ldp;
+    for (int e = threadIdx.x; e < d * ldp * ldp; e += AN_THREADS) {
+        const int s = e / (ldp * ldp), l = (e / ldp) % ldp, r = e % ldp;
+        dst[e] = (l < cl && r < cr) ? src[((int64_t)l * d + s) * cr + r] : 0.0;
+    }
+}
+
+// pairs (i', j) of one class in the rows [i_lo, i) of a chain of T sites
+__host__ __device__ inline int64_t pair_rows_before(int T, int i_lo, int i) {
+    return (int64_t)(i - i_lo) * (T - 1) - ((int64_t)i * (i - 1) / 2 - (int64_t)i_lo * (i_lo - 1) / 2);
+}
+
+struct PairArgs {
+    const double* Bp;           // [C][T][d][ldp][ldp]
+    const int32_t* chi;         // [C][T + 1], as k_an_canon left it
+    const double* Lall;         // [C][T][ldL][ldL]: L_j for j >= 1 (k_an_walk's Lout)
+    const double* obs;          // [T][d][d] or null
+    double* rho;                // [C rows_before(i) + c (T - 1 - i) + j - i - 1][d d][d d] of this block, or null
+    double* craw;               // [C][T][T]: tr(rho_ij O_i (x) O_j), or null
+    double* gws;                // scratch, wg_doubles per workgroup
+    int64_t wg_doubles;
+    int C, T, d, ldL, ld, lde, i_lo, i_hi;
+};
+
+// One chain per (class c, first site i): E^{ss'} = B_i^sT L_i B_i^s' for s <= s', then for j = i + 1 .. T - 1 and every kept block
+// and t':  Y = E^{ss'} B_j^t',  rho_ij[(s,t),(s',t')] = <B_j^t, Y>_F for every t,  E'^{ss'} += B_j^t'T Y.  A wave owns (block, 16
+// columns of Y): the NT row tiles of Y stay in its accumulators, which are the B operand of the second product as they lie (lane l
+// owns rows (l >> 4) + 4 r, the k index of the instruction), so Y is never stored.  The partial Frobenius products of a column tile go
+// to the workgroup's scratch and are added over the tiles in a fixed order: no atomics, and nothing depends on where a chain runs.
+// Blocks are ld x ld (ld a multiple of 4) with row stride lde; rows and columns beyond a bond are exact zeros, because Bp's are.
+template <int NT, bool kLds>
+__global__ __launch_bounds__(pair_threads(NT)) void k_an_pair(PairArgs g) {
+    extern __shared__ double smem[];
+    constexpr int ldp = 16 * NT, PT = pair_threads(NT);
+    __shared__ double red[PT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i16 = lane & 15, kq = lane >> 4;
+    const int T = g.T, d = g.d, ld = g.ld, lde = g.lde, ldL = g.ldL, np = d * (d + 1) / 2, dd = d * d;
+    const int64_t bs = (int64_t)ld * lde, tsz = (int64_t)ldp * ldp;
+    double* ws = g.gws + (int64_t)blockIdx.x * g.wg_doubles;
+    double* fro = ws;                                           // [np][NT][t'][t]
+    double* E = kLds ? smem : ws + (int64_t)np * NT * dd;
+    double* En = E + np * bs;
+    const int64_t nchains = (int64_t)(g.i_hi - g.i_lo) * g.C;
+    for (int64_t q = blockIdx.x; q < nchains; q += gridDim.x) {
+        const int i = g.i_lo + (int)(q / g.C), c = (int)(q % g.C);
+        const int32_t* ch = g.chi + (int64_t)c * (T + 1);
+        const double* Bc = g.Bp + (int64_t)c * T * d * tsz;
+        {   // E^{ss'} of site i (scalar: once per chain)
+            const double* Bi = Bc + (int64_t)i * d * tsz;
+            const int cl = ch[i], cr = ch[i + 1];
+            const double* L = g.Lall + ((int64_t)c * T + i) * ldL * ldL;
+            double* X = En;                                     // X = L_i B_i^s' (cl x cr)
+            for (int sp = 0; sp < d; ++sp) {
+                const double* Bs = Bi + sp * tsz;
+                for (int e = tid; e < cl * cr; e += PT) {
+                    const int a = e / cr, b = e % cr;
+                    double acc = 0.0;
+                    if (i == 0) acc = Bs[b];                    // L_0 = [1]
+                    else
+                        for (int l = 0; l < cl; ++l) acc += L[a * ldL + l] * Bs[l * ldp + b];
+                    X[a * lde + b] = acc;
+                }
+                __syncthreads();
+                for (int s = 0; s <= sp; ++s) {
+                    const double* Bt = Bi + s * tsz;
+                    double* Ep = E + (sp * (sp + 1) / 2 + s) * bs;
+                    for (int e = tid; e < ld * ld; e += PT) {
+                        const int a = e / ld, b = e % ld;
+                        double acc = 0.0;
+                        if (a < cr && b < cr)
+                            for (int l = 0; l < cl; ++l) acc += Bt[l * ldp + a] * X[l * lde + b];
+                        Ep[a * lde + b] = acc;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        const int64_t pair0 = (int64_t)g.C * pair_rows_before(T, g.i_lo, i) + (int64_t)c * (T - 1 - i);
+        for (int j = i + 1; j < T; ++j) {
+            const double* Bj = Bc + (int64_t)j * d * tsz;
+            const bool carry = j + 1 < T;
+            for (int item = wv; item < np * NT; item += PT / 64) {
+                const int p = item / NT, bb = item % NT, col = bb * 16 + i16;
+                const double* Ep = E + p * bs;
+                d4 en[NT];
+#pragma unroll
+                for (int u = 0; u < NT; ++u) en[u] = d4{0.0, 0.0, 0.0, 0.0};
+                for (int tp = 0; tp < d; ++tp) {
+                    const double* Bt = Bj + tp * tsz;
+                    d4 y[NT];
+#pragma unroll
+                    for (int lt = 0; lt < NT; ++lt) {
+                        const int row = lt * 16 + i16;
+                        const bool rok = row < ld;
+                        d4 acc = {0.0, 0.0, 0.0, 0.0};
+                        for (int k0 = 0; k0 < ld; k0 += 4) {
+                            const double a = rok ? Ep[row * lde + k0 + kq] : 0.0;
+                            acc = mfma_f64(a, Bt[(k0 + kq) * ldp + col], acc);
+                        }
+                        y[lt] = acc;
+                    }
+                    for (int t = 0; t < d; ++t) {
+                        const double* Bq = Bj + t * tsz;
+                        double f = 0.0;
+#pragma unroll
+                        for (int lt = 0; lt < NT; ++lt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) f = fma(Bq[(lt * 16 + kq + 4 * r) * ldp + col], y[lt][r], f);
+                        f = wave_sum(f);
+                        if (lane == 0) fro[((int64_t)item * d + tp) * d + t] = f;
+                    }
+                    if (carry) {
+#pragma unroll
+                        for (int at = 0; at < NT; ++at)
+#pragma unroll
+                            for (int lt = 0; lt < NT; ++lt)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) en[at] = mfma_f64(Bt[(lt * 16 + kq + 4 * r) * ldp + at * 16 + i16], y[lt][r], en[at]);
+                    }
+                }
+                if (carry) {
+                    double* Eo = En + p * bs;
+#pragma unroll
+                    for (int at = 0; at < NT; ++at)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = at * 16 + kq + 4 * r;
+                            if (row < ld && col < ld) Eo[row * lde + col] = en[at][r];
+                        }
+                }
+            }
+            __threadfence_block();
+            __syncthreads();
+            // rho_ij and its moment: the column tiles in order; the s > s' entries are the transposed block's
+            double* rout = g.rho ? g.rho + (pair0 + (j - i - 1)) * dd * dd : nullptr;
+            const double* Oi = g.obs ? g.obs + (int64_t)i * dd : nullptr;
+            const double* Oj = g.obs ? g.obs + (int64_t)j * dd : nullptr;
+            double mom = 0.0;
+            for (int e = tid; e < np * dd; e += PT) {
+                const int p = e / dd, tp = (e / d) % d, t = e % d;
+                double v = 0.0;
+                for (int bb = 0; bb < NT; ++bb) v += fro[(((int64_t)p * NT + bb) * d + tp) * d + t];
+                int sp = 0;
+                while ((sp + 1) * (sp + 2) / 2 <= p) ++sp;
+                const int s = p - sp * (sp + 1) / 2;
+                if (rout) {
+                    rout[(int64_t)(s * d + t) * dd + sp * d + tp] = v;
+                    if (s != sp) rout[(int64_t)(sp * d + tp) * dd + s * d + t] = v;
+                }
+                if (Oi) mom += (s == sp ? 1.0 : 2.0) * Oi[s * d + sp] * Oj[t * d + tp] * v;
+            }
+            if (Oi) {
+                mom = wave_sum(mom);
+                if (lane == 0) red[wv] = mom;
+                __syncthreads();
+                if (tid == 0) {
+                    double m = 0.0;
+                    for (int w = 0; w < PT / 64; ++w) m += red[w];
+                    g.craw[((int64_t)c * T + i) * T + j] = m;
+                    g.craw[((int64_t)c * T + j) * T + i] = m;
+                }
+            }
+            double* tmp = E; E = En; En = tmp;
+            __syncthreads();
+        }
+    }
+}
+
+template <int NT>
+hipError_t launch_pair_nt(const PairArgs& g, bool lds, int grid, size_t lds_bytes, hipStream_t s) {
+    if (lds) {
+        if (hipError_t e = hipFuncSetAttribute((const void*)k_an_pair<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PAIR_LDS_BYTES);
+            e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL((k_an_pair<NT, true>), dim3(grid), dim3(pair_threads(NT)), lds_bytes, s, g);
+    } else {
+        hipLaunchKernelGGL((k_an_pair<NT, false>), dim3(grid), dim3(pair_threads(NT)), 0, s, g);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_pair(int nt, const PairArgs& g, bool lds, int grid, size_t lds_bytes, hipStream_t s) {
+    switch (nt) {
+        case 1: return launch_pair_nt<1>(g, lds, grid, lds_bytes, s);
+        case 2: return launch_pair_nt<2>(g, lds, grid, lds_bytes, s);
+        case 3: return launch_pair_nt<3>(g, lds, grid, lds_bytes, s);
+        case 4: return launch_pair_nt<4>(g, lds, grid, lds_bytes, s);
+        case 5: return launch_pair_nt<5>(g, lds, grid, lds_bytes, s);
+        case 6: return launch_pair_nt<6>(g, lds, grid, lds_bytes, s);
+        case 7: return launch_pair_nt<7>(g, lds, grid, lds_bytes, s);
+        default: return launch_pair_nt<8>(g, lds, grid, lds_bytes, s);
     }
 }
 
@@ -585,6 +827,140 @@ hipError_t analysis_see_variation(const AnalysisHost& h, int cls, const double* 
         AN_TRY(hipEventRecord(ev[0], s));
     }
     if (seconds) *seconds = total;
+    return hipSuccess;
+}
+
+hipError_t analysis_pairs(const AnalysisHost& h, const double* obs, bool obs_per_site, size_t free_b, const char* chunk_gb, hipStream_t s,
+                          double* mi, double* mean, double* cov, double* seconds, double* phases) {
+    const int T = h.T, d = h.d, C = h.C, dd = d * d;
+    int cap = 1;
+    for (int j = 0; j <= T; ++j) cap = std::max(cap, (int)h.chi[j]);
+    const int ldL = cap + (cap & 1), nt = pair_tiles(cap), ldp = 16 * nt;
+    const int64_t S = (int64_t)cap * d * cap, mmL = (int64_t)ldL * ldL, npc = (int64_t)T * (T - 1) / 2;     // pairs per class
+    const bool want_mi = mi != nullptr, want_mom = mean || cov;
+    const PairPlan plan = pair_plan(C, T, d, cap, want_mi, AN_BLOCK_BYTES, free_b, chunk_gb);
+    const int nblocks = (int)plan.row0.size() - 1;
+    Bufs bufs;
+    double *sites, *work, *V, *rho1, *Lall, *Bp, *gws, *gwsw = nullptr, *rho = nullptr, *sij = nullptr, *s1 = nullptr, *craw = nullptr, *dobs = nullptr;
+    int32_t* chi;
+    AN_TRY(upload_model(h, 0, C, S, bufs, &sites, &chi, s));
+    AN_TRY(bufs.get(&work, (int64_t)C * 2 * S));
+    AN_TRY(bufs.get(&V, (int64_t)T * ldL));
+    AN_TRY(bufs.get(&rho1, (int64_t)C * T * dd));
+    AN_TRY(bufs.get(&Lall, (int64_t)C * T * mmL));
+    AN_TRY(bufs.get(&Bp, (int64_t)C * T * d * ldp * ldp));
+    AN_TRY(bufs.get(&gws, plan.workgroups * (pair_workgroup_bytes(d, cap) / 8)));
+    if (ldL > AN_LDS_LD) AN_TRY(bufs.get(&gwsw, 3 * mmL));
+    if (want_mi) {
+        AN_TRY(bufs.get(&rho, plan.rho_bytes / 8));
+        AN_TRY(bufs.get(&sij, C * npc));
+        AN_TRY(bufs.get(&s1, (int64_t)C * T));
+    }
+    if (want_mom) {
+        std::vector<double> ho((size_t)T * dd);
+        for (int j = 0; j < T; ++j) std::memcpy(&ho[(size_t)j * dd], obs + (obs_per_site ? (size_t)j * dd : 0), dd * sizeof(double));
+        AN_TRY(bufs.get(&dobs, (int64_t)T * dd));
+        AN_TRY(bufs.get(&craw, (int64_t)C * T * T));
+        AN_TRY(hipMemcpyAsync(dobs, ho.data(), ho.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        AN_TRY(hipStreamSynchronize(s));        // ho leaves scope
+    }
+    std::vector<double> e0(ldL, 0.0);
+    e0[0] = 1.0;
+    AN_TRY(hipMemcpyAsync(V, e0.data(), ldL * sizeof(double), hipMemcpyHostToDevice, s));
+    // events: the call's begin and end, and (begin, middle, end) of every block
+    struct Evs {
+        std::vector<hipEvent_t> e;
+        ~Evs() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
+    } evs;
+    for (int k = 0; k < 2 + 3 * nblocks; ++k) {
+        hipEvent_t x;
+        AN_TRY(hipEventCreate(&x));
+        evs.e.push_back(x);
+    }
+    AN_TRY(hipEventRecord(evs.e[0], s));
+    hipLaunchKernelGGL(k_an_canon, dim3(C), dim3(AN_THREADS), 0, s, sites, chi, T, d, S, work);
+    for (int c = 0; c < C; ++c)
+        launch_walk(sites + (int64_t)c * T * S, chi + (int64_t)c * (T + 1), T, d, S, ldL, V, 1, 1, rho1 + (int64_t)c * T * dd, Lall + (int64_t)c * T * mmL,
+                    gwsw, 1, s);
+    hipLaunchKernelGGL(k_an_pair_pack, dim3(T, C), dim3(AN_THREADS), 0, s, sites, chi, T, d, S, ldp, Bp);
+    AN_TRY(hipGetLastError());
+    std::vector<double> hr1((size_t)C * T * dd);
+    AN_TRY(hipMemcpyAsync(hr1.data(), rho1, hr1.size() * sizeof(double), hipMemcpyDeviceToHost, s));     // before the entropy kernel diagonalises it in place
+    PairArgs g{Bp, chi, Lall, dobs, rho, craw, gws, pair_workgroup_bytes(d, cap) / 8, C, T, d, ldL, pair_ld(cap), pair_stride(cap), 0, 0};
+    int64_t off = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        g.i_lo = plan.row0[b];
+        g.i_hi = plan.row0[b + 1];
+        const int64_t np_b = (int64_t)C * pair_rows_before(T, g.i_lo, g.i_hi), chains = (int64_t)C * (g.i_hi - g.i_lo);
+        AN_TRY(hipEventRecord(evs.e[2 + 3 * b], s));
+        if (T > 1) AN_TRY(launch_pair(nt, g, plan.lds, (int)std::min<int64_t>(plan.workgroups, chains), (size_t)pair_state_bytes(d, cap), s));
+        AN_TRY(hipEventRecord(evs.e[3 + 3 * b], s));
+        if (want_mi) {
+            if (np_b > 0) hipLaunchKernelGGL(k_an_pair_ent, dim3((unsigned)np_b), dim3(AN_THREADS), 0, s, rho, dd, sij + off);
+            if (b == 0) hipLaunchKernelGGL(k_an_pair_ent, dim3(C * T), dim3(AN_THREADS), 0, s, rho1, d, s1);
+        }
+        AN_TRY(hipGetLastError());
+        AN_TRY(hipEventRecord(evs.e[4 + 3 * b], s));
+        off += np_b;
+    }
+    AN_TRY(hipEventRecord(evs.e[1], s));
+    std::vector<double> hsij((size_t)(want_mi ? C * npc : 0)), hs1((size_t)(want_mi ? C * T : 0)), hcr((size_t)(want_mom ? (int64_t)C * T * T : 0));
+    if (want_mi) {
+        if (!hsij.empty()) AN_TRY(hipMemcpyAsync(hsij.data(), sij, hsij.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        AN_TRY(hipMemcpyAsync(hs1.data(), s1, hs1.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (want_mom) AN_TRY(hipMemcpyAsync(hcr.data(), craw, hcr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    AN_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    AN_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    if (seconds) *seconds = ms * 1e-3;
+    phases[0] = phases[1] = 0.0;
+    for (int b = 0; b < nblocks; ++b) {
+        AN_TRY(hipEventElapsedTime(&ms, evs.e[2 + 3 * b], evs.e[3 + 3 * b]));
+        phases[0] += ms * 1e-3;
+        AN_TRY(hipEventElapsedTime(&ms, evs.e[3 + 3 * b], evs.e[4 + 3 * b]));
+        phases[1] += ms * 1e-3;
+    }
+    // the one-site moments and the assembly of the symmetric outputs (C T^2 values) on the host
+    std::vector<double> mu((size_t)T);
+    for (int c = 0; c < C; ++c) {
+        if (want_mi) {
+            double* mo = mi + (size_t)c * T * T;
+            const double* sc = &hs1[(size_t)c * T];
+            int64_t o = 0;
+            for (int b = 0; b < nblocks; ++b) {
+                const int lo = plan.row0[b], hi = plan.row0[b + 1];
+                for (int i = lo; i < hi; ++i) {
+                    const double* row = hsij.data() + o + (int64_t)C * pair_rows_before(T, lo, i) + (int64_t)c * (T - 1 - i);
+                    for (int j = i + 1; j < T; ++j) mo[(size_t)i * T + j] = mo[(size_t)j * T + i] = sc[i] + sc[j] - row[j - i - 1];
+                }
+                o += (int64_t)C * pair_rows_before(T, lo, hi);
+            }
+            for (int i = 0; i < T; ++i) mo[(size_t)i * T + i] = sc[i];
+        }
+        if (want_mom) {
+            for (int i = 0; i < T; ++i) {
+                const double* r = &hr1[((size_t)c * T + i) * dd];
+                const double* O = obs + (obs_per_site ? (size_t)i * dd : 0);
+                double m1 = 0.0, m2 = 0.0;
+                for (int a = 0; a < d; ++a)
+                    for (int bq = 0; bq < d; ++bq) {
+                        double oo = 0.0;
+                        for (int k = 0; k < d; ++k) oo += O[a * d + k] * O[k * d + bq];
+                        const double ra = 0.5 * (r[a * d + bq] + r[bq * d + a]);
+                        m1 += ra * O[a * d + bq];
+                        m2 += ra * oo;
+                    }
+                mu[i] = m1;
+                if (mean) mean[(size_t)c * T + i] = m1;
+                if (cov) cov[((size_t)c * T + i) * T + i] = m2 - m1 * m1;
+            }
+            if (cov)
+                for (int i = 0; i < T; ++i)
+                    for (int j = i + 1; j < T; ++j)
+                        cov[((size_t)c * T + i) * T + j] = cov[((size_t)c * T + j) * T + i] = hcr[((size_t)c * T + i) * T + j] - mu[i] * mu[j];
+        }
+    }
     return hipSuccess;
 }
 

@@ -2920,6 +2920,29 @@ int mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, doubl
     return dm.kind ? analysis_domain(c, dm) : 0;
 }
 
+int mpst_pair_analysis(void* ctx, const mpst_impute_model* m, const double* obs, int32_t obs_per_site, double* mi_out, double* mean_out,
+                       double* cov_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    AnalysisHost h;
+    if (int rc = analysis_model(c, m, false, &h)) return rc;
+    if (!mi_out && !mean_out && !cov_out) return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
+    if ((mean_out || cov_out) && !obs) return fail(c, MPST_ERR_INVALID, "mean_out and cov_out need an observable (obs is NULL)");
+    if (obs_per_site != 0 && obs_per_site != 1)
+        return fail(c, MPST_ERR_INVALID, "obs_per_site must be 0 (obs[d][d]) or 1 (obs[T][d][d]), got %d", (int)obs_per_site);
+    if (mi_out && m->d > 11)
+        return fail(c, MPST_ERR_UNSUPPORTED, "mutual information holds d <= 11 (the pair matrix is d^2 x d^2, the Jacobi n <= 128; got d = %d); "
+                    "the moments have no such limit (mi_out = NULL)", m->d);
+    HIPC(c, hipSetDevice(c->device));
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(c, &free_b)) return rc;
+    double ph[2] = {0.0, 0.0};
+    HIPC(c, analysis_pairs(h, obs, obs_per_site != 0, free_b, chunk_gb_override(), c->stream, mi_out, mean_out, cov_out, seconds, ph));
+    c->impute_phase_s[0] = ph[0];
+    c->impute_phase_s[1] = ph[1];
+    return 0;
+}
+
 int mpst_normalize(void* ctx) {
     Ctx* c = (Ctx*)ctx;
     int rc = check_ready(c);

@@ -766,5 +766,10 @@ int analysis_lds_ld();
 hipError_t analysis_entanglement(const AnalysisHost& h, hipStream_t s, double* bee, double* see, AnalysisDomain* dom);
 hipError_t analysis_see_variation(const AnalysisHost& h, int cls, const double* phi, int64_t N, hipStream_t s, double* out, double* seconds,
                                   AnalysisDomain* dom);
+// Pair analysis: mutual information, mean and covariance of every pair of sites.  obs: [d][d], or [T][d][d] with
+// obs_per_site; each output may be null (mean / cov need obs).  free_b / chunk_gb: what the plan (mpst_query_plan.h: pair_plan) is cut
+// from.  phases[2]: device seconds of k_an_pair and of k_an_pair_ent.
+hipError_t analysis_pairs(const AnalysisHost& h, const double* obs, bool obs_per_site, size_t free_b, const char* chunk_gb, hipStream_t s,
+                          double* mi, double* mean, double* cov, double* seconds, double* phases);
 
 }  // namespace mpst

@@ -106,6 +106,58 @@ inline SitecondBlock sitecond_plan_block(int64_t N, int32_t T, int32_t cap, int3
     return {chunk, (chunk + SITECOND_TILE - 1) / SITECOND_TILE, sitecond_grid_workgroups(chunk * T)};
 }
 
+// ---- pair analysis (mpst_analysis.hip: k_an_pair) ----
+// A chain (class, i) carries d (d + 1) / 2 blocks E^{ss'}, s <= s', each ld x ld with ld = chi_max rounded up to the k-step of the
+// MFMA (4) and a row stride of ld + 4 (LDS banks).  E and the E' of the next site live in LDS while both fit beside the kernel's
+// static LDS; beyond that in global scratch, one region per workgroup.
+constexpr int64_t PAIR_LDS_BYTES = 156 * 1024;         // dynamic LDS of k_an_pair (160 KB less its static part)
+constexpr int PAIR_MAX_WORKGROUPS = 512;
+
+inline int pair_blocks(int d) { return d * (d + 1) / 2; }
+inline int pair_ld(int cap) { return (cap + 3) & ~3; }
+inline int pair_stride(int cap) { return pair_ld(cap) + 4; }
+inline int pair_tiles(int cap) { return (cap + 15) / 16; }       // 16-column tiles of a block
+inline int64_t pair_state_bytes(int d, int cap) { return 2ll * pair_blocks(d) * pair_ld(cap) * pair_stride(cap) * (int64_t)sizeof(double); }
+inline bool pair_state_in_lds(int d, int cap) { return pair_state_bytes(d, cap) <= PAIR_LDS_BYTES; }
+// global scratch of one workgroup: the Frobenius partials of a step, [block][column tile][t'][t], and the state where LDS does not hold it
+inline int64_t pair_workgroup_bytes(int d, int cap) {
+    return (int64_t)pair_blocks(d) * pair_tiles(cap) * d * d * (int64_t)sizeof(double) + (pair_state_in_lds(d, cap) ? 0 : pair_state_bytes(d, cap));
+}
+
+struct PairPlan {
+    bool lds;                       // the carried state lives in LDS
+    int64_t workgroups;             // of k_an_pair, persistent over the C T chains
+    int64_t rho_bytes;              // of the stored rho_ij of the largest block (0 without mutual information)
+    std::vector<int32_t> row0;      // block b is the rows i in [row0[b], row0[b + 1]) of every class: whole rows, at least one
+};
+// The stored rho_ij (d^4 doubles per pair, C (T - 1 - i) pairs in row i) are cut into blocks of whole rows under block_bytes and under
+// an eighth of the query budget; the rest of the budget caps the workgroups through their scratch, never below one.  The model itself
+// (its padded copy included) is not counted, as in the other queries.
+inline PairPlan pair_plan(int C, int T, int d, int cap, bool store_rho, int64_t block_bytes, size_t free_b, const char* chunk_gb) {
+    const double budget = query_budget(free_b, chunk_gb);
+    PairPlan p{pair_state_in_lds(d, cap), 1, 0, {0}};
+    if (store_rho) {
+        const double lim = std::min((double)block_bytes, budget / 8.0);
+        const double pair_b = (double)d * d * d * d * sizeof(double);
+        double acc = 0.0, worst = 0.0;
+        for (int i = 0; i < T; ++i) {
+            const double row = (double)C * (T - 1 - i) * pair_b;
+            if (i > p.row0.back() && acc + row > lim) {
+                p.row0.push_back(i);
+                acc = 0.0;
+            }
+            acc += row;
+            worst = std::max(worst, acc);
+        }
+        p.rho_bytes = (int64_t)worst;
+    }
+    p.row0.push_back(T);
+    const double left = store_rho ? budget * (7.0 / 8.0) : budget;      // a fixed share: the cap is monotone in the budget
+    const int64_t chains = (int64_t)C * T;
+    p.workgroups = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chains, PAIR_MAX_WORKGROUPS), (int64_t)(left / (double)pair_workgroup_bytes(d, cap))));
+    return p;
+}
+
 // the blocks [i0, i0 + count) of N instances, `chunk` at a time; stops at the first non-zero result of f and returns it
 template <typename F>
 inline int for_each_block(int64_t N, int64_t chunk, F&& f) {

@@ -457,4 +457,30 @@ function see_variation(tm::TrainedMPS, measure_series::Matrix, class::Int=0; dev
     return permutedims(out, (3, 2, 1))
 end
 
+"""pair_analysis(tm; observable): mutual information, mean and covariance of every pair of sites of each class MPS
+(mpst_pair_analysis).  `observable`: a symmetric (d, d) matrix for all sites, a (d, d, T) array with one per site, or `nothing`
+(no moments).  Returns (mi, mean, cov): (T, T, C), (T, C) and (T, T, C) arrays, natural log; the diagonal of `mi` holds the
+single-site entropies.  `mi` is `nothing` for d > 11."""
+function pair_analysis(tm::TrainedMPS; observable::Union{Nothing,Array{Float64}}=nothing, device::Integer=0)
+    sites, chi, label_site, label_idx, _ = pack_mps(tm.mps, Float64)
+    T, d, C = length(sites), size(sites[1], 1), dim(label_idx)
+    per_site = observable !== nothing && ndims(observable) == 3
+    obs = observable === nothing ? Float64[] : Array{Float64}(observable)       # symmetric tables: column-major = row-major
+    mi = d <= 11 ? zeros(Float64, T, T, C) : Float64[]
+    mean = zeros(Float64, T, C); cov = zeros(Float64, T, T, C)
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        GC.@preserve sites ptrs chi obs mi mean cov begin
+            model = impute_model_ref(ptrs, chi, 0, T, d, C, label_site, false, 0, nothing, nothing)
+            none = Ptr{Float64}(C_NULL)
+            check_analysis(c, ccall((:mpst_pair_analysis, LIB), Cint,
+                                    (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                                    c, model, observable === nothing ? none : pointer(obs), Int32(per_site), d <= 11 ? pointer(mi) : none,
+                                    observable === nothing ? none : pointer(mean), observable === nothing ? none : pointer(cov), secs))
+        end
+    end
+    return (d <= 11 ? mi : nothing), (observable === nothing ? nothing : mean), (observable === nothing ? nothing : cov)
+end
+
 end # module
