@@ -490,6 +490,24 @@ int  mpst_see_variation(void* ctx, const mpst_impute_model* m, int32_t cls, doub
 int  mpst_pair_analysis(void* ctx, const mpst_impute_model* m, const double* obs /* [d][d] or [T][d][d]; NULL: no moments */,
                         int32_t obs_per_site, double* mi_out /* [C][T][T] */, double* mean_out /* [C][T] */,
                         double* cov_out /* [C][T][T] */, double* seconds /* may be NULL */);
+/* Model overlaps: the inner products of the class states of K models.  With psi_{k,c} the label slice c of model k AS STORED (not
+ * renormalised), G_ab[c, c'] = <psi_{a,c} | psi_{b,c'}> = sum_s conj(psi_{a,c}(s)) psi_{b,c'}(s) for every requested pair (a, b).  The
+ * models agree in T, d, label_site and dtype; their bond dimensions and C may differ.  models[k] is read as mpst_entanglement reads its
+ * model (N, phi, label_idx unused); real and complex models, compute MPST_COMPUTE_F64.
+ *   pairs[P][2]   indices (a, b) into models; NULL: every a <= b in row order ((0,0), (0,1), .., (1,1), ..), K (K + 1) / 2 of them, P ignored
+ *   g_out[P][Cmax][Cmax], lg_out[P]   Cmax = max_k C_k.  Entry [c][c'] of pair p is G_ab[c, c'] = g exp(lg_out[p]), conjugate on a;
+ *                 (re, im) pairs of doubles for MPST_DTYPE_C64; entries beyond C_a x C_b are zero.  The environments are rescaled by an exact
+ *                 power of two at every site and the exponent is kept per pair, so chains of any length neither underflow nor lose bits.
+ *                 An environment that is exactly zero, or a G that is: g = 0, lg = -INFINITY.  Finite inputs never give NaN.
+ *   seconds       device time of the call, may be NULL
+ * The result of a pair depends neither on which other pairs travel along, nor on their order, nor on how the pairs are cut into blocks
+ * (by free device memory or MPST_IMPUTE_CHUNK_GB): no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: NULL models / g_out / lg_out, K < 1, a pair index outside [0, K), models that disagree in T, d, label_site or dtype;
+ * MPST_ERR_UNSUPPORTED: MPST_COMPUTE_F32, chi_max > 128, d > 16, d chi_max > 1024, C > 16.  A rejected call leaves the context as it was. */
+int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, int32_t K,
+                         const int32_t* pairs /* [P][2]; NULL: every a <= b, row order, P ignored */, int32_t P,
+                         double* g_out /* [P][Cmax][Cmax], (re, im) pairs for MPST_DTYPE_C64 */,
+                         double* lg_out /* [P] */, double* seconds /* may be NULL */);
 
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),

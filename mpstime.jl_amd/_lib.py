@@ -123,6 +123,7 @@ SYMBOLS = {
     "mpst_entanglement": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
     "mpst_see_variation": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
     "mpst_pair_analysis": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _i32, _dp, _dp, _dp, _dp]),
+    "mpst_model_overlaps": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, C.POINTER(_i32), _i32, _dp, _dp, _dp]),
     "mpst_get_impute_phases": (C.c_int, [_vp, _dp]),
     "mpst_get_impute_info": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "mpst_selftest_mfma": (C.c_int, [_vp, _dp, _dp, _i32, _dp]),

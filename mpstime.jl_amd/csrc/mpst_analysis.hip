@@ -667,20 +667,6 @@ void launch_walk(const double* sites, const int32_t* chi, int T, int d, int64_t 
 
 int walk_grid(int ld, int64_t nchains) { return (int)std::min<int64_t>(nchains, ld <= AN_LDS_LD ? 1024 : 512); }
 
-// device buffers of one call, freed on every exit
-struct Bufs {
-    std::vector<void*> p;
-    template <typename T>
-    hipError_t get(T** out, int64_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-    ~Bufs() { for (void* q : p) (void)hipFree(q); }
-};
-
 #define AN_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 
 // classes [c0, c0 + nc) of the host model, label slice folded in, to the device layout; chi per class

@@ -2943,6 +2943,49 @@ int mpst_pair_analysis(void* ctx, const mpst_impute_model* m, const double* obs,
     return 0;
 }
 
+// ---- model overlaps (mpst_overlap.hip) ------------------------------------------------------------------------------------
+int mpst_model_overlaps(void* ctx, const mpst_impute_model* models, int32_t K, const int32_t* pairs, int32_t P, double* g_out, double* lg_out,
+                        double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!models || !g_out || !lg_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (K < 1) return fail(c, MPST_ERR_INVALID, "K = %d: at least one model", (int)K);
+    if (pairs && P < 0) return fail(c, MPST_ERR_INVALID, "P = %d is negative", (int)P);
+    const mpst_impute_model& m0 = models[0];
+    OverlapHost h{K, m0.T, m0.d, m0.label_site, m0.dtype == MPST_DTYPE_C64, {}, {}, {}, {}};
+    for (int k = 0; k < K; ++k) {
+        const mpst_impute_model* m = models + k;
+        int cap = 0, rc;
+        if ((rc = check_model_shape(c, m, false, false, &cap)) || (rc = check_model_types(c, m, false))) return rc;
+        if (m->T != m0.T || m->d != m0.d || m->label_site != m0.label_site || m->dtype != m0.dtype)
+            return fail(c, MPST_ERR_INVALID, "model %d disagrees with model 0 in T, d, label site or element type (%d, %d, %d, %d against %d, %d, %d, %d)", k,
+                        m->T, m->d, m->label_site, m->dtype, m0.T, m0.d, m0.label_site, m0.dtype);
+        if (m->compute != MPST_COMPUTE_F64) return fail(c, MPST_ERR_UNSUPPORTED, "model overlaps run in fp64 only (compute = MPST_COMPUTE_F64)");
+        if (cap > CAP_LIMIT || m->d > 16 || m->d * cap > 1024 || m->C > 16)
+            return fail(c, MPST_ERR_UNSUPPORTED, "model overlaps hold chi_max <= %d, d <= 16, d chi_max <= 1024 and C <= 16 (model %d: %d, %d, %d)", CAP_LIMIT,
+                        k, cap, m->d, m->C);
+        h.chi.push_back(m->chi);
+        h.site.push_back(m->site);
+        h.ncls.push_back(m->C);
+    }
+    if (pairs) {
+        for (int64_t q = 0; q < 2ll * P; ++q)
+            if (pairs[q] < 0 || pairs[q] >= K) return fail(c, MPST_ERR_INVALID, "pairs[%lld][%d] = %d outside [0, %d)", (long long)(q / 2), (int)(q % 2), pairs[q], (int)K);
+        h.pairs.assign(pairs, pairs + 2ll * P);
+    } else {
+        for (int a = 0; a < K; ++a)
+            for (int b = a; b < K; ++b) {
+                h.pairs.push_back(a);
+                h.pairs.push_back(b);
+            }
+    }
+    HIPC(c, hipSetDevice(c->device));
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(c, &free_b)) return rc;
+    HIPC(c, model_overlaps(h, free_b, chunk_gb_override(), c->stream, g_out, lg_out, seconds));
+    return 0;
+}
+
 int mpst_normalize(void* ctx) {
     Ctx* c = (Ctx*)ctx;
     int rc = check_ready(c);

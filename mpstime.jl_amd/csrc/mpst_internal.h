@@ -751,6 +751,20 @@ void big_eig_destroy(BigEig* b);
 int launch_eig_big(const View& v, int lid, int going_left, BigEig* b, hipStream_t s);
 int launch_eig_big_raw(const double* G, int n, double* lam, double* E, int32_t* info, BigEig* b, hipStream_t s);
 
+// device buffers of one call of the analysis and overlap entry points, freed on every exit
+struct Bufs {
+    std::vector<void*> p;
+    template <typename T>
+    hipError_t get(T** out, int64_t n) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, (size_t)(n > 1 ? n : 1) * sizeof(T));
+        if (e == hipSuccess) p.push_back(q);
+        *out = (T*)q;
+        return e;
+    }
+    ~Bufs() { for (void* q : p) (void)hipFree(q); }
+};
+
 // mpst_analysis.hip: entanglement analysis (src/Analysis/analyse.jl) of a real model handed over on the host
 struct AnalysisHost {
     int T, d, C, label_site;
@@ -771,5 +785,16 @@ hipError_t analysis_see_variation(const AnalysisHost& h, int cls, const double* 
 // from.  phases[2]: device seconds of k_an_pair and of k_an_pair_ent.
 hipError_t analysis_pairs(const AnalysisHost& h, const double* obs, bool obs_per_site, size_t free_b, const char* chunk_gb, hipStream_t s,
                           double* mi, double* mean, double* cov, double* seconds, double* phases);
+
+// mpst_overlap.hip: inner products of the class states of K models.  The models agree in T, d, label site and element
+// type; pairs: (a, b) indices into them.  g_out[P][Cmax][Cmax] (pairs of doubles when cx), lg_out[P]: G = g exp(lg), conjugate on a.
+struct OverlapHost {
+    int K, T, d, label_site;
+    bool cx;
+    std::vector<const int32_t*> chi;            // [K] -> [T+1]
+    std::vector<const void* const*> site;       // [K] -> [T], ABI layout (s, l, r[, c]), column-major
+    std::vector<int32_t> ncls, pairs;           // [K]; [P][2]
+};
+hipError_t model_overlaps(const OverlapHost& h, size_t free_b, const char* chunk_gb, hipStream_t s, double* g_out, double* lg_out, double* seconds);
 
 }  // namespace mpst

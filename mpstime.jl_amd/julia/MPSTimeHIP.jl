@@ -483,4 +483,37 @@ function pair_analysis(tm::TrainedMPS; observable::Union{Nothing,Array{Float64}}
     return (d <= 11 ? mi : nothing), (observable === nothing ? nothing : mean), (observable === nothing ? nothing : cov)
 end
 
+"""model_overlaps(tms; complex=false): the inner products of the class states of the trained models `tms` (mpst_model_overlaps), which
+agree in length, physical dimension and label site.  Returns (G, lg, pairs): for the k-th pair (a, b) of `pairs` - every a <= b in row
+order, 1-based - `G[c', c, k] * exp(lg[k])` is <psi_{a,c} | psi_{b,c'}> of the label slices as stored (conjugate on a; Cmax x Cmax, zero
+beyond the classes of a and b); `lg[k] == -Inf` where the overlap is exactly zero.  The class overlap matrix of get_training_summary is
+`abs.(G[:, :, 1])` of one model, divided by the norms sqrt.(diag) on both sides."""
+function model_overlaps(tms::Vector{TrainedMPS}; complex::Bool=false, device::Integer=0)
+    E = complex ? ComplexF64 : Float64
+    K = length(tms)
+    packed = [pack_mps(tm.mps, E) for tm in tms]
+    sites = [p[1] for p in packed]; chis = [p[2] for p in packed]
+    T, d, label_site = length(sites[1]), size(sites[1][1], 1), packed[1][3]
+    Cs = [dim(p[4]) for p in packed]
+    Cmax = maximum(Cs)
+    pairs = [(a, b) for a in 1:K for b in a:K]
+    P = length(pairs)
+    G = zeros(E, Cmax, Cmax, P)                     # [c', c, pair] column-major = [pair][c][c'] row-major
+    lg = zeros(Float64, P)
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [[Ptr{Cvoid}(pointer(a)) for a in s] for s in sites]
+        GC.@preserve sites ptrs chis G lg begin
+            models = [MpstImputeModel(0, T, d, Cs[k], label_site, complex ? 1 : 0, 0, pointer(ptrs[k]), pointer(chis[k]), C_NULL, Ptr{Int32}(C_NULL))
+                      for k in 1:K]
+            GC.@preserve models begin
+                check(c, ccall((:mpst_model_overlaps, LIB), Cint,
+                               (Ptr{Cvoid}, Ptr{MpstImputeModel}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                               c, pointer(models), Int32(K), Ptr{Int32}(C_NULL), Int32(0), Ptr{Float64}(pointer(G)), pointer(lg), secs))
+            end
+        end
+    end
+    return G, lg, pairs
+end
+
 end # module
