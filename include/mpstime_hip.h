@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis, mpst_window_conditionals) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -464,6 +464,25 @@ int  mpst_site_conditionals(void* ctx, const mpst_impute_model* m, const double*
                             int32_t ngrid, const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out, double* err_out,
                             double* q_out /* [N][T][nq] */, double* seconds /* may be NULL */);
 
+/* Window conditionals: subsequence anomaly scores of COMPLETE series.  For every series i (class label_idx[i]), every start t and every
+ * width w = 1 .. max_width with t + w <= T,
+ *     nll_out[i][t][w-1] = ln l_c(i; {t, .., t+w-1}) - ln l_c(i; {}),
+ * l_c(i; M) the marginal likelihood of mpst_marginal_model with the sites in M missing: -ln of the Born probability of the window's
+ * values given all the others (for encodings orthonormal on the domain: the negative log conditional density per unit of domain^w).
+ * One walk over each series keeps its left and right rows; each start then runs max_width steps of the density recursion, one per width.
+ *   m           as in mpst_site_conditionals (label_idx required), compute MPST_COMPUTE_F64; all of phi is read
+ *   max_width   1 .. T
+ *   nll_out[N][T][max_width]   entries with t + w > T are NaN; +inf where the amplitude of the complete series vanishes; NaN for a width
+ *               (and the wider ones of its start) whose trace or closing form is not a positive finite number.  Never NaN for a finite,
+ *               non-degenerate input.
+ * seconds (may be NULL): device time of the call; mpst_get_impute_phases then returns (walk, window kernel).  The result of a (series,
+ * start) pair depends neither on how the instances are cut into blocks (free device memory, MPST_IMPUTE_CHUNK_GB) nor on what travels
+ * along: no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: NULL m / nll_out, label_idx NULL or out of range, max_width outside 1..T, non-positive dimensions;
+ * MPST_ERR_UNSUPPORTED: MPST_COMPUTE_F32, chi_max > 128, d > 16, C > 16.  A rejected call leaves the context as it was. */
+int  mpst_window_conditionals(void* ctx, const mpst_impute_model* m, int32_t max_width, double* nll_out /* [N][T][max_width] */,
+                              double* seconds /* may be NULL */);
+
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the
  * label slice of class c, normalised (expand_label_index, utils.jl:356-370).  Natural log throughout.
@@ -512,6 +531,7 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),
  * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
+ * mpst_window_conditionals: (walk, window kernel); after
  * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis

@@ -2656,6 +2656,51 @@ static int run_sitecond(Ctx* c, const ImpModel& m, const SitecondRequest& r) {
     return 0;
 }
 
+// One mpst_window_conditionals call
+struct WindowRequest {
+    int32_t max_width;
+    double *nll_out, *seconds;
+};
+// what a window call does around its blocks: a block's nll is its own on the device and goes to the caller's array after its kernels,
+// outside the phases
+struct WindowHooks {
+    Ctx* c; const WindowRequest& r; double* dev_nll; int64_t per;     // per: doubles of one instance, T * max_width
+    bool own_begin() const { return true; }
+    int prepare() { return 0; }
+    int before(int64_t, int64_t) { return 0; }
+    int after(int64_t i0, int64_t cnt) {
+        HIPC(c, hipMemcpyAsync(r.nll_out + (size_t)(i0 * per), dev_nll, (size_t)(cnt * per) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+// The window conditionals of a request: both rows of the walk and the block's nll are the scratch of a block of instances, the matrices
+// of the window kernel's workgroups beyond the LDS limit come on top (mpst_query_plan.h: window_plan_block).  The phases are the walk
+// and the window kernel.
+constexpr int WINDOW_MAX_CLASSES = 16;
+static int run_window(Ctx* c, const ImpModel& m, const WindowRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const bool big = window_big_route(m.cap, m.is_complex != 0);
+    const WindowBlock blk = window_plan_block(N, m.T, m.cap, zw, r.max_width, big, free_b, chunk_gb_override());
+    DevBuf<double> rows, nll, work;
+    if ((rc = dalloc(c, rows, blk.tiles * 2 * T * SITECOND_TILE * m.cap * zw)) || (rc = dalloc(c, nll, blk.chunk * T * r.max_width)) ||
+        (big && (rc = dalloc(c, work, blk.win_wgs * WINDOW_BIG_MATS * m.cap * m.cap * zw)))) return rc;
+    WinArgs g{};
+    g.lrows = rows, g.nll = nll, g.work = work, g.max_width = r.max_width;
+    return run_blocks(c, N, blk.chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        const int64_t walk_wgs = (cnt + SITECOND_TILE - 1) / SITECOND_TILE, win_wgs = std::min<int64_t>(blk.win_wgs, cnt * T);
+        if (launch_window(m, g, walk_wgs, win_wgs, c->stream, mid) < 0) return fail(c, MPST_ERR_DEVICE, "the window-conditional kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, WindowHooks{c, r, nll, T * r.max_width});
+}
+
 int mpst_get_impute_phases(void* ctx, double* seconds_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !seconds_out) return MPST_ERR_INVALID;
@@ -2869,6 +2914,23 @@ int mpst_site_conditionals(void* ctx, const mpst_impute_model* h, const double* 
     DevModel dm;
     if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
     return run_sitecond(c, dm.view, SitecondRequest{o, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out, o->nq > 0 ? q_out : nullptr, seconds});
+}
+
+int mpst_window_conditionals(void* ctx, const mpst_impute_model* h, int32_t max_width, double* nll_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !nll_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is conditioned under its own class");
+    int cap = 0, rc;
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, true))) return rc;
+    if (max_width < 1 || max_width > h->T) return fail(c, MPST_ERR_INVALID, "max_width must lie in 1 .. T = %d (got %d)", (int)h->T, (int)max_width);
+    if (h->compute == MPST_COMPUTE_F32) return fail(c, MPST_ERR_UNSUPPORTED, "window conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > WINDOW_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "window conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, WINDOW_MAX_CLASSES,
+                    cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_window(c, dm.view, WindowRequest{max_width, nll_out, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

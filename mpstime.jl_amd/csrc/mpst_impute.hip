@@ -1717,6 +1717,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_impute_batched.inl"
 #include "mpst_marginal.inl"
 #include "mpst_sitecond.inl"
+#include "mpst_window.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1733,6 +1734,9 @@ static int impute_lds_chi_limit(bool cx, bool f32) {
 int impute_chi_limit(bool, bool) { return CAP_LIMIT; }
 int64_t impute_work_elems(int cap, bool cx, bool f32) { return cap > impute_lds_chi_limit(cx, f32) ? 4ll * cap * cap * (cx ? 2 : 1) : 0; }
 int64_t marginal_work_elems(int cap, bool cx, bool f32) { return cap > impute_lds_chi_limit(cx, f32) ? (int64_t)MRG_BIG_MATS * cap * cap * (cx ? 2 : 1) : 0; }
+// window conditionals keep three of the environment pass's four matrices in LDS (E, the site matrix, T1)
+static size_t window_lds_bytes(int cap, bool cx) { return right_lds_bytes(cap, cx, false) / 4 * 3; }
+bool window_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
 
 // ---- the route of a call: which kernels, at which block size / occupancy / dynamic LDS -----------------------------------
 struct ImputeSwitches {
@@ -1835,6 +1839,11 @@ hipError_t impute_init_attrs(int device) {
     static std::atomic<unsigned long long> done{0};
     if (device >= 0 && device < 64 && (done.load(std::memory_order_acquire) >> device) & 1ull) return hipSuccess;
     for (hipError_t e : {imp_raise_lds<double, false>(), imp_raise_lds<double, true>(), imp_raise_lds<float, false>(), imp_raise_lds<float, true>()})
+        if (e != hipSuccess) return e;
+    for (hipError_t e : {hipFuncSetAttribute((const void*)k_win<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)window_lds_bytes(impute_lds_chi_limit(false, false), false)),
+                         hipFuncSetAttribute((const void*)k_win<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)window_lds_bytes(impute_lds_chi_limit(true, false), true))})
         if (e != hipSuccess) return e;
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
@@ -1940,6 +1949,25 @@ int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_
     if (mid) (void)hipEventRecord(mid, s);
     if (v.is_complex) hipLaunchKernelGGL((k_sc_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
     else hipLaunchKernelGGL((k_sc_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// window conditionals of a chunk: the walk that keeps both rows, sixteen instances per workgroup, then the window kernel, a workgroup
+// per (instance, start) pair at a time
+int launch_window(const ImpModel& v, const WinArgs& g, int64_t walk_wgs, int64_t win_wgs, hipStream_t s, hipEvent_t mid) {
+    const dim3 wgrid((unsigned)walk_wgs), kgrid((unsigned)win_wgs);
+    if (v.is_complex) hipLaunchKernelGGL((k_win_walk<true>), wgrid, dim3(SC_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_win_walk<false>), wgrid, dim3(SC_T), 0, s, v, g);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (mid) (void)hipEventRecord(mid, s);
+    const bool big = window_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : window_lds_bytes(v.cap, v.is_complex != 0);
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_win<true, true>), kgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_win<true, false>), kgrid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_win<false, true>), kgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_win<false, false>), kgrid, dim3(IMP_T), lds, s, v, g);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

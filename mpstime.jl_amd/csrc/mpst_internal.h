@@ -735,6 +735,19 @@ struct ScArgs {
 // SITECOND_TILE (instances per workgroup of the walk), sitecond_grid_workgroups (workgroups of the grid phase): mpst_query_plan.h
 // the walk for the instances g.first .. g.first + g.count, an event, the grid phase; v.label is read, v.compute_f32 must be 0.  0, or -1 on a launch error
 int launch_sitecond(const ImpModel& v, const ScArgs& g, hipStream_t s, hipEvent_t mid);
+// window conditionals (k_win_walk, k_win; mpst_window.inl): what both kernels take by value, for one chunk of instances
+struct WinArgs {
+    double* lrows;              // [walk workgroups][2 T][16][cap] (pairs): slot t holds l~_{t-1}, slot T + t holds r~_{t+1}
+    double* nll;                // [chunk][T][max_width], the chunk's own
+    double* work;               // [window workgroups][WINDOW_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null
+    int64_t first, count;       // the instances of this chunk
+    int max_width;
+};
+// the matrix step runs in global scratch (the environment pass's limit; mpst_query_plan.h: window_plan_block takes it as big_route)
+bool window_big_route(int cap, bool cx);
+// the walk (walk_wgs workgroups of SITECOND_TILE instances), an event, the window kernel on win_wgs workgroups; v.label is read,
+// v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_window(const ImpModel& v, const WinArgs& g, int64_t walk_wgs, int64_t win_wgs, hipStream_t s, hipEvent_t mid);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin

@@ -1,4 +1,4 @@
-// The host-side arithmetic of a model query (imputation, marginal likelihoods, site conditionals): the scratch budget, the order in
+// The host-side arithmetic of a model query (imputation, marginal likelihoods, site and window conditionals): the scratch budget, the order in
 // which instances are dealt out, and how many instances one launch takes.  Pure functions in plain C++17, no HIP and no environment:
 // free device memory and the MPST_IMPUTE_CHUNK_GB / MPST_IMP_NO_ORDER switches come in as arguments, which the caller reads.
 // tests/test_query_plan.py compiles it alone; mpst_internal.h includes it for everything else.
@@ -104,6 +104,38 @@ inline SitecondBlock sitecond_plan_block(int64_t N, int32_t T, int32_t cap, int3
     chunk = std::min<int64_t>(chunk, ((int64_t)1 << 30) / T);                                           // (instance, site) pairs in 32 bits
     if (chunk < N) chunk = std::max<int64_t>(SITECOND_TILE, chunk / SITECOND_TILE * SITECOND_TILE);
     return {chunk, (chunk + SITECOND_TILE - 1) / SITECOND_TILE, sitecond_grid_workgroups(chunk * T)};
+}
+
+// ---- window conditionals (mpst_window.inl: k_win_walk, k_win) ----
+constexpr int WINDOW_BIG_MATS = 4;              // chi x chi matrices of global scratch per workgroup of k_win beyond the LDS limit
+constexpr int WINDOW_MAX_WORKGROUPS = 4096;     // of k_win, a (instance, start) pair at a time
+constexpr int WINDOW_MAX_BIG_WORKGROUPS = 1024; // ... where each owns global scratch
+
+struct WindowBlock {
+    int64_t chunk, tiles, win_wgs;      // instances per launch; workgroups of its walk; workgroups of its window kernel
+};
+// Window conditionals.  With budget = query_budget(free_b, chunk_gb), in bytes:
+//     per instance    T * (2 * cap * zw + max_width) * 8      the left and the right rows of every site, and the block's nll
+//     per workgroup   WINDOW_BIG_MATS * cap * cap * zw * 8    of k_win, on the big route only (big_route: the matrix step in global scratch)
+//     chunk   = floor((big_route ? 3/4 : 1) * budget / per instance), at least 1, at most N and at most floor(2^30 / T)
+//               ((instance, start) pairs in 32 bits); a chunk smaller than N is whole tiles of SITECOND_TILE instances, at least one
+//     tiles   = ceil(chunk / SITECOND_TILE)
+//     win_wgs = min(chunk * T, WINDOW_MAX_WORKGROUPS); on the big route also at most WINDOW_MAX_BIG_WORKGROUPS and at most
+//               floor(budget / 4 / per workgroup), never below 1
+// The shares of the big route are fixed, so both results are monotone in the budget.
+inline WindowBlock window_plan_block(int64_t N, int32_t T, int32_t cap, int32_t zw, int32_t max_width, bool big_route, size_t free_b,
+                                     const char* chunk_gb) {
+    const double budget = query_budget(free_b, chunk_gb);
+    const double per_bytes = (double)T * (2.0 * cap * zw + max_width) * sizeof(double);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)((big_route ? 0.75 : 1.0) * budget / per_bytes)));
+    chunk = std::min<int64_t>(chunk, ((int64_t)1 << 30) / T);
+    if (chunk < N) chunk = std::max<int64_t>(SITECOND_TILE, chunk / SITECOND_TILE * SITECOND_TILE);
+    int64_t wgs = std::min<int64_t>(chunk * T, WINDOW_MAX_WORKGROUPS);
+    if (big_route) {
+        const double wg_bytes = (double)WINDOW_BIG_MATS * cap * cap * zw * sizeof(double);
+        wgs = std::min<int64_t>(std::min<int64_t>(wgs, WINDOW_MAX_BIG_WORKGROUPS), (int64_t)(0.25 * budget / wg_bytes));
+    }
+    return {chunk, (chunk + SITECOND_TILE - 1) / SITECOND_TILE, std::max<int64_t>(1, wgs)};
 }
 
 // ---- pair analysis (mpst_analysis.hip: k_an_pair) ----

@@ -29,7 +29,10 @@ constexpr int SC_NTW = CAP_LIMIT / 64;      // column tiles per wave
 constexpr int SC_PS = IMP_MAXD + 1;         // row stride of the site vectors / the partial dots
 constexpr int SC_KU = 8;                    // k-steps per batch of loads of the site tensor
 
-template <bool CX> __global__ __launch_bounds__(SC_T) void k_sc_walk(ImpModel v, ScArgs g) {
+// The walk of both callers, Args = ScArgs or WinArgs (first, count, lrows).  KEEP_R (window conditionals, mpst_window.inl): lrows has
+// 2 T slots per workgroup, the right walk stores its rescaled rows as the left walk does - slot T + j holds r~_{j+1}, what closes a
+// window that ends at site j - and forms no amplitudes.
+template <bool CX, bool KEEP_R, typename Args> __device__ __forceinline__ void sc_walk(const ImpModel& v, const Args& g) {
     constexpr int ZW = CX ? 2 : 1;
     __shared__ double Xr[SC_B * SC_LD], Xi[CX ? SC_B * SC_LD : 1];
     __shared__ double phr[SC_B * SC_PS], phi_[CX ? SC_B * SC_PS : 1];
@@ -41,7 +44,7 @@ template <bool CX> __global__ __launch_bounds__(SC_T) void k_sc_walk(ImpModel v,
     const int count = (int)min((int64_t)SC_B, g.count - start);
     const int64_t inst0 = g.first + start;
     const int ls = *v.label_site;
-    double* lrows = g.lrows + (int64_t)blockIdx.x * T * SC_B * cm * ZW;
+    double* lrows = g.lrows + (int64_t)blockIdx.x * (KEEP_R ? 2 : 1) * T * SC_B * cm * ZW;
     if (tid < SC_B) lab[tid] = tid < count ? v.label[inst0 + tid] : -1;
     const int orow = tid >> 4, osub = tid & 15;                     // sixteen threads per row outside the products
 
@@ -208,42 +211,58 @@ template <bool CX> __global__ __launch_bounds__(SC_T) void k_sc_walk(ImpModel v,
     }
     __threadfence_block();
     __syncthreads();
-    // ---- right walk: a_t and r_t from one product, t = T-1 .. 0 ----
-    unit_rows();
-    for (int t = T - 1; t >= 0; --t) {
-        load_phi(t);
+    if constexpr (KEEP_R) {
+        // ---- right walk, kept: r_{t+1} into slot T + t, t = T-1 .. 0 ----
+        unit_rows();
         __syncthreads();
-        const int Dout = step(t, false, t);
-        // a_t[s]: the four waves' partial dots in a fixed order; conj(phi_t) . a_t over the sixteen lanes of the row
-        {
-            const int s = osub;
-            double ar = 0.0, ai = 0.0;
-            if (s < d) {
-                ar = (wdr[(0 * SC_B + orow) * SC_PS + s] + wdr[(1 * SC_B + orow) * SC_PS + s]) +
-                     (wdr[(2 * SC_B + orow) * SC_PS + s] + wdr[(3 * SC_B + orow) * SC_PS + s]);
-                if constexpr (CX)
-                    ai = (wdi[(0 * SC_B + orow) * SC_PS + s] + wdi[(1 * SC_B + orow) * SC_PS + s]) +
-                         (wdi[(2 * SC_B + orow) * SC_PS + s] + wdi[(3 * SC_B + orow) * SC_PS + s]);
-            }
-            double pr = s < d ? phr[orow * SC_PS + s] : 0.0, pi = 0.0;
-            if constexpr (CX) pi = s < d ? phi_[orow * SC_PS + s] : 0.0;
-            double yr = pr * ar + pi * ai, yi = pr * ai - pi * ar;
-#pragma unroll
-            for (int o = 8; o >= 1; o >>= 1) {
-                yr += __shfl_xor(yr, o);
-                yi += __shfl_xor(yi, o);
-            }
-            if (orow < count) {
-                double* am = g.amp + ((start + orow) * T + t) * (int64_t)(d + 1) * ZW;
-                if (s < d) zstore<double, CX>(am, s, ar, ai);
-                if (s == 0) zstore<double, CX>(am, d, yr, yi);
-            }
+        rescale(1, 2 * T - 1);
+        for (int t = T - 1; t >= 1; --t) {
+            load_phi(t);
+            __syncthreads();
+            const int Dout = step(t, false, -1);
+            __syncthreads();
+            rescale(Dout, T + t - 1);
+            __syncthreads();
         }
-        __syncthreads();
-        rescale(Dout, -1);
-        __syncthreads();
+    } else {
+        // ---- right walk: a_t and r_t from one product, t = T-1 .. 0 ----
+        unit_rows();
+        for (int t = T - 1; t >= 0; --t) {
+            load_phi(t);
+            __syncthreads();
+            const int Dout = step(t, false, t);
+            // a_t[s]: the four waves' partial dots in a fixed order; conj(phi_t) . a_t over the sixteen lanes of the row
+            {
+                const int s = osub;
+                double ar = 0.0, ai = 0.0;
+                if (s < d) {
+                    ar = (wdr[(0 * SC_B + orow) * SC_PS + s] + wdr[(1 * SC_B + orow) * SC_PS + s]) +
+                         (wdr[(2 * SC_B + orow) * SC_PS + s] + wdr[(3 * SC_B + orow) * SC_PS + s]);
+                    if constexpr (CX)
+                        ai = (wdi[(0 * SC_B + orow) * SC_PS + s] + wdi[(1 * SC_B + orow) * SC_PS + s]) +
+                             (wdi[(2 * SC_B + orow) * SC_PS + s] + wdi[(3 * SC_B + orow) * SC_PS + s]);
+                }
+                double pr = s < d ? phr[orow * SC_PS + s] : 0.0, pi = 0.0;
+                if constexpr (CX) pi = s < d ? phi_[orow * SC_PS + s] : 0.0;
+                double yr = pr * ar + pi * ai, yi = pr * ai - pi * ar;
+#pragma unroll
+                for (int o = 8; o >= 1; o >>= 1) {
+                    yr += __shfl_xor(yr, o);
+                    yi += __shfl_xor(yi, o);
+                }
+                if (orow < count) {
+                    double* am = g.amp + ((start + orow) * T + t) * (int64_t)(d + 1) * ZW;
+                    if (s < d) zstore<double, CX>(am, s, ar, ai);
+                    if (s == 0) zstore<double, CX>(am, d, yr, yi);
+                }
+            }
+            __syncthreads();
+            rescale(Dout, -1);
+            __syncthreads();
+        }
     }
 }
+template <bool CX> __global__ __launch_bounds__(SC_T) void k_sc_walk(ImpModel v, ScArgs g) { sc_walk<CX, false>(v, g); }
 
 template <bool CX> __global__ __launch_bounds__(IMP_T) void k_sc_grid(ImpModel v, ScArgs g) {
     constexpr int ZW = CX ? 2 : 1;

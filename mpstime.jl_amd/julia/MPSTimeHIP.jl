@@ -383,6 +383,32 @@ function site_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_sit
     return nll, pit, med, err, q
 end
 
+"""
+    window_conditionals(sites, chi, label_site, phi, label_idx, max_width; device)
+
+For every COMPLETE series of `phi` ((d, T, N)), every start t and every width w = 1 .. `max_width` that fits, -ln of the Born
+probability of the values of the window t .. t+w-1 given all the others, under the class MPS of the series' label
+(`mpst_window_conditionals`; model arguments as `site_conditionals` takes them).  Returns `nll` (max_width, T, N): entry
+[w, t, i]; NaN where the window would pass the end of the chain.
+"""
+function window_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::Integer, phi::Array, label_idx::Vector{Int32},
+                             max_width::Integer; device::Integer=0)
+    d, T, N = size(phi)
+    cx = eltype(phi) <: Complex
+    nll = zeros(Float64, max(max_width, 1), T, N)
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        GC.@preserve sites ptrs chi phi label_idx begin
+            model = impute_model_ref(ptrs, chi, N, T, d, maximum(label_idx) + 1, label_site - 1, cx, 0, phi, label_idx)
+            check(c, ccall((:mpst_window_conditionals, LIB), Cint,
+                           (Ptr{Cvoid}, Ref{MpstImputeModel}, Int32, Ptr{Float64}, Ref{Float64}),
+                           c, model, max_width, nll, secs))
+        end
+    end
+    return nll
+end
+
 # ---- entanglement analysis (src/Analysis/analyse.jl) ---------------------------------------------------------------------
 const MPST_ERR_DOMAIN = -6
 
