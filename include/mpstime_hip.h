@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis, mpst_window_conditionals) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis, mpst_window_conditionals, mpst_marginal_conditionals) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -483,6 +483,45 @@ int  mpst_site_conditionals(void* ctx, const mpst_impute_model* m, const double*
 int  mpst_window_conditionals(void* ctx, const mpst_impute_model* m, int32_t max_width, double* nll_out /* [N][T][max_width] */,
                               double* seconds /* may be NULL */);
 
+/* Marginal site conditionals: the predictive distribution of every site of an INCOMPLETE series.  For instance i (class c_i =
+ * m->label_idx[i], the label slice as stored - its scale cancels everywhere) with the known sites K_i = {j : missing[i][j] == 0} and
+ * every site t, known or missing, the distribution of x_t given the known values of the OTHER sites, the missing ones summed over
+ * their physical index.  The convention is the Born rule, that of mpst_marginal_model, mpst_window_conditionals and
+ * mpst_pair_analysis (not the |rho phi|^2 of the sequential imputer; the two agree, up to a constant, only where the conditioned
+ * state is pure).  With A_j[s] = W_j[:, s, :] at a missing site, M_j = sum_q conj(phi[i][j][q]) W_j[:, q, :] at a known one and the
+ * density recursion of mpst_marginal_model, E' = sum_s A_j[s]^T E conj(A_j[s]) (the one term with M_j at a known site):
+ *     L_{t-1}   the density over the left bond of site t, from the sites 0 .. t-1 (initial value 1),
+ *     R_{t+1}   the density over its right bond, from the sites t+1 .. T-1,
+ *     rho_t[s, s'] = sum_{a a' b b'} L_{t-1}[a, a'] W_t[a, s, b] conj(W_t[a', s', b']) R_{t+1}[b, b'],
+ *     p_k = max(Re(sum_{s s'} conj(g_k[s]) rho_t[s, s'] g_k[s']), 0),   g_k row k of site t's grid table,
+ * cdf = cumul_integrate(grid_x, p, TrapezoidalEvenFast()), Z = cdf[ngrid-1], F = cdf / Z.  Site t itself is never conditioned on; at
+ * a complete series rho_t = a_t a_t^H with the a_t of mpst_site_conditionals.  L and R are rescaled to trace one at every site (long
+ * chains do not underflow); no scale is returned.
+ *   m                 as in mpst_site_conditionals (label_idx required), compute MPST_COMPUTE_F64; phi[i][j] is read at the known sites
+ *                     and at a missing site only when x[i][j] is finite
+ *   missing[N][T]     non-zero: the site is missing; NULL: nothing is missing
+ *   x[N][T]           the values in the encoding's domain: the observed one at a known site, at a missing site the held-out true value or
+ *                     NaN; NULL: no value anywhere (pit_out must then be NULL, nll_out is given at the known sites only)
+ *   grid_x, grid_phi, ngrid, o   as in mpst_site_conditionals
+ * Outputs per (i, t), [N][T]; each may be NULL and is then skipped (at least one must be given):
+ *   med_out, err_out, q_out[N][T][nq]   as in mpst_site_conditionals, rules and tie rules included
+ *   mean_out  trapezoid(grid_x * p) / Z
+ *   nll_out   -ln(phi[i][t]^H rho_t phi[i][t] / Z), at the exact encoded state; +inf where the numerator is not positive
+ *   pit_out   F at x[i][t], linear between the two neighbouring grid values; 0 below grid_x[0], 1 above grid_x[ngrid-1]
+ * nll_out and pit_out are produced wherever x[i][t] is finite: at a known site they are leave-one-out scores with the missing sites
+ * summed out, at a missing site held-out scores of the value the caller supplied; elsewhere they are NaN.  A site whose Z is not a
+ * positive finite number gives NaN in all its outputs.  Never NaN for finite, non-degenerate input.
+ * seconds (may be NULL): device time of the call; mpst_get_impute_phases then returns (walk, grid phase).  The result of an (instance,
+ * site) pair depends neither on how the instances are cut into blocks (free device memory, MPST_IMPUTE_CHUNK_GB) nor on what travels
+ * along: no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: NULL m / grid_x / grid_phi / o, all outputs NULL, pit_out without x, ngrid < 2, nq outside 0..16, a level outside
+ * (0, 1), q_out NULL with nq > 0, label_idx NULL or out of range, grid_per_site not 0 / 1; MPST_ERR_UNSUPPORTED: MPST_COMPUTE_F32,
+ * chi_max > 128, d > 16, C > 16.  A rejected call leaves the context as it was. */
+int  mpst_marginal_conditionals(void* ctx, const mpst_impute_model* m, const uint8_t* missing /* [N][T], NULL = nothing missing */,
+                                const double* x /* [N][T] */, const double* grid_x, const void* grid_phi, int32_t ngrid,
+                                const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out, double* err_out,
+                                double* mean_out, double* q_out /* [N][T][nq] */, double* seconds /* may be NULL */);
+
 /* Entanglement analysis (src/Analysis/analyse.jl) of a real model (dtype MPST_DTYPE_F64, compute MPST_COMPUTE_F64; complex
  * models: MPST_ERR_UNSUPPORTED, the reference cannot analyse them either), chi_max <= 128, d <= 16.  Every class MPS is the
  * label slice of class c, normalised (expand_label_index, utils.jl:356-370).  Natural log throughout.
@@ -531,7 +570,7 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
 /* normalize!(W), RealRealHighDimension.jl:852. */
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),
  * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
- * mpst_window_conditionals: (walk, window kernel); after
+ * mpst_window_conditionals: (walk, window kernel); after mpst_marginal_conditionals: (walk, grid phase); after
  * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis

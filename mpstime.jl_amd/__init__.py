@@ -19,7 +19,8 @@ from .analysis import bipartite_spectrum, single_site_spectrum, see_variation
 from .analysis import PairAnalysis, pair_analysis, position_operator, mutual_information, model_correlations
 from .marginal import log_marginals, class_posteriors
 from .conditionals import (SiteConditionals, site_conditionals, anomaly_scores, WindowConditionals,
-                           window_conditionals, window_conditionals_model, window_anomaly_scores)
+                           window_conditionals, window_conditionals_model, window_anomaly_scores, MarginalConditionals,
+                           marginal_conditionals, marginal_conditionals_model, impute_marginal, forecast)
 from .overlaps import ModelOverlaps, model_overlaps, class_overlaps
 from .summary import get_training_summary, training_stats, sweep_summary, print_opts
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
@@ -36,5 +37,6 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "classify_batch", "tune", "evaluate", "eval_loss", "fit_batch", "BatchFit", "MPSRandomSearch", "TuningLoss", "ClassificationLoss",
            "MisclassificationRate", "BalancedMisclassificationRate", "ImputationLoss", "make_windows", "make_stratified_cvfolds",
            "classify_many", "log_marginals", "class_posteriors", "SiteConditionals", "site_conditionals", "anomaly_scores", "WindowConditionals", "window_conditionals",
-           "window_conditionals_model", "window_anomaly_scores",
+           "window_conditionals_model", "window_anomaly_scores", "MarginalConditionals", "marginal_conditionals", "marginal_conditionals_model",
+           "impute_marginal", "forecast",
            "ModelOverlaps", "model_overlaps", "class_overlaps", "get_training_summary", "training_stats", "sweep_summary", "print_opts"]

@@ -121,6 +121,8 @@ SYMBOLS = {
     "mpst_marginal_model": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _dp]),
     "mpst_site_conditionals": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp, _vp, _i32, C.POINTER(SiteCondOpts), _dp, _dp, _dp, _dp, _dp, _dp]),
     "mpst_window_conditionals": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
+    "mpst_marginal_conditionals": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _dp, _vp, _i32, C.POINTER(SiteCondOpts), _dp, _dp, _dp, _dp,
+                                             _dp, _dp, _dp]),
     "mpst_entanglement": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
     "mpst_see_variation": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp]),
     "mpst_pair_analysis": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _i32, _dp, _dp, _dp, _dp]),

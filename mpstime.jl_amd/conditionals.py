@@ -14,8 +14,14 @@ probability of the values of a window ``t .. t+w-1`` given all the others, for e
 one pass per start - an anomaly map over (position, scale) for samples that are each plausible alone and implausible together.
 
 Everything is in the encoding's domain, as ``get_cdfs`` leaves its results (the transform is nonlinear under the sigmoid; a density
-in raw units would need its Jacobian).  Series with missing values are not this call's business: ``log_marginals`` scores them,
-``impute_dataset`` fills them.
+in raw units would need its Jacobian).  Both calls take COMPLETE series.
+
+``marginal_conditionals`` is the same question for INCOMPLETE series (``mpst_marginal_conditionals``, csrc/mpst_margcond.inl): the
+distribution of every site, known or missing, given only the values that were observed at the other sites, the missing ones summed
+out under the Born rule.  At a missing site it is the predictive distribution ``p(x_t | observed)`` - not the sequential imputer's
+chain of point estimates, whose bands narrow along a gap and depend on ``impute_order``; at a known site the leave-one-out score of a
+series with dropped samples.  ``impute_marginal`` fills every missing site from its own marginal conditional, ``forecast`` masks the
+last ``horizon`` sites and returns the point forecast and its bands, ``anomaly_scores(..., missing_mask=)`` scores incomplete series.
 """
 from __future__ import annotations
 
@@ -114,16 +120,172 @@ def site_conditionals(imp, rows=None, quantiles=None, get_wmad: bool = True, eng
     return (out, secs) if return_seconds else out
 
 
-def anomaly_scores(imp, rows=None, reduce="mean", engine: Optional[SweepEngine] = None, device: int = 0):
+def anomaly_scores(imp, rows=None, reduce="mean", engine: Optional[SweepEngine] = None, device: int = 0, missing_mask=None):
     """``-ln p(x_t | x_{!=t})`` of the complete series ``imp.X_test[rows]``, reduced over the sites: ``"mean"`` or ``"max"`` give (N,),
-    ``None`` the (N, T) profile that localises the anomaly."""
+    ``None`` the (N, T) profile that localises the anomaly.  ``missing_mask`` (rows, T): the series are incomplete - the scores of
+    the known sites are leave-one-out scores with the missing sites summed out (``marginal_conditionals``), the masked sites are NaN
+    in the profile and left out of the reduction (a row with nothing known reduces to NaN)."""
     if reduce not in ("mean", "max", None):
         raise ValueError(f'reduce must be "mean", "max" or None, not {reduce!r}')
+    if missing_mask is not None:
+        mask = np.asarray(missing_mask, dtype=bool)
+        nll = np.where(mask, np.nan, marginal_conditionals(imp, mask, rows, get_wmad=False, engine=engine, device=device).nll)
+        if reduce is None:
+            return nll
+        out = np.full(nll.shape[0], np.nan)
+        some = ~mask.all(axis=1)
+        out[some] = np.nanmean(nll[some], axis=1) if reduce == "mean" else np.nanmax(nll[some], axis=1)
+        return out
     _selected_rows(imp, rows)
     nll = site_conditionals(imp, rows, get_wmad=False, engine=engine, device=device).nll
     if reduce is None:
         return nll
     return nll.mean(axis=1) if reduce == "mean" else nll.max(axis=1)
+
+
+@dataclass
+class MarginalConditionals:
+    x: np.ndarray                       # (N, T) the values in the encoding's domain; NaN at a missing site without a true value
+    missing: np.ndarray                 # (N, T) bool
+    nll: np.ndarray                     # (N, T) -ln p(x_t | known others): leave-one-out at known sites, held-out at missing ones; NaN without a value
+    pit: np.ndarray                     # (N, T) F(x_t | known others), NaN likewise
+    median: np.ndarray                  # (N, T)
+    err: Optional[np.ndarray]           # (N, T) WMAD, None without get_wmad
+    mean: np.ndarray                    # (N, T) trapezoid(x p) / Z
+    quantiles: Optional[np.ndarray]     # (N, T, nq), None without levels
+    seconds: float = 0.0                # device seconds of the call
+
+
+def marginal_conditionals_model(eng: SweepEngine, W, phi, label_index, missing, x, grid_x, grid_phi, levels=None, get_wmad=True,
+                                label_site=None):
+    """mpst_marginal_conditionals on a model handed over in one call: ``W`` site tensors (Dl, d, Dr), the label site (Dl, d, Dr, C);
+    ``phi`` (N, T, d) the encoded values, real or complex - read at the known sites, and at a missing site only where ``x`` is finite;
+    ``label_index`` (N,) the classes; ``missing`` (N, T) True where a site is missing, None: nothing is; ``x`` (N, T) the values in the
+    encoding's domain, at a missing site the held-out true value or NaN; ``grid_x`` (ngrid,) evenly spaced candidate values and
+    ``grid_phi`` their states, (ngrid, d) or one table per site (T, ngrid, d); ``levels``: up to 16 numbers inside (0, 1).
+    Returns a ``MarginalConditionals``."""
+    lv = check_levels(levels)
+    cx = any(np.iscomplexobj(t) for t in W) or np.iscomplexobj(phi) or np.iscomplexobj(grid_phi)
+    dt = np.complex128 if cx else np.float64
+    model, keep = model_to_abi([np.asarray(t, dtype=dt) for t in W], np.asarray(phi, dtype=dt), "f64", label_site)
+    N, T, d = int(model.N), int(model.T), int(model.d)
+    lab = np.ascontiguousarray(label_index, dtype=np.int32)
+    xs = np.ascontiguousarray(x, dtype=np.float64)
+    m8 = None if missing is None else np.ascontiguousarray(np.asarray(missing) != 0, dtype=np.uint8)
+    gx = np.ascontiguousarray(grid_x, dtype=np.float64)
+    gp = np.ascontiguousarray(grid_phi, dtype=dt)
+    assert lab.shape == (N,) and xs.shape == (N, T) and gp.shape in ((len(gx), d), (T, len(gx), d))
+    assert m8 is None or m8.shape == (N, T)
+    model.label_idx = lab.ctypes.data_as(C.POINTER(C.c_int32))
+    dp = C.POINTER(C.c_double)
+    nq = 0 if lv is None else len(lv)
+    o = L.SiteCondOpts(int(gp.ndim == 3), int(bool(get_wmad)), nq, 0, None if lv is None else lv.ctypes.data_as(dp))
+    nll, pit, med, err, mean = (np.zeros((N, T)) for _ in range(5))
+    q = np.zeros((N, T, nq)) if nq else None
+    sec = C.c_double()
+    eng._chk(eng.lib.mpst_marginal_conditionals(eng.ctx, C.byref(model), None if m8 is None else m8.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                xs.ctypes.data_as(dp), gx.ctypes.data_as(dp), C.c_void_p(gp.ctypes.data), len(gx), C.byref(o),
+                                                nll.ctypes.data_as(dp), pit.ctypes.data_as(dp), med.ctypes.data_as(dp), err.ctypes.data_as(dp),
+                                                mean.ctypes.data_as(dp), None if q is None else q.ctypes.data_as(dp), C.byref(sec)))
+    del keep
+    miss = np.zeros((N, T), dtype=bool) if m8 is None else m8.astype(bool)
+    return MarginalConditionals(xs, miss, nll, pit, med, err if get_wmad else None, mean, q, sec.value)
+
+
+def _true_values(imp, enc, norms, raw, oob):
+    """The raw values through the test transform of the MASKED series: the train-fitted transforms, then the out-of-bounds rescale its
+    row got in ``_scaled_instances`` (not the one the complete series would get).  NaN stays NaN."""
+    from .encodings import transform_test_data
+    fin = np.isfinite(raw)
+    t, _ = transform_test_data(np.where(fin, raw, 0.0), norms, imp.opts, (0.0, 1.0), rescale_out_of_bounds=False)
+    for i, lo, hi in oob:
+        t[int(i)] = (t[int(i)] - lo) / hi
+    a, b = enc.range
+    return np.where(fin, (b - a) * t + a, np.nan)
+
+
+def _marginal_run(imp, missing_mask, rows, quantiles, get_wmad, engine, device):
+    from .imputation import _scaled_instances
+    levels = check_levels(quantiles)
+    rows = np.arange(imp.X_test.shape[0]) if rows is None else np.atleast_1d(np.asarray(rows))
+    mask = np.asarray(missing_mask, dtype=bool)
+    if mask.shape != (len(rows), imp.X_test.shape[1]):
+        raise ValueError(f"missing_mask must have the shape (rows, T) = {(len(rows), imp.X_test.shape[1])}, not {mask.shape}")
+    raw = np.asarray(imp.X_test, dtype=np.float64)[rows]
+    if not np.all(np.isfinite(raw[~mask])):
+        raise ValueError("a selected row holds a NaN or non-finite value at a site missing_mask calls known")
+    enc, norms, _, _, scaled, oob = _scaled_instances(imp, rows, mask)
+    lab = np.array([imp.class_map[c] for c in np.asarray(imp.y_test)[rows].tolist()], dtype=np.int32)
+    xr = imp.x_guess_range
+    N, T = scaled.shape
+    if N == 0:
+        z = np.zeros((0, T))
+        return MarginalConditionals(z, mask, z.copy(), z.copy(), z.copy(), z.copy() if get_wmad else None, z.copy(),
+                                    None if levels is None else np.zeros((0, T, len(levels)))), (enc, norms, scaled, oob, mask)
+    true = _true_values(imp, enc, norms, raw, oob)
+    a, b = enc.range
+    inside = np.isfinite(true) & (true >= a) & (true <= b)
+    x = np.where(mask, true, scaled)                                        # held-out values where the test set has them, NaN elsewhere
+    states = imp.encoder(np.where(mask & inside, true, scaled))             # a value outside the range is not encoded: its nll is NaN below
+    own = engine is None
+    eng = engine or SweepEngine(device)
+    try:
+        out = marginal_conditionals_model(eng, imp.mps, states, lab, mask, x, xr.xvals, xr.xvals_enc, levels=levels, get_wmad=get_wmad)
+    finally:
+        if own:
+            eng.close()
+    out.nll[mask & np.isfinite(true) & ~inside] = np.nan
+    return out, (enc, norms, scaled, oob, mask)
+
+
+def marginal_conditionals(imp, missing_mask, rows=None, quantiles=None, get_wmad: bool = True, engine: Optional[SweepEngine] = None,
+                          device: int = 0):
+    """The marginal site conditionals of ``imp.X_test[rows]`` (default: all) with the sites of ``missing_mask`` (rows, T) treated as
+    missing, each series under the MPS of its class ``imp.y_test``: a ``MarginalConditionals`` in the encoding's domain, as
+    ``site_conditionals`` leaves its results.  Pre-processing is imputation's own (``_scaled_instances``), so split and time-dependent
+    encodings go through the fitted encoder and the per-site tables.  Where the test set holds a finite value at a masked site it goes
+    through the same per-series transform as the masked series and gives the held-out ``nll`` / ``pit`` there (NaN where it holds
+    none); a true value outside the encoding's range gives ``nll`` NaN and ``pit`` 0 or 1.  ``quantiles``: up to 16 levels inside
+    (0, 1).  Raises ValueError on a non-finite value at a site the mask calls known, KeyError on a label the model was not trained on."""
+    return _marginal_run(imp, missing_mask, rows, quantiles, get_wmad, engine, device)[0]
+
+
+def impute_marginal(imp, missing_mask, rows=None, statistic: str = "median", quantiles=None, invert_transform: bool = True,
+                    engine: Optional[SweepEngine] = None, device: int = 0):
+    """Fill every missing site of ``imp.X_test[rows]`` with the ``statistic`` - ``"median"`` or ``"mean"`` - of its own marginal
+    conditional ``p(x_t | observed)``; known values are kept.  Unlike ``impute_dataset`` no site is conditioned on a value imputed
+    before it, so the result does not depend on an order.  Returns ``X_imputed`` (N, T), or ``(X_imputed, bands)`` with ``quantiles``:
+    bands (N, T, nq), the known value in every level at a known site.  Units and bands follow ``impute_dataset(..., quantiles=)``:
+    ``invert_transform`` maps everything back with the instance's own out-of-bounds rescale.  Quantiles and the median commute with
+    that monotone transform; the MEAN does not - with ``invert_transform`` the mean of the encoding's domain is mapped, which is not
+    the mean in the original units under a nonlinear transform (the sigmoid)."""
+    from .imputation import invert_test_transform
+    if statistic not in ("median", "mean"):
+        raise ValueError(f'statistic must be "median" or "mean", not {statistic!r}')
+    mc, (enc, norms, scaled, oob, mask) = _marginal_run(imp, missing_mask, rows, quantiles, False, engine, device)
+    ts = np.where(mask, mc.median if statistic == "median" else mc.mean, scaled)
+    bands = None if mc.quantiles is None else np.where(mask[:, :, None], mc.quantiles, scaled[:, :, None])
+    if invert_transform and ts.shape[0]:
+        ts = invert_test_transform(ts, oob, norms, imp.opts, enc.range)
+        if bands is not None:
+            bands = np.stack([invert_test_transform(bands[:, :, l], oob, norms, imp.opts, enc.range) for l in range(bands.shape[2])], axis=2)
+    return ts if bands is None else (ts, bands)
+
+
+def forecast(imp, horizon, rows=None, quantiles=(0.05, 0.95), statistic: str = "median", invert_transform: bool = True,
+             engine: Optional[SweepEngine] = None, device: int = 0):
+    """``impute_marginal`` with the last ``horizon`` sites masked: ``p(x_{T-horizon+k} | x_0 .. x_{T-horizon-1})`` for every step k of
+    the horizon from one call.  Returns ``(point, bands)``: the (N, horizon) point forecast and the (N, horizon, nq) bands."""
+    T = imp.X_test.shape[1]
+    if int(horizon) != horizon or not 1 <= int(horizon) <= T:
+        raise ValueError(f"horizon must be an integer in 1 .. T = {T}, not {horizon!r}")
+    h = int(horizon)
+    n = imp.X_test.shape[0] if rows is None else len(np.atleast_1d(np.asarray(rows)))
+    mask = np.zeros((n, T), dtype=bool)
+    mask[:, T - h:] = True
+    ts, bands = impute_marginal(imp, mask, rows, statistic=statistic, quantiles=quantiles, invert_transform=invert_transform, engine=engine,
+                                device=device)
+    return ts[:, T - h:], bands[:, T - h:]
 
 
 @dataclass

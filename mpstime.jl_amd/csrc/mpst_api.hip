@@ -2701,6 +2701,79 @@ static int run_window(Ctx* c, const ImpModel& m, const WindowRequest& r) {
     }, WindowHooks{c, r, nll, T * r.max_width});
 }
 
+// One mpst_marginal_conditionals call: the mask and the values (either may be NULL), the grid, and the six outputs, each of which may be NULL
+struct MargcondRequest {
+    const mpst_sitecond_opts* o;
+    const uint8_t* missing;
+    const double *x, *grid_x;
+    const void* grid_phi;
+    int32_t ngrid;
+    double *nll_out, *pit_out, *med_out, *err_out, *mean_out, *q_out, *seconds;
+};
+// what a marginal-conditionals call does around its blocks: a block's outputs are its own on the device and go to the caller's arrays
+// after its kernels, outside the phases
+struct MargcondHooks {
+    Ctx* c; int64_t T; int nq;
+    double* dev[6]; double* host[6];    // nll, pit, med, err, mean, q
+    bool own_begin() const { return true; }
+    int prepare() { return 0; }
+    int before(int64_t, int64_t) { return 0; }
+    int after(int64_t i0, int64_t cnt) {
+        for (int k = 0; k < 6; ++k) {
+            if (!host[k]) continue;
+            const int64_t per = T * (k == 5 ? nq : 1);
+            HIPC(c, hipMemcpyAsync(host[k] + (size_t)(i0 * per), dev[k], (size_t)(cnt * per) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+// The marginal site conditionals of a request: the kept densities, rho_t and the outputs of a block of instances are its scratch, the
+// walk's matrices beyond the LDS limit come on top (mpst_query_plan.h: margcond_plan_block); the grid phase keeps ngrid doubles of
+// density and prefix sums per workgroup, whatever the block.  The phases are the walk and the grid phase.
+constexpr int MARGCOND_MAX_CLASSES = 16;
+static int run_margcond(Ctx* c, const ImpModel& m, const MargcondRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1, nq = r.o->nq;
+    const bool per_site = r.o->grid_per_site == 1;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const bool big = margcond_big_route(m.cap, m.is_complex != 0);
+    const int outputs = (r.nll_out ? 1 : 0) + (r.pit_out ? 1 : 0) + (r.med_out ? 1 : 0) + (r.err_out ? 1 : 0) + (r.mean_out ? 1 : 0) + nq;
+    const MargcondBlock blk = margcond_plan_block(N, m.T, m.cap, m.d, zw, outputs, big, free_b, chunk_gb_override());
+    const int64_t chunk = blk.chunk, mat = (int64_t)m.cap * m.cap * zw;
+    DevBuf<double> dx, gx, gp, lev, nll, pit, med, err, mean, q, dens, rho, work, pb, sb;
+    DevBuf<uint8_t> miss;
+    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, grid_doubles(m, per_site, r.ngrid))) || (rc = dalloc(c, dens, chunk * T * mat)) ||
+        (rc = dalloc(c, rho, chunk * T * m.d * m.d * zw)) || (big && (rc = dalloc(c, work, chunk * MARGCOND_BIG_MATS * mat))) ||
+        (rc = dalloc(c, pb, blk.grid_wgs * r.ngrid)) || (rc = dalloc(c, sb, blk.grid_wgs * r.ngrid)) ||
+        (r.x && (rc = dalloc(c, dx, N * T))) || (r.missing && (rc = dalloc(c, miss, N * T))) ||
+        (nq > 0 && ((rc = dalloc(c, lev, nq)) || (rc = dalloc(c, q, chunk * T * nq)))) ||
+        (r.nll_out && (rc = dalloc(c, nll, chunk * T))) || (r.pit_out && (rc = dalloc(c, pit, chunk * T))) ||
+        (r.med_out && (rc = dalloc(c, med, chunk * T))) || (r.err_out && (rc = dalloc(c, err, chunk * T))) ||
+        (r.mean_out && (rc = dalloc(c, mean, chunk * T)))) return rc;
+    HIPC(c, hipMemcpy(gx, r.grid_x, (size_t)r.ngrid * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)grid_doubles(m, per_site, r.ngrid) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.x) HIPC(c, hipMemcpy(dx, r.x, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.missing) HIPC(c, hipMemcpy(miss, r.missing, (size_t)(N * T), hipMemcpyHostToDevice));
+    if (nq > 0) HIPC(c, hipMemcpy(lev, r.o->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+    McArgs g{};
+    g.missing = miss, g.x = dx, g.grid_x = gx, g.grid_phi = gp, g.levels = lev;
+    g.grid_site_stride = per_site ? (int64_t)r.ngrid * m.d * zw : 0;
+    g.nll = nll, g.pit = pit, g.med = med, g.err = err, g.mean = mean, g.q = q;
+    g.dens = dens, g.rho = rho, g.work = work, g.pbuf = pb, g.sbuf = sb;
+    g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.o->get_err ? 1 : 0;
+    return run_blocks(c, N, chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        if (launch_margcond(m, g, std::min<int64_t>(blk.grid_wgs, cnt * T), c->stream, mid) < 0)
+            return fail(c, MPST_ERR_DEVICE, "the marginal-conditional kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, MargcondHooks{c, T, nq, {nll, pit, med, err, mean, q}, {r.nll_out, r.pit_out, r.med_out, r.err_out, r.mean_out, nq > 0 ? r.q_out : nullptr}});
+}
+
 int mpst_get_impute_phases(void* ctx, double* seconds_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !seconds_out) return MPST_ERR_INVALID;
@@ -2931,6 +3004,29 @@ int mpst_window_conditionals(void* ctx, const mpst_impute_model* h, int32_t max_
     DevModel dm;
     if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
     return run_window(c, dm.view, WindowRequest{max_width, nll_out, seconds});
+}
+
+int mpst_marginal_conditionals(void* ctx, const mpst_impute_model* h, const uint8_t* missing, const double* x, const double* grid_x,
+                               const void* grid_phi, int32_t ngrid, const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out,
+                               double* err_out, double* mean_out, double* q_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !grid_x || !grid_phi || !o) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (!nll_out && !pit_out && !med_out && !err_out && !mean_out && !q_out) return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
+    if (pit_out && !x) return fail(c, MPST_ERR_INVALID, "pit_out needs the values x");
+    if (ngrid < 2) return fail(c, MPST_ERR_INVALID, "fewer than 2 grid values");
+    int cap = 0, rc;
+    if ((rc = check_grid_per_site(c, o->grid_per_site)) || (rc = check_levels(c, o->nq, o->levels, q_out))) return rc;
+    if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is conditioned under its own class");
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, true))) return rc;
+    if (h->compute == MPST_COMPUTE_F32) return fail(c, MPST_ERR_UNSUPPORTED, "marginal conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > MARGCOND_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "marginal conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT,
+                    MARGCOND_MAX_CLASSES, cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_margcond(c, dm.view, MargcondRequest{o, missing, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out, mean_out,
+                                                    o->nq > 0 ? q_out : nullptr, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

@@ -1718,6 +1718,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_marginal.inl"
 #include "mpst_sitecond.inl"
 #include "mpst_window.inl"
+#include "mpst_margcond.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1737,6 +1738,8 @@ int64_t marginal_work_elems(int cap, bool cx, bool f32) { return cap > impute_ld
 // window conditionals keep three of the environment pass's four matrices in LDS (E, the site matrix, T1)
 static size_t window_lds_bytes(int cap, bool cx) { return right_lds_bytes(cap, cx, false) / 4 * 3; }
 bool window_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
+// marginal site conditionals keep the environment pass's four matrices in LDS (L, the site matrix, K_s, R)
+bool margcond_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
 
 // ---- the route of a call: which kernels, at which block size / occupancy / dynamic LDS -----------------------------------
 struct ImputeSwitches {
@@ -1844,6 +1847,11 @@ hipError_t impute_init_attrs(int device) {
                                              (int)window_lds_bytes(impute_lds_chi_limit(false, false), false)),
                          hipFuncSetAttribute((const void*)k_win<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)window_lds_bytes(impute_lds_chi_limit(true, false), true))})
+        if (e != hipSuccess) return e;
+    for (hipError_t e : {hipFuncSetAttribute((const void*)k_mc_walk<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(false, false), false, false)),
+                         hipFuncSetAttribute((const void*)k_mc_walk<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(true, false), true, false))})
         if (e != hipSuccess) return e;
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
@@ -1968,6 +1976,25 @@ int launch_window(const ImpModel& v, const WinArgs& g, int64_t walk_wgs, int64_t
         if (big) hipLaunchKernelGGL((k_win<false, true>), kgrid, dim3(IMP_T), 0, s, v, g);
         else hipLaunchKernelGGL((k_win<false, false>), kgrid, dim3(IMP_T), lds, s, v, g);
     }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// marginal site conditionals of a chunk: the walk, a workgroup per instance, then the grid phase, a workgroup per (instance, site) pair
+// at a time
+int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStream_t s, hipEvent_t mid) {
+    const dim3 wgrid((unsigned)g.count), ggrid((unsigned)grid_wgs);
+    const bool big = margcond_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : right_lds_bytes(v.cap, v.is_complex != 0, false);
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_mc_walk<true, true>), wgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_mc_walk<true, false>), wgrid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_mc_walk<false, true>), wgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_mc_walk<false, false>), wgrid, dim3(IMP_T), lds, s, v, g);
+    }
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (mid) (void)hipEventRecord(mid, s);
+    if (v.is_complex) hipLaunchKernelGGL((k_mc_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_mc_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

@@ -748,6 +748,27 @@ bool window_big_route(int cap, bool cx);
 // the walk (walk_wgs workgroups of SITECOND_TILE instances), an event, the window kernel on win_wgs workgroups; v.label is read,
 // v.compute_f32 must be 0.  0, or -1 on a launch error
 int launch_window(const ImpModel& v, const WinArgs& g, int64_t walk_wgs, int64_t win_wgs, hipStream_t s, hipEvent_t mid);
+// marginal site conditionals (k_mc_walk, k_mc_grid; mpst_margcond.inl): what both kernels take by value, for one chunk of instances
+struct McArgs {
+    const uint8_t* missing;     // [N][T] or null (nothing missing)
+    const double* x;            // [N][T] values (encoding domain), NaN where there is none; null: nll at the known sites only, no pit
+    const double* grid_x;       // [ngrid]
+    const double* grid_phi;     // [ngrid][d] or [T][ngrid][d] (pairs: complex)
+    int64_t grid_site_stride;
+    const double* levels;       // [nq]
+    double *nll, *pit, *med, *err, *mean, *q;   // [chunk][T] ([chunk][T][nq]), the chunk's own; null: skipped
+    double* dens;               // [chunk][T][cap * cap] (pairs): slot t holds R_{t+1} at trace one, leading dimension chi_{t+1}
+    double* rho;                // [chunk][T][d * d] (pairs)
+    double* work;               // [chunk][MARGCOND_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null
+    double *pbuf, *sbuf;        // [grid workgroups][ngrid]
+    int64_t first, count;       // the instances of this chunk
+    int ngrid, nq, get_err;
+};
+// the walk's matrices live in global scratch (the environment pass's limit; mpst_query_plan.h: margcond_plan_block takes it as big_route)
+bool margcond_big_route(int cap, bool cx);
+// the walk (a workgroup per instance), an event, the grid phase on grid_wgs workgroups; v.label is read, v.compute_f32 must be 0.
+// 0, or -1 on a launch error
+int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStream_t s, hipEvent_t mid);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin

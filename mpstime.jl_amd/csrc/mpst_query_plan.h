@@ -190,6 +190,34 @@ inline PairPlan pair_plan(int C, int T, int d, int cap, bool store_rho, int64_t 
     return p;
 }
 
+// ---- marginal site conditionals (mpst_margcond.inl: k_mc_walk, k_mc_grid) ----
+constexpr int MARGCOND_BIG_MATS = 5;            // chi x chi matrices of global scratch per workgroup of k_mc_walk beyond the LDS limit
+constexpr int MARGCOND_MAX_GRID_WORKGROUPS = 4096;      // of k_mc_grid, an (instance, site) pair at a time
+
+struct MargcondBlock {
+    int64_t chunk, grid_wgs;            // instances per launch (= workgroups of its walk); workgroups of its grid phase
+    int64_t per_bytes;                  // scratch bytes of one instance
+};
+// Marginal site conditionals.  With budget = query_budget(free_b, chunk_gb), in bytes:
+//     per instance    T * (cap * cap * zw + d * d * zw + outputs) * 8     the kept densities of every site, rho_t of every site and the
+//                                                                         block's own outputs (`outputs` doubles per (instance, site):
+//                                                                         one for each of nll, pit, med, err, mean asked for, and nq)
+//                   + MARGCOND_BIG_MATS * cap * cap * zw * 8              on the big route only: the walk is a workgroup per instance
+//     chunk    = floor(budget / per instance), at least 1, at most N and at most floor((2^30 - 1) / T), so that chunk * T < 2^30
+//                ((instance, site) pairs in 32 bits); whole instances, no rounding: a workgroup of the walk is one instance
+//     grid_wgs = min(chunk * T, MARGCOND_MAX_GRID_WORKGROUPS)
+// x and the mask ([N][T], 9 bytes per pair) and the 2 * ngrid doubles of every grid workgroup live for the whole call and are not
+// counted, as in the site conditionals.
+inline MargcondBlock margcond_plan_block(int64_t N, int32_t T, int32_t cap, int32_t d, int32_t zw, int32_t outputs, bool big_route, size_t free_b,
+                                         const char* chunk_gb) {
+    const double budget = query_budget(free_b, chunk_gb);
+    const double mat = (double)cap * cap * zw;
+    const double per = ((double)T * (mat + (double)d * d * zw + outputs) + (big_route ? MARGCOND_BIG_MATS * mat : 0.0)) * sizeof(double);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(budget / per)));
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (((int64_t)1 << 30) - 1) / T));
+    return {chunk, std::max<int64_t>(1, std::min<int64_t>(chunk * T, MARGCOND_MAX_GRID_WORKGROUPS)), (int64_t)per};
+}
+
 // the blocks [i0, i0 + count) of N instances, `chunk` at a time; stops at the first non-zero result of f and returns it
 template <typename F>
 inline int for_each_block(int64_t N, int64_t chunk, F&& f) {

@@ -492,6 +492,14 @@ class SweepEngine:
         return site_conditionals_model(self, W, phi, label_index, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad, compute=compute,
                                        label_site=label_site)
 
+    def marginal_conditionals(self, W, phi, label_index, missing, x, grid_x, grid_phi, levels=None, get_wmad=True, label_site=None):
+        """mpst_marginal_conditionals: the distribution of every site, known or missing, of every series given the known values of
+        its OTHER sites, the missing ones summed out (Born rule), each under the class ``label_index[i]``; see
+        ``conditionals.marginal_conditionals_model``.  Returns a ``MarginalConditionals``."""
+        from .conditionals import marginal_conditionals_model
+        return marginal_conditionals_model(self, W, phi, label_index, missing, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad,
+                                           label_site=label_site)
+
     def window_conditionals(self, W, phi, label_index, max_width, label_site=None):
         """mpst_window_conditionals: -ln P(x_t .. x_{t+w-1} | the rest) of every COMPLETE series, every start t and every width
         w <= ``max_width``, each under the class ``label_index[i]``; see ``conditionals.window_conditionals_model``.
@@ -501,7 +509,7 @@ class SweepEngine:
 
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call; after ``site_conditionals``: (walk, grid phase);
-        after ``window_conditionals``: (walk, window kernel)."""
+        after ``window_conditionals``: (walk, window kernel); after ``marginal_conditionals``: (walk, grid phase)."""
         out = np.zeros(2)
         self._chk(self.lib.mpst_get_impute_phases(self.ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return float(out[0]), float(out[1])

@@ -409,6 +409,41 @@ function window_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_s
     return nll
 end
 
+"""
+    marginal_conditionals(sites, chi, label_site, phi, label_idx, missing, x, xvals, xvals_enc; get_err, levels, device)
+
+For every series of `phi` ((d, T, N)) with the sites `missing` ((T, N) UInt8, non-zero: missing) and every site t, known or missing,
+the distribution of x_t given the known values of the other sites, the missing ones summed out (Born rule), under the class MPS of
+the series' label (`mpst_marginal_conditionals`; model and grid arguments as `site_conditionals` takes them).  `x` (T, N): the value
+in the encoding's domain - the held-out true value or NaN at a missing site, where `phi` is read only when it is finite.  Returns
+`(nll, pit, median, err, mean, q)`: (T, N) arrays, `nll` and `pit` NaN at missing sites without a value, and `q` (nq, T, N)
+(`nothing` without `levels`).
+"""
+function marginal_conditionals(sites::Vector{<:Array}, chi::Vector{Int32}, label_site::Integer, phi::Array, label_idx::Vector{Int32},
+                               missing::Matrix{UInt8}, x::Matrix{Float64}, xvals::Vector{Float64}, xvals_enc::Array;
+                               get_err::Bool=true, levels::Union{Nothing,Vector{Float64}}=nothing, device::Integer=0)
+    d, T, N = size(phi)
+    cx = eltype(phi) <: Complex
+    nq = levels === nothing ? 0 : length(levels)
+    nll = zeros(Float64, T, N); pit = zeros(Float64, T, N); med = zeros(Float64, T, N); err = zeros(Float64, T, N)
+    mean = zeros(Float64, T, N)
+    q = nq > 0 ? zeros(Float64, nq, T, N) : nothing
+    secs = Ref(0.0)
+    with_context(device) do c
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in sites]
+        o = Ref(MpstSiteCondOpts(ndims(xvals_enc) == 3 ? 1 : 0, get_err ? 1 : 0, nq, 0, nq > 0 ? pointer(levels) : Ptr{Float64}(C_NULL)))
+        GC.@preserve sites ptrs chi phi label_idx levels o begin
+            model = impute_model_ref(ptrs, chi, N, T, d, maximum(label_idx) + 1, label_site - 1, cx, 0, phi, label_idx)
+            check(c, ccall((:mpst_marginal_conditionals, LIB), Cint,
+                           (Ptr{Cvoid}, Ref{MpstImputeModel}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Cvoid},
+                            Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                           c, model, missing, x, xvals, xvals_enc, length(xvals), Base.unsafe_convert(Ptr{Cvoid}, o), nll, pit, med, err,
+                           mean, nq > 0 ? pointer(q) : C_NULL, secs))
+        end
+    end
+    return nll, pit, med, err, mean, q
+end
+
 # ---- entanglement analysis (src/Analysis/analyse.jl) ---------------------------------------------------------------------
 const MPST_ERR_DOMAIN = -6
 
