@@ -619,7 +619,10 @@ int  mpst_get_info(void* ctx, int32_t* out /*[16]*/);
  * point; the query does not wait for the stream), out[18] the bonds of a sweep run FOUR launches (k_grad_s, k_gram_upd, k_eig_trivec, k_bond_tail: verification +
  * polish of the eigenvectors, back-split, update_caches!, the next bond's tensor and the next bond's overlaps in the last one;
  * Float64, KLD, d*chi_max <= 128, chi_max <= 32, one rank, update_iters = 1, no track_cost), out[19] sweeps / bond steps in which a
- * tail launch's verification failed and the rest ran on the six-launch chain (whose k_eig_fin has the Jacobi fallback). */
+ * tail launch's verification failed and the rest ran on the six-launch chain (whose k_eig_fin has the Jacobi fallback), out[20] on
+ * the four-launch chain the part of the tail that needs no eigenvector (the dense S tile of every 16-series tile, the next bond's
+ * overlap product) is formed by side workgroups of the k_eig_trivec launch and read back by k_bond_tail (0: MPST_TAIL_PRE=0, the
+ * tail forms both itself; the same bits either way). */
 int  mpst_get_info_n(void* ctx, int32_t* out, int32_t n);
 /* in-kernel phase times (us) of the last eigensolver launch: tridiagonalisation, bisection,
  * tridiagonal eigenvectors, back-transformation, verification+re-orthonormalisation; us[5] = shader
@@ -629,9 +632,15 @@ int  mpst_get_eig_phases(void* ctx, double* us /*[6]*/);
  * last launch, which stands for k_eig_fin + update_caches! + the back-split (RealRealHighDimension.jl:107-203) and the next bond's
  * yhat pass (loss_functions.jl:248-262).  Which bond leaves stamps: MPST_TAIL_STAMP="lid,going_left" (default: the middle bond of the
  * backward half-sweep).  us[0..15] workgroup 0, which also hosts a job of the next bond's tensor when the sweep goes on: start,
- * candidate vectors requested, factors requested, bond dimensions known, everything requested, factors in LDS, truncation rule,
- * candidates in LDS, verified + polished, overlap product issued, dense S tile, new environment rows, z + row dot, tile done, role
- * done, stores drained; us[16..31] the same for the last workgroup (a tile, no role); us[48..51] bonds since the context was created
+ * candidate vectors requested, the side workgroups' results requested, bond dimensions known, everything requested, trace pieces
+ * published, truncation rule, candidates and S tile in LDS, verified + polished, role operands requested, new environment rows,
+ * z + row dot, tile done, role done, stores drained (15 stamps).  With MPST_TAIL_PRE=0 the tail forms the S tile and the overlap
+ * product itself and the sequence is the longer one: start, candidate vectors requested, factors requested, bond dimensions known,
+ * everything requested, factors in LDS, truncation rule, candidates in LDS, verified + polished, overlap product issued, role operands
+ * requested, barrier B1 passed, dense S tile formed, new environment rows, z + row dot, tile done (a role host's last two stamps,
+ * role done and stores drained, do not fit the 16 slots and are not kept); us[16..31] the same for the last workgroup (a tile, no
+ * role); us[32..35] the side workgroups of that bond's k_eig_trivec launch (out[20] of mpst_get_info_n): how many, earliest start,
+ * latest start, latest end - negative, that launch precedes the tail; us[48..51] bonds since the context was created
  * by how far from orthonormal their candidate vectors were: |Z^T Z - I| below 1e-13 (nothing to do), below 1e-8 (first-order polish),
  * below 3e-5 (second-order), above (two passes); us[52], us[53], us[54] the earliest start, the latest end and the latest start over
  * ALL workgroups of the stamped launch */

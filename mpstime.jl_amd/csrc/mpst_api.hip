@@ -137,8 +137,12 @@ struct TrainWs {
     // four-launch chain (k_grad_s, k_gram_upd, k_eig_trivec, k_bond_tail): bt_new once more as [c][y][x] for the tail's contraction going
     // right; a tail whose on-device verification failed marks the sweep (DevScalars::redo) and the rest of it is redone on the six-launch chain
     DevBuf<double> btnT;
-    DevBuf<unsigned long long> tail_span;    // diagnostics: (start, end) stamps of every workgroup of the stamped k_bond_tail launch
+    // ... and what the side workgroups of k_eig_trivec leave for the tail (TailSide): [ntiles][TS_ST] dense S tiles, [ntiles][TS_P] overlap products
+    DevBuf<double> tail_St, tail_P;
+    // diagnostics: (start, end) stamps of every workgroup of the stamped k_bond_tail launch, [2 * TS_SPAN]; behind them the same of the side workgroups
+    DevBuf<unsigned long long> tail_span;
     bool chain4_ok = false;
+    bool tail_pre = false;    // chain4_ok and not MPST_TAIL_PRE=0: side workgroups form the S tile and the overlap product, else the tail itself
     int tail_force_fail = -1, tail_launches = 0;      // test hook (MPST_TAIL_FORCE_REDO=n): the n-th tail launch of the workspace reports a failed verification
     // sliced bond GEMMs (k_yhat_s / k_grad_s): slice contributions to yhat, loss pieces, arrival tickets
     DevBuf<double> b2_ypart, b2_lossp;
@@ -483,9 +487,13 @@ int workspace_f64(Ctx* c, TrainWs& w, int64_t Lmax) {
         // (a context that is advanced in batches keeps the six-launch chain mpst_sweep_batch runs: its solo and its batched sweeps agree bit for bit)
         w.chain4_ok = w.fused && w.b2 && c->batch_hint <= 1 && !(e4 && e4[0] == '0');
         if (const char* ff = getenv("MPST_TAIL_FORCE_REDO")) w.tail_force_fail = atoi(ff);
+        const char* ep = getenv("MPST_TAIL_PRE");
+        w.tail_pre = w.chain4_ok && !(ep && ep[0] == '0');
         if (w.chain4_ok && (rc = dalloc(c, w.btnT, c->C * Lmax))) return rc;
-        if (w.chain4_ok && (rc = dalloc(c, w.tail_span, 2 * 2048))) return rc;
-        if (w.chain4_ok) HIPC(c, hipMemset(w.tail_span, 0, 2 * 2048 * sizeof(unsigned long long)));
+        if (w.tail_pre && (rc = dalloc(c, w.tail_St, (int64_t)tr.ntiles * TS_ST))) return rc;
+        if (w.tail_pre && (rc = dalloc(c, w.tail_P, (int64_t)tr.ntiles * TS_P))) return rc;
+        if (w.chain4_ok && (rc = dalloc(c, w.tail_span, 4 * TS_SPAN))) return rc;
+        if (w.chain4_ok) HIPC(c, hipMemset(w.tail_span, 0, 4 * TS_SPAN * sizeof(unsigned long long)));
     }
     w.n_norm_part = (int)((c->C * Lmax + 63) / 64);      // RED_E entries per workgroup of k_fused_reduce
     if ((rc = dalloc(c, w.norm_scratch, (int64_t)3 * c->mps.cap * c->mps.cap))) return rc;
@@ -822,11 +830,21 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
             launch_gram_upd(vg, lid, going_left, iters == 1, s);
         }
         if (use4) {
-            { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s); }
-            ProfScope p(c, K_ENV);                                                // verification, back-split, update_caches!, next yhat
             const int nxt = going_left ? lid - 1 : lid + 1;
             const int want = (nxt >= 0 && nxt <= c->T - 2) ? 1 : 0;
-            launch_bond_tail(v, lid, going_left, chain, want | (c->ws.tail_launches++ == c->ws.tail_force_fail ? 4 : 0), c->ws.tail_span, s);
+            // what of the tail needs no eigenvector rides in the eigensolver's launch, on the CUs it leaves empty (TailSide)
+            TailSide sd{};
+            const TailSide* pre = c->ws.tail_pre ? &sd : nullptr;
+            if (pre) {
+                tail_side_operands(v, lid, going_left, sd);
+                sd.St = c->ws.tail_St;
+                sd.P = c->ws.tail_P;
+                sd.span = tail_stamped(v, lid, going_left) ? c->ws.tail_span + 2 * TS_SPAN : nullptr;
+                sd.want_next = want;
+            }
+            { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s, pre); }
+            ProfScope p(c, K_ENV);                                                // verification, back-split, update_caches!, next yhat
+            launch_bond_tail(v, lid, going_left, chain, want | (c->ws.tail_launches++ == c->ws.tail_force_fail ? 4 : 0), c->ws.tail_span, pre, s);
             if (want) {
                 c->ynext_lid = nxt;
                 c->ynext_epoch = c->epoch;
@@ -3208,7 +3226,7 @@ int mpst_get_info(void* ctx, int32_t* out) {
 }
 
 int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
-    int32_t full[20];
+    int32_t full[21];
     if (!out || n < 0) return MPST_ERR_INVALID;
     int rc = mpst_get_info(ctx, full);
     if (rc) return rc;
@@ -3218,12 +3236,14 @@ int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
         // [18] the bonds of a sweep run the four-launch chain (k_bond_tail); [19] sweeps / bond steps whose tail was redone on the six-launch chain
         full[18] = bond_uses_tail(c4, v4, c4->opt.track_cost != 0) ? 1 : 0;
         full[19] = c4->tail_redos;
+        // [20] on that chain, the S tile and the overlap product of the tail come from side workgroups of the k_eig_trivec launch (0: MPST_TAIL_PRE=0)
+        full[20] = (full[18] && c4->ws.tail_pre) ? 1 : 0;
     }
     // bonds the subspace eigensolver attempted / whose result was accepted (the rest went to the exact solver), as of the last sweep,
     // batch or bond step that returned: cached at their synchronisation point, the query itself never waits for the stream
     full[16] = ((Ctx*)ctx)->ss_counts[0];
     full[17] = ((Ctx*)ctx)->ss_counts[1];
-    for (int i = 0; i < n && i < 20; ++i) out[i] = full[i];
+    for (int i = 0; i < n && i < 21; ++i) out[i] = full[i];
     return 0;
 }
 
@@ -3245,7 +3265,8 @@ int mpst_get_eig_phases(void* ctx, double* us) {
 }
 
 // phase stamps of the last stamped k_bond_tail launch (us since workgroup 0 started; -1: not taken): us[0..15] workgroup 0 (which also
-// hosts a job of the next bond's tensor when the sweep goes on), us[16..31] the last workgroup (no role) (see include/mpstime_hip.h)
+// hosts a job of the next bond's tensor when the sweep goes on), us[16..31] the last workgroup (no role), us[32..35] the side workgroups
+// of the bond's k_eig_trivec launch (see include/mpstime_hip.h)
 int mpst_get_tail_phases(void* ctx, double* us) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !c->ws.sc || !us) return MPST_ERR_INVALID;
@@ -3280,6 +3301,26 @@ int mpst_get_tail_phases(void* ctx, double* us) {
             us[52] = 0.01 * ((double)s0 - t0);
             us[53] = 0.01 * ((double)e1 - t0);
             us[54] = 0.01 * ((double)s1 - t0);
+        }
+    }
+    // the side workgroups of that bond's k_eig_trivec launch (the launch BEFORE the tail: negative times): how many left a (start, end),
+    // earliest start, latest start, latest end
+    us[32] = us[33] = us[34] = us[35] = 0.0;
+    {
+        const size_t ns = (size_t)std::min<unsigned long long>(t[61], (unsigned long long)TS_SPAN);
+        if (ns > 0 && c->ws.tail_span && c->ws.tail_pre && t[16]) {
+            std::vector<unsigned long long> sp(2 * ns);
+            HIPC(c, hipMemcpy(sp.data(), c->ws.tail_span + 2 * TS_SPAN, sp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            unsigned long long s0 = ~0ull, s1 = 0ull, e1 = 0ull;
+            for (size_t i = 0; i < ns; ++i) {
+                s0 = std::min(s0, sp[2 * i]);
+                s1 = std::max(s1, sp[2 * i]);
+                e1 = std::max(e1, sp[2 * i + 1]);
+            }
+            us[32] = (double)ns;
+            us[33] = 0.01 * ((double)s0 - t0);
+            us[34] = 0.01 * ((double)s1 - t0);
+            us[35] = 0.01 * ((double)e1 - t0);
         }
     }
     return 0;

@@ -25,6 +25,7 @@
 //    unconditionally robust; column k converges to lambda_k v_k.
 #include "mpst_internal.h"
 #include "mpst_eig_common.inl"
+#include "mpst_tail_side.inl"
 #include <type_traits>
 
 namespace mpst {
@@ -1072,8 +1073,82 @@ __device__ __forceinline__ void trivec_body(const View& v, int lid, int going_le
     if (tid >= VEC_THREADS) return;
     vec_core<true>(pb, k, smem, cnt_s, red_s, arg_s, ws, st, lo, hi, tnorm);
 }
+// ---- the side workgroups of the headline launch (TailSide, mpst_tail_side.inl): the 32 eigenvector workgroups leave 224 CUs of the
+// chip empty for the 144 us the launch takes, and part of what k_bond_tail does afterwards needs nothing the eigensolver computes - the
+// dense S tile of every 16-series tile and the next bond's overlap product P = O bt_new (bt_new is final after k_gram_upd, the
+// Khatri-Rao factors exist before the bond starts).  One side workgroup per tile forms both and stores them for the tail: it reads,
+// multiplies, stores and ends - no workgroup waits for another.  The eigenvector workgroups keep the lowest block indices (dispatched
+// first) and the launch's LDS request (157 KB) keeps every other workgroup off their CUs.
+// The role sits behind a block-index branch at the top of the kernel and is INLINED there: as a called function it has to save the
+// callee-saved VGPRs it touches (188 bytes of scratch per lane instead of 20 for every workgroup of the launch, whatever the function's
+// linkage) and the sweep measured SLOWER than without side workgroups (profiles/tail_side_workgroups.md); inlined, the eigenvector
+// workgroups' code keeps its 128 registers, its 20 bytes of scratch and its four spilled registers with their reloads where they
+// were.  What keeps the role itself within the launch's 128 registers per lane:
+// bt_new's entries are requested a batch ahead of their MFMAs instead of all 32 up front, and d == 4 has no code path of its own (the
+// general one forms the same products of the same two factors).
+// Eight waves: wave w owns columns 16w .. 16w+15 of P, the same batches into the same two accumulators as the tail's own product; the
+// tail reads pacc0 + pacc1 in the accumulator layout.  The launch's other eight waves leave at once (a terminated wave no longer counts
+// at s_barrier).
+__device__ __forceinline__ void tail_side_role(const View& v, int lid, int going_left, const TailSide& sd) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x;
+    if (tid >= 512) return;
+    const int t = (int)blockIdx.x - sd.first;
+    unsigned long long* span = (sd.span && tid == 0 && t < TS_SPAN) ? sd.span + 2 * t : nullptr;
+    if (span) span[0] = __builtin_amdgcn_s_memrealtime();
+    if (span && t == 0) v.sc->eig_stamps[61] = (unsigned long long)min((int)gridDim.x - sd.first, TS_SPAN);
+    const int lane = tid & 63, wave = tid >> 6;
+    const int i16 = lane & 15, kq = lane >> 4;
+    const int d = v.d, want_next = sd.want_next;
+    double* Sf = smem;                              // the factors of the S side, of the O side
+    double* Of = Sf + BT_FAC;
+    // the loader role of a thread: threads [0, 256) the S side, [256, 512) the O side (as in k_bond_tail)
+    const bool lower = tid < 256;
+    const int lrow = (tid & 255) >> 4, lj = tid & 15;
+    const Span tl = tile_span_k(v, t);
+    FacRegs f{0.0, 0.0, 0.0};
+    if (lower || want_next) f = tail_fac_request(lower ? sd.Sprev : sd.Oprev, lower ? sd.phS : sd.phO, tl, lrow, lj, v.cap, d);
+    const int Dl = v.chi[lid], Dr = v.chi[lid + 2];
+    const int X = Dl * d, Y = d * Dr;
+    // S: the side the kept eigenvectors live on (Y going left, X going right); O: the other side; bt_new as [k = O index][n = S index]
+    const int DS = sd.Sprev ? (going_left ? Dr : Dl) : 1, DO = sd.Oprev ? (going_left ? Dl : Dr) : 1;
+    const int KO = going_left ? X : Y, NS = going_left ? Y : X;
+    const KrSide ks = kr_side(Sf, DS, d, !going_left), ko = kr_side(Of, DO, d, going_left != 0);
+    const int KP = (KO + 3) & ~3, ZS = DS * d;
+    tail_fac_store(lower ? Sf : Of, f, lrow, lj, lower ? DS : DO, (lower ? sd.Sprev : sd.Oprev) == nullptr);
+    lds_barrier();
+    // Both results leave with write-through (agent-scope) stores: with plain stores the 8 MB of a headline bond stay dirty in the L2s
+    // until the launch ends, and the launch and the two launches after the tail measured longer (profiles/tail_side_workgroups.md)
+    auto store_wt = [](double* p, double x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    {
+        double* __restrict__ Stt = sd.St + (int64_t)t * TS_ST;
+        const int row = tid >> 5, z0 = tid & 31;    // 4 entries per thread: z0, z0 + 32, ...
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int z = z0 + 32 * m;
+            store_wt(&Stt[row * 128 + z], z < ZS ? kr_at(ks, row, (unsigned)z) : 0.0);
+        }
+    }
+    if (want_next) {
+        const BmSource src = tail_bm_source(sd.M + (int64_t)tl.cls * ((int64_t)X * Y), wave, i16, kq, KO, NS);
+        d4 pacc0 = {0.0, 0.0, 0.0, 0.0}, pacc1 = {0.0, 0.0, 0.0, 0.0};
+        double bm[32];
+        tail_overlap_product<false, true>(ko, KP, i16, kq, bm, src, pacc0, pacc1);
+        double* __restrict__ Pt = sd.P + (int64_t)t * TS_P + wave * 256 + lane;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) store_wt(&Pt[r * 64], pacc0[r] + pacc1[r]);
+    }
+    if (span) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        span[1] = __builtin_amdgcn_s_memrealtime();
+    }
+}
 __global__ __launch_bounds__(TRI_T) void k_eig_trivec(View v, int lid, int going_left, const double* rawG, int rawn,
-                                                            int rawalg, double* __restrict__ ws, unsigned long long* stamps) {
+                                                            int rawalg, double* __restrict__ ws, unsigned long long* stamps, TailSide sd) {
+    if (sd.first > 0 && (int)blockIdx.x >= sd.first) {
+        tail_side_role(v, lid, going_left, sd);
+        return;
+    }
     trivec_body(v, lid, going_left, rawG, rawn, rawalg, ws, stamps);
 }
 __device__ __noinline__ void vec_core_call(const EigProblem& pb, const int k, double* smem, int* cnt_s, double* red_s, int* arg_s,
@@ -1340,13 +1415,19 @@ bool eig_merged() {
 
 // workgroups of the eigenvector kernels (one eigenpair each): the kept dimension n, at least 32, at most the TRI_KMAX they deliver
 static int eig_vec_blocks(int n) { return n < TRI_KMAX ? (n < 32 ? 32 : n) : TRI_KMAX; }
-void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s) {
+void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s, const TailSide* side) {
     unsigned long long* st = v.sc ? v.sc->eig_stamps : nullptr;
     const dim3 gvec(eig_vec_blocks(v.chi_max));
-    if (stage == 0 && eig_merged())
-        hipLaunchKernelGGL(k_eig_trivec, gvec, dim3(TRI_T), vec_lds_bytes(), s, v, lid, going_left, (const double*)nullptr, 0, 0,
-                           v.eig_ws, st);
-    else if (stage == 0)
+    if (stage == 0 && eig_merged()) {
+        // the tail's side workgroups, one per 16-series tile, behind the eigenvector workgroups
+        TailSide sd{};
+        if (side) {
+            sd = *side;
+            sd.first = (int32_t)gvec.x;
+        }
+        hipLaunchKernelGGL(k_eig_trivec, dim3(gvec.x + (side ? v.ntiles : 0)), dim3(TRI_T), vec_lds_bytes(), s, v, lid, going_left,
+                           (const double*)nullptr, 0, 0, v.eig_ws, st, sd);
+    } else if (stage == 0)
         hipLaunchKernelGGL(k_eig_tri, dim3(1), dim3(TRI_T), eig_lds_bytes(), s, v, lid, going_left,
                            (const double*)nullptr, 0, 0, v.eig_ws, st);
     else if (stage == 1) {
@@ -1393,7 +1474,7 @@ void launch_eig_raw(const double* G, int n, int alg, double* lam, double* E, int
     hipLaunchKernelGGL(k_eig_clear, dim3(1), dim3(256), 0, s, lam, E, n);
     if (eig_merged())
         hipLaunchKernelGGL(k_eig_trivec, dim3(RAW_KMAX), dim3(TRI_T), vec_lds_bytes(), s, v, 0, 0, G, n, alg, ws,
-                           (unsigned long long*)nullptr);
+                           (unsigned long long*)nullptr, TailSide{});
     else {
         hipLaunchKernelGGL(k_eig_tri, dim3(1), dim3(TRI_T), eig_lds_bytes(), s, v, 0, 0, G, n, alg, ws,
                            (unsigned long long*)nullptr);

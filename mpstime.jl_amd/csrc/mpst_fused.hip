@@ -14,6 +14,7 @@
 #include "mpst_internal.h"
 #include "mpst_bond_plan.h"
 #include "mpst_eig_common.inl"
+#include "mpst_tail_side.inl"
 #include <algorithm>
 #include <cassert>
 #include <cstring>
@@ -830,18 +831,7 @@ __device__ __forceinline__ double ld_agent(const double* p) { return __hip_atomi
 
 constexpr int YS_T = 512;        // 8 waves, one 16-series tile each
 
-// class-pure tile t of the data set from the tables in the kernel arguments (no dependent global load)
-__device__ __forceinline__ Span tile_span_k(const View& v, int t) {
-    int c = 0;
-#pragma unroll 1
-    for (int k = 1; k < v.C; ++k) c += (t >= v.kcls_tile[k]) ? 1 : 0;
-    Span s;
-    s.cls = c;
-    s.start = v.kcls_off[c] + TILE_S * (t - v.kcls_tile[c]);
-    s.count = t < v.ntiles ? min(TILE_S, v.kcls_off[c + 1] - s.start) : 0;
-    s.pad = 0;
-    return s;
-}
+// (tile_span_k, the class-pure tile t of the data set from the tables in the kernel arguments: mpst_tail_side.inl)
 
 // grid.x = nslc * ngw (see launch_yhat_s): workgroup id -> (group walker = id % ngw, slice = id / ngw); grid.y = passes (MSE: C)
 // Every wave stages, consumes and stores its own tile: no workgroup barrier, one round trip to memory per group.
@@ -1373,8 +1363,10 @@ __device__ __forceinline__ void grad_s_body(const View& v, int lid, int ksplit, 
 //               = O_i^T bt_new_c (E (E^T S_i)) / ||bt_new||
 //    with S_i / O_i the Khatri-Rao vectors of this bond on the side the eigenvectors live on / the other side (the environment of
 //    the other side is the next bond's outer environment contracted with the neighbouring site: it exists in the cache).  The
-//    product P = O bt_new (256 MFMAs per tile) needs neither E nor the new environment and runs before the polish; a wave owns 16
-//    columns of it and forms z = E env' for the same 16 columns in the accumulator layout, so the row dot needs no exchange;
+//    product P = O bt_new (256 MFMAs per tile) needs neither E nor the new environment: like the dense S tile it is formed by the side
+//    workgroups of the bond's k_eig_trivec launch and read back here (bond_tail_body<.., PRE>; MPST_TAIL_PRE=0: formed here, after the
+//    polish); a wave owns 16 columns of it and forms z = E env' for the same 16 columns in the accumulator layout, so the row dot
+//    needs no exchange;
 //  * split / chain workgroups: the back-split and the next bond's tensor as in k_env_split, with E from LDS.
 // A failed verification (genuinely clustered kept eigenvalues: k_eig_fin would fall through to its Jacobi solver) sets the sticky
 // DevScalars::redo (= 1 + the bond's position in the sweep) and leaves the MPS, the caches and the chained tensor alone; every later tail
@@ -1384,39 +1376,13 @@ constexpr int BT_T = 512;                    // 8 waves
 constexpr int BT_ZS = 36;                    // LDS row stride of the candidate / kept eigenvectors: rows 16 apart in 16 different bank pairs
                                              // (with the 32 of k_eig_fin's layout the A operand of Z D is a 16-way conflict: 3 us per polish)
 constexpr int BT_ENVS = 34;                  // LDS row stride of the 16 x 32 tile of new environment rows
-constexpr int BT_ELS = 37, BT_PLS = 21;      // LDS row strides of the staged factors (odd: the 16 rows a wave reads hit 16 bank pairs): 32 bond
-                                             // entries / 16 site states and zeros behind them (the padded K extent reads up to 4 beyond the live ones)
-constexpr int BT_FAC = 16 * (BT_ELS + BT_PLS);
-constexpr int BT_SS = 129;                   // row stride of the dense S tile (over D / Dh / misc once the polish is done)
+// (BT_ELS, BT_PLS, BT_FAC - the staged Khatri-Rao factors of a tile - with KrSide / kr_side / kr_at: mpst_tail_side.inl, shared with the side
+// workgroups of k_eig_trivec)
+constexpr int BT_SS = 129;                   // row stride of the dense S tile
 constexpr int BT_LDS_DOUBLES = 128 * BT_ZS + 32 * 32 + 1024 + 128 + 2048 + 16 * BT_ENVS + 128;     // 76 KB
+constexpr int BT_LDS_DOUBLES_PRE = BT_LDS_DOUBLES + 16 * BT_SS;      // 92 KB: the S tile the side workgroups formed has LDS of its own
 static_assert(2 * BT_FAC <= 2048, "the factors live where the pieces of env' go later");
-static_assert(16 * BT_SS <= 32 * 32 + 1024 + 128, "the dense S tile lives in the polish scratch");
-
-// One side's Khatri-Rao vectors of a 16-series tile, kept as their FACTORS in LDS (environment row, site vector); entry z of row i
-// is formed where it is wanted: left  z = a d + s: prev_i[a] phi_i[s];  right  z = s Dp + b: phi_i[s] prev_i[b]
-// (the one product stage16 forms: the same bits).  Division by d / Dp with a multiply (z < 1024).
-struct KrSide {
-    const double* env;      // [16][BT_ELS]
-    const double* ph;       // [16][BT_PLS]
-    unsigned magic, div;
-    bool left;
-};
-__device__ __forceinline__ KrSide kr_side(const double* fac, int Dp, int d, bool left) {
-    KrSide k;
-    k.env = fac;
-    k.ph = fac + 16 * BT_ELS;
-    k.div = (unsigned)(left ? d : Dp);
-    k.magic = (65536u + k.div - 1u) / k.div;
-    k.left = left;
-    return k;
-}
-__device__ __forceinline__ double kr_at(const KrSide& k, int row, unsigned z) {
-    const unsigned q = (z * k.magic) >> 16, r = z - q * k.div;
-    // (entries the padded extent of a product asks for beyond the live ones: on the right the site index reaches 21 at d = 11 .. 16 with a
-    // bond of 3 and 31 with a bond of 1 - tests/fuzz_chain4.py found the first; it is clamped onto the row's zero pad, as is the bond index on the left)
-    const unsigned ie = min(k.left ? q : r, (unsigned)(BT_ELS - 1)), ip = min(k.left ? r : q, (unsigned)(BT_PLS - 1));
-    return k.env[row * BT_ELS + ie] * k.ph[row * BT_PLS + ip];
-}
+static_assert(16 * BT_SS <= 32 * 32 + 1024 + 128, "formed in the tail, the dense S tile lives in the polish scratch");
 
 // =====================================================================================================================
 // k_env_walk (round 6): construct_caches (RealRealHighDimension.jl:45-103) in ONE launch.  The environments of different series never
@@ -1791,6 +1757,7 @@ struct TailArgs {
     double* out;                    // the new environment rows
     int32_t lid, going_left, nsplit, nchain, flags;     // flags: 1 the next bond's overlaps are wanted, 2 leave phase stamps
     unsigned long long* span;       // stamped launch: (start, end) of every workgroup, or null
+    const double *preSt, *preP;     // k_bond_tail<.., true>: the S tiles / overlap products the side workgroups of k_eig_trivec left (TailSide)
 };
 
 // Verification + re-orthonormalisation of the K candidate vectors Z ([c * BT_ZS + k], zero beyond the live rows / columns), all 8 waves:
@@ -1952,7 +1919,11 @@ __device__ __forceinline__ int truncate_rule_lanes(const double lam_lane, const 
 }
 
 // D4: d == 4 (the headline shapes): on the left side a = u, s = kq are immediates
-template <bool D4>
+// PRE: the dense S tile and the overlap product P were formed by the side workgroups of this bond's k_eig_trivec launch (TailSide,
+// mpst_tail_side.inl) and are read back here, requested with the candidate vectors - no O-side factors, no 64 registers of bt_new held
+// across the polish, no product and no S formation between the polish and env'.  The same values in the same places: everything from
+// env' on is the same code.  !PRE (MPST_TAIL_PRE=0): the tail forms both itself.
+template <bool D4, bool PRE>
 __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ double red[16];
@@ -1975,7 +1946,9 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
         else if (bid == (int)gridDim.x - 1) stp = v.sc->eig_stamps + 32;
     }
     int sti = 0;
-#define TSTAMP() do { if (stp) stp[sti++] = __builtin_amdgcn_s_memrealtime(); } while (0)
+    // (16 slots per region: with the side workgroups' results a role host takes 15 stamps; forming them itself it would take 18 - the
+    // last two, role done and stores drained, are then not kept)
+#define TSTAMP() do { if (stp && sti < 16) stp[sti] = __builtin_amdgcn_s_memrealtime(); ++sti; } while (0)
     TSTAMP();
     // ... and every workgroup of a stamped launch leaves its own start and end: the launch's span, and how the workgroups are spread over it
     unsigned long long* spanp = ((ta.flags & 2) && tid == 0 && ta.span && bid < 2048) ? ta.span + 2 * bid : nullptr;
@@ -1992,7 +1965,7 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
     double* envs = part + 2048;                    // [16][BT_ENVS] new environment rows of the tile
     double* redy = envs + 16 * BT_ENVS;            // [8][16] the waves' pieces of yhat
     double* cpart = Dl;                            // [4][2][256] the chain role's partial tiles (the polish scratch and the S tile are long consumed)
-    double* St = Dl;                               // [16][BT_SS] the dense S tile, once the polish is done
+    double* St = PRE ? redy + 128 : Dl;            // [16][BT_SS] the dense S tile: LDS of its own, or over the polish scratch once the polish is done
     const double* __restrict__ ws = v.eig_ws;
     // the loader role of a thread: threads [0, 256) the S side, [256, 512) the O side; 16 threads per series row, two bond entries and
     // one site state each
@@ -2010,26 +1983,34 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
     const double res_in = ws[WS_RES + (tid & 31)];                       // (used by threads < nk only)
     const int redo_in = v.sc->redo;
     TSTAMP();      // [1] candidates requested
-    Span tl{0, 0, 0, 0};
-    double fe0 = 0.0, fe1 = 0.0, fp = 0.0;
-    {
-        tl = tile_span_k(v, bid);                   // (count 0 beyond the last tile: a workgroup that is there for its role only)
-        if (lower || want_next) {
-            // whole rows (the capacity is a kernel argument); what lies beyond the live bond is dropped when the dimensions are known
-            const double* prev = lower ? ta.Sprev : ta.Oprev;
-            const double* ph = lower ? ta.phS : ta.phO;
-            const bool valid = lrow < tl.count;
-            const int64_t smp = tl.count > 0 ? tl.start + (valid ? lrow : 0) : 0;
-            // (unconditional loads from clamped addresses: see tail_chain_request; a tile beyond the data set has count 0 and start 0)
-            const double x0 = prev ? prev[smp * v.cap + min(lj, v.cap - 1)] : 1.0;
-            const double x1 = prev ? prev[smp * v.cap + min(lj + 16, v.cap - 1)] : 1.0;
-            const double xp = ph[smp * d + min(lj, d - 1)];
-            fe0 = (valid && lj < v.cap) ? x0 : 0.0;
-            fe1 = (valid && lj + 16 < v.cap) ? x1 : 0.0;
-            fp = (valid && lj < d) ? xp : 0.0;
+    const Span tl = tile_span_k(v, bid);            // (count 0 beyond the last tile: a workgroup that is there for its role only)
+    FacRegs fr{0.0, 0.0, 0.0};
+    double sin[4] = {0.0, 0.0, 0.0, 0.0}, pin[4] = {0.0, 0.0, 0.0, 0.0};
+    if (PRE) {
+        // this thread's four entries of the S tile (row tid >> 5, z = (tid & 31) + 32 m: where the in-tail formation puts them) and, in the
+        // accumulator layout, this lane's four sums of P.  A workgroup beyond the last tile has no side workgroup: zeros, as the factors of
+        // its empty tile give (unconditional loads from a clamped tile index)
+        const bool has = bid < v.ntiles;
+        const int64_t ts = min(bid, v.ntiles - 1);
+        const double* __restrict__ Sg = ta.preSt + ts * TS_ST + (tid >> 5) * 128 + (tid & 31);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const double x = Sg[32 * m];
+            sin[m] = has ? x : 0.0;
         }
+        if (want_next) {
+            const double* __restrict__ Pt = ta.preP + ts * TS_P + wave * 256 + lane;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double x = Pt[64 * r];
+                pin[r] = has ? x : 0.0;
+            }
+        }
+    } else if (lower || want_next) {
+        // whole rows (the capacity is a kernel argument); what lies beyond the live bond is dropped when the dimensions are known
+        fr = tail_fac_request(lower ? ta.Sprev : ta.Oprev, lower ? ta.phS : ta.phO, tl, lrow, lj, v.cap, d);
     }
-    TSTAMP();      // [2] factors requested
+    TSTAMP();      // [2] factors / the side workgroups' results requested
     // ---- ... then those that need the bond dimensions -----------------------------------------------------------------------
     const EigProblem pb = resolve(v, lid, going_left, nullptr, 0, 0);
     const BondDimsF b = bond_dims_f(v, lid);
@@ -2044,34 +2025,15 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
     if (stp) { asm volatile("" :: "s"(KO), "s"(NS)); }
     TSTAMP();      // [3] bond dimensions known
     d4 pacc0 = {0.0, 0.0, 0.0, 0.0}, pacc1 = {0.0, 0.0, 0.0, 0.0};
-    double bm[32];          // requested operands of the workgroup's role: the tile's slice of bt_new / see tail_chain_request, tail_split_load
-    if (want_next) {
-        // this wave's 16 columns of bt_new, every k-step: no predicates (sixteen exec-masked loads in a row keep the memory
-        // pipeline from ever holding a tile's worth of requests).  Rows beyond the live ones meet zeros of the O side, columns
-        // beyond them zeros of z: their (finite) values are read from clamped addresses and do not matter.
-        const unsigned col = (unsigned)min(16 * wave + i16, NS - 1);
-        const double* __restrict__ M = ta.M + (int64_t)tl.cls * b.L;        // (uniform base + 32-bit lane offsets)
-#pragma unroll
-        for (int u = 0; u < 32; ++u) bm[u] = M[(unsigned)min(4 * u + kq, KO - 1) * (unsigned)NS + col];
-    }
+    double bm[32];          // !PRE: this wave's 16 columns of the tile's class of bt_new, every k-step (tail_bm_request)
+    const BmSource bsrc = tail_bm_source(ta.M + (int64_t)tl.cls * b.L, wave, i16, kq, KO, NS);        // (uniform base + 32-bit lane offsets)
+    if (!PRE && want_next) tail_bm_request(bsrc, bm);
     const double gd_ = pb.G[(size_t)min(tid, n - 1) * (n + 1)];
     const double gdiag = tid < n ? gd_ : 0.0;
     lam_in = lane < K0 ? lam_in : 0.0;
-    {
-        const int Dp = lower ? DS : DO;
-        const bool bnd = (lower ? ta.Sprev : ta.Oprev) == nullptr;      // chain end: the one live entry is 1
-        fe0 = lj < Dp ? fe0 : 0.0;
-        fe1 = (lj + 16 < Dp && !bnd) ? fe1 : 0.0;
-    }
     TSTAMP();      // [4] everything requested
-    {
-        double* fac = lower ? Sf : Of;
-        fac[lrow * BT_ELS + lj] = fe0;
-        fac[lrow * BT_ELS + lj + 16] = fe1;
-        if (lj < BT_ELS - 32) fac[lrow * BT_ELS + 32 + lj] = 0.0;
-        fac[16 * BT_ELS + lrow * BT_PLS + lj] = fp;
-        if (lj < BT_PLS - 16) fac[16 * BT_ELS + lrow * BT_PLS + 16 + lj] = 0.0;
-    }
+    // (chain end: the one live entry is 1)
+    if (!PRE) tail_fac_store(lower ? Sf : Of, fr, lrow, lj, lower ? DS : DO, (lower ? ta.Sprev : ta.Oprev) == nullptr);
     {
         const double trw = wave_sum(gdiag);         // pieces of the trace: they meet at the barrier the factors need anyway
         if (lane == 0) red[wave] = trw;
@@ -2090,8 +2052,12 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
         const int c = i >> 5, kk = i & 31;
         Zl[c * BT_ZS + kk] = (c < n && kk < nk) ? zin[m] : 0.0;
     }
+    if (PRE) {                                      // the S tile to its own LDS (nobody reads it before env')
+#pragma unroll
+        for (int m = 0; m < 4; ++m) St[(tid >> 5) * BT_SS + (tid & 31) + 32 * m] = sin[m];
+    }
     __syncthreads();
-    TSTAMP();      // [5] candidates in LDS
+    TSTAMP();      // [5] candidates (and the S tile) in LDS
     bool ok = triflag == 1.0 && redo_in == 0 && !(ta.flags & 4);
     double emax0 = 0.0;
     if (ok) ok = tail_polish(Zl, Dl, Dh, misc, n, nk, (tid < nk ? res_in : 0.0) / (tnorm_in > 0.0 ? tnorm_in : 1.0), emax0, true);
@@ -2103,42 +2069,12 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
         }
         return;
     }
-    // P = O bt_new AFTER the polish: its operand (128 KB of bt_new per workgroup: the CU's L1 moves 64 bytes a cycle) has arrived by now,
-    // the candidates came first
-    {
-        if (want_next) {
-            // P = O bt_new, this wave's 16 columns.  A wave issues one MFMA per 64 cycles whatever their dependencies (profiles/ubench/
-            // mfma_rate.hip), so what a product costs is 64 cycles per MFMA PLUS every operand latency the wave waits out in between:
-            // operands are fetched a batch of 8 k-steps ahead (left to itself the compiler reads, waits, multiplies, reads ...).
-            // Whole batches: beyond the live extent the O side is zero.
-            double ab[4][8];
-            auto fetch = [&](int bt) {
-                if (D4 && ko.left) {
-                    const double* er = ko.env + i16 * BT_ELS + 8 * bt;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) ab[bt][u] = er[u];
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) ab[bt][u] = kr_at(ko, i16, 4u * (8 * bt + u) + kq);
-                }
-            };
-            const double phf = (D4 && ko.left) ? ko.ph[i16 * BT_PLS + kq] : 1.0;
-            fetch(0);
-#pragma unroll
-            for (int bt = 0; bt < 4; ++bt) {
-                if (bt < 3) fetch(bt + 1);
-                asm volatile("" ::: "memory");
-                if (32 * bt < KP) {
-#pragma unroll
-                    for (int u = 0; u < 8; u += 2) {
-                        pacc0 = mfma_f64(ab[bt][u] * phf, bm[8 * bt + u], pacc0);
-                        pacc1 = mfma_f64(ab[bt][u + 1] * phf, bm[8 * bt + u + 1], pacc1);
-                    }
-                }
-            }
-        }
+    // formed here, P = O bt_new comes AFTER the polish: its operand (128 KB of bt_new per workgroup: the CU's L1 moves 64 bytes a cycle)
+    // has arrived by now, the candidates came first
+    if (!PRE) {
+        if (want_next) tail_overlap_product<D4, false>(ko, KP, i16, kq, bm, bsrc, pacc0, pacc1);      // P = O bt_new, this wave's 16 columns
+        TSTAMP();  // [10] P issued
     }
-    TSTAMP();      // [10] P issued
     // the role's operands into the registers the overlap product has just released: they arrive under the rest of the tile's work
     // (registers of their own: the overlap product's MFMAs may still be reading bm)
     double rr[16];
@@ -2165,18 +2101,21 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
     const double* __restrict__ Ef = Zl;
     // ---- the dense S tile, by all waves (env' then pays one LDS read per MFMA, whichever side S is).  It goes over the polish scratch:
     // the barrier keeps it off the error pieces a slower wave may still be reading (tail_polish returns without one when nothing is to do)
-    lds_barrier();                                  // B1 (LDS-only barriers from here on: __syncthreads() would also wait for the role's operands)
-    TSTAMP();      // B1 passed
-    {
-        const int row = tid >> 5, z0 = tid & 31;    // 4 entries per thread: z0, z0 + 32, ...
+    // (PRE: the tile is in LDS of its own since the candidates went there, and E is final behind tail_polish's last barrier: no barrier here)
+    if (!PRE) {
+        lds_barrier();                              // B1 (LDS-only barriers from here on: __syncthreads() would also wait for the role's operands)
+        TSTAMP();  // B1 passed
+        {
+            const int row = tid >> 5, z0 = tid & 31;    // 4 entries per thread: z0, z0 + 32, ...
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int z = z0 + 32 * m;
-            St[row * BT_SS + z] = z < ZS ? kr_at(ks, row, (unsigned)z) : 0.0;
+            for (int m = 0; m < 4; ++m) {
+                const int z = z0 + 32 * m;
+                St[row * BT_SS + z] = z < ZS ? kr_at(ks, row, (unsigned)z) : 0.0;
+            }
         }
+        lds_barrier();                              // B2
+        TSTAMP();  // [7] S tile formed
     }
-    lds_barrier();                                  // B2
-    TSTAMP();      // [7] S tile formed
     // env' = S E, the sums of k_env / k_env_split (mpst_internal.h: four chains over the quarters of the contraction): wave = (column tile,
     // quarter), the quarters meet in LDS as (q0 + q1) + (q2 + q3).  At most 32 vectors are kept here: two column tiles.
     {
@@ -2225,7 +2164,7 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
             for (int u = 0; u < 8; ++u) zacc = mfma_f64(za[u], zb[u], zacc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const double x = sum16((pacc0[r] + pacc1[r]) * zacc[r]);
+                const double x = sum16((PRE ? pin[r] : pacc0[r] + pacc1[r]) * zacc[r]);      // (pin: that very sum, formed by the side workgroup)
                 if (i16 == 0) redy[wave * 16 + kq + 4 * r] = x;
             }
         }
@@ -2253,9 +2192,9 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
 #undef TSTAMP
 #undef TEND
 }
-template <bool D4>
+template <bool D4, bool PRE>
 __global__ __launch_bounds__(BT_T) void k_bond_tail(View v, TailArgs ta) {
-    bond_tail_body<D4>(v, ta);
+    bond_tail_body<D4, PRE>(v, ta);
 }
 
 // ---- the kernels proper: one fit per launch (View in the kernel arguments), or K independent fits of the same shape per
@@ -2364,8 +2303,10 @@ hipError_t b2_init_attrs(int device) {
 #define X(AW2, D2, FS, KC, NW, THREADS) RAISE((k_grad_s<AW2, D2, FS, KC, NW>), 96 * 1024) RAISE((k_grad_s_b<AW2, D2, FS, KC, NW>), 96 * 1024)
     GRAD_S_LIST(X)
 #undef X
-    RAISE(k_bond_tail<true>, BT_LDS_DOUBLES * sizeof(double))
-    RAISE(k_bond_tail<false>, BT_LDS_DOUBLES * sizeof(double))
+    RAISE((k_bond_tail<true, false>), BT_LDS_DOUBLES * sizeof(double))
+    RAISE((k_bond_tail<false, false>), BT_LDS_DOUBLES * sizeof(double))
+    RAISE((k_bond_tail<true, true>), BT_LDS_DOUBLES_PRE * sizeof(double))
+    RAISE((k_bond_tail<false, true>), BT_LDS_DOUBLES_PRE * sizeof(double))
 #undef RAISE
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
@@ -2442,7 +2383,26 @@ void launch_env_split(const View& v, int lid, int going_left, int chain, hipStre
 bool bond_tail_supported(const View& v) {
     return v.zw != 2 && v.loss == MPST_LOSS_KLD && v.chi_max <= 32 && v.cap <= 32 && v.d * v.cap <= MAX_DIM && v.svd_alg != MPST_SVD_JACOBI && v.d >= 2 && v.d <= 16;
 }
-void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next /* bit 0; bit 2: forced failure (test hook) */, unsigned long long* span, hipStream_t s) {
+// S: the side this bond's environment step extends, O: the other side's row next to the bond
+void tail_side_operands(const View& v, int lid, int going_left, TailSide& sd) {
+    const int64_t cs = (int64_t)v.N * v.cap;
+    const EnvStep st = env_step_of_bond(lid, going_left, v.T), ot = env_step_of_bond(lid, !going_left, v.T);
+    sd.Sprev = env_row(st.left_side ? v.LE : v.RE, st.prev_site, cs);
+    sd.Oprev = env_row(ot.left_side ? v.LE : v.RE, ot.prev_site, cs);
+    sd.phS = v.phi + (int64_t)st.site * v.N * v.d;
+    sd.phO = v.phi + (int64_t)ot.site * v.N * v.d;
+    sd.M = going_left ? v.btn : v.btnT;
+}
+// which bond's tail leaves its phase stamps (mpst_get_tail_phases): MPST_TAIL_STAMP="lid,going_left", default the middle bond going left
+bool tail_stamped(const View& v, int lid, int going_left) {
+    static const std::pair<int, int> stamp = [] {
+        const char *e = getenv("MPST_TAIL_STAMP"), *q = e ? strchr(e, ',') : nullptr;
+        return std::make_pair(e ? atoi(e) : -1, q ? atoi(q + 1) : 1);
+    }();
+    return lid == (stamp.first >= 0 ? stamp.first : (v.T - 1) / 2) && (going_left != 0) == (stamp.second != 0);
+}
+void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next /* bit 0; bit 2: forced failure (test hook) */, unsigned long long* span,
+                      const TailSide* pre, hipStream_t s) {
     const int dm = v.d * v.cap;
     TailArgs ta;
     ta.lid = lid;
@@ -2451,25 +2411,27 @@ void launch_bond_tail(const View& v, int lid, int going_left, int chain, int wan
     ta.nchain = chain_blocks(v, chain);
     ta.flags = (want_next & 1) | (want_next & 4);      // bit 2: test hook - this launch reports a failed verification
     ta.span = span;
-    // S: the side this bond's environment step extends, O: the other side's row next to the bond
-    const int64_t cs = (int64_t)v.N * v.cap;
-    const EnvStep st = env_step_of_bond(lid, going_left, v.T), ot = env_step_of_bond(lid, !going_left, v.T);
-    ta.Sprev = env_row(st.left_side ? v.LE : v.RE, st.prev_site, cs);
-    ta.Oprev = env_row(ot.left_side ? v.LE : v.RE, ot.prev_site, cs);
-    ta.phS = v.phi + (int64_t)st.site * v.N * v.d;
-    ta.phO = v.phi + (int64_t)ot.site * v.N * v.d;
-    ta.M = going_left ? v.btn : v.btnT;
-    ta.out = env_row(st.left_side ? v.LE : v.RE, st.out_site, cs);
-    // which bond's tail leaves its phase stamps (mpst_get_tail_phases): MPST_TAIL_STAMP="lid,going_left", default the middle bond going left
-    static const std::pair<int, int> stamp = [] {
-        const char *e = getenv("MPST_TAIL_STAMP"), *q = e ? strchr(e, ',') : nullptr;
-        return std::make_pair(e ? atoi(e) : -1, q ? atoi(q + 1) : 1);
-    }();
-    if (lid == (stamp.first >= 0 ? stamp.first : (v.T - 1) / 2) && (going_left != 0) == (stamp.second != 0)) ta.flags |= 2;
-    const size_t lds = (size_t)BT_LDS_DOUBLES * sizeof(double);
+    TailSide o{};
+    tail_side_operands(v, lid, going_left, o);
+    ta.Sprev = o.Sprev;
+    ta.Oprev = o.Oprev;
+    ta.phS = o.phS;
+    ta.phO = o.phO;
+    ta.M = o.M;
+    ta.preSt = pre ? pre->St : nullptr;
+    ta.preP = pre ? pre->P : nullptr;
+    const EnvStep st = env_step_of_bond(lid, going_left, v.T);
+    ta.out = env_row(st.left_side ? v.LE : v.RE, st.out_site, (int64_t)v.N * v.cap);
+    if (tail_stamped(v, lid, going_left)) ta.flags |= 2;
+    const size_t lds = (size_t)(pre ? BT_LDS_DOUBLES_PRE : BT_LDS_DOUBLES) * sizeof(double);
     const dim3 grid(std::max(v.ntiles, ta.nchain + ta.nsplit));           // one 16-series tile per workgroup; the first ones carry a role as well
-    if (v.d == 4) hipLaunchKernelGGL(k_bond_tail<true>, grid, dim3(BT_T), lds, s, v, ta);
-    else hipLaunchKernelGGL(k_bond_tail<false>, grid, dim3(BT_T), lds, s, v, ta);
+    if (pre) {
+        if (v.d == 4) hipLaunchKernelGGL((k_bond_tail<true, true>), grid, dim3(BT_T), lds, s, v, ta);
+        else hipLaunchKernelGGL((k_bond_tail<false, true>), grid, dim3(BT_T), lds, s, v, ta);
+    } else {
+        if (v.d == 4) hipLaunchKernelGGL((k_bond_tail<true, false>), grid, dim3(BT_T), lds, s, v, ta);
+        else hipLaunchKernelGGL((k_bond_tail<false, false>), grid, dim3(BT_T), lds, s, v, ta);
+    }
 }
 void launch_grad_norm(const View& v, int lid, hipStream_t s) {
     hipLaunchKernelGGL(k_grad_norm, dim3(v.n_norm_part), dim3(64), 0, s, v, lid);

@@ -546,7 +546,27 @@ void launch_gram_upd(const View& v, int lid, int going_left, int first_iter, hip
 void launch_env_split(const View& v, int lid, int going_left, int chain /* also assemble the next bond's tensor */, hipStream_t s);
 // the four-launch chain's last launch (k_bond_tail): k_eig_fin's verification + polish, environment update, back-split, the next
 // bond's tensor (chain) and the next bond's overlaps (want_next) in one
-void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next, unsigned long long* span /* [2 * 2048] or null */, hipStream_t s);
+// What of that needs none of the eigensolver's output - the dense S tile of every 16-series tile and, when the next bond's overlaps are
+// wanted, the overlap product P = O bt_new - is formed by SIDE WORKGROUPS of the k_eig_trivec launch (one per tile, block indices
+// [first, first + ntiles) behind the eigenvector workgroups, on CUs that launch leaves empty; mpst_eig.hip: tail_side_role) and read
+// back by the tail.  first == 0: a launch without side workgroups.
+constexpr int TS_ST = 16 * 128;              // doubles per tile of the S tiles: [row][z], zeros beyond the live extent
+constexpr int TS_P = 8 * 4 * 64;             // ... and of the overlap products: [wave][accumulator register][lane], the two accumulators added
+constexpr int TS_SPAN = 2048;                // workgroups of a stamped launch that leave their (start, end)
+struct TailSide {
+    const double *Sprev, *Oprev;    // environment rows of the side the eigenvectors live on / of the other side (null: chain end)
+    const double *phS, *phO;        // the two sites' encoded series
+    const double* M;                // bt_new as [c][k = O index][n = S index]: btn going left, btnT going right
+    double* St;                     // [ntiles][TS_ST]
+    double* P;                      // [ntiles][TS_P], written when want_next
+    unsigned long long* span;       // stamped launch: (start, end) of every side workgroup, or null
+    int32_t first, want_next;
+};
+void tail_side_operands(const View& v, int lid, int going_left, TailSide& sd);       // Sprev .. M of bond lid (the tail's own operands)
+bool tail_stamped(const View& v, int lid, int going_left);                            // this bond's tail leaves its phase stamps (MPST_TAIL_STAMP)
+// pre: what the side workgroups of this bond's k_eig_trivec launch left (St, P), or null: the tail forms both itself
+void launch_bond_tail(const View& v, int lid, int going_left, int chain, int want_next, unsigned long long* span /* [2 * TS_SPAN] or null */,
+                      const TailSide* pre, hipStream_t s);
 bool bond_tail_supported(const View& v);
 // construct_caches in one launch: a workgroup walks the whole chain with its 16 series (k_env_walk); left_side: LE, else RE
 void launch_env_walk(const View& v, int left_side, int nstep /* sites, from the chain end */, hipStream_t s);
@@ -771,7 +791,8 @@ bool margcond_big_route(int cap, bool cx);
 int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStream_t s, hipEvent_t mid);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
-void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s);   // stage 0 tri (or tri + vec merged), 1 vec, 2 fin
+// stage 0 tri (or tri + vec merged), 1 vec, 2 fin; side (stage 0, merged only): the launch carries the tail's side workgroups
+void launch_eig(const View& v, int lid, int going_left, int stage, hipStream_t s, const TailSide* side = nullptr);
 void launch_eig_tail(const View& v, int lid, int going_left, int rawn, const double* Gt, int ld, double* Vall, double* dd, double* ee,
                      double* tau, const int32_t* abort_flag, const int32_t* skip, hipStream_t s);   // last 128 steps of a larger reduction on one CU
 bool eig_merged();   // k_eig_trivec instead of k_eig_tri + k_eig_vec (default; MPST_EIG_SPLIT=1 restores the three-kernel chain)

@@ -537,9 +537,9 @@ class SweepEngine:
         return {k: (us[i], int(cnt[i])) for i, k in enumerate(L.KERNEL_CLASSES)}
 
     def info(self):
-        out = (C.c_int32 * 20)()
-        self._chk(self.lib.mpst_get_info_n(self.ctx, out, 20))
-        return {"four_launch_chain": bool(out[18]), "tail_redos": out[19],
+        out = (C.c_int32 * 21)()
+        self._chk(self.lib.mpst_get_info_n(self.ctx, out, 21))
+        return {"four_launch_chain": bool(out[18]), "tail_redos": out[19], "tail_side_workgroups": bool(out[20]),
                 "subspace_attempted": out[16], "subspace_accepted": out[17], "fused": bool(out[0]), "large_bond": bool(out[1]), "nparts": out[2], "nchunks": out[3], "cap": out[4],
                 "ranks": out[5], "graph": bool(out[6]), "library_eig_fallbacks": out[7], "persistent_tridiag_aborts": out[8],
                 "xcd_local_misplaced": out[9], "sliced_bond_gemms": bool(out[10]), "grad_shares": out[11],
@@ -556,13 +556,22 @@ class SweepEngine:
         workgroup of the next bond's tensor, the first back-split workgroup."""
         us = np.zeros(55)
         self._chk(self.lib.mpst_get_tail_phases(self.ctx, us.ctypes.data_as(C.POINTER(C.c_double))))
-        tile = ("start", "candidates_requested", "factors_requested", "bond_dims_known", "all_requested", "factors_in_lds", "truncation",
-                "candidates_in_lds", "polished", "overlap_product_issued", "role_requested", "b1_passed", "s_tile_formed", "env_rows", "z_rowdot", "tile_done", "role_done",
-                "stores_drained")
-        role = tile
+        if self.info()["tail_side_workgroups"]:
+            # the S tile and the overlap product come from the side workgroups of k_eig_trivec: 15 stamps
+            host = ("start", "candidates_requested", "side_results_requested", "bond_dims_known", "all_requested", "trace_published", "truncation",
+                    "candidates_in_lds", "polished", "role_requested", "env_rows", "z_rowdot", "tile_done", "role_done", "stores_drained")
+        else:
+            # MPST_TAIL_PRE=0, both formed in the tail: 18 stamps, of which the 16 slots keep the first 16
+            host = ("start", "candidates_requested", "factors_requested", "bond_dims_known", "all_requested", "factors_in_lds", "truncation",
+                    "candidates_in_lds", "polished", "overlap_product_issued", "role_requested", "b1_passed", "s_tile_formed", "env_rows", "z_rowdot",
+                    "tile_done", "role_done", "stores_drained")
+        plain = tuple(k for k in host if k != "role_done")          # a workgroup without a role takes no such stamp
         pick = lambda names, x: {k: round(float(v), 2) for k, v in zip(names, x) if v >= 0 or k == "start"}
-        # workgroup 0 (hosts a job of the next bond's tensor when the sweep goes on), the first back-split host, the last workgroup (no role)
-        return {"host_of_a_chain_job": pick(tile, us[:16]), "plain_tile": pick(role, us[16:32]),
+        # workgroup 0 (hosts a job of the next bond's tensor when the sweep goes on), the last workgroup (no role); the side workgroups of the
+        # bond's k_eig_trivec launch ran before the tail: negative times
+        return {"host_of_a_chain_job": pick(host, us[:16]), "plain_tile": pick(plain, us[16:32]),
+                "side_workgroups": {"count": int(us[32]), "first_start": round(float(us[33]), 2), "last_start": round(float(us[34]), 2),
+                                    "last_end": round(float(us[35]), 2)},
                 "bonds_by_candidate_orthogonality": dict(zip(("below_1e-13", "below_1e-8", "below_3e-5", "above"), [int(x) for x in us[48:52]])),
                 "all_workgroups": {"first_start": round(float(us[52]), 2), "last_start": round(float(us[54]), 2), "last_end": round(float(us[53]), 2)}}
 
