@@ -571,7 +571,8 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
 /* Device seconds of the last imputation call split into its two kernels: [0] the environment pass (k_imp_right, MFMA),
  * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
  * mpst_window_conditionals: (walk, window kernel); after mpst_marginal_conditionals: (walk, grid phase); after
- * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel). */
+ * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel); after
+ * mpst_prefix_marginals: (environment kernel k_prefix_env, walk-and-score kernel k_prefix_score). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid
@@ -645,6 +646,22 @@ int  mpst_get_eig_phases(void* ctx, double* us /*[6]*/);
  * below 3e-5 (second-order), above (two passes); us[52], us[53], us[54] the earliest start, the latest end and the latest start over
  * ALL workgroups of the stamped launch */
 int  mpst_get_tail_phases(void* ctx, double* us /*[55]*/);
+
+/* Prefix marginals: for every series i, every prefix length t = 0 .. T and every class c the log likelihood of the first t values with
+ * the sites t .. T-1 summed out - what mpst_marginal_model gives for the suffix mask of t (missing[i][j] = j >= t), for all T + 1 masks
+ * from one walk per series:
+ *     logp_out[i][t][c] = ln l_c(i; t),   l_c(i; t) = x_t G_c^t x_t^H,
+ * x_t the row walk through the known sites 0 .. t-1 and G_c^t the density recursion from the right end through the sites T-1 .. t, which
+ * depends on the model only and is computed once per call.  Index 0 is ln ||W_c||^2 for every series, index T the complete series.
+ * m as in mpst_marginal_model: the label slice of the model AS STORED; label_idx is not read, all of phi is; real and complex models,
+ * compute MPST_COMPUTE_F64.  A likelihood that is zero (or not finite) is -INFINITY; if it is the walk of a series that vanished at
+ * site j, every prefix longer than j of that series is -INFINITY.  Never NaN.  A series gives the same bits whichever series travel with
+ * it and however the series are cut into blocks (free device memory, MPST_IMPUTE_CHUNK_GB).  seconds (may be NULL) = device time;
+ * mpst_get_impute_phases then gives (environment kernel, walk-and-score kernel).
+ * MPST_ERR_INVALID: NULL m / logp_out, a malformed model; MPST_ERR_UNSUPPORTED: compute other than MPST_COMPUTE_F64, chi_max > 128,
+ * d > 16, C > 16; MPST_ERR_NOMEM: the (label_site + 1) C + (T - label_site) tables of chi_max^2 elements do not fit the query budget - they
+ * are not cut over t.  A rejected call leaves the context as it was. */
+int  mpst_prefix_marginals(void* ctx, const mpst_impute_model* m, double* logp_out /* [N][T+1][C] */, double* seconds /* may be NULL */);
 
 #ifdef __cplusplus
 }

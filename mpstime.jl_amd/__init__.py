@@ -22,6 +22,8 @@ from .conditionals import (SiteConditionals, site_conditionals, anomaly_scores, 
                            window_conditionals, window_conditionals_model, window_anomaly_scores, MarginalConditionals,
                            marginal_conditionals, marginal_conditionals_model, impute_marginal, forecast)
 from .overlaps import ModelOverlaps, model_overlaps, class_overlaps
+from .prefix import (EarlyClassification, prefix_log_marginals, prefix_posteriors, classify_early, early_accuracy_curve,
+                     causal_scores)
 from .summary import get_training_summary, training_stats, sweep_summary, print_opts
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
                      BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
@@ -39,4 +41,5 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "classify_many", "log_marginals", "class_posteriors", "SiteConditionals", "site_conditionals", "anomaly_scores", "WindowConditionals", "window_conditionals",
            "window_conditionals_model", "window_anomaly_scores", "MarginalConditionals", "marginal_conditionals", "marginal_conditionals_model",
            "impute_marginal", "forecast",
-           "ModelOverlaps", "model_overlaps", "class_overlaps", "get_training_summary", "training_stats", "sweep_summary", "print_opts"]
+           "ModelOverlaps", "model_overlaps", "class_overlaps", "EarlyClassification", "prefix_log_marginals", "prefix_posteriors",
+           "classify_early", "early_accuracy_curve", "causal_scores", "get_training_summary", "training_stats", "sweep_summary", "print_opts"]

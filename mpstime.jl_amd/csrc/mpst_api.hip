@@ -16,6 +16,7 @@
 #include "mpst_internal.h"
 #include "mpst_batch_groups.h"
 #include "mpst_bond_plan.h"
+#include "mpst_prefix_plan.h"
 
 using namespace mpst;
 
@@ -2719,6 +2720,59 @@ static int run_window(Ctx* c, const ImpModel& m, const WindowRequest& r) {
     }, WindowHooks{c, r, nll, T * r.max_width});
 }
 
+// One mpst_prefix_marginals call
+struct PrefixRequest {
+    int32_t C, label_site;
+    double *logp_out, *seconds;
+};
+// what a prefix call does around its blocks: a block's results are its own on the device and go to the caller's array after its walk,
+// outside the phases
+struct PrefixHooks {
+    Ctx* c; const PrefixRequest& r; double* dev_logp; int64_t per;      // per: doubles of one instance, (T + 1) * C
+    bool own_begin() const { return true; }
+    int prepare() { return 0; }
+    int before(int64_t, int64_t) { return 0; }
+    int after(int64_t i0, int64_t cnt) {
+        HIPC(c, hipMemcpyAsync(r.logp_out + (size_t)(i0 * per), dev_logp, (size_t)(cnt * per) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+// The prefix marginals of a request: the G tables of the model live for the whole call and must fit the budget as they are, the class
+// rows of the walk and the block's results are the scratch of a block of instances (mpst_prefix_plan.h: prefix_plan).  The phases are
+// the environment kernel, which the first block launches ahead of its walk, and the walk with its scores.
+constexpr int PREFIX_MAX_CLASSES = 16;
+static int run_prefix(Ctx* c, const ImpModel& m, const PrefixRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1, Cn = r.C;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const bool big = prefix_big_route(m.cap, m.is_complex != 0);
+    const PrefixPlan p = prefix_plan(N, m.T, Cn, r.label_site, m.cap, zw, big, free_b, chunk_gb_override());
+    if (p.nomem)
+        return fail(c, MPST_ERR_NOMEM, "the %lld environment tables of the model need %.3f GB of device memory, the budget of a query is %.3f GB: "
+                    "they are not cut over the prefix length", (long long)p.mats, (double)p.table_bytes / (double)(1ull << 30),
+                    query_budget(free_b, chunk_gb_override()) / (double)(1ull << 30));
+    const int64_t mat = (int64_t)m.cap * m.cap * zw;
+    DevBuf<double> G, lnG, work, crows, lp;
+    if ((rc = dalloc(c, G, p.mats * mat)) || (rc = dalloc(c, lnG, (T + 1) * Cn)) || (big && (rc = dalloc(c, work, (int64_t)Cn * PREFIX_ENV_BIG_MATS * mat))) ||
+        (rc = dalloc(c, crows, p.tiles * (Cn + 1) * PREFIX_TILE * m.cap * zw)) || (rc = dalloc(c, lp, p.chunk * (T + 1) * Cn))) return rc;
+    PrefixArgs g{};
+    g.G = G, g.lnG = lnG, g.work = work, g.crows = crows, g.logp = lp, g.C = Cn;
+    bool tables = false;
+    return run_blocks(c, N, p.chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        if (!tables && launch_prefix_env(m, g, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the prefix environment kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+        tables = true;
+        HIPC(c, hipEventRecord(mid, c->stream));
+        if (launch_prefix_score(m, g, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the prefix walk did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, PrefixHooks{c, r, lp, (T + 1) * Cn});
+}
+
 // One mpst_marginal_conditionals call: the mask and the values (either may be NULL), the grid, and the six outputs, each of which may be NULL
 struct MargcondRequest {
     const mpst_sitecond_opts* o;
@@ -3045,6 +3099,22 @@ int mpst_marginal_conditionals(void* ctx, const mpst_impute_model* h, const uint
     if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
     return run_margcond(c, dm.view, MargcondRequest{o, missing, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out, mean_out,
                                                     o->nq > 0 ? q_out : nullptr, seconds});
+}
+
+int mpst_prefix_marginals(void* ctx, const mpst_impute_model* h, double* logp_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    int cap = 0, rc;
+    if ((rc = check_model_shape(c, h, true, false, &cap))) return rc;
+    if (h->compute != MPST_COMPUTE_F64) return fail(c, MPST_ERR_UNSUPPORTED, "prefix marginals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if ((rc = check_model_types(c, h, false))) return rc;
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > PREFIX_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "prefix marginals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, PREFIX_MAX_CLASSES,
+                    cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, false, &dm))) return rc;
+    return run_prefix(c, dm.view, PrefixRequest{h->C, h->label_site, logp_out, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

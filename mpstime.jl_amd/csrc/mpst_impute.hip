@@ -32,6 +32,7 @@
 // Limits: d <= 16, chi <= 128.  The environment pass keeps two padded chi x chi matrices (+ a 16-row block) in LDS up to
 // chi = 64 (complex fp64: 48); beyond that k_imp_right_big works out of global scratch.
 #include "mpst_internal.h"
+#include "mpst_prefix_plan.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1719,6 +1720,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_sitecond.inl"
 #include "mpst_window.inl"
 #include "mpst_margcond.inl"
+#include "mpst_prefix.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1740,6 +1742,9 @@ static size_t window_lds_bytes(int cap, bool cx) { return right_lds_bytes(cap, c
 bool window_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
 // marginal site conditionals keep the environment pass's four matrices in LDS (L, the site matrix, K_s, R)
 bool margcond_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
+// the prefix marginals' recursion keeps three of them (E, the site matrix, T1)
+static size_t prefix_env_lds_bytes(int cap, bool cx) { return right_lds_bytes(cap, cx, false) / 4 * 3; }
+bool prefix_big_route(int cap, bool cx) { return cap > impute_lds_chi_limit(cx, false); }
 
 // ---- the route of a call: which kernels, at which block size / occupancy / dynamic LDS -----------------------------------
 struct ImputeSwitches {
@@ -1852,6 +1857,11 @@ hipError_t impute_init_attrs(int device) {
                                              (int)right_lds_bytes(impute_lds_chi_limit(false, false), false, false)),
                          hipFuncSetAttribute((const void*)k_mc_walk<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)right_lds_bytes(impute_lds_chi_limit(true, false), true, false))})
+        if (e != hipSuccess) return e;
+    for (hipError_t e : {hipFuncSetAttribute((const void*)k_prefix_env<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)prefix_env_lds_bytes(impute_lds_chi_limit(false, false), false)),
+                         hipFuncSetAttribute((const void*)k_prefix_env<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)prefix_env_lds_bytes(impute_lds_chi_limit(true, false), true))})
         if (e != hipSuccess) return e;
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
@@ -1995,6 +2005,27 @@ int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStr
     if (mid) (void)hipEventRecord(mid, s);
     if (v.is_complex) hipLaunchKernelGGL((k_mc_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
     else hipLaunchKernelGGL((k_mc_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// prefix marginals: the tables of the model, a workgroup per class
+int launch_prefix_env(const ImpModel& v, const PrefixArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)g.C);
+    const bool big = prefix_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : prefix_env_lds_bytes(v.cap, v.is_complex != 0);
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_prefix_env<true, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_prefix_env<true, false>), grid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_prefix_env<false, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_prefix_env<false, false>), grid, dim3(IMP_T), lds, s, v, g);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and the walk of a chunk with its scores, sixteen instances per workgroup
+int launch_prefix_score(const ImpModel& v, const PrefixArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)((g.count + SC_B - 1) / SC_B));
+    if (v.is_complex) hipLaunchKernelGGL((k_prefix_score<true>), grid, dim3(SC_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_prefix_score<false>), grid, dim3(SC_T), 0, s, v, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

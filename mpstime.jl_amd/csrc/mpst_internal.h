@@ -789,6 +789,22 @@ bool margcond_big_route(int cap, bool cx);
 // the walk (a workgroup per instance), an event, the grid phase on grid_wgs workgroups; v.label is read, v.compute_f32 must be 0.
 // 0, or -1 on a launch error
 int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStream_t s, hipEvent_t mid);
+// prefix marginals (k_prefix_env, k_prefix_score; mpst_prefix.inl): what both kernels take by value, for one chunk of instances
+struct PrefixArgs {
+    double* G;                  // [prefix_table_mats][cap * cap] (pairs): G_c^t at trace one, leading dimension chi_t (mpst_prefix_plan.h: the slots)
+    double* lnG;                // [T + 1][C]: ln tr of the recursion down to bond t
+    double* work;               // [C][PREFIX_ENV_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null
+    double* crows;              // [walk workgroups][C + 1][16][cap] (pairs): the rows of every class past the label site, the shared row
+    double* logp;               // [chunk][T + 1][C], the chunk's own
+    int64_t first, count;       // the instances of this chunk
+    int C;
+};
+// the density recursion runs in global scratch (the environment pass's limit; mpst_prefix_plan.h: prefix_plan takes it as big_route)
+bool prefix_big_route(int cap, bool cx);
+// the tables of a model (a workgroup per class), once per call; then the walk of a chunk, sixteen instances per workgroup.  v.label is
+// not read, v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_prefix_env(const ImpModel& v, const PrefixArgs& g, hipStream_t s);
+int launch_prefix_score(const ImpModel& v, const PrefixArgs& g, hipStream_t s);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 // stage 0 tri (or tri + vec merged), 1 vec, 2 fin; side (stage 0, merged only): the launch carries the tail's side workgroups

@@ -485,6 +485,12 @@ class SweepEngine:
         from .marginal import marginal_model
         return marginal_model(self, W, phi, missing, compute=compute, label_site=label_site)
 
+    def prefix_model(self, W, phi, compute="f64", label_site=None):
+        """mpst_prefix_marginals: (logp (N, T + 1, C), seconds), the log likelihood of the first t values of every instance under
+        every class with the sites from t on marginalised, t = 0 .. T; see ``prefix.prefix_model``."""
+        from .prefix import prefix_model
+        return prefix_model(self, W, phi, compute=compute, label_site=label_site)
+
     def site_conditionals(self, W, phi, label_index, x, grid_x, grid_phi, levels=None, get_wmad=True, compute="f64", label_site=None):
         """mpst_site_conditionals: the leave-one-out conditional p(x_t | x_{!=t}) of every site of every COMPLETE series, each under
         the class ``label_index[i]``; see ``conditionals.site_conditionals_model``.  Returns (nll, pit, median, err, q, seconds)."""
