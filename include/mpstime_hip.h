@@ -588,6 +588,24 @@ int  mpst_normalize(void* ctx);
 /* Diagnostics used by bench.py / tests (no reference counterpart). */
 int  mpst_selftest_mfma(void* ctx, const double* A /*16xK row-major*/, const double* B /*Kx16*/,
                         int32_t K, double* C_out /*16x16*/);
+/* mpst_selftest_eig: one solve of the bond eigensolver on a symmetric positive semi-definite G.  n <= 128 runs the solver of the
+ * fused chain, larger n the large-bond solvers.  lambda_out descending; column k of E_out is vector k; *sweeps reports the route:
+ * -1 tridiagonal route, verified on the device; 0 tridiagonal route rejected by its verification, Jacobi delivered; > 0 Jacobi
+ * asked for, its sweeps; n > 128: -3 blocked solver verified, -2 multi-workgroup Jacobi.  Delivered: the min(n, 32) largest pairs on
+ * the tridiagonal route (bit 3: min(n, 64)), everything on a Jacobi route (zero vectors for zero eigenvalues), min(n, 128) pairs
+ * above 128; the rest of lambda_out / E_out is zero.  The bits of alg:
+ *   bits 0-1  0 tridiagonal route with its fallback, 1 (MPST_SVD_JACOBI) Jacobi alone; n > 128: 0 blocked solver, the Jacobi
+ *             solver if its verification asks for it, 2 the Jacobi solver alone.
+ *   bit 2 (4)   pair mode, n even: G = [[A, -B], [B, A]] is the real embedding of the Hermitian A + iB, whose every eigenvalue G has
+ *             twice.  One vector u per pair is computed; column 2k holds u, column 2k + 1 its partner J u = (-u_im, u_re), and
+ *             lambda_out[2k] = lambda_out[2k + 1].
+ *   bit 3 (8)   n <= 128: up to 64 eigenpairs instead of 32 (what a bond with chi_max up to 64 asks for), of which the vectors of
+ *             pairs above 1e-13 of the largest are verified and delivered (the rule of the subspace solver's Rayleigh-Ritz problem).
+ *   bit 4 (16)  n <= 128: through the gated launcher of that Rayleigh-Ritz problem (always the tridiagonal route with 64 pairs, so bit
+ *             3 is implied and bits 0-2 must be 0), its gate word set to 1.
+ *   bit 5 (32)  with bit 4: gate word 0.  lambda_out, E_out and *sweeps are filled with -7 (-7.0) on the device beforehand and must
+ *             come back so: a closed gate makes both launches leave at once.
+ * MPST_ERR_INVALID: bit 3 or 4 with n > 128, bit 5 without bit 4, bit 4 with any of bits 0-2, any higher bit. */
 int  mpst_selftest_eig(void* ctx, const double* G /*n*n symmetric*/, int32_t n, int32_t alg,
                        double* lambda_out /*n*/, double* E_out /*n*n row-major [i][k]*/, int32_t* sweeps);
 /* Per-kernel timing with HIP events recorded on the engine's own stream around every launch

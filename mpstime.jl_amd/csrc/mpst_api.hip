@@ -3443,9 +3443,16 @@ int mpst_selftest_eig(void* ctx, const double* G, int32_t n, int32_t alg, double
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (n < 1 || n > DIM_LIMIT) return fail(c, MPST_ERR_INVALID, "n must be in 1..%d", DIM_LIMIT);
+    if (alg < 0 || (alg & ~63)) return fail(c, MPST_ERR_INVALID, "alg %d: only bits 0..5 have a meaning", alg);
+    if (n > MAX_DIM && (alg & (8 | 16)))
+        return fail(c, MPST_ERR_INVALID, "alg bits 3 and 4 (64 eigenpairs, gated launcher) belong to the n <= %d solver, n = %d", MAX_DIM, n);
+    if ((alg & 32) && !(alg & 16)) return fail(c, MPST_ERR_INVALID, "alg bit 5 (closed gate) needs bit 4 (gated launcher)");
+    if ((alg & 16) && (alg & 7))
+        return fail(c, MPST_ERR_INVALID, "alg bit 4: the gated launcher has one algorithm (tridiagonal, 64 eigenpairs), bits 0-2 must be 0");
+    const bool gated = (alg & 16) != 0, gate_open = !(alg & 32);
     HIPC(c, hipSetDevice(c->device));
     DevBuf<double> dG, dl, dE, dws;
-    DevBuf<int32_t> ds;
+    DevBuf<int32_t> ds, dgate;
     hipError_t ea = eig_init_attrs(c->device);
     if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
     int rc;
@@ -3477,6 +3484,18 @@ int mpst_selftest_eig(void* ctx, const double* G, int32_t n, int32_t alg, double
             big_eig_destroy(be);
             if (rc) return fail(c, rc, "the large-bond Jacobi solver could not be launched");
         }
+    } else if (gated) {
+        // the gated launcher clears nothing: zeros under an open gate, the sentinel under a closed one (which must come back untouched)
+        constexpr double SENTINEL = -7.0;        // documented in mpstime_hip.h
+        const double fill = gate_open ? 0.0 : SENTINEL;
+        const int32_t gate = gate_open ? 1 : 0, info0 = gate_open ? 0 : (int32_t)SENTINEL;
+        std::vector<double> hfill((size_t)n * n, fill);
+        if ((rc = dalloc(c, dgate, 1))) return rc;
+        HIPC(c, hipMemcpy(dl, hfill.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dE, hfill.data(), (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(ds, &info0, sizeof info0, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(dgate, &gate, sizeof gate, hipMemcpyHostToDevice));
+        launch_eig_raw_gated(dG, n, dl, dE, ds, dws, dgate, c->stream);
     } else {
         launch_eig_raw(dG, n, alg, dl, dE, ds, dws, c->stream);
     }

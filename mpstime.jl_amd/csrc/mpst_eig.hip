@@ -158,16 +158,26 @@ __device__ int jacobi_solve(const double* __restrict__ G, int n, double* smem, d
     const int tid = threadIdx.x;
     const int np = (n + 1) & ~1;
     EigShared sh = carve(smem, np);
+    // The iteration runs on G times an exact power of two that brings it to unit scale (a PSD matrix is bounded by its largest
+    // diagonal entry; every wave finds it for itself): the rotation test forms app * aqq, the FOURTH power of G's scale, which is
+    // infinite from 1e77 on and zero below 1e-77 - nothing is rotated and the columns of G come back as they went in.  Exact both
+    // ways: the same bits as without it wherever that product stays in range.
+    double gmax = 0.0;
+    for (int i = tid & 63; i < n; i += 64) gmax = fmax(gmax, fabs(G[(size_t)i * n + i]));
+    gmax = wave_max(gmax);
+    int ge = 0;
+    if (gmax > 0.0 && gmax < INFINITY) ge = max(__builtin_amdgcn_frexp_exp(gmax) - 1, -1022);
+    const double sdn = __builtin_amdgcn_ldexp(1.0, -ge), sup = __builtin_amdgcn_ldexp(1.0, ge);
     __syncthreads();
     for (int i = tid; i < np * np; i += EIG_THREADS) {
         const int col = i / np, row = i - col * np;
-        sh.Gs[i] = (row < n && col < n) ? G[(size_t)row * n + col] : 0.0;
+        sh.Gs[i] = (row < n && col < n) ? G[(size_t)row * n + col] * sdn : 0.0;
     }
     __syncthreads();
     const int sweeps = jacobi_core(sh, np);
     if (tid < np) {
         const int rk = sh.rank[tid];
-        if (rk < n) lam_out[rk] = sh.nrm[tid];
+        if (rk < n) lam_out[rk] = sh.nrm[tid] * sup;
     }
     for (int i = tid; i < np * np; i += EIG_THREADS) {
         const int col = i / np, row = i - col * np;
@@ -1471,14 +1481,16 @@ void launch_eig_raw_gated(const double* G, int n, double* lam, double* E, int32_
 
 void launch_eig_raw(const double* G, int n, int alg, double* lam, double* E, int32_t* info, double* ws, hipStream_t s) {
     View v{};
+    // one workgroup per eigenpair resolve() asks for: RAW_KMAX, with bit 3 of alg up to TRI_KMAX
+    const dim3 gvec((alg & 8) ? eig_vec_blocks(n) : RAW_KMAX);
     hipLaunchKernelGGL(k_eig_clear, dim3(1), dim3(256), 0, s, lam, E, n);
     if (eig_merged())
-        hipLaunchKernelGGL(k_eig_trivec, dim3(RAW_KMAX), dim3(TRI_T), vec_lds_bytes(), s, v, 0, 0, G, n, alg, ws,
+        hipLaunchKernelGGL(k_eig_trivec, gvec, dim3(TRI_T), vec_lds_bytes(), s, v, 0, 0, G, n, alg, ws,
                            (unsigned long long*)nullptr, TailSide{});
     else {
         hipLaunchKernelGGL(k_eig_tri, dim3(1), dim3(TRI_T), eig_lds_bytes(), s, v, 0, 0, G, n, alg, ws,
                            (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(k_eig_vec, dim3(RAW_KMAX), dim3(VEC_THREADS), vec_lds_bytes(), s, v, 0, 0, n, alg, ws,
+        hipLaunchKernelGGL(k_eig_vec, gvec, dim3(VEC_THREADS), vec_lds_bytes(), s, v, 0, 0, n, alg, ws,
                            (unsigned long long*)nullptr);
     }
     hipLaunchKernelGGL(k_eig_fin, dim3(1), dim3(EIG_THREADS), eig_lds_bytes(), s, v, 0, 0, G, n, alg, ws, lam, E, info,

@@ -88,15 +88,21 @@ __device__ bool verify_and_polish(FinShared t, int n, int K) {
     double* D = t.D;
     bool ok = true;
     {
+        // The candidates come from division-free minors: products of eight factors |d_j - x| <= 2 ||T|| between two rescalings.
+        // From ||T|| = 2^126 on they overflow (garbage, which the checks below catch); below 2^-83 the small ones (pairs down to
+        // 1e-13 = 2^-43 of the largest are delivered: eight factors of that size and one at rounding level, 2^-53) pass through the
+        // subnormal range and merely lose digits - eigenvalues off by 2e-12 ||T|| with residuals far below the threshold.  Outside
+        // [2^-80, 2^120] the route is not trusted and the Jacobi path, which rescales, takes over.
+        const double tn = t.misc[2];
         double rres = 0.0;
-        if (tid < K) rres = t.misc[32 + tid] / (t.misc[2] > 0.0 ? t.misc[2] : 1.0);
+        if (tid < K) rres = t.misc[32 + tid] / (tn > 0.0 ? tn : 1.0);
         rres = wave_max(rres);
         __syncthreads();
         if (lane == 0) t.misc[8 + wave] = rres;
         __syncthreads();
         double rmax = 0.0;
         for (int w = 0; w < EIG_THREADS / 64; ++w) rmax = fmax(rmax, t.misc[8 + w]);
-        ok = rmax < 1e-8 && rmax == rmax;
+        ok = rmax < 1e-8 && rmax == rmax && tn >= 0x1p-80 && tn <= 0x1p120;
     }
     static_assert(EIG_THREADS == 512, "the MFMA tiling below is written for 8 waves");
     const int jl = lane & 15, q4 = lane >> 4;

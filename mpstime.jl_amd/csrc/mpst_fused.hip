@@ -2058,7 +2058,8 @@ __device__ __forceinline__ void bond_tail_body(const View& v, const TailArgs& ta
     }
     __syncthreads();
     TSTAMP();      // [5] candidates (and the S tile) in LDS
-    bool ok = triflag == 1.0 && redo_in == 0 && !(ta.flags & 4);
+    // (||T|| outside [2^-80, 2^120]: the minors of the tridiagonal route leave the normal range, see verify_and_polish - the same rule)
+    bool ok = triflag == 1.0 && redo_in == 0 && !(ta.flags & 4) && tnorm_in >= 0x1p-80 && tnorm_in <= 0x1p120;
     double emax0 = 0.0;
     if (ok) ok = tail_polish(Zl, Dl, Dh, misc, n, nk, (tid < nk ? res_in : 0.0) / (tnorm_in > 0.0 ? tnorm_in : 1.0), emax0, true);
     TSTAMP();      // [6] verified + polished

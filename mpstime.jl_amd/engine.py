@@ -592,6 +592,25 @@ class SweepEngine:
         return out
 
     def selftest_eig(self, G, alg=0):
+        """mpst_selftest_eig: one solve of the bond eigensolver on the symmetric positive semi-definite ``G`` (n <= 128: the solver of
+        the fused chain; larger: the large-bond solvers).  Returns ``(lam, E, info)``: ``lam`` descending (n entries), column k of
+        ``E`` (n x n) vector k, ``info`` the route: -1 tridiagonal route verified on the device, 0 its verification handed over to
+        Jacobi, > 0 sweeps of the Jacobi path asked for; n > 128: -3 blocked solver, -2 multi-workgroup Jacobi.  Delivered are the
+        min(n, 32) largest pairs on the tridiagonal route (min(n, 64) with bit 3), everything on a Jacobi route (zero vectors for zero
+        eigenvalues) and min(n, 128) pairs above 128; the rest is zero.  ``alg`` is a bit field:
+
+        * bits 0-1: 0 tridiagonal route with its fallback, 1 Jacobi alone; n > 128: 0 blocked solver (Jacobi if its verification asks
+          for it), 2 Jacobi alone.
+        * bit 2 (4): pair mode, n even.  ``G = [[A, -B], [B, A]]`` embeds the Hermitian ``A + iB``; ``lam`` holds every eigenvalue of
+          it twice (``lam[2k] == lam[2k + 1]``), column ``2k`` of ``E`` the computed vector ``u`` (complex: ``E[:n//2, 2k] + 1j *
+          E[n//2:, 2k]``) and column ``2k + 1`` its partner ``J u = (-u_im, u_re)``.
+        * bit 3 (8), n <= 128: up to 64 eigenpairs; vectors only for pairs above 1e-13 of the largest.
+        * bit 4 (16), n <= 128: through the gated launcher of the subspace solver's Rayleigh-Ritz problem with an open gate (always the
+          tridiagonal route with 64 pairs: bits 0-2 must be 0).
+        * bit 5 (32), with bit 4: closed gate.  ``lam``, ``E`` and ``info`` are filled with -7 on the device first and must come back
+          untouched.
+
+        Bit 3 or 4 with n > 128, bit 5 without bit 4, bit 4 with bits 0-2 and higher bits raise MPSTError(MPST_ERR_INVALID)."""
         G = np.ascontiguousarray(G, dtype=np.float64)
         n = G.shape[0]
         lam = np.zeros(n)
