@@ -219,6 +219,31 @@ int  mpst_encode_split_dataset(void* ctx, int which, const double* X, const int3
                                const int64_t* n_global_per_class, double* oob_fix, double* seconds);
 int  mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo,
                               const mpst_split_opts* sp, void* phi_out, double* oob_fix, double* seconds);
+/* Sahand-Legendre bases (src/Encodings/bases.jl:111-129; sahand_legendre, basis_structs.jl:141-151): d polynomials orthonormalised
+ * under the square root of a kernel density estimate of the training values, fitted on the host ("Sahand-Legendre
+ * encodings").  A value x at site t is encoded as
+ *   phi_n(x) = max(sqrt(max(pdf_t(x), 0)), minx_t) / scale_t * sum_i cvecs_t[n][i] x^i,      n = 0 .. d-1
+ * where pdf_t is the quadratic B-spline through the estimate's npoints grid values: with u = (x - lo) / step + 1, i = round(u)
+ * clamped to 1 .. npoints and s = u - i it is coef[i-1] (s - 1/2)^2 / 2 + coef[i] (3/4 - s^2) + coef[i+1] (s + 1/2)^2 / 2 inside
+ * [lo, lo + (npoints - 1) step] and 0 outside.  A site whose cvecs are all zero encodes to zeros; its other tables are not read.
+ * mpst_encode_kde_dataset / mpst_encode_kde_values are mpst_encode_dataset / mpst_encode_values with this basis: eo->basis is
+ * ignored and not written (the states are real); the tables are copied to the device for the call and released with it.
+ * MPST_ERR_INVALID: NULL kd or array, npoints < 3, per_site not 0 / 1, d < 1 or d > 16, and - at a site whose cvecs are not all
+ * zero - a step, scale or minx that is not positive and finite. */
+typedef struct {
+    int32_t npoints, per_site;      /* K; 0: one table for all sites, 1: T tables */
+    const double* lo;               /* [S], S = per_site ? T : 1 */
+    const double* step;             /* [S] */
+    const double* coef;             /* [S][K + 2] */
+    const double* minx;             /* [S] */
+    const double* scale;            /* [S] */
+    const double* cvecs;            /* [S][d][d], row n = function n, column i = power i */
+} mpst_kde_opts;
+int  mpst_encode_kde_dataset(void* ctx, int which, const double* X, const int32_t* label_idx,
+                             int64_t N, int32_t T, int32_t d, int32_t C, mpst_encode_opts* eo, const mpst_kde_opts* kd,
+                             const int64_t* n_global_per_class, double* oob_fix, double* seconds);
+int  mpst_encode_kde_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo,
+                            const mpst_kde_opts* kd, void* phi_out, double* oob_fix, double* seconds);
 /* Encoded values of data set `which` back to the host, [N][T][d] in the context's element type
  * (EncodedTimeSeriesSet.timeseries). */
 int  mpst_get_encoded(void* ctx, int which, double* phi_out);

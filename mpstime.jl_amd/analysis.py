@@ -105,7 +105,7 @@ def see_variation(W, measure_series, cls: int = 0, engine: Optional[SweepEngine]
     if X.shape[0] == 0:
         return np.zeros((0, T, T))
     opts = safe_options(W.opts)
-    enc, _, encoder = fit_encoding_from_training_data(opts, W.train_data.original_data, W.train_data.labels)
+    enc, _, encoder = fit_encoding_from_training_data(opts, W.train_data.original_data, W.train_data.labels, getattr(W, "custom_encoding", None))
     _, norms = transform_train_data(W.train_data.original_data, opts, enc.range)
     scaled, _ = transform_test_data(X, norms, opts, enc.range)
     phi = encoder(scaled)
@@ -151,7 +151,7 @@ def position_operator(W, npoints: int = 2001):
     split and time-dependent bases need nothing further.  For a basis orthonormal on the range, tr(rho_t X_t) is the model's mean
     of the (scaled) series at site t."""
     opts = safe_options(W.opts)
-    enc, _, encoder = fit_encoding_from_training_data(opts, W.train_data.original_data, W.train_data.labels)
+    enc, _, encoder = fit_encoding_from_training_data(opts, W.train_data.original_data, W.train_data.labels, getattr(W, "custom_encoding", None))
     T = len(W.mps)
     a, b = enc.range
     x = np.linspace(a, b, int(npoints))

@@ -1261,6 +1261,32 @@ int split_validate(Ctx* c, int32_t T, int32_t d, mpst_encode_opts* eo, const mps
     return 0;
 }
 
+// the checks of a Sahand-Legendre request (include/mpstime_hip.h); eo->basis is ignored and left alone: the states are doubles
+bool kde_site_is_zero(const mpst_kde_opts* kd, int64_t site, int32_t d) {
+    for (int64_t q = 0; q < (int64_t)d * d; ++q)
+        if (kd->cvecs[site * d * d + q] != 0.0) return false;
+    return true;
+}
+int kde_validate(Ctx* c, int32_t T, int32_t d, const mpst_kde_opts* kd) {
+    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
+    if (!kd || !kd->lo || !kd->step || !kd->coef || !kd->minx || !kd->scale || !kd->cvecs)
+        return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
+    if (kd->npoints < 3) return fail(c, MPST_ERR_INVALID, "a density estimate has at least 3 grid points (got %d)", (int)kd->npoints);
+    if (kd->per_site != 0 && kd->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
+    if (d < 1 || d > 16) return fail(c, MPST_ERR_INVALID, "the Sahand-Legendre bases are encoded for d = 1 .. 16 (got %d)", (int)d);
+    const int64_t nsite = kd->per_site ? T : 1;
+    auto bad = [](double v) { return !(v > 0.0) || !std::isfinite(v); };
+    for (int64_t t = 0; t < nsite; ++t) {
+        if (kde_site_is_zero(kd, t, d)) continue;
+        if (bad(kd->step[t]) || bad(kd->scale[t]) || bad(kd->minx[t]))
+            return fail(c, MPST_ERR_INVALID, "site %lld: step, scale and minx must be positive and finite (got %g, %g, %g)", (long long)t,
+                        kd->step[t], kd->scale[t], kd->minx[t]);
+    }
+    return 0;
+}
+// the closed-form basis a request encodes with (a Sahand-Legendre request: none - a real one stands in wherever only real / complex matters)
+int request_basis(const mpst_encode_opts* eo, const mpst_kde_opts* kd) { return kd ? MPST_BASIS_LEGENDRE_NO_NORM : eo->basis; }
+
 bool fits_sigmoid(const mpst_encode_opts* eo) { return eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test; }
 int preprocess_validate(Ctx* c, const mpst_encode_opts* eo, int64_t N, int32_t T) {
     if (eo->fit_sigmoid && eo->is_test) return fail(c, MPST_ERR_INVALID, "fit_sigmoid: the RobustSigmoid is fitted on the training set only");
@@ -1282,18 +1308,21 @@ struct DataSetRequest {
     mpst_encode_opts* eo = nullptr;
     bool split = false;
     const mpst_split_opts* sp = nullptr;
+    const mpst_kde_opts* kd = nullptr;      // a Sahand-Legendre basis (mpst_encode_kde_dataset)
 };
 
 // Every check that can reject the call, in the order the entry points report them; fills r.dtype of an encode call and the plan.
 // Reads the context, changes nothing of it.
 int dataset_validate(Ctx* c, DataSetRequest& r, DataSetPlan* plan) {
     if (r.eo) {
-        if (int rc = r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false)) return rc;
+        if (int rc = r.kd ? kde_validate(c, r.T, r.d, r.kd)
+                          : r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false))
+            return rc;
     }
     if (r.which != MPST_TRAIN && r.which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
     if (r.eo) {
         // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
-        const bool bcx = basis_is_complex(r.eo->basis);
+        const bool bcx = basis_is_complex(request_basis(r.eo, r.kd));
         r.dtype = c->have_dtype ? c->dtype : (bcx ? MPST_C128 : MPST_F64);
         if (bcx && (r.dtype == MPST_F64 || r.dtype == MPST_F32))
             return fail(c, MPST_ERR_INVALID, "Using a complex valued encoding but the MPS is real. If using a complex-valued custom encoding, set 'dtype <: Complex' in MPSOptions");   // RealRealHighDimension.jl:462-464
@@ -1375,11 +1404,27 @@ int timed_launch(Ctx* c, double* seconds, Launch launch) {
 
 // preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
 // mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
-// sp: a split basis over eo->basis (its edges are uploaded for the call), or null.  eo has passed preprocess_validate.
-int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp, double* dphi,
-                       double* oob_fix, double* seconds) {
+// sp: a split basis over eo->basis (its edges are uploaded for the call), or null; kd: a Sahand-Legendre basis (its tables are
+// uploaded for the call), or null.  eo has passed preprocess_validate.
+int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
+                       const mpst_kde_opts* kd, double* dphi, double* oob_fix, double* seconds) {
     int rc;
     DevBuf<double> dbins, dX, part, lohi, fix;      // released on every exit path, the HIPC early returns included
+    // the Sahand-Legendre tables, packed [lo | step | minx | scale | coef | cvecs]: one upload.  Like the bin edges they belong to the
+    // call - nothing reads them once the states are written -, so the context holds nothing of a call that fails later
+    DevBuf<double> ktab;
+    DevBuf<int32_t> kzero;
+    const int64_t ks = kd ? (kd->per_site ? T : 1) : 0, kcoef_n = kd ? ks * ((int64_t)kd->npoints + 2) : 0;
+    if (kd) {
+        std::vector<int32_t> zero((size_t)ks);
+        for (int64_t t = 0; t < ks; ++t) zero[(size_t)t] = kde_site_is_zero(kd, t, d);
+        std::vector<double> tab;
+        tab.reserve((size_t)(4 * ks + kcoef_n + ks * d * d));
+        for (const double* p : {kd->lo, kd->step, kd->minx, kd->scale}) tab.insert(tab.end(), p, p + ks);
+        tab.insert(tab.end(), kd->coef, kd->coef + kcoef_n);
+        tab.insert(tab.end(), kd->cvecs, kd->cvecs + ks * d * d);
+        if ((rc = upload(c, kzero, zero)) || (rc = upload(c, ktab, tab))) return rc;
+    }
     if (sp) {
         const size_t nedge = (size_t)(sp->per_site ? T : 1) * (size_t)(sp->nbins + 1);
         if ((rc = dalloc(c, dbins, (int64_t)nedge))) return rc;
@@ -1409,9 +1454,10 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     }
     EncDev e{};
     e.N = N; e.T = T; e.d = d;
-    e.norm = eo->basis == MPST_BASIS_LEGENDRE;
-    e.fourier = basis_is_complex(eo->basis);
-    e.basis = eo->basis;
+    const int basis = request_basis(eo, kd);
+    e.norm = basis == MPST_BASIS_LEGENDRE;
+    e.fourier = basis_is_complex(basis);
+    e.basis = basis;
     e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax; e.is_test = test;
     e.med = eo->median; e.s = eo->iqr / 1.35;
     e.lb = eo->data_lb; e.ub = eo->data_ub; e.a = eo->range_a; e.b = eo->range_b;
@@ -1421,6 +1467,12 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     if (sp) {
         e.bins = dbins; e.bin_stride = sp->per_site ? sp->nbins + 1 : 0;
         e.nbins = sp->nbins; e.aux_dim = sp->aux_dim;
+    }
+    if (kd) {
+        const double* p = ktab;
+        e.kde_lo = p; e.kde_step = p + ks; e.kde_minx = p + 2 * ks; e.kde_scale = p + 3 * ks; e.kde_coef = p + 4 * ks;
+        e.kde_cvecs = p + 4 * ks + kcoef_n;
+        e.kde_zero = kzero; e.kde_npoints = kd->npoints; e.kde_per_site = kd->per_site;
     }
     if ((rc = timed_launch(c, &secs, [&] {
             launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
@@ -1438,21 +1490,22 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     return 0;
 }
 
-// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset
+// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset, with kd, mpst_encode_kde_dataset
 int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
                           mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
-                          double* seconds) {
+                          double* seconds, bool kde = false, const mpst_kde_opts* kd = nullptr) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp};
+    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp, kd};
+    if (kde && !kd) return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
     return dataset_set(c, r, [&](double* dphi) {
-        const bool bcx = basis_is_complex(eo->basis);
-        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds);
+        const bool bcx = basis_is_complex(request_basis(eo, kd));
+        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, kd, dphi, oob_fix, seconds);
         // the basis' own type (fp64, real or pairs) aside, then cast to the context's
         DevBuf<double> tmp;
         int rc;
-        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, tmp, oob_fix, seconds))) return rc;
+        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, kd, tmp, oob_fix, seconds))) return rc;
         launch_tcast(tmp, bcx ? 1 : 0, dphi, c->zw == 2, dtype_is_f32(r.dtype), N * T * d, c->stream);
         HIPC(c, hipGetLastError());
         HIPC(c, hipStreamSynchronize(c->stream));
@@ -1460,19 +1513,21 @@ int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_i
     });
 }
 
-// mpst_encode_values and, with split = true, mpst_encode_split_values
+// mpst_encode_values and, with split = true, mpst_encode_split_values, with kde = true, mpst_encode_kde_values
 int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
-                         void* phi_out, double* oob_fix, double* seconds) {
+                         void* phi_out, double* oob_fix, double* seconds, bool kde = false, const mpst_kde_opts* kd = nullptr) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
     int rc;
-    if ((rc = split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) || (rc = preprocess_validate(c, eo, N, T))) return rc;
+    if ((rc = kde ? kde_validate(c, T, d, kd) : split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) ||
+        (rc = preprocess_validate(c, eo, N, T)))
+        return rc;
     HIPC(c, hipSetDevice(c->device));
-    const size_t w = (size_t)d * (basis_is_complex(eo->basis) ? 2 : 1);
+    const size_t w = (size_t)d * (basis_is_complex(request_basis(eo, kd)) ? 2 : 1);
     DevBuf<double> dphi;
-    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, dphi, oob_fix, seconds))) return rc;
+    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, kd, dphi, oob_fix, seconds))) return rc;
     std::vector<double> tmp((size_t)N * T * w);
     HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
     transpose_rows(phi_out, tmp.data(), T, N, w * sizeof(double));
@@ -1691,6 +1746,17 @@ int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t
 int mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
                              void* phi_out, double* oob_fix, double* seconds) {
     return encode_values(ctx, X, N, T, d, eo, true, sp, phi_out, oob_fix, seconds);
+}
+
+int mpst_encode_kde_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
+                            int32_t C, mpst_encode_opts* eo, const mpst_kde_opts* kd, const int64_t* n_global_per_class, double* oob_fix,
+                            double* seconds) {
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, true, kd);
+}
+
+int mpst_encode_kde_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_kde_opts* kd,
+                           void* phi_out, double* oob_fix, double* seconds) {
+    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, true, kd);
 }
 
 int mpst_get_encoded(void* ctx, int which, double* phi_out) {

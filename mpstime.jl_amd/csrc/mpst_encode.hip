@@ -1,4 +1,5 @@
-// mpst_encode.hip - device-side preprocessing + encoding: the closed-form bases and the split bases over them.
+// mpst_encode.hip - device-side preprocessing + encoding: the closed-form bases, the split bases over them and the fitted
+// Sahand-Legendre bases.
 //
 // Replaces, for the real bases the array sweep can train on, the host pipeline
 //   transform_train_data / transform_test_data  (src/utils.jl:161-275)
@@ -214,6 +215,46 @@ __global__ __launch_bounds__(256) void k_encode_split(EncDev e, const double* __
     }
 }
 
+// Sahand-Legendre bases (bases.jl:111-129): the same thread mapping and front end.  The thread reads its site's density estimate -
+// three neighbouring coefficients of the quadratic B-spline through the K grid values (consecutive threads share the site: the table
+// stays in the cache) -, takes f0 = max(sqrt(max(pdf, 0)), minx) and writes f0 / scale * sum_i cvecs[n][i] x^i for the d functions.
+// The spline index is clamped to 1 .. K, so the three reads stay inside the K + 2 coefficients whatever x is.  A site whose
+// coefficients are all zero (nothing to fit there) writes zeros and reads none of its tables.
+__global__ __launch_bounds__(256) void k_encode_kde(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= e.N * e.T) return;
+    const int64_t t = idx / e.N, i = idx - t * e.N;
+    const int64_t s = e.kde_per_site ? t : 0;
+    const int d = e.d;
+    double* out = phi + idx * d;
+    if (e.kde_zero[s]) {
+        for (int n = 0; n < d; ++n) out[n] = 0.0;
+        return;
+    }
+    const double x = enc_value(e, X, t, i);
+    const int K = e.kde_npoints;
+    const double lo = e.kde_lo[s], step = e.kde_step[s];
+    double p = 0.0;
+    if (!(x < lo || x > lo + (K - 1) * step)) {
+        const double u = (x - lo) / step + 1.0;
+        const double r = fmin(fmax(rint(u), 1.0), (double)K);          // round half to even, as the host's rint
+        const double f = u - r;
+        const double* __restrict__ c = e.kde_coef + s * (K + 2) + (int64_t)r;
+        p = c[-1] * (0.5 * ((f - 0.5) * (f - 0.5))) + c[0] * (0.75 - f * f) + c[1] * (0.5 * ((f + 0.5) * (f + 0.5)));
+    }
+    const double f0 = fmax(sqrt(fmax(p, 0.0)), e.kde_minx[s]);
+    const double scale = e.kde_scale[s];
+    const double* __restrict__ cv = e.kde_cvecs + s * d * d;
+    for (int n = 0; n < d; ++n) {
+        double acc = 0.0, xp = 1.0;
+        for (int q = 0; q < d; ++q) {
+            acc += cv[n * d + q] * xp;
+            xp *= x;
+        }
+        out[n] = acc * f0 / scale;
+    }
+}
+
 // ---- RobustSigmoid fit: median and inter-quartile range of all training values ---------------------------------
 // type-7 quantiles (Julia's / NumPy's default) of the sorted values; the interpolation is written as NumPy's _lerp so that
 // the host restatement and this kernel agree to the bit (Julia's a + g (b - a) differs from it by at most one ulp)
@@ -254,7 +295,8 @@ void launch_encode(const EncDev& e, const double* X, double* phi, double* part, 
     }
     if (fix) hipLaunchKernelGGL(k_enc_series_fix, dim3((unsigned)((e.N + 3) / 4)), dim3(256), 0, s, e, X, fix);
     const dim3 grid((unsigned)((e.N * e.T + 255) / 256));
-    if (e.bins) hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi);
+    if (e.kde_coef) hipLaunchKernelGGL(k_encode_kde, grid, dim3(256), 0, s, e, X, phi);
+    else if (e.bins) hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi);
     else hipLaunchKernelGGL(k_encode, grid, dim3(256), 0, s, e, X, phi);
 }
 

@@ -647,6 +647,11 @@ struct EncDev {
     const double* bins;     // device [T][nbins + 1] edges (bin_stride = nbins + 1) or [nbins + 1] shared by all sites (bin_stride = 0)
     int64_t bin_stride;
     int32_t nbins, aux_dim;
+    // Sahand-Legendre bases (k_encode_kde; kde_coef == null: the kernels above): the tables of site t start at index t * kde_per_site
+    const double *kde_lo, *kde_step, *kde_coef;       // device [S], [S], [S][kde_npoints + 2]: the density's grid and spline coefficients
+    const double *kde_minx, *kde_scale, *kde_cvecs;   // device [S], [S], [S][d][d]
+    const int32_t* kde_zero;                          // device [S]: 1 where the site's coefficients are all zero
+    int32_t kde_npoints, kde_per_site;
 };
 size_t order_stats_temp_bytes(int64_t n);
 hipError_t launch_order_stats(const double* X, double* sorted, void* temp, size_t temp_bytes, int64_t n, double* out3, hipStream_t s);

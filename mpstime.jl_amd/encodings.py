@@ -3,8 +3,8 @@
 Mirrors src/utils.jl:161-295 (RobustSigmoid + MinMax) and src/Encodings (encode_dataset,
 Encodings/encodings.jl:33-156; bases, Encodings/bases.jl).  These run once per fit on the
 host in the reference as well.  Encodings whose basis differs from site to site (Encodings/splitbases.jl,
-basis_structs.jl) are fitted once by ``fit_encoding`` and applied through the encoder it returns; SLTD,
-Sahand-Legendre and projected bases (they need a kernel density estimator) raise.
+basis_structs.jl) are fitted once by ``fit_encoding`` and applied through the encoder it returns; so are the Sahand-Legendre
+bases (``sahand_legendre``), fitted to a kernel density estimate of the training values.  Projected bases raise.
 """
 from __future__ import annotations
 
@@ -306,6 +306,259 @@ def function_basis(fn, is_complex, range, is_time_dependent=False, is_data_drive
     return Encoding(name, bool(is_complex), tuple(range), encode, bool(is_time_dependent), bool(is_data_driven), init)
 
 
+# ---------------------------------------------------------------------------------------
+# Sahand-Legendre bases (bases.jl:111-129, :158-206, :269-342): polynomials orthonormalised under the square root of a kernel
+# density estimate of the training values - one estimate per site (time dependent) or one for all values
+# ---------------------------------------------------------------------------------------
+KDE_NPOINTS = 2048
+
+
+@dataclass
+class UnivariateKDE:
+    """KernelDensity.jl's default univariate estimate (Normal kernel) as ``kde_pdf`` needs it: the grid starts at ``lo`` with spacing
+    ``step``, ``h`` is the bandwidth, ``coef`` the K + 2 coefficients of the quadratic B-spline through the K grid values."""
+
+    lo: float
+    step: float
+    h: float
+    coef: np.ndarray
+
+    @property
+    def npoints(self):
+        return len(self.coef) - 2
+
+    @property
+    def hi(self):
+        return self.lo + (self.npoints - 1) * self.step
+
+
+_THOMAS = {}
+
+
+def _thomas_factors(m):
+    """the site-independent half of the Thomas algorithm for the m x m matrix tridiag(1/8, 3/4, 1/8): (c', 1 / pivot)"""
+    if m not in _THOMAS:
+        cp, inv = np.empty(m), np.empty(m)
+        prev = 0.0
+        for i in range(m):
+            inv[i] = 1.0 / (0.75 - 0.125 * prev)
+            prev = cp[i] = 0.125 * inv[i]
+        _THOMAS[m] = (cp, inv)
+    return _THOMAS[m]
+
+
+def _spline_coefficients(dens):
+    """Quadratic B-spline coefficients c[0..K+1] of the grid values dens (K, S), one column per estimate:
+    c[i-1]/8 + 3c[i]/4 + c[i+1]/8 = dens[i] (i = 1..K) with zero second difference of c at either end.  The end conditions put
+    c[1] = dens[1] and c[K] = dens[K]; what is left is tridiagonal with constant bands, solved for all columns at once."""
+    K = dens.shape[0]
+    c = np.empty((K + 2,) + dens.shape[1:])
+    c[1], c[K] = dens[0], dens[K - 1]
+    m = K - 2
+    rhs = dens[1:K - 1].copy()
+    rhs[0] -= 0.125 * c[1]
+    rhs[m - 1] -= 0.125 * c[K]
+    cp, inv = _thomas_factors(m)
+    rhs[0] *= inv[0]
+    for i in range(1, m):
+        rhs[i] = (rhs[i] - 0.125 * rhs[i - 1]) * inv[i]
+    for i in range(m - 2, -1, -1):
+        rhs[i] -= cp[i] * rhs[i + 1]
+    c[2:K] = rhs
+    c[0] = 2.0 * c[1] - c[2]
+    c[K + 1] = 2.0 * c[K] - c[K - 1]
+    return c
+
+
+def _kde_columns(X, inside, bandwidth=None, npoints=KDE_NPOINTS):
+    """One density estimate per column of X (n, S) from the entries where ``inside``: (lo, step, h, coef (S, K + 2), n (S,)).
+    A column without entries gets lo = 0, step = 1, h = 0 and zero coefficients."""
+    X = np.asarray(X, dtype=np.float64)
+    K = int(npoints)
+    S = X.shape[1]
+    n = inside.sum(axis=0)
+    has = n > 0
+    nn = np.maximum(n, 1)
+    Xs = np.sort(np.where(inside, X, np.inf), axis=0)                          # entries first, in order
+    Xz = np.where(inside, X, 0.0)
+    cols = np.arange(S)
+    if bandwidth is None:
+        mean = Xz.sum(axis=0) / nn
+        std = np.sqrt(np.where(inside, (X - mean) ** 2, 0.0).sum(axis=0) / np.maximum(n - 1, 1))
+
+        def quantile(q):                                                       # type 7, the interpolation written as NumPy's
+            pos = q * (nn - 1)
+            lo_i = np.floor(pos).astype(np.int64)
+            hi_i = np.minimum(lo_i + 1, nn - 1)
+            t = pos - lo_i
+            a_, b_ = np.where(has, Xs[lo_i, cols], 0.0), np.where(has, Xs[hi_i, cols], 0.0)
+            dba = b_ - a_
+            return np.where(a_ == b_, a_, np.where(t >= 0.5, b_ - dba * (1.0 - t), a_ + dba * t))
+
+        w = np.minimum(std, (quantile(0.75) - quantile(0.25)) / 1.34)
+        w = np.where(w == 0.0, np.where(std == 0.0, 1.0, std), w)
+        h = np.where(n <= 1, 0.9, 0.9 * w * nn ** (-0.2))
+    else:
+        h = np.full(S, float(bandwidth))
+    xmin = np.where(has, Xs[0], 0.0)
+    xmax = np.where(has, Xs[np.maximum(n - 1, 0), cols], 0.0)
+    lo, hi = xmin - 4.0 * h, xmax + 4.0 * h
+    step = (hi - lo) / (K - 1)
+    lo, step, h = np.where(has, lo, 0.0), np.where(has, step, 1.0), np.where(has, h, 0.0)
+    # linear binning: k is the first grid index with grid[k] >= x (grid[k] = lo + k step), j = k - 1
+    with np.errstate(invalid="ignore"):
+        k = np.ceil((Xz - lo) / step).astype(np.int64)
+    k -= (lo + (k - 1) * step) >= Xz
+    k += (lo + k * step) < Xz
+    ok = inside & (k >= 1) & (k <= K - 1)
+    kk = np.where(ok, k, 1)
+    scale = 1.0 / (nn * step * step)
+    wj = np.where(ok, ((lo + kk * step) - Xz) * scale, 0.0)
+    wk = np.where(ok, (Xz - (lo + (kk - 1) * step)) * scale, 0.0)
+    flat = (cols * K + kk).ravel()
+    cells = (np.bincount(flat - 1, weights=wj.ravel(), minlength=S * K) + np.bincount(flat, weights=wk.ravel(), minlength=S * K)).reshape(S, K)
+    # the Normal kernel in Fourier space, coefficient m at omega_m = 2 pi m / (K step)
+    omega = 2.0 * np.pi * np.arange(K // 2 + 1)[None, :] / (K * step[:, None])
+    dens = np.fft.irfft(np.fft.rfft(cells, axis=1) * np.exp(-0.5 * (h[:, None] * omega) ** 2), n=K, axis=1)
+    dens = np.where(has[:, None], np.maximum(dens, 0.0), 0.0)
+    coef = np.ascontiguousarray(_spline_coefficients(np.ascontiguousarray(dens.T)).T)
+    return lo, step, h, coef, n
+
+
+def kde(xs, bandwidth=None, npoints=KDE_NPOINTS) -> UnivariateKDE:
+    """kde(xs[; bandwidth]) of KernelDensity.jl with its defaults: Normal kernel, Silverman's bandwidth, ``npoints`` grid points
+    from min - 4h to max + 4h, linear binning, the kernel applied in Fourier space, negative values clamped."""
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 1)
+    lo, step, h, coef, _ = _kde_columns(xs, np.ones(xs.shape, dtype=bool), bandwidth, npoints)
+    return UnivariateKDE(float(lo[0]), float(step[0]), float(h[0]), coef[0])
+
+
+def _pdf_rows(lo, step, coef, x):
+    """the spline of row r (lo[r], step[r], coef[r]) at x[r, :]: the interpolant inside [lo, lo + (K - 1) step], 0 outside"""
+    K = coef.shape[1] - 2
+    lo, step = lo[:, None], step[:, None]
+    u = (x - lo) / step + 1.0
+    i = np.where(np.isnan(u), 1.0, np.clip(np.rint(u), 1, K))                  # a NaN value reads index 1, as on the device, and stays NaN
+    s = u - i
+    i = i.astype(np.int64)
+    take = lambda off: np.take_along_axis(coef, i + off, axis=1)
+    val = take(-1) * (0.5 * (s - 0.5) ** 2) + take(0) * (0.75 - s ** 2) + take(1) * (0.5 * (s + 0.5) ** 2)
+    return np.where((x < lo) | (x > lo + (K - 1) * step), 0.0, val)
+
+
+def kde_pdf(k: UnivariateKDE, x):
+    """pdf(kde, x) (KernelDensity.jl: the quadratic B-spline interpolant of the grid values, zero outside the grid); x of any shape"""
+    x = np.asarray(x, dtype=np.float64)
+    return _pdf_rows(np.array([k.lo]), np.array([k.step]), k.coef[None, :], x.reshape(1, -1)).reshape(x.shape)
+
+
+def _trapezoid(y, x):
+    return ((y[..., 1:] + y[..., :-1]) * 0.5 * np.diff(x)).sum(axis=-1)
+
+
+def remove_zeros(xs_samps, f0):
+    """remove_zeros! (bases.jl:269-291), in place on f0 (S,) or, row by row, (R, S): entries up to 1 % of the largest become the
+    smallest entry above that, then f0 is divided by the trapezoid integral of its square - by the integral, not its root, as the
+    reference does.  Returns (minval, norm); (0, 1) and f0 untouched where no entry is above the threshold."""
+    rows = f0 if f0.ndim == 2 else f0[None, :]
+    a = np.abs(rows)
+    bad = a <= 0.01 * a.max(axis=1, keepdims=True)
+    good = ~bad.all(axis=1)
+    minval = np.where(good, np.where(bad, np.inf, a).min(axis=1), 0.0)
+    np.copyto(rows, np.where(bad & good[:, None], minval[:, None], rows))
+    norm = np.where(good, _trapezoid(rows * rows, xs_samps), 1.0)
+    rows /= norm[:, None]
+    return (minval, norm) if f0.ndim == 2 else (float(minval[0]), float(norm[0]))
+
+
+def sahand_legendre_coeffs(xs_samp, f0, d):
+    """sahand_legendre_coeffs (bases.jl:158-206) for f0 (S,) -> (d, d), or row by row (R, S) -> (R, d, d): row n holds the
+    coefficients of function n, column i belongs to x^i.  Operation for operation - the n = 1 row takes c_1 = -1 / M[1][0]."""
+    xs_samp = np.asarray(xs_samp, dtype=np.float64)
+    rows = f0 if f0.ndim == 2 else f0[None, :]
+    R = rows.shape[0]
+    f2 = rows * rows
+    mom = np.stack([_trapezoid(xs_samp ** p * f2, xs_samp) for p in range(2 * d - 1)], axis=1)      # (R, 2d - 1)
+    M = mom[:, np.add.outer(np.arange(d), np.arange(d))]                                            # M[i][j] = moment i + j
+    cv = np.zeros((R, d, d))
+    cv[:, 0, 0] = 1.0
+    for n in range(1, d):
+        cv[:, n, 0] = 1.0
+        if n == 1:
+            cv[:, 1, 1] = -1.0 / M[:, 1, 0]
+        else:
+            C = cv[:, :n, :n]
+            rhs = -np.einsum("rmj,rj->rm", C, M[:, 0, :n])
+            A = np.einsum("rmj,rij->rmi", C, M[:, 1:n + 1, :n])
+            cv[:, n, 1:n + 1] = np.linalg.solve(A, rhs[..., None])[..., 0]
+        c = cv[:, n, :n + 1]
+        cv[:, n] /= np.sqrt(np.einsum("ri,rij,rj->r", c, M[:, :n + 1, :n + 1], c))[:, None]
+    return cv if f0.ndim == 2 else cv[0]
+
+
+def _sahand_legendre_fit(X, d, rng, nsamples, bandwidth):
+    """The fit of one Sahand-Legendre basis per column of X (n, S) (bases.jl:310-342): (kdes, minxs, scales, cVecs)."""
+    a, b = rng
+    X = np.asarray(X, dtype=np.float64)
+    lo, step, h, coef, n = _kde_columns(X, (a <= X) & (X <= b), bandwidth)
+    xs_samps = np.linspace(a, b, nsamples)
+    S = X.shape[1]
+    minxs, scales, cvecs = np.zeros(S), np.ones(S), np.zeros((S, d, d))
+    has = np.flatnonzero(n > 0)
+    if len(has):
+        f0 = np.sqrt(np.maximum(_pdf_rows(lo[has], step[has], coef[has], np.broadcast_to(xs_samps, (len(has), nsamples))), 0.0))
+        minxs[has], scales[has] = remove_zeros(xs_samps, f0)
+        fit = minxs[has] != 0.0
+        if fit.any():
+            cvecs[has[fit]] = sahand_legendre_coeffs(xs_samps, f0[fit], d)
+    kdes = [UnivariateKDE(float(lo[t]), float(step[t]), float(h[t]), coef[t]) for t in range(S)]
+    return kdes, minxs, scales, cvecs
+
+
+def init_sahand_legendre_time_dependent(X_norm, y=None, opts=None, range=None, max_samples=None, bandwidth=None):
+    """bases.jl:310-342: [kdes, minxs, scales, cVecs], one entry per site.  A site without a value inside the range (the reference
+    leaves its estimate undefined) and a site whose wavefunction is zero at every sample get zero coefficients."""
+    X = np.asarray(X_norm, dtype=np.float64)
+    nsamples = max(200, X.shape[1]) if max_samples is None else int(max_samples)
+    kdes, minxs, scales, cvecs = _sahand_legendre_fit(X, opts.d, (-1.0, 1.0) if range is None else range, nsamples, bandwidth)
+    return [kdes, minxs, scales, cvecs]
+
+
+def init_sahand_legendre(X_norm, y=None, opts=None, range=None, max_samples=None, bandwidth=None):
+    """bases.jl:294-307: [kde, minx, scale, cVecs] from all values at once.  The reference samples ``range(-a, b, S)``, a constant
+    vector for (-1, 1); the samples here run from a to b as in the time-dependent form."""
+    X = np.asarray(X_norm, dtype=np.float64)
+    nsamples = max(200, X.shape[1]) if max_samples is None else int(max_samples)
+    kdes, minxs, scales, cvecs = _sahand_legendre_fit(X.reshape(-1, 1), opts.d, (-1.0, 1.0) if range is None else range, nsamples, bandwidth)
+    return [kdes[0], float(minxs[0]), float(scales[0]), cvecs[0]]
+
+
+def sahand_legendre_encode(x, d, *args):
+    """sahand_legendre_encode (bases.jl:111-129) for an array of values: ``(x, d, kde, minx, scale, cVecs)`` or, time dependent,
+    ``(x, d, ti, kdes, minxs, scales, cVecs)`` with ``ti`` the site counted from 0.
+    phi_n(x) = max(sqrt(max(pdf(kde, x), 0)), minx) / scale * sum_i cVecs[n][i] x^i."""
+    if len(args) == 5:
+        ti, kdes, minxs, scales, cvecs = args
+        args = (kdes[ti], minxs[ti], scales[ti], cvecs[ti])
+    k, minx, scale, cvecs = args
+    x = np.asarray(x, dtype=np.float64)
+    cvecs = np.asarray(cvecs, dtype=np.float64)[:d, :d]
+    if not cvecs.any():
+        return np.zeros(x.shape + (d,))
+    f0 = np.maximum(np.sqrt(np.maximum(kde_pdf(k, x), 0.0)), minx)
+    poly = np.zeros(x.shape + (d,))
+    for i in range(d):                                                         # sum(c x^i) in the order of i, as :115 adds it
+        poly += cvecs[:, i] * (x ** i)[..., None]
+    return poly * f0[..., None] / scale
+
+
+def sahand_legendre(time_dependent: bool = True) -> Encoding:
+    """sahand_legendre(istimedependent) (basis_structs.jl:141-151)."""
+    name = "Sahand-Legendre" + (" Time Dependent" if time_dependent else " Time Independent")
+    init = init_sahand_legendre_time_dependent if time_dependent else init_sahand_legendre
+    return Encoding(name, False, (-1.0, 1.0), sahand_legendre_encode, bool(time_dependent), True, init)
+
+
 _SPLIT_PREFIXES = (("hist_split_", "hist._split_", "histogram_split_"), ("unif_split_", "unif._split_", "uniform_split_"))
 
 
@@ -326,7 +579,8 @@ def model_encoding(symbol, custom: Optional[Encoding] = None, project: bool = Fa
             raise ValueError("To use a custom encoding, pass custom_encoding")
         return custom
     if data_driven:
-        raise NotImplementedError(f"encoding {canon} is data-driven through a kernel density estimate, which this package does not ship")
+        raise NotImplementedError(f"encoding {canon} is not built from its symbol: set encoding='Custom' and pass "
+                                  f"custom_encoding=sahand_legendre(time_dependent={canon == 'SLTD'})")
     fn = {"Legendre_No_Norm": legendre_encode_no_norm, "Legendre_Norm": legendre_encode, "Fourier": fourier_encode,
           "Stoudenmire": angle_encode, "Sahand": sahand_encode, "Uniform": uniform_encode}[canon]
     return Encoding(canon, iscomplex, rng, fn)
@@ -335,6 +589,18 @@ def model_encoding(symbol, custom: Optional[Encoding] = None, project: bool = Fa
 def symbolic_encoding(enc: Encoding) -> str:
     """Inverse of model_encoding (options.jl:281-296); basis_tests.jl:8 pins the round trip."""
     return enc.name.replace(" ", "_").replace("-", "_")
+
+
+def encoding_from_name(name) -> Optional[Encoding]:
+    """The Encoding of a stored ``Encoding.name`` where a constructor of this package builds it - the Sahand-Legendre bases and
+    whatever model_encoding builds from the name's symbol -, else None (a function_basis has to be handed over again)."""
+    for enc in (sahand_legendre(True), sahand_legendre(False)):
+        if enc.name == name:
+            return enc
+    try:
+        return model_encoding(str(name).replace(" ", "_").replace("-", "_"))
+    except (ValueError, NotImplementedError):
+        return None
 
 
 def opts_encoding(opts, custom: Optional[Encoding] = None) -> Encoding:
@@ -368,6 +634,19 @@ class FittedEncoder:
     def bins(self):
         """the split bases' edges: (nbins + 1,) shared by all sites or (T, nbins + 1); None for any other encoding"""
         return np.asarray(self.args[1][0]) if self.enc.aux_enc is not None else None
+
+    @property
+    def kde(self):
+        """the Sahand-Legendre bases' fitted tables as the device takes them (mpst_kde_opts): a dict of ``npoints``, ``per_site`` and
+        the arrays lo, step (S,), coef (S, K + 2), minx, scale (S,), cvecs (S, d, d), S = T or 1; None for any other encoding"""
+        if self.enc.encode is not sahand_legendre_encode:
+            return None
+        kdes, minxs, scales, cvecs = self.args
+        if not self.enc.istimedependent:
+            kdes, minxs, scales, cvecs = [kdes], [minxs], [scales], [cvecs]
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        return dict(npoints=kdes[0].npoints, per_site=int(self.enc.istimedependent), lo=c([k.lo for k in kdes]), step=c([k.step for k in kdes]),
+                    coef=c([k.coef for k in kdes]), minx=c(minxs), scale=c(scales), cvecs=c(cvecs)[:, :self.d, :self.d].copy())
 
 
 def fit_encoding(enc: Encoding, X_norm, y, opts: MPSOptions):

@@ -110,7 +110,8 @@ def _device_basis(basis):
     except Exception:
         pass
     if basis not in L.BASIS:
-        raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)} and split bases over them, not {basis!r}")
+        raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, split bases over them and - "
+                                                  f"with kde=, their fitted encoder - the Sahand-Legendre bases, not {basis!r}")
     return basis, rng, split
 
 
@@ -142,6 +143,30 @@ def _split_opts(aux_basis, d, T, bins):
     nbins = b.shape[-1] - 1
     sp = L.mpst_split_opts(L.BASIS[aux_basis], int(d) // nbins, nbins, int(b.ndim == 2), b.ctypes.data_as(C.POINTER(C.c_double)))
     return sp, b
+
+
+def _kde_opts(kde, d, T):
+    """mpst_kde_opts of a fitted Sahand-Legendre encoding - ``kde`` is its FittedEncoder (``fit_encoding(...)[1]``) or that encoder's
+    ``kde`` tables - and the arrays the struct points into (keep them alive over the call).  The shapes are checked here: the
+    library reads (S, K + 2) and (S, d, d) doubles behind the pointers, S = T or 1."""
+    tab = getattr(kde, "kde", kde)
+    if not isinstance(tab, dict):
+        raise ValueError("a Sahand-Legendre encoding is encoded with the tables its fit produced: pass kde (fit_encoding(...)[1])")
+    K, per_site = int(tab["npoints"]), int(tab["per_site"])
+    S = T if per_site else 1
+    shapes = dict(lo=(S,), step=(S,), coef=(S, K + 2), minx=(S,), scale=(S,), cvecs=(S, int(d), int(d)))
+    arr = {k: np.ascontiguousarray(tab[k], dtype=np.float64) for k in shapes}
+    for k, shp in shapes.items():
+        if arr[k].shape != shp:
+            raise ValueError(f"kde table {k!r} must have shape {shp}, got {arr[k].shape}")
+    kd = L.mpst_kde_opts(K, per_site, *[arr[k].ctypes.data_as(C.POINTER(C.c_double)) for k in shapes])
+    return kd, arr
+
+
+def _kde_basis(basis, kde):
+    """what _device_basis returns, for a call with ``kde`` tables: eo.basis is ignored, the range is the encoding's"""
+    from .encodings import Encoding
+    return "Legendre_No_Norm", (tuple(basis.range) if isinstance(basis, Encoding) and basis.range else (-1.0, 1.0)), False
 
 
 class SweepEngine:
@@ -217,15 +242,16 @@ class SweepEngine:
 
     def encode_dataset(self, which, X_sorted, label_index, C_classes, basis="Legendre_No_Norm", d=None, sigmoid_transform=True,
                        minmax=True, data_bounds=(0.0, 1.0), enc_range=(-1.0, 1.0), norms=None, rescale_out_of_bounds=True,
-                       global_counts=None, sigmoid_fit=None, bins=None):
+                       global_counts=None, sigmoid_fit=None, bins=None, kde=None):
         """Preprocess + encode the raw (N, T) matrix on the device (mpst_encode_dataset).  ``X_sorted`` must already be
         sorted by class.  ``norms=None`` fits a training set (median/IQR on the host, min/max on the device) and
         returns ``(norms, seconds)``; with ``norms`` from the training fit the data is treated as a test set and
         ``(oob, seconds)`` comes back, ``oob`` in the format of transform_test_data (utils.jl:243-266).
         A split encoding (name or Encoding) goes through mpst_encode_split_dataset with ``bins``, the edges its fit produced
-        (``fit_encoding(...)[1].bins``: (nbins + 1,) or (T, nbins + 1))."""
+        (``fit_encoding(...)[1].bins``: (nbins + 1,) or (T, nbins + 1)); a Sahand-Legendre encoding through mpst_encode_kde_dataset
+        with ``kde``, its fitted encoder (``fit_encoding(...)[1]``)."""
         from .encodings import Norms
-        basis, _, split = _device_basis(basis)
+        basis, _, split = _device_basis(basis) if kde is None else _kde_basis(basis, kde)
         X = np.ascontiguousarray(X_sorted, dtype=np.float64)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
         N, T = X.shape
@@ -243,7 +269,10 @@ class SweepEngine:
         head = (self.ctx, which, X.ctypes.data_as(dp), lab.ctypes.data_as(C.POINTER(C.c_int32)), N, T, d, int(C_classes), C.byref(eo))
         tail = (gc.ctypes.data_as(C.POINTER(C.c_int64)) if gc is not None else None, fix.ctypes.data_as(dp) if fix is not None else None,
                 C.byref(sec))
-        if split:
+        if kde is not None:
+            kd, _keep = _kde_opts(kde, d, T)
+            self._chk(self.lib.mpst_encode_kde_dataset(*head, C.byref(kd), *tail))
+        elif split:
             sp, _keep = _split_opts(basis, d, T, bins)
             self._chk(self.lib.mpst_encode_split_dataset(*head, C.byref(sp), *tail))
         else:
@@ -258,13 +287,14 @@ class SweepEngine:
         return oob, sec.value
 
     def encode_values(self, X, basis="Legendre_No_Norm", d=4, sigmoid_transform=False, minmax=False, data_bounds=(0.0, 1.0),
-                      enc_range=None, norms=None, rescale_out_of_bounds=False, bins=None):
+                      enc_range=None, norms=None, rescale_out_of_bounds=False, bins=None, kde=None):
         """mpst_encode_values: the device preprocessing + encoding kernels on a raw (N, T) matrix, states back to the host -
         (N, T, d) float64 for the Legendre / Uniform bases, complex128 for "Fourier", "Stoudenmire", "Sahand".  Defaults: X is already in the encoding's
         domain (no transforms, identity range map); with transforms the [0, 1] data is mapped onto ``enc_range``
         (default: the basis' own range, (-1, 1) for Legendre / Fourier, (0, 1) for Stoudenmire / Sahand / Uniform).  ``norms`` as for encode_dataset (a test set) or None.
-        A split encoding with its fitted ``bins`` goes through mpst_encode_split_values, as in encode_dataset."""
-        basis, basis_range, split = _device_basis(basis)
+        A split encoding with its fitted ``bins`` goes through mpst_encode_split_values, a Sahand-Legendre encoding with its fitted
+        encoder ``kde`` through mpst_encode_kde_values, as in encode_dataset."""
+        basis, basis_range, split = _device_basis(basis) if kde is None else _kde_basis(basis, kde)
         X = np.ascontiguousarray(X, dtype=np.float64)
         N, T = X.shape
         if enc_range is None:
@@ -276,7 +306,10 @@ class SweepEngine:
         out = np.zeros((N, T, int(d)), dtype=np.complex128 if cx else np.float64)
         sec = C.c_double()
         head = (self.ctx, X.ctypes.data_as(C.POINTER(C.c_double)), N, T, int(d), C.byref(eo))
-        if split:
+        if kde is not None:
+            kd, _keep = _kde_opts(kde, int(d), T)
+            self._chk(self.lib.mpst_encode_kde_values(*head, C.byref(kd), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
+        elif split:
             sp, _keep = _split_opts(basis, int(d), T, bins)
             self._chk(self.lib.mpst_encode_split_values(*head, C.byref(sp), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
         else:

@@ -80,6 +80,7 @@ class ImputationProblem:                # imputation.jl:10-20
     x_guess_range: EncodedDataRange
     class_map: dict
     encoder: object = None              # FittedEncoder: the reference's enc_args (:88), bound
+    custom_encoding: object = None      # the Encoding behind opts.encoding == "Custom" (TrainedMPS.custom_encoding)
 
 
 def init_imputation_problem(W, X_test, y_test=None, dx: float = 1e-4, guess_range=None, verbosity: int = 1):
@@ -87,7 +88,8 @@ def init_imputation_problem(W, X_test, y_test=None, dx: float = 1e-4, guess_rang
     values ``range(guess_range...; step=dx)`` and their encoded states are tabulated once."""
     opts = safe_options(W.opts)
     td = W.train_data
-    enc, _, encoder = fit_encoding_from_training_data(opts, td.original_data, td.labels)          # :88
+    custom = getattr(W, "custom_encoding", None)
+    enc, _, encoder = fit_encoding_from_training_data(opts, td.original_data, td.labels, custom)  # :88
     if guess_range is None:
         guess_range = tuple(enc.range)
     X_test = np.asarray(X_test, dtype=np.float64)
@@ -103,16 +105,16 @@ def init_imputation_problem(W, X_test, y_test=None, dx: float = 1e-4, guess_rang
         print(f" - Dataset has {td.original_data.shape[0]} training samples and {X_test.shape[0]} testing samples.")
         print(f" - {len(classes)} class(es) were detected.")
     return ImputationProblem(W.mps, td.original_data, np.asarray(td.labels), X_test, y_test, opts, rng,
-                             {c: i for i, c in enumerate(classes.tolist())}, encoder)
+                             {c: i for i, c in enumerate(classes.tolist())}, encoder, custom)
 
 
 def _scaled_instances(imp: ImputationProblem, rows, masks, fill=None):
     """get_predictions' pre-processing (imputation.jl:283-297) for several instances at once: the missing region is
     overwritten with ``fill`` (default: the training mean) BEFORE the test transform (its per-series out-of-bounds rescale sees
     the masked series), the full series is transformed separately as the target in the encoding's domain."""
-    enc = opts_encoding(imp.opts)
+    enc = opts_encoding(imp.opts, imp.custom_encoding)
     if imp.encoder is None:
-        imp.encoder = fit_encoding_from_training_data(imp.opts, imp.X_train, imp.y_train)[2]
+        imp.encoder = fit_encoding_from_training_data(imp.opts, imp.X_train, imp.y_train, imp.custom_encoding)[2]
     _, norms = transform_train_data(imp.X_train, imp.opts, enc.range)
     raw = imp.X_test[rows]
     full, _ = transform_test_data(raw, norms, imp.opts, enc.range)

@@ -341,6 +341,62 @@ function impute_dist(c::Ptr{Cvoid}, which::Integer, missing::Matrix{UInt8}, xval
     return x, err, q, cdf
 end
 
+# ---- Sahand-Legendre encodings on the device ----------------------------------------------------------------------------------
+struct MpstEncodeOpts            # mpst_encode_opts
+    basis::Int32
+    sigmoid_transform::Int32
+    minmax::Int32
+    is_test::Int32
+    rescale_out_of_bounds::Int32
+    fit_sigmoid::Int32
+    median::Float64
+    iqr::Float64
+    lo::Float64
+    hi::Float64
+    data_lb::Float64
+    data_ub::Float64
+    range_a::Float64
+    range_b::Float64
+end
+struct MpstKdeOpts               # mpst_kde_opts
+    npoints::Int32               # K grid points of every density estimate
+    per_site::Int32              # 0: one table for all sites, 1: T tables
+    lo::Ptr{Float64}             # (S,), S = per_site == 1 ? T : 1
+    step::Ptr{Float64}           # (S,)
+    coef::Ptr{Float64}           # (K + 2, S): the quadratic B-spline coefficients of site s in column s
+    minx::Ptr{Float64}           # (S,)
+    scale::Ptr{Float64}          # (S,)
+    cvecs::Ptr{Float64}          # (d, d, S): cvecs[i, n, s] multiplies x^(i-1) in function n of site s (the reference's cVecs[s][n, i])
+end
+
+"""
+    encode_kde_values(X, d, lo, step, coef, minx, scale, cvecs; per_site, device)
+
+The Sahand-Legendre states of the values `X` ((T, N), already in the encoding's range) from the fitted tables
+(`mpst_encode_kde_values`, no preprocessing): `lo`, `step`, `minx`, `scale` (S,), `coef` (K + 2, S) and `cvecs` (d, d, S) with
+S = T (`per_site`) or 1 - column-major arrays, so site s is contiguous as the C side reads it.  Returns `phi` (d, T, N).
+"""
+function encode_kde_values(X::Matrix{Float64}, d::Integer, lo::Vector{Float64}, step::Vector{Float64}, coef::Matrix{Float64},
+                           minx::Vector{Float64}, scale::Vector{Float64}, cvecs::Array{Float64,3}; per_site::Bool=true, device::Integer=0)
+    T, N = size(X)
+    S = per_site ? T : 1
+    K = size(coef, 1) - 2
+    (length(lo), length(step), length(minx), length(scale), size(coef, 2), size(cvecs)) == (S, S, S, S, S, (d, d, S)) ||
+        throw(ArgumentError("the tables must hold one entry per site (or one in all): S = $S"))
+    phi = zeros(Float64, d, T, N)
+    secs = Ref(0.0)
+    with_context(device) do c
+        eo = Ref(MpstEncodeOpts(1, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0))      # no transforms, identity range map
+        kd = Ref(MpstKdeOpts(K, per_site ? 1 : 0, pointer(lo), pointer(step), pointer(coef), pointer(minx), pointer(scale), pointer(cvecs)))
+        GC.@preserve X lo step coef minx scale cvecs eo kd begin
+            check(c, ccall((:mpst_encode_kde_values, LIB), Cint,
+                           (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}),
+                           c, X, N, T, d, Base.unsafe_convert(Ptr{Cvoid}, eo), Base.unsafe_convert(Ptr{Cvoid}, kd), phi, C_NULL, secs))
+        end
+    end
+    return phi
+end
+
 # ---- leave-one-out site conditionals ----------------------------------------------------------------------------------------
 struct MpstSiteCondOpts          # mpst_sitecond_opts
     grid_per_site::Int32         # 0: xvals_enc (d, ngrid) shared by all sites, 1: (d, ngrid, T), one table per site

@@ -65,10 +65,11 @@ def marginal_states(mps, X, missing_mask):
         raise ValueError("X holds a NaN or non-finite value at an unmasked position: mask it or remove it")
     opts = safe_options(mps.opts)
     td = mps.train_data
-    encoder = fit_encoding_from_training_data(opts, td.original_data, td.labels)[2]
+    custom = getattr(mps, "custom_encoding", None)
+    encoder = fit_encoding_from_training_data(opts, td.original_data, td.labels, custom)[2]
     filled = np.where(mask, np.mean(td.original_data), raw)          # (the unmasked transform of _scaled_instances must not see NaN)
     imp = ImputationProblem(mps.mps, td.original_data, np.asarray(td.labels), filled, np.zeros(len(filled), dtype=np.int64), opts, None,
-                            {}, encoder)
+                            {}, encoder, custom)
     scaled = _scaled_instances(imp, np.arange(len(filled)), mask)[4]
     return np.asarray(encoder(scaled)), mask
 

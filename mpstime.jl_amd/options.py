@@ -27,6 +27,7 @@ _ENCODINGS = {
     "sltd": ("SLTD", False, (-1.0, 1.0), True),
     "sahand_legendre_time_dependent": ("SLTD", False, (-1.0, 1.0), True),
     "sahand_legendre": ("Sahand_Legendre", False, (-1.0, 1.0), True),
+    "sahand_legendre_time_independent": ("Sahand_Legendre", False, (-1.0, 1.0), True),     # symbolic_encoding of the constructor's names
     "custom": ("Custom", False, None, False),
 }
 

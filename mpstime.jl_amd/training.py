@@ -14,7 +14,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, fit_encoding, fit_encoding_from_training_data, opts_encoding,
+from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, encoding_from_name, fit_encoding, fit_encoding_from_training_data, opts_encoding,
                         transform_data, transform_train_data)
 from .engine import SweepEngine
 from .options import MPSOptions, engine_options, numpy_dtype, safe_options
@@ -22,14 +22,18 @@ from .options import MPSOptions, engine_options, numpy_dtype, safe_options
 
 @dataclass
 class TrainedMPS:
-    """TrainedMPS (src/Structs/options.jl:422-427): (mps, opts, train_data)."""
+    """TrainedMPS (src/Structs/options.jl:422-427): (mps, opts, train_data).  The reference's Options holds the encoding object;
+    MPSOptions here holds its name, so a model trained with ``encoding="Custom"`` carries the object in ``custom_encoding`` and
+    everything that re-derives the encoding from the model (classify, imputation, analysis, marginals) reads it from there."""
 
     mps: List[np.ndarray]          # site tensors (Dl, d, Dr[, C]); label on the last site
     opts: MPSOptions
     train_data: EncodedTimeSeriesSet
+    custom_encoding: Optional[Encoding] = None
 
     def __eq__(self, other):       # src/Structs/operations.jl:4-36
         return (isinstance(other, TrainedMPS) and self.opts == other.opts and len(self.mps) == len(other.mps)
+                and getattr(self.custom_encoding, "name", None) == getattr(other.custom_encoding, "name", None)
                 and all(np.array_equal(a, b) for a, b in zip(self.mps, other.mps)))
 
 
@@ -66,7 +70,7 @@ _INFO_TEST_KEYS = ("test_acc", "test_KL_div", "test_conf")
 
 def fit_encoded(W, training_states_meta: EncodedTimeSeriesSet, testing_states_meta: Optional[EncodedTimeSeriesSet],
                 opts: MPSOptions = MPSOptions(), engine: Optional[SweepEngine] = None, device: int = 0,
-                shard=None, preloaded: bool = False, batch_hint: Optional[int] = None):
+                shard=None, preloaded: bool = False, batch_hint: Optional[int] = None, custom_encoding: Optional[Encoding] = None):
     """fitMPS(W::MPS, training_states_meta, testing_states_meta, opts) (:587-890).
 
     Returns (TrainedMPS, training_information, testing_states_meta).  training_information has the
@@ -75,6 +79,7 @@ def fit_encoded(W, training_states_meta: EncodedTimeSeriesSet, testing_states_me
     ``preloaded``: the engine already holds both data sets (device-side encoding, fitMPS(device_encode=True)).
     ``batch_hint``: the engine's gradient share count as for a fit advanced in batches of about that many
     (SweepEngine.set_batch_hint): what ``fit_batch`` (tuning.py) sets, so that a fit gives the same bits alone and in a batch.
+    ``custom_encoding``: the Encoding behind ``opts.encoding == "Custom"``, kept in the TrainedMPS.
     """
     opts = safe_options(opts)
     eopt = engine_options(opts)
@@ -177,7 +182,7 @@ def fit_encoded(W, training_states_meta: EncodedTimeSeriesSet, testing_states_me
     finally:
         if own_engine:
             eng.close()
-    return TrainedMPS(Wout, opts, tr), info, te
+    return TrainedMPS(Wout, opts, tr, custom_encoding), info, te
 
 
 def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = MPSOptions(),
@@ -186,11 +191,12 @@ def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = M
     overloads without test data / labels (:413,:416).  X_* are (N, T) matrices, rows = series.
     Returns (TrainedMPS, training_information, encoded_test_states).
 
-    ``device_encode=True`` (the closed-form bases - Legendre, Fourier, Stoudenmire, Sahand, Uniform - and histogram_split /
-    uniform_split over them, whose bins are fitted on the host first) preprocesses and encodes on the GPU
+    ``device_encode=True`` (the closed-form bases - Legendre, Fourier, Stoudenmire, Sahand, Uniform -, histogram_split /
+    uniform_split over them and the Sahand-Legendre bases, all fitted on the host first) preprocesses and encodes on the GPU
     (mpst_encode_dataset): the raw matrices are uploaded, the product states are downloaded once for the
     returned EncodedTimeSeriesSets."""
     W, X_train, y_train, X_test, y_test, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding, W)
+    kw["custom_encoding"] = enc if opts.encoding.lower() == "custom" else None
     if device_encode:
         return _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_keys, **kw)
     train_states, test_states = _encode_fit(X_train, y_train, X_test, y_test, opts, enc, class_keys)
@@ -264,9 +270,13 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
             # the one fit of the encoding's arguments: on the host, from the training matrix through the host transform
             # (encodings.jl:130-131); the device encodes both data sets with these bins
             _, encoder = fit_encoding(enc, transform_train_data(Xs, opts, enc.range)[0], ys, opts)
-            if encoder.bins is None:
-                raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases are encoded on the device")
-            common.update(basis=enc, bins=encoder.bins)
+            if encoder.bins is not None:
+                common.update(basis=enc, bins=encoder.bins)
+            elif encoder.kde is not None:
+                common.update(basis=enc, kde=encoder)
+            else:
+                raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases and the "
+                                          "Sahand-Legendre bases are encoded on the device")
         norms, _ = eng.encode_dataset(0, Xs, li, C, **common)
         train_states = EncodedTimeSeriesSet(eng.get_encoded(0), ys, li, Xs, counts)
         test_states = EncodedTimeSeriesSet.empty()
@@ -274,7 +284,7 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
             Xt, yt, lt, ct = sorted_set(X_test, y_test)
             eng.encode_dataset(1, Xt, lt, C, norms=norms, **common)
             test_states = EncodedTimeSeriesSet(eng.get_encoded(1), yt, lt, Xt, ct)
-        return fit_encoded(W, train_states, test_states, opts, engine=eng, preloaded=True)
+        return fit_encoded(W, train_states, test_states, opts, engine=eng, preloaded=True, custom_encoding=kw.get("custom_encoding"))
     finally:
         if own:
             eng.close()
@@ -287,9 +297,9 @@ def classify_states(mps: TrainedMPS, X_or_states) -> EncodedTimeSeriesSet:
         return X_or_states
     opts = safe_options(mps.opts)
     X_test = np.asarray(X_or_states, dtype=np.float64)
-    enc = opts_encoding(opts)
+    enc = opts_encoding(opts, mps.custom_encoding)
     _, Xte_s, _, _ = transform_data(mps.train_data.original_data, X_test, opts, enc.range)          # :160
-    _, _, encoder = fit_encoding_from_training_data(opts, mps.train_data.original_data, mps.train_data.labels)
+    _, _, encoder = fit_encoding_from_training_data(opts, mps.train_data.original_data, mps.train_data.labels, mps.custom_encoding)
     n = X_test.shape[0]
     return encode_dataset(X_test, Xte_s, np.full(n, -1), enc, opts.d, {-1: 0}, encoder)            # :175 (unsorted: all one label)
 
@@ -350,11 +360,12 @@ def save_trained_mps(path, trained: TrainedMPS):
     """The counterpart of ``@save fpath mps`` (test/save_load.jl:17-24) for this package: the three fields of TrainedMPS
     (src/Structs/options.jl:422-427) - site tensors, the MPSOptions, the EncodedTimeSeriesSet - in one .npz.  (JLD2 /
     HDF5 cannot be written here: no HDF5 library in the image; the reference's own .jld2 fixture is read by
-    tests/golden/extract_jld2_fixture.py.)"""
+    tests/golden/extract_jld2_fixture.py.)  Of a custom encoding the name is stored: its functions are not data."""
     import json
     td = trained.train_data
     opts = {k: (list(v) if isinstance(v, tuple) else v) for k, v in trained.opts.asdict().items()}
-    np.savez_compressed(path, n_sites=len(trained.mps), opts=json.dumps(opts), timeseries=td.phi, labels=td.labels,
+    extra = {} if trained.custom_encoding is None else {"custom_encoding_name": trained.custom_encoding.name}
+    np.savez_compressed(path, n_sites=len(trained.mps), opts=json.dumps(opts), **extra, timeseries=td.phi, labels=td.labels,
                         label_index=td.label_index, original_data=td.original_data, class_distribution=td.class_distribution,
                         **{f"mps_{j}": t for j, t in enumerate(trained.mps)})
 
@@ -373,9 +384,12 @@ def mps_content_digest(mps) -> str:
     return h.hexdigest()
 
 
-def load_trained_mps(path) -> TrainedMPS:
+def load_trained_mps(path, custom_encoding: Optional[Encoding] = None) -> TrainedMPS:
     """A model saved by save_trained_mps (.npz) - or, for a path ending in .jld2, a TrainedMPS the reference itself saved
-    with JLD2 (jld2.py)."""
+    with JLD2 (jld2.py).  A model trained with ``encoding="Custom"`` gets its encoding back from ``custom_encoding``, or - when
+    none is given - from the stored name where a constructor of this package builds it (``encoding_from_name``); an encoding handed
+    over must carry the stored name.  A file without a name (saved before names were stored) or with a name no constructor
+    builds loads with ``custom_encoding`` None, as such files always did: set the field before the model is used."""
     import json
     if str(path).endswith(".jld2"):
         from .jld2 import load_trained_mps_jld2
@@ -388,4 +402,11 @@ def load_trained_mps(path) -> TrainedMPS:
         if isinstance(o[k], list):
             o[k] = tuple(o[k])
     td = EncodedTimeSeriesSet(z["timeseries"], z["labels"], z["label_index"], z["original_data"], z["class_distribution"])
-    return TrainedMPS([z[f"mps_{j}"] for j in range(int(z["n_sites"]))], MPSOptions(**o), td)
+    opts = MPSOptions(**o)
+    if opts.encoding.lower() == "custom":
+        name = str(z["custom_encoding_name"]) if "custom_encoding_name" in z.files else None
+        if custom_encoding is None and name is not None:
+            custom_encoding = encoding_from_name(name)
+        if name is not None and custom_encoding is not None and custom_encoding.name != name:
+            raise ValueError(f"the model was trained with the custom encoding {name!r}, not {custom_encoding.name!r}")
+    return TrainedMPS([z[f"mps_{j}"] for j in range(int(z["n_sites"]))], opts, td, custom_encoding)

@@ -289,8 +289,8 @@ def _batchable(opts: MPSOptions, n_train: int) -> bool:
 class _Fit:
     """a job on its engine, between build_caches and get_mps: fit_encoded's steps (RealRealHighDimension.jl:587-890), one at a time"""
 
-    def __init__(self, idx, W, tr, te, opts, device):
-        self.idx, self.tr, self.te, self.opts = idx, tr, te, opts
+    def __init__(self, idx, W, tr, te, opts, device, custom_encoding=None):
+        self.idx, self.tr, self.te, self.opts, self.custom_encoding = idx, tr, te, opts, custom_encoding
         self.has_test = len(te) > 0
         self.sweeps_done, self.done, self.error = 0, False, None
         C = int(W[-1].shape[3])
@@ -336,19 +336,20 @@ class _Fit:
                 return BatchFit(error=self.error, batched=True)
             self.eng.normalize()
             self.log(float("nan"))
-            return BatchFit(TrainedMPS(self.eng.get_mps(), self.opts, self.tr), self.info, self.te, True)
+            return BatchFit(TrainedMPS(self.eng.get_mps(), self.opts, self.tr, self.custom_encoding), self.info, self.te, True)
         finally:
             self.eng.close()
 
 
-def fit_batch(jobs, device: int = 0) -> List[BatchFit]:
+def fit_batch(jobs, device: int = 0, custom_encoding=None) -> List[BatchFit]:
     """Run many fitMPS jobs to completion together.  ``jobs``: (X_train, y_train, opts) tuples (a fourth and fifth entry: X_test,
     y_test).  Every job is encoded and gets its starting MPS exactly as fitMPS would; jobs of one shape (T, d, C, chi_max, chi_init,
     loss, train_classes_separately, and the same gradient share count) then advance together, sweep by sweep, in chunks of at most
     64 fits per launch chain (``sweep_batch``; the fits may differ in their series and class counts).  ``exit_early`` and a smaller
     ``nsweeps`` take a fit out of its group; a decomposition failure stops that fit alone (``error``).  Jobs the batched chain
     does not take (typed or complex fits, update_iters > 1, d chi_max > 128, track_cost, per-sweep losses) go through ``fitMPS`` one
-    by one: ``batched`` is False for them.  Results are those of ``fitMPS(..., batch_hint=BATCH_HINT)``, bit for bit."""
+    by one: ``batched`` is False for them.  Results are those of ``fitMPS(..., batch_hint=BATCH_HINT)``, bit for bit.
+    ``custom_encoding``: the Encoding of the jobs whose options say ``encoding="Custom"``, as fitMPS takes it."""
     out: List[Optional[BatchFit]] = [None] * len(jobs)
     fits: List[_Fit] = []
     try:
@@ -356,18 +357,19 @@ def fit_batch(jobs, device: int = 0) -> List[BatchFit]:
             X_train, y_train, opts = job[0], job[1], safe_options(job[2])
             X_test = job[3] if len(job) > 3 else None
             y_test = job[4] if len(job) > 4 else None
+            custom = custom_encoding if opts.encoding.lower() == "custom" else None
             if not _batchable(opts, len(X_train)):
                 try:
-                    m, info, te = fitMPS(X_train, y_train, X_test, y_test, opts=opts, device=device)
+                    m, info, te = fitMPS(X_train, y_train, X_test, y_test, opts=opts, device=device, custom_encoding=custom)
                     out[i] = BatchFit(m, info, te, False)
                 except L.SVDError as err:
                     out[i] = BatchFit(error=err, batched=False)
                 continue
-            W, Xtr, ytr, Xte, yte, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts)
+            W, Xtr, ytr, Xte, yte, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts, custom)
             tr, te = _encode_fit(Xtr, ytr, Xte, yte, opts, enc, class_keys)
             if opts.verbosity > -1:
                 print(f"Using {opts.update_iters} iterations per update.")
-            fits.append(_Fit(i, W, tr, te, opts, device))
+            fits.append(_Fit(i, W, tr, te, opts, device, custom))
         while True:
             live = [f for f in fits if not f.done and f.error is None]
             if not live:
@@ -456,7 +458,7 @@ def default_opts0(objective):
 
 def tune(Xs, ys, nfolds, parameters, optimiser=MPSRandomSearch(), objective=None, opts0=None, windows=None, pms=None,
          logspace_eta=False, maxiters=250, rng=1, foldmethod=make_stratified_cvfolds, verbosity=1, method="median", device=0,
-         return_info=False):
+         return_info=False, custom_encoding=None):
     """tune (tuning.jl:209-512): k-fold cross-validated search over ``parameters`` (``key=[values]``, ``key=(lb, ub)``,
     ``key=(lb, step, ub)``; numeric MPSOptions fields only).  Returns ``(best_params, cache)`` - ``best_params`` a dict of option
     values, ``cache`` {tuple of option values in key order: mean loss over the folds}; with ``return_info`` a third entry
@@ -464,7 +466,7 @@ def tune(Xs, ys, nfolds, parameters, optimiser=MPSRandomSearch(), objective=None
     ``mean(eval_loss(...))``, a diverged fit scores inf, the first strict minimum in trial order wins.  All trials x folds fits go
     to ``fit_batch`` at once and are scored with ``classify_batch`` (ImputationLoss: ``impute_dataset`` per model).  ``rng``: a
     NumPy seed or Generator - not Julia's stream; ``foldmethod``: a callable (Xs, ys, nfolds, rng=) or a list of
-    (train_inds, val_inds) pairs, used as is."""
+    (train_inds, val_inds) pairs, used as is.  ``custom_encoding``: the Encoding behind ``opts0.encoding == "Custom"``."""
     objective = ImputationLoss() if objective is None else objective
     opts0 = default_opts0(objective) if opts0 is None else safe_options(opts0)
     nparams = len(parameters)
@@ -490,7 +492,7 @@ def tune(Xs, ys, nfolds, parameters, optimiser=MPSRandomSearch(), objective=None
         for tr_i, _ in folds[:nfolds]:
             jobs.append((Xs[tr_i], ys[tr_i], opts))
     t0 = time.time()
-    fits = fit_batch(jobs, device=device)
+    fits = fit_batch(jobs, device=device, **({} if custom_encoding is None else {"custom_encoding": custom_encoding}))
     X_vals = [Xs[va] for _ in todo for _, va in folds[:nfolds]]
     y_vals = [ys[va] for _ in todo for _, va in folds[:nfolds]]
     ok = [k for k, f in enumerate(fits) if f.error is None]
@@ -539,14 +541,14 @@ def evaluate(Xs, ys, nfolds, tuning_parameters, tuning_optimiser=MPSRandomSearch
              tuning_opts0=None, n_cvfolds=5, fold_inds=None, logspace_eta=False, rng=1, tuning_rng=None,
              foldmethod=make_stratified_cvfolds, tuning_foldmethod=make_stratified_cvfolds, eval_pms=None, eval_windows=None,
              tuning_pms=None, tuning_windows=None, tuning_maxiters=250, write=False, writedir="evals", simname=None,
-             overwrite=False, method="median", device=0):
+             overwrite=False, method="median", device=0, custom_encoding=None):
     """evaluate (evaluate.jl:136-306): the outer resampling loop.  For every outer fold ``tune`` runs on its training part with
     ``n_cvfolds`` inner folds, then a model with the best options is trained on the whole training part and scored on the test
     part.  The final fits of all outer folds form ONE ``fit_batch``.  Returns one dict per fold of ``fold_inds`` (0-based) with
     the reference's keys: fold, objective, train_inds, test_inds, optimiser, tuning_windows, tuning_pms, eval_windows, eval_pms,
     time, opts, cache, loss.  ``write``: every fold is stored as ``<writedir>/<simname>_tmp/f<fold>.json`` (+ ``.npz``: the
     trained model, save_trained_mps's format) and a fold found there is loaded instead of being refitted (``overwrite`` refits).
-    Folds and grids follow NumPy seeds, not Julia's streams."""
+    Folds and grids follow NumPy seeds, not Julia's streams.  ``custom_encoding``: the Encoding behind ``encoding="Custom"``."""
     objective = ImputationLoss() if objective is None else objective
     opts0 = default_opts0(objective) if opts0 is None else safe_options(opts0)
     tuning_opts0 = opts0 if tuning_opts0 is None else safe_options(tuning_opts0)
@@ -582,10 +584,12 @@ def evaluate(Xs, ys, nfolds, tuning_parameters, tuning_optimiser=MPSRandomSearch
         tw = make_windows(tuning_windows, tuning_pms, Xs, irng) if isinstance(objective, ImputationLoss) else None
         best, cache = tune(Xs[tr_i], ys[tr_i], n_cvfolds, tuning_parameters, tuning_optimiser, objective=objective, opts0=tuning_opts0,
                            windows=tw, logspace_eta=logspace_eta, maxiters=tuning_maxiters, rng=irng, foldmethod=tuning_foldmethod,
-                           verbosity=verbosity - 1, method=method, device=device)
+                           verbosity=verbosity - 1, method=method, device=device,
+                           **({} if custom_encoding is None else {"custom_encoding": custom_encoding}))
         opts = best if isinstance(best, MPSOptions) else opts0.set(**best)
         pending.append((fold, tbeg, opts, cache))
-    finals = fit_batch([(Xs[folds[f][0]], ys[folds[f][0]], o) for f, _, o, _ in pending], device=device)
+    finals = fit_batch([(Xs[folds[f][0]], ys[folds[f][0]], o) for f, _, o, _ in pending], device=device,
+                       **({} if custom_encoding is None else {"custom_encoding": custom_encoding}))
     for (fold, tbeg, opts, cache), fit in zip(pending, finals):
         tr_i, te_i = folds[fold]
         if fit.error is not None:
