@@ -244,6 +244,30 @@ int  mpst_encode_kde_dataset(void* ctx, int which, const double* X, const int32_
                              const int64_t* n_global_per_class, double* oob_fix, double* seconds);
 int  mpst_encode_kde_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo,
                             const mpst_kde_opts* kd, void* phi_out, double* oob_fix, double* seconds);
+/* Projected bases (legendre(project = true), fourier(project = true): basis_structs.jl:114-139, bases.jl:94-107, :345-397): the
+ * closed-form family, of which every site evaluates its own list of d members, chosen on the host ("Projected bases").
+ * A value x at site t is encoded, slot j = 0 .. d-1, as
+ *   MPST_BASIS_LEGENDRE_NO_NORM   sqrt((2k + 1) / 2) P_k(x),                k = orders[t][j]   (Bonnet recursion, as mpst_encode_values)
+ *   MPST_BASIS_LEGENDRE           the same times inv_norm[t]
+ *   MPST_BASIS_FOURIER            cispi(f x) / sqrt(d), an (re, im) pair,   f = orders[t][j]   (signed)
+ * The list of a site need not be sorted and may repeat an order.  inv_norm is read for MPST_BASIS_LEGENDRE only and may be NULL
+ * otherwise.  max_order bounds every |orders[t][j]|.
+ * mpst_encode_proj_dataset / mpst_encode_proj_values are mpst_encode_dataset / mpst_encode_values with this basis: eo->basis is
+ * ignored and not written; the tables are copied to the device for the call and released with it.
+ * MPST_ERR_INVALID: NULL pj or orders; a basis other than the three above; d < 1 or d > 16; max_order < 0, above 7 * 16 (Legendre)
+ * or above 5 * 16 (Fourier); an order below 0 (Legendre) or with |order| > max_order; MPST_BASIS_LEGENDRE with a NULL inv_norm or
+ * an entry of it that is not positive and finite.  Every entry is checked before anything is launched. */
+typedef struct {
+    int32_t basis;                  /* MPST_BASIS_LEGENDRE / _LEGENDRE_NO_NORM / _FOURIER */
+    const int32_t* orders;          /* [T][d]: Legendre orders, or signed Fourier frequencies */
+    const double* inv_norm;         /* [T], or NULL */
+    int32_t max_order;
+} mpst_proj_opts;
+int  mpst_encode_proj_dataset(void* ctx, int which, const double* X, const int32_t* label_idx,
+                              int64_t N, int32_t T, int32_t d, int32_t C, mpst_encode_opts* eo, const mpst_proj_opts* pj,
+                              const int64_t* n_global_per_class, double* oob_fix, double* seconds);
+int  mpst_encode_proj_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo,
+                             const mpst_proj_opts* pj, void* phi_out, double* oob_fix, double* seconds);
 /* Encoded values of data set `which` back to the host, [N][T][d] in the context's element type
  * (EncodedTimeSeriesSet.timeseries). */
 int  mpst_get_encoded(void* ctx, int which, double* phi_out);

@@ -8,7 +8,9 @@ from .options import MPSOptions, safe_options
 from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, model_encoding, symbolic_encoding,
                         transform_data, transform_train_data, transform_test_data, legendre_encode,
                         legendre_encode_no_norm, fourier_encode, get_fourier_freqs, angle_encode, sahand_encode,
-                        uniform_encode, sahand_legendre, sahand_legendre_encode, UnivariateKDE, kde, kde_pdf)
+                        uniform_encode, sahand_legendre, sahand_legendre_encode, UnivariateKDE, kde, kde_pdf, legendre,
+                        legendre_no_norm, fourier, series_expand, construct_kerneldensity_wavefunction, project_legendre,
+                        project_fourier, projected_legendre_encode, projected_legendre_encode_no_norm, projected_fourier_encode)
 from .training import (TrainedMPS, fitMPS, fit_encoded, classify, generate_startingMPS, trendy_sine, save_trained_mps,
                        load_trained_mps, mps_content_digest)
 from .distributed import Shard, split_encoded
@@ -43,4 +45,6 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "impute_marginal", "forecast",
            "ModelOverlaps", "model_overlaps", "class_overlaps", "EarlyClassification", "prefix_log_marginals", "prefix_posteriors",
            "classify_early", "early_accuracy_curve", "causal_scores", "get_training_summary", "training_stats", "sweep_summary", "print_opts",
-           "sahand_legendre", "sahand_legendre_encode", "UnivariateKDE", "kde", "kde_pdf"]
+           "sahand_legendre", "sahand_legendre_encode", "UnivariateKDE", "kde", "kde_pdf",
+           "legendre", "legendre_no_norm", "fourier", "series_expand", "construct_kerneldensity_wavefunction", "project_legendre", "project_fourier",
+           "projected_legendre_encode", "projected_legendre_encode_no_norm", "projected_fourier_encode"]

@@ -58,6 +58,10 @@ class mpst_kde_opts(C.Structure):
                 ("cvecs", C.POINTER(C.c_double))]
 
 
+class mpst_proj_opts(C.Structure):
+    _fields_ = [("basis", C.c_int32), ("orders", C.POINTER(C.c_int32)), ("inv_norm", C.POINTER(C.c_double)), ("max_order", C.c_int32)]
+
+
 BASIS = {"Legendre_Norm": 0, "Legendre_No_Norm": 1, "Fourier": 2, "Stoudenmire": 3, "Sahand": 4, "Uniform": 5}      # canonical names (options.jl:243-279; :Legendre == :Legendre_No_Norm)
 
 # every symbol include/mpstime_hip.h declares: name -> (restype, argtypes)
@@ -100,6 +104,9 @@ SYMBOLS = {
     "mpst_encode_kde_dataset": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(_i32), _i64, _i32, _i32, _i32, C.POINTER(mpst_encode_opts),
                                           C.POINTER(mpst_kde_opts), C.POINTER(_i64), _dp, _dp]),
     "mpst_encode_kde_values": (C.c_int, [_vp, _dp, _i64, _i32, _i32, C.POINTER(mpst_encode_opts), C.POINTER(mpst_kde_opts), _vp, _dp, _dp]),
+    "mpst_encode_proj_dataset": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(_i32), _i64, _i32, _i32, _i32, C.POINTER(mpst_encode_opts),
+                                           C.POINTER(mpst_proj_opts), C.POINTER(_i64), _dp, _dp]),
+    "mpst_encode_proj_values": (C.c_int, [_vp, _dp, _i64, _i32, _i32, C.POINTER(mpst_encode_opts), C.POINTER(mpst_proj_opts), _vp, _dp, _dp]),
     "mpst_get_encoded": (C.c_int, [_vp, C.c_int, _dp]),
     "mpst_set_options": (C.c_int, [_vp, C.POINTER(mpst_options)]),
     "mpst_set_mps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i32), _i32, _i32]),

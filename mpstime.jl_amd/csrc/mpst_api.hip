@@ -1284,8 +1284,48 @@ int kde_validate(Ctx* c, int32_t T, int32_t d, const mpst_kde_opts* kd) {
     }
     return 0;
 }
-// the closed-form basis a request encodes with (a Sahand-Legendre request: none - a real one stands in wherever only real / complex matters)
-int request_basis(const mpst_encode_opts* eo, const mpst_kde_opts* kd) { return kd ? MPST_BASIS_LEGENDRE_NO_NORM : eo->basis; }
+// the checks of a projected-basis request (include/mpstime_hip.h): every entry the kernel turns into a trip count or an index.
+// eo->basis is ignored and left alone
+constexpr int32_t PROJ_MAX_D = 16, PROJ_MAX_LEGENDRE = 7 * PROJ_MAX_D, PROJ_MAX_FOURIER = 5 * PROJ_MAX_D;
+int proj_validate(Ctx* c, int32_t T, int32_t d, const mpst_proj_opts* pj) {
+    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
+    if (!pj || !pj->orders) return fail(c, MPST_ERR_INVALID, "NULL projected-basis options or order table");
+    const bool fourier = pj->basis == MPST_BASIS_FOURIER;
+    if (!fourier && pj->basis != MPST_BASIS_LEGENDRE && pj->basis != MPST_BASIS_LEGENDRE_NO_NORM)
+        return fail(c, MPST_ERR_INVALID, "a projected basis is Legendre, Legendre without norm or Fourier (got basis %d)", (int)pj->basis);
+    if (d < 1 || d > PROJ_MAX_D) return fail(c, MPST_ERR_INVALID, "the projected bases are encoded for d = 1 .. %d (got %d)", (int)PROJ_MAX_D, (int)d);
+    const int32_t cap = fourier ? PROJ_MAX_FOURIER : PROJ_MAX_LEGENDRE;
+    if (pj->max_order < 0 || pj->max_order > cap)
+        return fail(c, MPST_ERR_INVALID, "max_order must be within 0 .. %d (got %d)", (int)cap, (int)pj->max_order);
+    for (int64_t q = 0; q < (int64_t)T * d; ++q) {
+        const int32_t o = pj->orders[q];
+        if ((o < 0 && !fourier) || o > pj->max_order || o < -pj->max_order)
+            return fail(c, MPST_ERR_INVALID, "site %lld, slot %lld: order %d outside %s%d .. %d", (long long)(q / d), (long long)(q % d), (int)o,
+                        fourier ? "-" : "", fourier ? (int)pj->max_order : 0, (int)pj->max_order);
+    }
+    if (pj->basis == MPST_BASIS_LEGENDRE) {
+        if (!pj->inv_norm) return fail(c, MPST_ERR_INVALID, "NULL inv_norm for the normalised projected Legendre basis");
+        for (int32_t t = 0; t < T; ++t)
+            if (!(pj->inv_norm[t] > 0.0) || !std::isfinite(pj->inv_norm[t]))
+                return fail(c, MPST_ERR_INVALID, "site %d: inv_norm must be positive and finite (got %g)", (int)t, pj->inv_norm[t]);
+    }
+    return 0;
+}
+
+// A basis that comes with fitted tables instead of eo->basis: Sahand-Legendre (kd) or projected (pj).  `kind` says which entry point
+// was called, so that a NULL struct is that entry point's error; only that kind's pointer is ever set
+struct FittedBasis {
+    enum Kind { NONE, KDE, PROJ } kind = NONE;
+    const mpst_kde_opts* kd = nullptr;
+    const mpst_proj_opts* pj = nullptr;
+    static FittedBasis kde(const mpst_kde_opts* kd) { FittedBasis fb; fb.kind = KDE; fb.kd = kd; return fb; }
+    static FittedBasis proj(const mpst_proj_opts* pj) { FittedBasis fb; fb.kind = PROJ; fb.pj = pj; return fb; }
+};
+// the closed-form basis a request encodes with (a Sahand-Legendre request: none - a real one stands in wherever only real / complex
+// matters; a projected request: its family)
+int request_basis(const mpst_encode_opts* eo, const FittedBasis& fb) {
+    return fb.pj ? fb.pj->basis : fb.kd ? MPST_BASIS_LEGENDRE_NO_NORM : eo->basis;
+}
 
 bool fits_sigmoid(const mpst_encode_opts* eo) { return eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test; }
 int preprocess_validate(Ctx* c, const mpst_encode_opts* eo, int64_t N, int32_t T) {
@@ -1308,21 +1348,22 @@ struct DataSetRequest {
     mpst_encode_opts* eo = nullptr;
     bool split = false;
     const mpst_split_opts* sp = nullptr;
-    const mpst_kde_opts* kd = nullptr;      // a Sahand-Legendre basis (mpst_encode_kde_dataset)
+    FittedBasis fb;                         // a Sahand-Legendre basis (mpst_encode_kde_dataset) or a projected one (mpst_encode_proj_dataset)
 };
 
 // Every check that can reject the call, in the order the entry points report them; fills r.dtype of an encode call and the plan.
 // Reads the context, changes nothing of it.
 int dataset_validate(Ctx* c, DataSetRequest& r, DataSetPlan* plan) {
     if (r.eo) {
-        if (int rc = r.kd ? kde_validate(c, r.T, r.d, r.kd)
-                          : r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false))
+        if (int rc = r.fb.kind == FittedBasis::PROJ ? proj_validate(c, r.T, r.d, r.fb.pj)
+                     : r.fb.kind == FittedBasis::KDE ? kde_validate(c, r.T, r.d, r.fb.kd)
+                     : r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false))
             return rc;
     }
     if (r.which != MPST_TRAIN && r.which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
     if (r.eo) {
         // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
-        const bool bcx = basis_is_complex(request_basis(r.eo, r.kd));
+        const bool bcx = basis_is_complex(request_basis(r.eo, r.fb));
         r.dtype = c->have_dtype ? c->dtype : (bcx ? MPST_C128 : MPST_F64);
         if (bcx && (r.dtype == MPST_F64 || r.dtype == MPST_F32))
             return fail(c, MPST_ERR_INVALID, "Using a complex valued encoding but the MPS is real. If using a complex-valued custom encoding, set 'dtype <: Complex' in MPSOptions");   // RealRealHighDimension.jl:462-464
@@ -1404,11 +1445,31 @@ int timed_launch(Ctx* c, double* seconds, Launch launch) {
 
 // preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
 // mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
-// sp: a split basis over eo->basis (its edges are uploaded for the call), or null; kd: a Sahand-Legendre basis (its tables are
-// uploaded for the call), or null.  eo has passed preprocess_validate.
+// sp: a split basis over eo->basis (its edges are uploaded for the call), or null; fb: a Sahand-Legendre or a projected basis (its
+// tables are uploaded for the call), or neither.  eo has passed preprocess_validate, the tables their own checks.
 int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
-                       const mpst_kde_opts* kd, double* dphi, double* oob_fix, double* seconds) {
+                       const FittedBasis& fb, double* dphi, double* oob_fix, double* seconds) {
     int rc;
+    const mpst_kde_opts* kd = fb.kd;
+    const mpst_proj_opts* pj = fb.pj;
+    // the projected bases' tables: per site the d orders in ascending order, then the slot of each (int32), and the norms (doubles,
+    // the normalised Legendre basis only).  The sort (stable, so equal orders keep their slots' order) turns the site's list into
+    // what k_encode_proj walks once.  They belong to the call like the tables below
+    DevBuf<int32_t> ptab;
+    DevBuf<double> pinv;
+    if (pj) {
+        std::vector<int32_t> tab((size_t)T * 2 * d);
+        for (int32_t t = 0; t < T; ++t) {
+            int32_t* ord = tab.data() + (size_t)t * 2 * d;
+            int32_t* slot = ord + d;
+            const int32_t* src = pj->orders + (size_t)t * d;
+            for (int32_t j = 0; j < d; ++j) slot[j] = j;
+            std::stable_sort(slot, slot + d, [&](int32_t a, int32_t b) { return src[a] < src[b]; });
+            for (int32_t j = 0; j < d; ++j) ord[j] = src[slot[j]];
+        }
+        if ((rc = upload(c, ptab, tab))) return rc;
+        if (pj->basis == MPST_BASIS_LEGENDRE && (rc = upload(c, pinv, std::vector<double>(pj->inv_norm, pj->inv_norm + T)))) return rc;
+    }
     DevBuf<double> dbins, dX, part, lohi, fix;      // released on every exit path, the HIPC early returns included
     // the Sahand-Legendre tables, packed [lo | step | minx | scale | coef | cvecs]: one upload.  Like the bin edges they belong to the
     // call - nothing reads them once the states are written -, so the context holds nothing of a call that fails later
@@ -1454,7 +1515,7 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     }
     EncDev e{};
     e.N = N; e.T = T; e.d = d;
-    const int basis = request_basis(eo, kd);
+    const int basis = request_basis(eo, fb);
     e.norm = basis == MPST_BASIS_LEGENDRE;
     e.fourier = basis_is_complex(basis);
     e.basis = basis;
@@ -1474,6 +1535,10 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
         e.kde_cvecs = p + 4 * ks + kcoef_n;
         e.kde_zero = kzero; e.kde_npoints = kd->npoints; e.kde_per_site = kd->per_site;
     }
+    if (pj) {
+        e.proj_tab = ptab;
+        e.proj_inv = pj->basis == MPST_BASIS_LEGENDRE ? (const double*)pinv : nullptr;
+    }
     if ((rc = timed_launch(c, &secs, [&] {
             launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
             return hipGetLastError();
@@ -1490,22 +1555,22 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     return 0;
 }
 
-// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset, with kd, mpst_encode_kde_dataset
+// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset, with fb, mpst_encode_kde_dataset / mpst_encode_proj_dataset
 int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
                           mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
-                          double* seconds, bool kde = false, const mpst_kde_opts* kd = nullptr) {
+                          double* seconds, const FittedBasis& fb = FittedBasis()) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp, kd};
-    if (kde && !kd) return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
+    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp, fb};
+    if (fb.kind == FittedBasis::KDE && !fb.kd) return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
     return dataset_set(c, r, [&](double* dphi) {
-        const bool bcx = basis_is_complex(request_basis(eo, kd));
-        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, kd, dphi, oob_fix, seconds);
+        const bool bcx = basis_is_complex(request_basis(eo, fb));
+        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, fb, dphi, oob_fix, seconds);
         // the basis' own type (fp64, real or pairs) aside, then cast to the context's
         DevBuf<double> tmp;
         int rc;
-        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, kd, tmp, oob_fix, seconds))) return rc;
+        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, fb, tmp, oob_fix, seconds))) return rc;
         launch_tcast(tmp, bcx ? 1 : 0, dphi, c->zw == 2, dtype_is_f32(r.dtype), N * T * d, c->stream);
         HIPC(c, hipGetLastError());
         HIPC(c, hipStreamSynchronize(c->stream));
@@ -1513,21 +1578,21 @@ int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_i
     });
 }
 
-// mpst_encode_values and, with split = true, mpst_encode_split_values, with kde = true, mpst_encode_kde_values
+// mpst_encode_values and, with split = true, mpst_encode_split_values, with fb, mpst_encode_kde_values / mpst_encode_proj_values
 int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
-                         void* phi_out, double* oob_fix, double* seconds, bool kde = false, const mpst_kde_opts* kd = nullptr) {
+                         void* phi_out, double* oob_fix, double* seconds, const FittedBasis& fb = FittedBasis()) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
     int rc;
-    if ((rc = kde ? kde_validate(c, T, d, kd) : split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) ||
+    if ((rc = fb.kind == FittedBasis::PROJ ? proj_validate(c, T, d, fb.pj) : fb.kind == FittedBasis::KDE ? kde_validate(c, T, d, fb.kd) : split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) ||
         (rc = preprocess_validate(c, eo, N, T)))
         return rc;
     HIPC(c, hipSetDevice(c->device));
-    const size_t w = (size_t)d * (basis_is_complex(request_basis(eo, kd)) ? 2 : 1);
+    const size_t w = (size_t)d * (basis_is_complex(request_basis(eo, fb)) ? 2 : 1);
     DevBuf<double> dphi;
-    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, kd, dphi, oob_fix, seconds))) return rc;
+    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, fb, dphi, oob_fix, seconds))) return rc;
     std::vector<double> tmp((size_t)N * T * w);
     HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
     transpose_rows(phi_out, tmp.data(), T, N, w * sizeof(double));
@@ -1751,12 +1816,23 @@ int mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, i
 int mpst_encode_kde_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                             int32_t C, mpst_encode_opts* eo, const mpst_kde_opts* kd, const int64_t* n_global_per_class, double* oob_fix,
                             double* seconds) {
-    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, true, kd);
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, FittedBasis::kde(kd));
 }
 
 int mpst_encode_kde_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_kde_opts* kd,
                            void* phi_out, double* oob_fix, double* seconds) {
-    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, true, kd);
+    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, FittedBasis::kde(kd));
+}
+
+int mpst_encode_proj_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
+                             int32_t C, mpst_encode_opts* eo, const mpst_proj_opts* pj, const int64_t* n_global_per_class, double* oob_fix,
+                             double* seconds) {
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, FittedBasis::proj(pj));
+}
+
+int mpst_encode_proj_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_proj_opts* pj,
+                            void* phi_out, double* oob_fix, double* seconds) {
+    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, FittedBasis::proj(pj));
 }
 
 int mpst_get_encoded(void* ctx, int which, double* phi_out) {

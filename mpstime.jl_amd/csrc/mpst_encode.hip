@@ -1,5 +1,5 @@
-// mpst_encode.hip - device-side preprocessing + encoding: the closed-form bases, the split bases over them and the fitted
-// Sahand-Legendre bases.
+// mpst_encode.hip - device-side preprocessing + encoding: the closed-form bases, the split bases over them, the fitted
+// Sahand-Legendre bases and the projected bases.
 //
 // Replaces, for the real bases the array sweep can train on, the host pipeline
 //   transform_train_data / transform_test_data  (src/utils.jl:161-275)
@@ -255,6 +255,56 @@ __global__ __launch_bounds__(256) void k_encode_kde(EncDev e, const double* __re
     }
 }
 
+// Projected bases (bases.jl:94-107; DESIGN.md, "Projected bases"): the same thread mapping and front end.  Site t evaluates its own
+// d members of the Legendre / Fourier family.  Its table (e.proj_tab + 2 d t; consecutive threads share the site, so it comes from
+// the cache) holds the d orders in ascending order and, behind them, the slot each one is written to - the host sorted the site's
+// list, so an unsorted list or a repeated order costs nothing here and every slot is written exactly once.
+// Legendre: the Bonnet recursion of enc_legendre runs up to the site's largest order and stops at every listed one.
+// Fourier: sincospi(f x) / sqrt(d) as enc_fourier, f signed.
+// Bounds: q runs over 0 .. d-1, so the reads stay inside the site's 2 d entries; the slots are a permutation of 0 .. d-1 and the
+// orders are within 0 .. 7 * 16 (the host built and checked both); x enters no index, so a NaN value only gives NaN states.
+__global__ __launch_bounds__(256) void k_encode_proj(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= e.N * e.T) return;
+    const int64_t t = idx / e.N, i = idx - t * e.N;
+    const double x = enc_value(e, X, t, i);
+    const int d = e.d;
+    const int32_t* __restrict__ ord = e.proj_tab + t * 2 * d;
+    const int32_t* __restrict__ slot = ord + d;
+    if (e.fourier) {
+        double* out = phi + idx * d * 2;
+        const double inv = 1.0 / sqrt((double)d);
+        for (int q = 0; q < d; ++q) {
+            double sn, cs;
+            sincospi((double)ord[q] * x, &sn, &cs);
+            out[2 * slot[q]] = cs * inv;
+            out[2 * slot[q] + 1] = sn * inv;
+        }
+        return;
+    }
+    double* out = phi + idx * d;
+    const double inv = e.proj_inv ? e.proj_inv[t] : 1.0;
+    const int last = ord[d - 1];
+    double p0 = 1.0, p1 = x;
+    int q = 0;
+    for (int k = 0; k <= last; ++k) {
+        double p;
+        if (k == 0) p = 1.0;
+        else if (k == 1) p = x;
+        else {
+            const int m = k - 1;
+            p = ((2 * m + 1) * x * p1 - m * p0) / (m + 1);
+            p0 = p1;
+            p1 = p;
+        }
+        if (ord[q] != k) continue;
+        double v = p * sqrt((2.0 * k + 1.0) / 2.0);
+        if (e.proj_inv) v = v * inv;
+        for (; q < d && ord[q] == k; ++q) out[slot[q]] = v;
+        if (q == d) break;
+    }
+}
+
 // ---- RobustSigmoid fit: median and inter-quartile range of all training values ---------------------------------
 // type-7 quantiles (Julia's / NumPy's default) of the sorted values; the interpolation is written as NumPy's _lerp so that
 // the host restatement and this kernel agree to the bit (Julia's a + g (b - a) differs from it by at most one ulp)
@@ -295,7 +345,8 @@ void launch_encode(const EncDev& e, const double* X, double* phi, double* part, 
     }
     if (fix) hipLaunchKernelGGL(k_enc_series_fix, dim3((unsigned)((e.N + 3) / 4)), dim3(256), 0, s, e, X, fix);
     const dim3 grid((unsigned)((e.N * e.T + 255) / 256));
-    if (e.kde_coef) hipLaunchKernelGGL(k_encode_kde, grid, dim3(256), 0, s, e, X, phi);
+    if (e.proj_tab) hipLaunchKernelGGL(k_encode_proj, grid, dim3(256), 0, s, e, X, phi);
+    else if (e.kde_coef) hipLaunchKernelGGL(k_encode_kde, grid, dim3(256), 0, s, e, X, phi);
     else if (e.bins) hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi);
     else hipLaunchKernelGGL(k_encode, grid, dim3(256), 0, s, e, X, phi);
 }

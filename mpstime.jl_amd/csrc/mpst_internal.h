@@ -652,6 +652,9 @@ struct EncDev {
     const double *kde_minx, *kde_scale, *kde_cvecs;   // device [S], [S], [S][d][d]
     const int32_t* kde_zero;                          // device [S]: 1 where the site's coefficients are all zero
     int32_t kde_npoints, kde_per_site;
+    // projected bases (k_encode_proj; proj_tab == null: the kernels above): `basis` is the family
+    const int32_t* proj_tab;                          // device [T][2 d]: the site's d orders in ascending order, then the slot of each
+    const double* proj_inv;                           // device [T]: 1 / norm of the site (MPST_BASIS_LEGENDRE), or null
 };
 size_t order_stats_temp_bytes(int64_t n);
 hipError_t launch_order_stats(const double* X, double* sorted, void* temp, size_t temp_bytes, int64_t n, double* out3, hipStream_t s);

@@ -4,7 +4,8 @@ Mirrors src/utils.jl:161-295 (RobustSigmoid + MinMax) and src/Encodings (encode_
 Encodings/encodings.jl:33-156; bases, Encodings/bases.jl).  These run once per fit on the
 host in the reference as well.  Encodings whose basis differs from site to site (Encodings/splitbases.jl,
 basis_structs.jl) are fitted once by ``fit_encoding`` and applied through the encoder it returns; so are the Sahand-Legendre
-bases (``sahand_legendre``), fitted to a kernel density estimate of the training values.  Projected bases raise.
+bases (``sahand_legendre``), fitted to a kernel density estimate of the training values, and the projected bases
+(``legendre(project=True)``, ``fourier(project=True)``), which pick every site's members of the closed-form family from such an estimate.
 """
 from __future__ import annotations
 
@@ -559,13 +560,185 @@ def sahand_legendre(time_dependent: bool = True) -> Encoding:
     return Encoding(name, False, (-1.0, 1.0), sahand_legendre_encode, bool(time_dependent), True, init)
 
 
+# ---------------------------------------------------------------------------------------
+# Projected bases (basis_structs.jl:114-139, bases.jl:94-107, :141-154, :345-397): the closed-form Legendre / Fourier family, of
+# which every site keeps the d members that carry most of the square root of a kernel density estimate of its training values
+# ---------------------------------------------------------------------------------------
+PROJ_LEGENDRE_TERMS, PROJ_FOURIER_TERMS = 7, 10                                # max_series_terms = 7d (bases.jl:390), 10d (:370)
+
+
+def construct_kerneldensity_wavefunction(xs, xs_samps, max_samples=None, bandwidth=None):
+    """bases.jl:141-154.  ``xs_samps`` an array: wf = sqrt(max(pdf(kde(xs), xs_samps), 0)); a (lo, hi) tuple: the sample points
+    range(lo, hi, max_samples) - max(200, 2 len(xs)) of them by default - and wf.  The reference takes the root of the spline as it
+    is and throws on a slightly negative value: the clamp is this package's definition, and so is wf = 0 for no values at all."""
+    xs = np.asarray(xs, dtype=np.float64).ravel()
+    if isinstance(xs_samps, tuple):
+        samps = np.linspace(xs_samps[0], xs_samps[1], max(200, 2 * len(xs)) if max_samples is None else int(max_samples))
+        return samps, construct_kerneldensity_wavefunction(xs, samps, bandwidth=bandwidth)
+    xs_samps = np.asarray(xs_samps, dtype=np.float64)
+    if len(xs) == 0:
+        return np.zeros(xs_samps.shape)
+    return np.sqrt(np.maximum(kde_pdf(kde(xs, bandwidth), xs_samps), 0.0))
+
+
+def _trapezoid_weights(x):
+    """w with sum(w * y) = _trapezoid(y, x), the same terms grouped by sample instead of by interval"""
+    h = 0.5 * np.diff(x)
+    w = np.zeros(len(x))
+    w[:-1] += h
+    w[1:] += h
+    return w
+
+
+def _select_terms(abs2, d):
+    """partialsortperm(abs2, 1:d; rev=true) (bases.jl:354) per row: the 1-based positions of the d largest entries in descending
+    order, ties to the smaller position (the sort is stable)"""
+    return (np.argsort(-abs2, axis=-1, kind="stable")[..., :d] + 1).astype(np.int64)
+
+
+def series_expand(basis, xs, ys, d):
+    """series_expand (bases.jl:346-355): c_p = trapezoid(ys conj(b_p(xs)), xs) for the functions ``basis`` - a list of callables, or
+    their values at xs as a (P, S) array -, then the 1-based positions of the d largest |c_p|^2, largest first."""
+    xs = np.asarray(xs, dtype=np.float64)
+    B = np.asarray(basis) if not callable(basis[0]) else np.stack([np.asarray(f(xs)) * np.ones(xs.shape) for f in basis])
+    c = _trapezoid(np.asarray(ys) * np.conj(B), xs)
+    return _select_terms(c.real ** 2 + c.imag ** 2, d)
+
+
+def _projected_wavefunctions(X, rng, max_samples, bandwidth):
+    """(xs_samps (S,), wf (T, S)): construct_kerneldensity_wavefunction of every column of X (N, T), all columns at once"""
+    a, b = rng
+    X = np.asarray(X, dtype=np.float64)
+    N, T = X.shape
+    S = max(200, 2 * N) if max_samples is None else int(max_samples)            # the length before the range filter (bases.jl:370)
+    lo, step, h, coef, n = _kde_columns(X, (a <= X) & (X <= b), bandwidth)
+    xs = np.linspace(-1.0, 1.0, S)                                              # (-1, 1) whatever the range is (:372, :392)
+    wf = np.zeros((T, S))
+    has = np.flatnonzero(n > 0)
+    if len(has):
+        wf[has] = np.sqrt(np.maximum(_pdf_rows(lo[has], step[has], coef[has], np.broadcast_to(xs, (len(has), S))), 0.0))
+    return xs, wf
+
+
+def _cospi(y):
+    """cos(pi y) with the argument reduced first: y - 2 rint(y / 2) is exact, so only the rounding of y itself is left - the
+    device's sincospi(y) has the same property"""
+    return np.cos(np.pi * (y - 2.0 * np.rint(0.5 * y)))
+
+
+def _sinpi(y):
+    return np.sin(np.pi * (y - 2.0 * np.rint(0.5 * y)))
+
+
+def project_legendre(X_norm, y=None, opts=None, range=None, d=None, max_series_terms=None, max_samples=None, bandwidth=None):
+    """project_legendre (bases.jl:385-397) of the (N, T) training matrix: ``[ds]`` with ds (T, d) the 1-based positions, among the
+    first 7d normalised Legendre polynomials (position p = order p - 1), of the d largest |c_p|^2 of the site's wavefunction.  One
+    density estimate call and one (T, S) x (S, 7d) product for all sites."""
+    d = int(opts.d if d is None else d)
+    P = PROJ_LEGENDRE_TERMS * d if max_series_terms is None else int(max_series_terms)
+    xs, wf = _projected_wavefunctions(X_norm, (-1.0, 1.0) if range is None else range, max_samples, bandwidth)
+    c = wf @ (_legendre_table(xs, P) * _trapezoid_weights(xs)[:, None])
+    return [_select_terms(c * c, d)]
+
+
+def project_fourier(X_norm, y=None, opts=None, range=None, d=None, max_series_terms=None, max_samples=None, bandwidth=None):
+    """project_fourier (bases.jl:365-376): ``[ds]`` with ds (T, d) the 1-based positions in get_fourier_freqs(10 d) = 0, 1, -1, 2, ...
+    of the d largest |c_p|^2.  The wavefunction is real, so c_{-f} = conj(c_f): the coefficients are computed for f >= 0 only and
+    those of -f are DEFINED as their conjugates.  |c|^2 of +f and -f is then the same number to the last bit, and of such a pair +f,
+    which stands first in the list, is selected first - computed separately the two would differ in the last bits and the rounding
+    would pick.  (The reference has no method that takes the matrix and the options, bases.jl:397 exists for Legendre only: this
+    init is this package's definition of what the constructor names.)"""
+    d = int(opts.d if d is None else d)
+    P = PROJ_FOURIER_TERMS * d if max_series_terms is None else int(max_series_terms)
+    if P > PROJ_FOURIER_TERMS * d:
+        raise ValueError(f"max_series_terms = {P}: the encoder reads the positions in get_fourier_freqs({PROJ_FOURIER_TERMS} d)")
+    xs, wf = _projected_wavefunctions(X_norm, (-1.0, 1.0) if range is None else range, max_samples, bandwidth)
+    freqs = np.asarray(get_fourier_freqs(P))
+    ang = xs[:, None] * np.arange(np.abs(freqs).max() + 1, dtype=np.float64)
+    w = _trapezoid_weights(xs)[:, None]
+    re, im = wf @ (_cospi(ang) * w), wf @ (-_sinpi(ang) * w)                    # conj(cispi(f x)), f >= 0
+    abs2 = re * re + im * im
+    return [_select_terms(abs2[:, np.abs(freqs)], d)]
+
+
+def _site_positions(ds, ti):
+    ds = np.asarray(ds)
+    return (ds if ds.ndim == 1 else ds[ti]).astype(np.int64)
+
+
+def projected_legendre_orders(ds):
+    """The Legendre orders legendre_encode(x, nds, ds) (bases.jl:94-105) evaluates for the selected positions ds: Pl(x, p) with p the
+    1-based position itself, one above the order p - 1 of the term that was selected.  Kept: it is what a model trained by the
+    reference contains.  (An upstream fix is ``ds - 1`` here and nowhere else.)"""
+    return np.asarray(ds, dtype=np.int64)
+
+
+def projected_legendre_inv_norm(orders):
+    """1 / sqrt(Pl(1, m; normalized) m) with m the largest order of each site (bases.jl:98-102), orders (..., d)"""
+    m = np.asarray(orders).max(axis=-1).astype(np.float64)
+    return 1.0 / np.sqrt(np.sqrt((2.0 * m + 1.0) / 2.0) * m)
+
+
+def projected_fourier_freqs(ds, d):
+    """The signed frequencies of the selected positions ds in get_fourier_freqs(10 d)"""
+    return np.asarray(get_fourier_freqs(PROJ_FOURIER_TERMS * int(d)), dtype=np.int64)[np.asarray(ds, dtype=np.int64) - 1]
+
+
+def projected_legendre_encode(x, d, ti, ds, norm=True):
+    """legendre_encode(x, nds, ti, ds; norm) (bases.jl:94-107) for an array of values, ``ti`` the site counted from 0, ds (T, d) the
+    fit's positions (or one site's (d,)): sqrt((2k + 1) / 2) P_k(x) for k in projected_legendre_orders(ds[ti]), with ``norm``
+    divided by sqrt(Pl(1, m; normalized) m), m the site's largest order."""
+    orders = projected_legendre_orders(_site_positions(ds, ti))
+    out = _legendre_table(x, int(orders.max()) + 1)[..., orders]
+    if norm:
+        out = out * projected_legendre_inv_norm(orders)
+    return out
+
+
+def projected_legendre_encode_no_norm(x, d, ti, ds):
+    return projected_legendre_encode(x, d, ti, ds, norm=False)
+
+
+def projected_fourier_encode(x, d, ti, ds):
+    """cispi(f_p x) / sqrt(d) for the site's selected positions p.  The reference's fourier_encode(x, nds, ds) (bases.jl) cannot be
+    called and would use the position as the frequency: this is this package's definition, by intent."""
+    x = np.asarray(x, dtype=np.float64)
+    y = x[..., None] * projected_fourier_freqs(_site_positions(ds, ti), d).astype(np.float64)
+    inv = 1.0 / math.sqrt(d)
+    return (_cospi(y) * inv) + 1j * (_sinpi(y) * inv)
+
+
+def legendre(norm: bool = False, project: bool = False) -> Encoding:
+    """legendre(; norm, project) (basis_structs.jl:126-137).  ``project``: the projected basis, time dependent and data driven."""
+    if not project:
+        return model_encoding("Legendre_Norm" if norm else "Legendre_No_Norm")
+    return Encoding("Projected Legendre_Norm" if norm else "Projected Legendre", False, (-1.0, 1.0),
+                    projected_legendre_encode if norm else projected_legendre_encode_no_norm, True, True, project_legendre)
+
+
+def legendre_no_norm(project: bool = False) -> Encoding:
+    """basis_structs.jl:139."""
+    return legendre(norm=False, project=project)
+
+
+def fourier(project: bool = False) -> Encoding:
+    """fourier(; project) (basis_structs.jl:114-124)."""
+    if not project:
+        return model_encoding("Fourier")
+    return Encoding("Projected Fourier", True, (-1.0, 1.0), projected_fourier_encode, True, True, project_fourier)
+
+
+_PROJ_DEVICE_BASIS = {projected_legendre_encode: "Legendre_Norm", projected_legendre_encode_no_norm: "Legendre_No_Norm",
+                      projected_fourier_encode: "Fourier"}
+
 _SPLIT_PREFIXES = (("hist_split_", "hist._split_", "histogram_split_"), ("unif_split_", "unif._split_", "uniform_split_"))
 
 
 def model_encoding(symbol, custom: Optional[Encoding] = None, project: bool = False) -> Encoding:
     """options.jl:243-279."""
     if project:
-        raise NotImplementedError("projected_basis=True (projected Legendre / Fourier bases) is not implemented")
+        raise NotImplementedError("projected_basis=True is not built from the options: set encoding='Custom' and pass "
+                                  "custom_encoding=legendre(project=True), legendre(norm=True, project=True) or fourier(project=True)")
     if isinstance(symbol, Encoding):
         return symbol
     s = str(symbol).lstrip(":").lower()
@@ -579,8 +752,11 @@ def model_encoding(symbol, custom: Optional[Encoding] = None, project: bool = Fa
             raise ValueError("To use a custom encoding, pass custom_encoding")
         return custom
     if data_driven:
-        raise NotImplementedError(f"encoding {canon} is not built from its symbol: set encoding='Custom' and pass "
-                                  f"custom_encoding=sahand_legendre(time_dependent={canon == 'SLTD'})")
+        ctor = {"SLTD": "sahand_legendre(time_dependent=True)", "Sahand_Legendre": "sahand_legendre(time_dependent=False)",
+                "Projected_Legendre": "legendre(project=True)", "Projected_Legendre_Norm": "legendre(norm=True, project=True)",
+                "Projected_Fourier": "fourier(project=True)"}[canon]
+        what = "a projected basis (projected_basis)" if canon.startswith("Projected_") else f"encoding {canon}"
+        raise NotImplementedError(f"{what} is not built from its symbol: set encoding='Custom' and pass custom_encoding={ctor}")
     fn = {"Legendre_No_Norm": legendre_encode_no_norm, "Legendre_Norm": legendre_encode, "Fourier": fourier_encode,
           "Stoudenmire": angle_encode, "Sahand": sahand_encode, "Uniform": uniform_encode}[canon]
     return Encoding(canon, iscomplex, rng, fn)
@@ -592,9 +768,9 @@ def symbolic_encoding(enc: Encoding) -> str:
 
 
 def encoding_from_name(name) -> Optional[Encoding]:
-    """The Encoding of a stored ``Encoding.name`` where a constructor of this package builds it - the Sahand-Legendre bases and
-    whatever model_encoding builds from the name's symbol -, else None (a function_basis has to be handed over again)."""
-    for enc in (sahand_legendre(True), sahand_legendre(False)):
+    """The Encoding of a stored ``Encoding.name`` where a constructor of this package builds it - the Sahand-Legendre bases, the
+    projected bases and whatever model_encoding builds from the name's symbol -, else None (a function_basis has to be handed over again)."""
+    for enc in (sahand_legendre(True), sahand_legendre(False), legendre(project=True), legendre(norm=True, project=True), fourier(project=True)):
         if enc.name == name:
             return enc
     try:
@@ -647,6 +823,20 @@ class FittedEncoder:
         c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         return dict(npoints=kdes[0].npoints, per_site=int(self.enc.istimedependent), lo=c([k.lo for k in kdes]), step=c([k.step for k in kdes]),
                     coef=c([k.coef for k in kdes]), minx=c(minxs), scale=c(scales), cvecs=c(cvecs)[:, :self.d, :self.d].copy())
+
+    @property
+    def orders(self):
+        """the projected bases' fitted tables as the device takes them (mpst_proj_opts): a dict of ``basis`` ("Legendre_Norm",
+        "Legendre_No_Norm" or "Fourier"), ``orders`` (T, d) int32 - the Legendre orders or signed Fourier frequencies that are
+        evaluated, not the fit's positions - and ``inv_norm`` (T,), ones unless the basis is "Legendre_Norm"; None for any other
+        encoding"""
+        basis = _PROJ_DEVICE_BASIS.get(self.enc.encode)
+        if basis is None:
+            return None
+        ds = np.asarray(self.args[0], dtype=np.int64)
+        orders = projected_fourier_freqs(ds, self.d) if basis == "Fourier" else projected_legendre_orders(ds)
+        inv = projected_legendre_inv_norm(orders) if basis == "Legendre_Norm" else np.ones(len(orders))
+        return dict(basis=basis, orders=np.ascontiguousarray(orders, dtype=np.int32), inv_norm=np.ascontiguousarray(inv, dtype=np.float64))
 
 
 def fit_encoding(enc: Encoding, X_norm, y, opts: MPSOptions):

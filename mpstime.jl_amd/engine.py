@@ -111,7 +111,7 @@ def _device_basis(basis):
         pass
     if basis not in L.BASIS:
         raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, split bases over them and - "
-                                                  f"with kde=, their fitted encoder - the Sahand-Legendre bases, not {basis!r}")
+                                                  f"with kde= / orders=, their fitted encoder - the Sahand-Legendre and the projected bases, not {basis!r}")
     return basis, rng, split
 
 
@@ -167,6 +167,39 @@ def _kde_basis(basis, kde):
     """what _device_basis returns, for a call with ``kde`` tables: eo.basis is ignored, the range is the encoding's"""
     from .encodings import Encoding
     return "Legendre_No_Norm", (tuple(basis.range) if isinstance(basis, Encoding) and basis.range else (-1.0, 1.0)), False
+
+
+def _proj_opts(orders, d, T):
+    """mpst_proj_opts of a fitted projected encoding - ``orders`` is its FittedEncoder (``fit_encoding(...)[1]``) or that encoder's
+    ``orders`` tables - and the arrays the struct points into (keep them alive over the call).  The shapes are checked here: the
+    library reads (T, d) integers and (T,) doubles behind the pointers; it checks their values."""
+    tab = getattr(orders, "orders", orders)
+    if not isinstance(tab, dict):
+        raise ValueError("a projected encoding is encoded with the orders its fit selected: pass orders (fit_encoding(...)[1])")
+    o = np.ascontiguousarray(tab["orders"], dtype=np.int32)
+    if o.shape != (T, int(d)):
+        raise ValueError(f"orders table 'orders' must have shape {(T, int(d))}, got {o.shape}")
+    inv = None
+    if tab.get("inv_norm") is not None:
+        inv = np.ascontiguousarray(tab["inv_norm"], dtype=np.float64)
+        if inv.shape != (T,):
+            raise ValueError(f"orders table 'inv_norm' must have shape {(T,)}, got {inv.shape}")
+    max_order = int(np.abs(o.astype(np.int64)).max())
+    pj = L.mpst_proj_opts(L.BASIS[tab["basis"]], o.ctypes.data_as(C.POINTER(C.c_int32)),
+                          inv.ctypes.data_as(C.POINTER(C.c_double)) if inv is not None else None, max_order)
+    return pj, (o, inv)
+
+
+def _fitted_basis(basis, kde, orders):
+    """what _device_basis returns, for a call with ``kde`` or ``orders`` tables, which exclude each other"""
+    if kde is not None and orders is not None:
+        raise ValueError("kde= and orders= belong to different encodings: pass one of them")
+    if kde is not None:
+        return _kde_basis(basis, kde)
+    tab = getattr(orders, "orders", orders)
+    if not isinstance(tab, dict) or tab.get("basis") not in ("Legendre_Norm", "Legendre_No_Norm", "Fourier"):
+        raise ValueError("a projected encoding is encoded with the orders its fit selected: pass orders (fit_encoding(...)[1])")
+    return (tab["basis"],) + _kde_basis(basis, orders)[1:]              # the family decides real / complex; eo.basis itself is ignored
 
 
 class SweepEngine:
@@ -242,16 +275,17 @@ class SweepEngine:
 
     def encode_dataset(self, which, X_sorted, label_index, C_classes, basis="Legendre_No_Norm", d=None, sigmoid_transform=True,
                        minmax=True, data_bounds=(0.0, 1.0), enc_range=(-1.0, 1.0), norms=None, rescale_out_of_bounds=True,
-                       global_counts=None, sigmoid_fit=None, bins=None, kde=None):
+                       global_counts=None, sigmoid_fit=None, bins=None, kde=None, orders=None):
         """Preprocess + encode the raw (N, T) matrix on the device (mpst_encode_dataset).  ``X_sorted`` must already be
         sorted by class.  ``norms=None`` fits a training set (median/IQR on the host, min/max on the device) and
         returns ``(norms, seconds)``; with ``norms`` from the training fit the data is treated as a test set and
         ``(oob, seconds)`` comes back, ``oob`` in the format of transform_test_data (utils.jl:243-266).
         A split encoding (name or Encoding) goes through mpst_encode_split_dataset with ``bins``, the edges its fit produced
         (``fit_encoding(...)[1].bins``: (nbins + 1,) or (T, nbins + 1)); a Sahand-Legendre encoding through mpst_encode_kde_dataset
-        with ``kde``, its fitted encoder (``fit_encoding(...)[1]``)."""
+        with ``kde``, its fitted encoder (``fit_encoding(...)[1]``); a projected encoding through mpst_encode_proj_dataset with
+        ``orders``, its fitted encoder or that encoder's ``orders`` tables."""
         from .encodings import Norms
-        basis, _, split = _device_basis(basis) if kde is None else _kde_basis(basis, kde)
+        basis, _, split = _device_basis(basis) if kde is None and orders is None else _fitted_basis(basis, kde, orders)
         X = np.ascontiguousarray(X_sorted, dtype=np.float64)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
         N, T = X.shape
@@ -272,6 +306,9 @@ class SweepEngine:
         if kde is not None:
             kd, _keep = _kde_opts(kde, d, T)
             self._chk(self.lib.mpst_encode_kde_dataset(*head, C.byref(kd), *tail))
+        elif orders is not None:
+            pj, _keep = _proj_opts(orders, d, T)
+            self._chk(self.lib.mpst_encode_proj_dataset(*head, C.byref(pj), *tail))
         elif split:
             sp, _keep = _split_opts(basis, d, T, bins)
             self._chk(self.lib.mpst_encode_split_dataset(*head, C.byref(sp), *tail))
@@ -287,14 +324,15 @@ class SweepEngine:
         return oob, sec.value
 
     def encode_values(self, X, basis="Legendre_No_Norm", d=4, sigmoid_transform=False, minmax=False, data_bounds=(0.0, 1.0),
-                      enc_range=None, norms=None, rescale_out_of_bounds=False, bins=None, kde=None):
+                      enc_range=None, norms=None, rescale_out_of_bounds=False, bins=None, kde=None, orders=None):
         """mpst_encode_values: the device preprocessing + encoding kernels on a raw (N, T) matrix, states back to the host -
         (N, T, d) float64 for the Legendre / Uniform bases, complex128 for "Fourier", "Stoudenmire", "Sahand".  Defaults: X is already in the encoding's
         domain (no transforms, identity range map); with transforms the [0, 1] data is mapped onto ``enc_range``
         (default: the basis' own range, (-1, 1) for Legendre / Fourier, (0, 1) for Stoudenmire / Sahand / Uniform).  ``norms`` as for encode_dataset (a test set) or None.
         A split encoding with its fitted ``bins`` goes through mpst_encode_split_values, a Sahand-Legendre encoding with its fitted
-        encoder ``kde`` through mpst_encode_kde_values, as in encode_dataset."""
-        basis, basis_range, split = _device_basis(basis) if kde is None else _kde_basis(basis, kde)
+        encoder ``kde`` through mpst_encode_kde_values, a projected encoding with its fitted encoder ``orders`` through
+        mpst_encode_proj_values (complex128 for projected Fourier), as in encode_dataset."""
+        basis, basis_range, split = _device_basis(basis) if kde is None and orders is None else _fitted_basis(basis, kde, orders)
         X = np.ascontiguousarray(X, dtype=np.float64)
         N, T = X.shape
         if enc_range is None:
@@ -309,6 +347,9 @@ class SweepEngine:
         if kde is not None:
             kd, _keep = _kde_opts(kde, int(d), T)
             self._chk(self.lib.mpst_encode_kde_values(*head, C.byref(kd), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
+        elif orders is not None:
+            pj, _keep = _proj_opts(orders, int(d), T)
+            self._chk(self.lib.mpst_encode_proj_values(*head, C.byref(pj), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
         elif split:
             sp, _keep = _split_opts(basis, int(d), T, bins)
             self._chk(self.lib.mpst_encode_split_values(*head, C.byref(sp), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))

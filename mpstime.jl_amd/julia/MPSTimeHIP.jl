@@ -397,6 +397,71 @@ function encode_kde_values(X::Matrix{Float64}, d::Integer, lo::Vector{Float64}, 
     return phi
 end
 
+# ---- projected bases on the device --------------------------------------------------------------------------------------------
+struct MpstProjOpts              # mpst_proj_opts
+    basis::Int32                 # 0 legendre(norm = true), 1 legendre_no_norm, 2 fourier
+    orders::Ptr{Int32}           # (d, T): column t holds site t's Legendre orders or signed Fourier frequencies
+    inv_norm::Ptr{Float64}       # (T,): 1 / sqrt(Pl(1, m; normalized) m), m the site's largest order; read for basis 0 only, else C_NULL
+    max_order::Int32             # bounds every |orders[j, t]|
+end
+
+# the checks the library cannot make (it sees pointers, not lengths) and the struct; preserve `orders` and `inv_norm` over the call
+function proj_opts(basis::Integer, orders::Matrix{Int32}, inv_norm::Union{Nothing,Vector{Float64}}, d::Integer, T::Integer)
+    size(orders) == (d, T) || throw(ArgumentError("orders must be (d, T) = ($d, $T), got $(size(orders))"))
+    isnothing(inv_norm) || length(inv_norm) == T || throw(ArgumentError("inv_norm must hold one entry per site"))
+    return MpstProjOpts(basis, pointer(orders), isnothing(inv_norm) ? Ptr{Float64}(C_NULL) : pointer(inv_norm), maximum(abs, orders))
+end
+
+"""
+    encode_proj_values(X, orders; basis, inv_norm, device)
+
+The projected-basis states of the values `X` ((T, N), already in (-1, 1)) from the order lists the fit selected
+(`mpst_encode_proj_values`, no preprocessing).  `orders` is (d, T): for `basis` 0 / 1 (projected `legendre(norm=true)` /
+`legendre_no_norm`) the Legendre orders that are evaluated - the reference's `legendre_encode(x, nds, ds)` evaluates `Pl(x, p)`
+for the selected position `p`, so `orders = ds` -, for `basis` 2 (projected `fourier`) the signed frequencies
+`get_fourier_freqs(10d)[ds]`.  Returns `phi` (d, T, N), `Float64` or, for `basis` 2, `ComplexF64`.
+"""
+function encode_proj_values(X::Matrix{Float64}, orders::Matrix{Int32}; basis::Integer=1, inv_norm::Union{Nothing,Vector{Float64}}=nothing,
+                            device::Integer=0)
+    T, N = size(X)
+    d = size(orders, 1)
+    phi = zeros(basis == 2 ? ComplexF64 : Float64, d, T, N)
+    secs = Ref(0.0)
+    with_context(device) do c
+        eo = Ref(MpstEncodeOpts(1, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0, 1.0))      # no transforms, identity range map
+        GC.@preserve X orders inv_norm eo begin
+            pj = Ref(proj_opts(basis, orders, inv_norm, d, T))
+            check(c, ccall((:mpst_encode_proj_values, LIB), Cint,
+                           (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}),
+                           c, X, N, T, d, Base.unsafe_convert(Ptr{Cvoid}, eo), Base.unsafe_convert(Ptr{Cvoid}, pj), phi, C_NULL, secs))
+        end
+    end
+    return phi
+end
+
+"""
+    encode_proj_dataset!(c, which, X, labels, C, eo, orders; basis, inv_norm)
+
+`mpst_encode_proj_dataset` on the context `c`: the raw series `X` ((T, N), sorted by class, `labels` 0-based) go through the
+preprocessing `eo` describes and the projected basis, and become data set `which` (0 train, 1 test) of the context.  `eo` comes back
+with what a training set fitted (median, iqr, lo, hi): hand it on, with `is_test = 1`, for the test set.  Returns the device seconds.
+"""
+function encode_proj_dataset!(c::Ptr{Cvoid}, which::Integer, X::Matrix{Float64}, labels::Vector{Int32}, C::Integer, eo::Ref{MpstEncodeOpts},
+                              orders::Matrix{Int32}; basis::Integer=1, inv_norm::Union{Nothing,Vector{Float64}}=nothing)
+    T, N = size(X)
+    d = size(orders, 1)
+    length(labels) == N || throw(ArgumentError("one label per series"))
+    secs = Ref(0.0)
+    GC.@preserve X labels orders inv_norm eo begin
+        pj = Ref(proj_opts(basis, orders, inv_norm, d, T))
+        check(c, ccall((:mpst_encode_proj_dataset, LIB), Cint,
+                       (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Int32}, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64},
+                        Ref{Float64}),
+                       c, which, X, labels, N, T, d, C, Base.unsafe_convert(Ptr{Cvoid}, eo), Base.unsafe_convert(Ptr{Cvoid}, pj), C_NULL, C_NULL, secs))
+    end
+    return secs[]
+end
+
 # ---- leave-one-out site conditionals ----------------------------------------------------------------------------------------
 struct MpstSiteCondOpts          # mpst_sitecond_opts
     grid_per_site::Int32         # 0: xvals_enc (d, ngrid) shared by all sites, 1: (d, ngrid, T), one table per site

@@ -28,6 +28,9 @@ _ENCODINGS = {
     "sahand_legendre_time_dependent": ("SLTD", False, (-1.0, 1.0), True),
     "sahand_legendre": ("Sahand_Legendre", False, (-1.0, 1.0), True),
     "sahand_legendre_time_independent": ("Sahand_Legendre", False, (-1.0, 1.0), True),     # symbolic_encoding of the constructor's names
+    "projected_legendre": ("Projected_Legendre", False, (-1.0, 1.0), True),                 # symbolic_encoding of legendre(project=True), ...
+    "projected_legendre_norm": ("Projected_Legendre_Norm", False, (-1.0, 1.0), True),
+    "projected_fourier": ("Projected_Fourier", True, (-1.0, 1.0), True),
     "custom": ("Custom", False, None, False),
 }
 

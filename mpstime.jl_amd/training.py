@@ -17,7 +17,7 @@ import numpy as np
 from .encodings import (EncodedTimeSeriesSet, Encoding, encode_dataset, encoding_from_name, fit_encoding, fit_encoding_from_training_data, opts_encoding,
                         transform_data, transform_train_data)
 from .engine import SweepEngine
-from .options import MPSOptions, engine_options, numpy_dtype, safe_options
+from .options import MPSOptions, encoding_info, engine_options, numpy_dtype, safe_options
 
 
 @dataclass
@@ -192,7 +192,7 @@ def fitMPS(X_train, y_train=None, X_test=None, y_test=None, opts: MPSOptions = M
     Returns (TrainedMPS, training_information, encoded_test_states).
 
     ``device_encode=True`` (the closed-form bases - Legendre, Fourier, Stoudenmire, Sahand, Uniform -, histogram_split /
-    uniform_split over them and the Sahand-Legendre bases, all fitted on the host first) preprocesses and encodes on the GPU
+    uniform_split over them, the Sahand-Legendre bases and the projected bases, all fitted on the host first) preprocesses and encodes on the GPU
     (mpst_encode_dataset): the raw matrices are uploaded, the product states are downloaded once for the
     returned EncodedTimeSeriesSets."""
     W, X_train, y_train, X_test, y_test, opts, enc, class_keys = _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding, W)
@@ -220,6 +220,9 @@ def _fit_inputs(X_train, y_train, X_test, y_test, opts, custom_encoding=None, W=
     if X_test.size and X_test.shape[1] != T:
         raise AssertionError("The number of sites supported by the MPS, training, and testing data do not match! ")
     enc = opts_encoding(opts, custom_encoding)
+    if enc.iscomplex and encoding_info(opts.encoding)[0] == "Custom" and numpy_dtype(opts.dtype).kind != "c":
+        raise ValueError(f"the custom encoding {enc.name} is complex valued but dtype = {opts.dtype} is real: set dtype='ComplexF64' "
+                         "(or 'ComplexF32') in MPSOptions")                                              # :466-468, for the custom route
     if enc.iscomplex and opts.dtype == "Float64":
         raise RuntimeError("Using a complex valued encoding but the MPS is real. If using a complex-valued custom "
                            "encoding, set 'dtype <: Complex' in MPSOptions")                              # :466-468
@@ -274,9 +277,11 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
                 common.update(basis=enc, bins=encoder.bins)
             elif encoder.kde is not None:
                 common.update(basis=enc, kde=encoder)
+            elif encoder.orders is not None:
+                common.update(basis=enc, orders=encoder)
             else:
-                raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases and the "
-                                          "Sahand-Legendre bases are encoded on the device")
+                raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases, the "
+                                          "Sahand-Legendre bases and the projected bases are encoded on the device")
         norms, _ = eng.encode_dataset(0, Xs, li, C, **common)
         train_states = EncodedTimeSeriesSet(eng.get_encoded(0), ys, li, Xs, counts)
         test_states = EncodedTimeSeriesSet.empty()
