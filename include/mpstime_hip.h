@@ -690,7 +690,10 @@ int  mpst_get_info(void* ctx, int32_t* out /*[16]*/);
  * tail launch's verification failed and the rest ran on the six-launch chain (whose k_eig_fin has the Jacobi fallback), out[20] on
  * the four-launch chain the part of the tail that needs no eigenvector (the dense S tile of every 16-series tile, the next bond's
  * overlap product) is formed by side workgroups of the k_eig_trivec launch and read back by k_bond_tail (0: MPST_TAIL_PRE=0, the
- * tail forms both itself; the same bits either way). */
+ * tail forms both itself; the same bits either way), out[21] with rebuild_caches the two construct_caches of a sweep are hidden beside
+ * the eigensolver: the side workgroups of every k_eig_trivec launch rebuild one environment row of a site that is already final, and a
+ * walk of two steps closes each half-sweep (needs out[20] and the one-launch walk; 0: MPST_REBUILD_SIDE=0 or rebuild_caches off - the
+ * full walks; the same bits either way), out[22] rows rebuilt that way in the last sweep that returned: 2 max(0, T - 3) where out[21]. */
 int  mpst_get_info_n(void* ctx, int32_t* out, int32_t n);
 /* in-kernel phase times (us) of the last eigensolver launch: tridiagonalisation, bisection,
  * tridiagonal eigenvectors, back-transformation, verification+re-orthonormalisation; us[5] = shader

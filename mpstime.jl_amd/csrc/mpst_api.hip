@@ -143,6 +143,7 @@ struct TrainWs {
     // diagnostics: (start, end) stamps of every workgroup of the stamped k_bond_tail launch, [2 * TS_SPAN]; behind them the same of the side workgroups
     DevBuf<unsigned long long> tail_span;
     bool chain4_ok = false;
+    bool rebuild_side = false;    // tail_pre and not MPST_REBUILD_SIDE=0: with rebuild_caches the side workgroups rebuild the caches, a row per bond
     bool tail_pre = false;    // chain4_ok and not MPST_TAIL_PRE=0: side workgroups form the S tile and the overlap product, else the tail itself
     int tail_force_fail = -1, tail_launches = 0;      // test hook (MPST_TAIL_FORCE_REDO=n): the n-th tail launch of the workspace reports a failed verification
     // sliced bond GEMMs (k_yhat_s / k_grad_s): slice contributions to yhat, loss pieces, arrival tickets
@@ -225,6 +226,7 @@ struct Ctx {
     int ynext_lid = -1;
     uint64_t ynext_epoch = 0, ynext_seq = 0, bond_seq = 0;
     int tail_redos = 0;
+    int rebuild_steps = 0;      // rows rebuilt beside the eigensolver in the last sweep (DevScalars::rebuild_steps)
     int32_t ss_counts[2] = {0, 0};      // subspace eigensolver: bonds attempted / accepted, read where a sweep or a bond step synchronises anyway
     int64_t big_fallbacks = 0;        // bonds on which the blocked solver's verification asked for the library
     bool big_opt_active = false;
@@ -490,6 +492,8 @@ int workspace_f64(Ctx* c, TrainWs& w, int64_t Lmax) {
         if (const char* ff = getenv("MPST_TAIL_FORCE_REDO")) w.tail_force_fail = atoi(ff);
         const char* ep = getenv("MPST_TAIL_PRE");
         w.tail_pre = w.chain4_ok && !(ep && ep[0] == '0');
+        const char* er = getenv("MPST_REBUILD_SIDE");
+        w.rebuild_side = w.tail_pre && !(er && er[0] == '0');
         if (w.chain4_ok && (rc = dalloc(c, w.btnT, c->C * Lmax))) return rc;
         if (w.tail_pre && (rc = dalloc(c, w.tail_St, (int64_t)tr.ntiles * TS_ST))) return rc;
         if (w.tail_pre && (rc = dalloc(c, w.tail_P, (int64_t)tr.ntiles * TS_P))) return rc;
@@ -573,7 +577,8 @@ static void refresh_ss_counts(Ctx* c) {
 int enqueue_reset_status(Ctx* c) {
     static_assert(offsetof(DevScalars, eig_fallbacks) == offsetof(DevScalars, status) + 8, "status / eig_sweeps_total / eig_fallbacks adjacent");
     HIPC(c, hipMemsetAsync(&c->ws.sc.h->status, 0, 12, c->stream));
-    HIPC(c, hipMemsetAsync(&c->ws.sc.h->redo, 0, 4, c->stream));
+    static_assert(offsetof(DevScalars, rebuild_steps) == offsetof(DevScalars, redo) + 4, "redo / rebuild_steps adjacent");
+    HIPC(c, hipMemsetAsync(&c->ws.sc.h->redo, 0, 8, c->stream));
     return 0;
 }
 
@@ -766,7 +771,8 @@ struct Chain4Hold {
 // ---- the per-bond launch chain (RealRealHighDimension.jl:733-762 / :777-801) ---------------
 // have_bt: the bond tensor of this bond was already assembled by the previous bond's environment
 // kernel; b.next_lid >= 0: assemble that bond's tensor inside this bond's environment kernel.
-int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = false, int trace_row = -1) {
+// rebuild_side: the bond's eigensolver launch carries a rebuild job (rebuild_side_on)
+int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = false, int trace_row = -1, bool rebuild_side = false) {
     const int lid = b.lid, going_left = b.going_left, next_bt_lid = b.next_lid;
     if (c->typed) return enqueue_bond_typed(c, lid, going_left, trace_row);
     hipStream_t s = c->stream;
@@ -842,6 +848,7 @@ int enqueue_bond(Ctx* c, const View& v_in, const BondSlot& b, bool have_bt = fal
                 sd.P = c->ws.tail_P;
                 sd.span = tail_stamped(v, lid, going_left) ? c->ws.tail_span + 2 * TS_SPAN : nullptr;
                 sd.want_next = want;
+                if (rebuild_side) tail_side_rebuild_job(v, lid, going_left, sd);
             }
             { ProfScope p(c, K_EIG_TRI); launch_eig(v, lid, going_left, 0, s, pre); }
             ProfScope p(c, K_ENV);                                                // verification, back-split, update_caches!, next yhat
@@ -886,15 +893,25 @@ bool env_walk_on(const Ctx* c, const View& v) {
     return !c->typed && !(e && e[0] == '0') && env_walk_supported(v);
 }
 
+// The two construct_caches of a sweep (rebuild_caches) hidden beside the eigensolver: every bond's k_eig_trivec launch rebuilds one row
+// on its side workgroups (TailSide::rb_site) and a closing walk of two steps per half-sweep does the rest.  Only where a bond runs the
+// four-launch chain with side workgroups and a walk could do the rebuild; MPST_REBUILD_SIDE=0: the full walks.  Profiling sweeps keep
+// the full walks (their per-kernel times are those of the launches they name).
+bool rebuild_side_on(const Ctx* c, const View& v) {
+    return c->opt.rebuild_caches && c->ws.rebuild_side && c->ws.tail_pre && c->prof_mask == 0 && bond_uses_tail(c, v, c->opt.track_cost != 0) &&
+           env_walk_on(c, v);
+}
+
 // construct_caches (RealRealHighDimension.jl:45-103) around the label site ls: LE[0 .. ls-1] and RE[T-1 .. ls+1].  ls = T - 1 is
 // construct_caches(W; going_left=true), ls = 0 going_left=false.  One launch per side where every workgroup can walk the chain with
 // its 16 series (k_env_walk: the bits of the per-site launches; a side without sites launches nothing), else one per site.
-void enqueue_caches(Ctx* c, const View& v, int ls) {
+// first > 0: the rows of the first `first` steps of each side exist already (the side workgroups rebuilt them): the walks start there.
+void enqueue_caches(Ctx* c, const View& v, int ls, int first = 0) {
     if (c->typed) return enqueue_caches_typed(c, ls, ls);
     ProfScope p(c, K_ENV);
     if (env_walk_on(c, v)) {
-        launch_env_walk(v, 1, std::min(ls, c->T - 1), c->stream);
-        launch_env_walk(v, 0, c->T - 1 - ls, c->stream);
+        launch_env_walk(v, 1, std::min(ls, c->T - 1), c->stream, first);
+        launch_env_walk(v, 0, c->T - 1 - ls, c->stream, first);
         return;
     }
     for (int j = 0; j < ls && j <= c->T - 2; ++j) launch_env_step(c, v, env_step(j, 1, c->T), ENV_M_SITE);
@@ -939,6 +956,7 @@ int read_back(Ctx* c, Ctx* rep, const DevScalars* sc, mpst_sweep_stats* st) {
     st->max_chi = *std::max_element(chi.begin(), chi.end());
     st->eig_sweeps_total = sc->eig_sweeps_total;
     st->eig_fallbacks = sc->eig_fallbacks;
+    c->rebuild_steps = sc->rebuild_steps;
     if (sc->status) c->caches_valid = false;        // the state after a failed bond is unspecified: set_mps + build_caches to go on
     return 0;
 }
@@ -1039,15 +1057,19 @@ int enqueue_sweep(Ctx* c, const View& v, int k0 = 0) {
     c->ynext_lid = -1;
     // unless the tensor is rescaled first or the caches are rebuilt in between, bond k+1's tensor is assembled by bond k's last launch
     const int nb = c->T - 1;
+    // the rebuilds ride beside the eigensolver, a row per bond, and close with a walk of two steps (a sweep from its first bond only: the
+    // recovery of a marked sweep runs the six-launch chain and keeps the full walks)
+    const bool side = k0 == 0 && rebuild_side_on(c, v);
+    const int first = side ? rebuild_side_first(c->T) : 0;
     bool have = false;
     for (int k = k0; k < 2 * nb; ++k) {
         const bool rebuild_after = c->opt.rebuild_caches && k == nb - 1;
         const BondSlot b = (v.rescale_before || rebuild_after) ? bond_slot(k, nb).unchained() : bond_slot(k, nb);
-        if (int rc = enqueue_bond(c, v, b, have, k)) return rc;
+        if (int rc = enqueue_bond(c, v, b, have, k, side)) return rc;
         have = assembles_next(b, c->ws.fused);
-        if (rebuild_after) enqueue_caches(c, v, 0);      // :770
+        if (rebuild_after) enqueue_caches(c, v, 0, first);      // :770
     }
-    if (c->opt.rebuild_caches) enqueue_caches(c, v, c->T - 1);                  // :804
+    if (c->opt.rebuild_caches) enqueue_caches(c, v, c->T - 1, first);                  // :804
     return 0;
 }
 
@@ -1058,13 +1080,14 @@ int enqueue_sweep(Ctx* c, const View& v, int k0 = 0) {
 template <typename Enqueue>
 int finish_marked(Ctx* c, DevScalars* sc, Enqueue&& enqueue) {
     c->tail_redos++;
-    const int tail_fallbacks = sc->eig_fallbacks;
+    const int tail_fallbacks = sc->eig_fallbacks, side_steps = sc->rebuild_steps;
     Chain4Hold hold(c);
     if (int rc = enqueue(make_view(c, MPST_TRAIN))) return rc;
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));
     if (int rc = read_scalars(c, c, sc)) return rc;
     sc->eig_fallbacks += tail_fallbacks;
+    sc->rebuild_steps += side_steps;        // (the rows rebuilt before the mark; the recovery itself rebuilds with full walks)
     return 0;
 }
 
@@ -3438,7 +3461,7 @@ int mpst_get_info(void* ctx, int32_t* out) {
 }
 
 int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
-    int32_t full[21];
+    int32_t full[23];
     if (!out || n < 0) return MPST_ERR_INVALID;
     int rc = mpst_get_info(ctx, full);
     if (rc) return rc;
@@ -3450,12 +3473,16 @@ int mpst_get_info_n(void* ctx, int32_t* out, int32_t n) {
         full[19] = c4->tail_redos;
         // [20] on that chain, the S tile and the overlap product of the tail come from side workgroups of the k_eig_trivec launch (0: MPST_TAIL_PRE=0)
         full[20] = (full[18] && c4->ws.tail_pre) ? 1 : 0;
+        // [21] with rebuild_caches, the side workgroups also rebuild the caches, a row per bond (0: MPST_REBUILD_SIDE=0, or any of the above off);
+        // [22] rows they rebuilt in the last sweep: 2 max(0, T - 3) where [21], 0 elsewhere
+        full[21] = rebuild_side_on(c4, v4) ? 1 : 0;
+        full[22] = c4->rebuild_steps;
     }
     // bonds the subspace eigensolver attempted / whose result was accepted (the rest went to the exact solver), as of the last sweep,
     // batch or bond step that returned: cached at their synchronisation point, the query itself never waits for the stream
     full[16] = ((Ctx*)ctx)->ss_counts[0];
     full[17] = ((Ctx*)ctx)->ss_counts[1];
-    for (int i = 0; i < n && i < 21; ++i) out[i] = full[i];
+    for (int i = 0; i < n && i < 23; ++i) out[i] = full[i];
     return 0;
 }
 

@@ -1099,6 +1099,9 @@ __device__ __forceinline__ void trivec_body(const View& v, int lid, int going_le
 // Eight waves: wave w owns columns 16w .. 16w+15 of P, the same batches into the same two accumulators as the tail's own product; the
 // tail reads pacc0 + pacc1 in the accumulator layout.  The launch's other eight waves leave at once (a terminated wave no longer counts
 // at s_barrier).
+// With rebuild_caches the role then rebuilds one environment row of its 16 series (TailSide::rb_site, env_step_tile: the step of
+// k_env_walk): the two construct_caches walks of a sweep, T - 1 dependent steps each during which nothing else runs, shrink to two
+// closing walks of two steps.
 __device__ __forceinline__ void tail_side_role(const View& v, int lid, int going_left, const TailSide& sd) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x;
@@ -1148,6 +1151,33 @@ __device__ __forceinline__ void tail_side_role(const View& v, int lid, int going
 #pragma unroll
         for (int r = 0; r < 4; ++r) store_wt(&Pt[r * 64], pacc0[r] + pacc1[r]);
     }
+    // ---- the rebuild job: one environment step on this tile's 16 series (TailSide::rb_site), after what the tail waits for has left.
+    // Its operands are requested only here: the eigenvector workgroups' register allocation is that of a launch without the job.
+    // A sweep marked for redo holds sites that are not final (some with the label index): no step.
+    asm volatile("" ::: "memory");
+    if (sd.rb_site >= 0 && v.sc->redo == 0) {
+        const int j = sd.rb_site;
+        const bool ls = sd.rb_left != 0, end = sd.rb_prev == nullptr;
+        const int cj = v.chi[j], cj1 = v.chi[j + 1];
+        const int Dp = ls ? cj : cj1, Dout = ls ? cj1 : cj;
+        double* Zt = Of + BT_FAC;                   // LDS of its own behind the factors: no wave still reading those is disturbed
+        double* part = Zt + 16 * EW_ZS;
+        double* ph = Zt + EW_STEP_LDS;
+        double* prevs = ph + 16 * EW_PHS;
+        double bv[8];
+        env_step_load_b(v.sites + (int64_t)j * v.site_stride, ls, Dp, Dout, d, bv);
+        if (tid < 16 * d) {
+            const int prow = tid / d, ps = tid - prow * d;
+            ph[prow * EW_PHS + ps] = prow < tl.count ? v.phi[((int64_t)j * v.N + tl.start + prow) * d + ps] : 0.0;
+        }
+        if (!end) {
+            const int row = tid >> 5, a = tid & 31;
+            const double x = sd.rb_prev[(int64_t)(tl.start + min(row, max(tl.count - 1, 0))) * v.cap + min(a, v.cap - 1)];
+            prevs[row * EW_PS + a] = x;
+        }
+        env_step_tile<true>(Zt, part, ph, prevs, end, ls, end ? 1 : Dp, Dout, d, tl.count, bv, sd.rb_out + (int64_t)tl.start * v.cap, v.cap, [] {});
+        if (t == 0 && tid == 0) v.sc->rebuild_steps = v.sc->rebuild_steps + 1;
+    }
     if (span) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         span[1] = __builtin_amdgcn_s_memrealtime();
@@ -1155,7 +1185,9 @@ __device__ __forceinline__ void tail_side_role(const View& v, int lid, int going
 }
 __global__ __launch_bounds__(TRI_T) void k_eig_trivec(View v, int lid, int going_left, const double* rawG, int rawn,
                                                             int rawalg, double* __restrict__ ws, unsigned long long* stamps, TailSide sd) {
-    if (sd.first > 0 && (int)blockIdx.x >= sd.first) {
+    // (unlikely: the role is laid out BEHIND the eigenvector path, which then starts at the kernel's entry.  With the rebuild step the role is
+    // 2.5 KB longer, and in front of the eigenvector path it cost the launch 0.5 us whether or not a job ran: profiles/rebuild_side.md)
+    if (__builtin_expect(sd.first > 0 && (int)blockIdx.x >= sd.first, 0)) {
         tail_side_role(v, lid, going_left, sd);
         return;
     }

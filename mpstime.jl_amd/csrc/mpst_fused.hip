@@ -1394,32 +1394,36 @@ static_assert(16 * BT_SS <= 32 * 32 + 1024 + 128, "formed in the tail, the dense
 // quarter); the row just computed stays in LDS as the next step's `prev`; the next site's vectors and this wave's share of the next
 // site tensor are requested while the current step computes.  Bond dimensions up to 32, d * chi <= 128.
 // =====================================================================================================================
-constexpr int EW_T = 512;
-constexpr int EW_ZS = 130;                   // row stride of the dense Khatri-Rao tile
-constexpr int EW_PS = 34;                    // row stride of the kept environment rows
+// (EW_T, EW_ZS, EW_PS, EW_PHS and the step itself - env_step_tile / env_step_load_b: mpst_tail_side.inl, shared with the side workgroups
+// of k_eig_trivec, which rebuild one row per bond while the eigensolver runs)
 constexpr int EW_TMAX = 1023;                // longest chain (the bond dimensions are staged in LDS)
-__global__ __launch_bounds__(EW_T) void k_env_walk(View v, int left_side, int nstep) {
-    __shared__ __attribute__((aligned(16))) double Zt[16 * EW_ZS];
+// first: the walk starts mid-chain at step `first` with `prev` read from memory (the row step first - 1 left there) instead of 1; the rows
+// of the steps before it are not touched
+__global__ __launch_bounds__(EW_T) void k_env_walk(View v, int left_side, int first, int nstep) {
+    __shared__ __attribute__((aligned(16))) double Zt[EW_STEP_LDS];
     __shared__ __attribute__((aligned(16))) double prevs[16 * EW_PS];
-    __shared__ __attribute__((aligned(16))) double part[8 * 256];
+    double* part = Zt + 16 * EW_ZS;
     __shared__ int chis[EW_TMAX + 1];             // the bond dimensions: a scalar load from memory per step would be a dependent microsecond each
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i16 = lane & 15, kq = lane >> 4;
+    const int tid = threadIdx.x;
     const int d = v.d, T = v.T;
     for (int i = tid; i <= T; i += EW_T) chis[i] = v.chi[i];
     const Span tl = tile_span_k(v, (int)blockIdx.x);
-    __syncthreads();
-    const int nt = wave & 1, q = wave >> 1;
-    const int col = nt * 16 + i16;
     const int64_t cs = (int64_t)v.N * v.cap;
     double* base = left_side ? v.LE : v.RE;
     // sites in walking order: left 0 .. T-2 (LE[j] from LE[j-1] and site j), right T-1 .. 1 (RE[j] from RE[j+1] and site j); nstep of them
     auto site_of = [&](int st) { return left_side ? st : T - 1 - st; };
+    // a walk that starts mid-chain: the row before its first step, from memory (entries beyond the live ones are never read)
+    if (first > 0) {
+        const int row = tid >> 5, a = tid & 31;
+        const double x = base[(int64_t)site_of(first - 1) * cs + (int64_t)(tl.start + min(row, max(tl.count - 1, 0))) * v.cap + min(a, v.cap - 1)];
+        prevs[row * EW_PS + a] = x;
+    }
+    __syncthreads();
     // the sites' vectors come from HBM (2+ us away, more than a step takes): they are fetched a CHUNK of sites ahead - thread = (site of
     // the chunk, row, s) - and parked in LDS, two chunks deep
     const int per = 16 * d;
     const int CH = min(8, EW_T / per);              // sites per chunk (d <= 16: at least 2)
-    __shared__ double phs[2][8 * 16 * 17];
+    __shared__ double phs[2][8 * 16 * EW_PHS];
     const int cs_site = tid / per, cs_rem = tid - cs_site * per;
     const int prow = cs_rem / d, ps = cs_rem - prow * d;
     auto load_phi_chunk = [&](int c0) -> double {   // this thread's value of the chunk that starts at step c0
@@ -1427,77 +1431,38 @@ __global__ __launch_bounds__(EW_T) void k_env_walk(View v, int left_side, int ns
         const bool ok = cs_site < CH && st < nstep && prow < tl.count;
         return ok ? v.phi[((int64_t)site_of(st) * v.N + tl.start + prow) * d + ps] : 0.0;
     };
-    // this wave's share of a site tensor as the B operand of its quarter: M[z][col], z = 4 (q ks4 + u) + kq
+    // this wave's share of a site tensor as the B operand of its quarter (env_step_load_b)
     auto load_b = [&](int st, double (&bv)[8]) {
         const int j = site_of(st);
         const int Dp = left_side ? __builtin_amdgcn_readfirstlane(chis[j]) : __builtin_amdgcn_readfirstlane(chis[j + 1]);
         const int Dout = left_side ? __builtin_amdgcn_readfirstlane(chis[j + 1]) : __builtin_amdgcn_readfirstlane(chis[j]);
-        const int Z = Dp * d, nsteps = ((Z + 3) & ~3) >> 2, ks4 = env_ks4(nsteps);
-        const double* M = v.sites + (int64_t)j * v.site_stride;
-        // left: M[(a,s)][k], row stride chi[j+1];  right: M[k][(s,b)] read transposed, column stride d * chi[j+1]
-        const int64_t sz = left_side ? Dout : 1, sk = left_side ? 1 : (int64_t)d * __builtin_amdgcn_readfirstlane(chis[j + 1]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int z = 4 * (q * ks4 + u) + kq;
-            bv[u] = (col < Dout && u < ks4 && z < Z) ? M[(int64_t)z * sz + (int64_t)col * sk] : 0.0;
-        }
+        env_step_load_b(v.sites + (int64_t)j * v.site_stride, left_side != 0, Dp, Dout, d, bv);
     };
     double bv[8], bvn[8];                           // this step's and the next step's B operand; the one after is requested inside the step
-    double phq = load_phi_chunk(0);                 // chunk 0 ...
-    load_b(0, bv);
+    double phq = load_phi_chunk(first);             // chunk 0 ...
+    load_b(first, bv);
 #pragma unroll
     for (int u = 0; u < 8; ++u) bvn[u] = 0.0;
-    if (nstep > 1) load_b(1, bvn);
-    if (cs_site < CH) phs[0][cs_site * 272 + prow * 17 + ps] = phq;
-    phq = load_phi_chunk(CH);                       // ... and chunk 1 in flight
-    for (int st = 0; st < nstep; ++st) {
+    if (first + 1 < nstep) load_b(first + 1, bvn);
+    if (cs_site < CH) phs[0][cs_site * 16 * EW_PHS + prow * EW_PHS + ps] = phq;
+    phq = load_phi_chunk(first + CH);               // ... and chunk 1 in flight
+    for (int st = first; st < nstep; ++st) {
         const int j = site_of(st);
         const int Dp = st == 0 ? 1 : (left_side ? __builtin_amdgcn_readfirstlane(chis[j]) : __builtin_amdgcn_readfirstlane(chis[j + 1]));
         const int Dout = left_side ? __builtin_amdgcn_readfirstlane(chis[j + 1]) : __builtin_amdgcn_readfirstlane(chis[j]);
-        const int Z = Dp * d, ZP = (Z + 3) & ~3, nsteps = ZP >> 2, ks4 = env_ks4(nsteps);
-        const int ch = st / CH, cin = st - ch * CH;
-        if (cin == 0 && st > 0) {
+        const int ch = (st - first) / CH, cin = (st - first) - ch * CH;
+        if (cin == 0 && st > first) {
             // a new chunk begins: the one fetched during the last chunk goes to LDS (the buffer of the chunk before the last is free),
             // the next one is requested
-            if (cs_site < CH) phs[ch & 1][cs_site * 272 + prow * 17 + ps] = phq;
-            phq = load_phi_chunk((ch + 1) * CH);
+            if (cs_site < CH) phs[ch & 1][cs_site * 16 * EW_PHS + prow * EW_PHS + ps] = phq;
+            phq = load_phi_chunk(first + (ch + 1) * CH);
         }
-        // (LDS-only barriers: __syncthreads() would also wait for the acknowledgement of the last step's stores and for the operands
-        // requested two steps ahead - the very round trips the walk is built to hide)
-        lds_barrier();                              // (also: the previous step's rows are in prevs, its Zt is consumed)
-        // ---- the Khatri-Rao tile of this step: Zt[i][z] = prev_i[a] phi_i[s], left z = a d + s, right z = s Dp + a ----
-        {
-            const double* ph = phs[ch & 1] + cin * 272;
-            const int row = tid >> 5, a = tid & 31;  // 16 rows x 32 bond entries
-            const double pa = (a < Dp && row < tl.count) ? (st == 0 ? 1.0 : prevs[row * EW_PS + a]) : 0.0;
-            if (a < Dp) {
-                for (int s = 0; s < d; ++s) Zt[row * EW_ZS + (left_side ? a * d + s : s * Dp + a)] = pa * ph[row * 17 + s];
-            }
-            for (int z = Z + a; z < ZP; z += 32) Zt[row * EW_ZS + z] = 0.0;
-        }
-        lds_barrier();
         double bvnn[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) bvnn[u] = 0.0;
-        if (st + 2 < nstep) load_b(st + 2, bvnn);   // two steps ahead: the site tensors come from the L2, about a step away
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        if (nt * 16 < Dout) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int step = q * ks4 + u;
-                acc = mfma_f64(Zt[i16 * EW_ZS + 4 * min(step, nsteps - 1) + kq], bv[u], acc);      // (bv is zero beyond the contraction)
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[(q * 2 + nt) * 256 + r * 64 + lane] = acc[r];
-        lds_barrier();
-        {
-            const int tnt = tid >> 8, e = tid & 255;
-            const double sum = (part[tnt * 256 + e] + part[(2 + tnt) * 256 + e]) + (part[(4 + tnt) * 256 + e] + part[(6 + tnt) * 256 + e]);
-            const int i = ((e >> 4) & 3) + 4 * (e >> 6), c = tnt * 16 + (e & 15);
-            if (i < tl.count && c < Dout) base[(int64_t)j * cs + (int64_t)(tl.start + i) * v.cap + c] = sum;
-            prevs[i * EW_PS + c] = sum;
-        }
+        env_step_tile<false>(Zt, part, phs[ch & 1] + cin * 16 * EW_PHS, prevs, st == 0, left_side != 0, Dp, Dout, d, tl.count, bv,
+                             base + (int64_t)j * cs + (int64_t)tl.start * v.cap, v.cap,
+                             [&] { if (st + 2 < nstep) load_b(st + 2, bvnn); });      // two steps ahead: the site tensors come from the L2, about a step away
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             bv[u] = bvn[u];
@@ -1505,8 +1470,10 @@ __global__ __launch_bounds__(EW_T) void k_env_walk(View v, int left_side, int ns
         }
     }
 }
-void launch_env_walk(const View& v, int left_side, int nstep, hipStream_t s) {
-    if (nstep > 0) hipLaunchKernelGGL(k_env_walk, dim3(v.ntiles), dim3(EW_T), 0, s, v, left_side, std::min(nstep, v.T - 1));
+// steps [first, nstep) of the walk from the chain end (first > 0: the row of step first - 1 is in memory)
+void launch_env_walk(const View& v, int left_side, int nstep, hipStream_t s, int first) {
+    nstep = std::min(nstep, v.T - 1);
+    if (nstep > 0 && first >= 0 && first < nstep) hipLaunchKernelGGL(k_env_walk, dim3(v.ntiles), dim3(EW_T), 0, s, v, left_side, first, nstep);
 }
 bool env_walk_supported(const View& v) { return v.zw != 2 && v.cap <= 32 && v.d * v.cap <= MAX_DIM && v.d >= 2 && v.d <= 16 && v.T >= 2 && v.T <= EW_TMAX; }
 
@@ -2393,6 +2360,20 @@ void tail_side_operands(const View& v, int lid, int going_left, TailSide& sd) {
     sd.phS = v.phi + (int64_t)st.site * v.N * v.d;
     sd.phO = v.phi + (int64_t)ot.site * v.N * v.d;
     sd.M = going_left ? v.btn : v.btnT;
+}
+// the row bond lid's eigensolver launch rebuilds (tail_side_rebuild_site): going left RE[j] from RE[j+1], going right LE[j] from LE[j-1]
+void tail_side_rebuild_job(const View& v, int lid, int going_left, TailSide& sd) {
+    const int64_t cs = (int64_t)v.N * v.cap;
+    const int j = tail_side_rebuild_site(lid, going_left, v.T);
+    sd.rb_site = j;
+    sd.rb_left = going_left ? 0 : 1;
+    sd.rb_prev = nullptr;
+    sd.rb_out = nullptr;
+    if (j < 0) return;
+    double* rows = going_left ? v.RE : v.LE;
+    const int pj = going_left ? j + 1 : j - 1;
+    sd.rb_prev = (pj >= 0 && pj <= v.T - 1) ? rows + (int64_t)pj * cs : nullptr;
+    sd.rb_out = rows + (int64_t)j * cs;
 }
 // which bond's tail leaves its phase stamps (mpst_get_tail_phases): MPST_TAIL_STAMP="lid,going_left", default the middle bond going left
 bool tail_stamped(const View& v, int lid, int going_left) {

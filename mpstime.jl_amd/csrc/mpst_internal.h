@@ -317,6 +317,8 @@ struct DevScalars {
     int32_t redo;               // k_bond_tail: 1 + the position in the sweep of a bond whose on-device verification failed - every later tail launch of the
                                 // sweep leaves at once and the host finishes the sweep from that bond on the chain that has the Jacobi fallback (sticky
                                 // until the host clears it)
+    int32_t rebuild_steps;      // environment rows rebuilt by side workgroups of k_eig_trivec in this sweep (TailSide::rb_site; tile 0 counts, one
+                                // plain store per launch; cleared with redo)
     unsigned long long eig_stamps[64];  // s_memrealtime (100 MHz) at the phase boundaries of the last eigensolve
 };
 
@@ -561,7 +563,24 @@ struct TailSide {
     double* P;                      // [ntiles][TS_P], written when want_next
     unsigned long long* span;       // stamped launch: (start, end) of every side workgroup, or null
     int32_t first, want_next;
+    // The rebuild job (construct_caches beside the eigensolver): after its S tile and P, a side workgroup performs ONE environment step on
+    // its 16 series - row rb_out of site rb_site from rb_prev (null: chain end, 1 is taken), the site's vectors and the site tensor - the
+    // step of k_env_walk (env_step_tile), with write-through stores.  rb_site < 0: no job.  The site is final and its row is read by
+    // no launch of the bond that carries the job (tail_side_rebuild_site); a sweep marked for redo (DevScalars::redo) skips the step.
+    const double* rb_prev;
+    double* rb_out;
+    int32_t rb_site = -1, rb_left = 0;
 };
+// The site whose row bond lid's k_eig_trivec launch rebuilds, or -1.  The rule: a row is never written in a launch of a bond whose chain
+// reads it, and only from a site tensor that is final.  Bond lid reads LE[lid-1] and RE[lid+2]; going left the sites beyond lid + 1 are
+// final, going right those before lid.  Hence a lag of two: going left RE[lid+3] (from RE[lid+4], written a bond earlier), going right
+// LE[lid-2] (from LE[lid-3]).  That leaves RE[2], RE[1] / LE[T-3], LE[T-2] of a half-sweep to a closing walk (rebuild_side_first).
+inline int tail_side_rebuild_site(int lid, int going_left, int T) {
+    const int j = going_left ? lid + 3 : lid - 2;
+    return (j >= 0 && j <= T - 1) ? j : -1;
+}
+inline int rebuild_side_first(int T) { return T - 3 > 0 ? T - 3 : 0; }      // first step of the closing walk = hidden steps per half-sweep
+void tail_side_rebuild_job(const View& v, int lid, int going_left, TailSide& sd);     // rb_* of bond lid
 void tail_side_operands(const View& v, int lid, int going_left, TailSide& sd);       // Sprev .. M of bond lid (the tail's own operands)
 bool tail_stamped(const View& v, int lid, int going_left);                            // this bond's tail leaves its phase stamps (MPST_TAIL_STAMP)
 // pre: what the side workgroups of this bond's k_eig_trivec launch left (St, P), or null: the tail forms both itself
@@ -569,7 +588,8 @@ void launch_bond_tail(const View& v, int lid, int going_left, int chain, int wan
                       const TailSide* pre, hipStream_t s);
 bool bond_tail_supported(const View& v);
 // construct_caches in one launch: a workgroup walks the whole chain with its 16 series (k_env_walk); left_side: LE, else RE
-void launch_env_walk(const View& v, int left_side, int nstep /* sites, from the chain end */, hipStream_t s);
+// first > 0: only steps [first, nstep), the row of step first - 1 read from memory
+void launch_env_walk(const View& v, int left_side, int nstep /* sites, from the chain end */, hipStream_t s, int first = 0);
 bool env_walk_supported(const View& v);
 // the headline chain for K independent fits of one shape per launch (blockIdx.z selects the fit's View in the device array vs)
 void launch_yhat_s_b(const View& v, const View* vs, int K, int lid, hipStream_t s);

@@ -138,4 +138,77 @@ __device__ __forceinline__ void tail_overlap_product(const KrSide& ko, int KP, i
     }
 }
 
+// ---- one environment step of a 16-series tile: what k_env_walk (mpst_fused.hip) does T - 1 times in a row and a side workgroup of
+// k_eig_trivec once per launch (the rebuild job of TailSide).  512 threads, 8 waves = (column tile nt, quarter q of the contraction).
+// The product of k_env, bit for bit: the Khatri-Rao tile Zt[i][z] = prev_i[a] phi_i[s] (left z = a d + s, right z = s Dp + a), four MFMA
+// chains over env_ks4(nsteps) k-steps each, added as (q0 + q1) + (q2 + q3).  Both callers run this one body: the same products, the
+// same sums, the same row.
+constexpr int EW_T = 512;
+constexpr int EW_ZS = 130;                   // row stride of the dense Khatri-Rao tile
+constexpr int EW_PS = 34;                    // row stride of the kept environment rows
+constexpr int EW_PHS = 17;                   // row stride of a site's staged vectors
+constexpr int EW_STEP_LDS = 16 * EW_ZS + 8 * 256;      // Zt, then the eight partial tiles
+
+// this wave's share of site tensor M as the B operand of its quarter: M[z][col], z = 4 (q ks4 + u) + kq
+// left: M[(a,s)][k], row stride Dout;  right: M[k][(s,b)] read transposed, column stride d * Dp (Dp, Dout: the bond dimensions from memory)
+__device__ __forceinline__ void env_step_load_b(const double* M, bool left_side, int Dp, int Dout, int d, double (&bv)[8]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kq = lane >> 4, col = (wave & 1) * 16 + (lane & 15), q = wave >> 1;
+    const int Z = Dp * d, nsteps = ((Z + 3) & ~3) >> 2, ks4 = env_ks4(nsteps);
+    const int64_t sz = left_side ? Dout : 1, sk = left_side ? 1 : (int64_t)d * Dp;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int z = 4 * (q * ks4 + u) + kq;
+        bv[u] = (col < Dout && u < ks4 && z < Z) ? M[(int64_t)z * sz + (int64_t)col * sk] : 0.0;
+    }
+}
+
+// ph: the site's vectors [16][EW_PHS]; prevs: [16][EW_PS], the previous row on entry (first: chain end, 1 is taken instead), this step's on
+// return; both written by the caller before the call (the first barrier is in here).  out: the row of the tile's first series (stride
+// cap); WT: write-through stores (the side workgroups).  ahead(): what the caller requests while the step computes.
+template <bool WT, class Ahead>
+__device__ __forceinline__ void env_step_tile(double* __restrict__ Zt, double* __restrict__ part, const double* __restrict__ ph, double* __restrict__ prevs,
+                                              const bool first, const bool left_side, const int Dp, const int Dout, const int d, const int count,
+                                              const double (&bv)[8], double* __restrict__ out, const int cap, Ahead&& ahead) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i16 = lane & 15, kq = lane >> 4;
+    const int nt = wave & 1, q = wave >> 1;
+    const int Z = Dp * d, ZP = (Z + 3) & ~3, nsteps = ZP >> 2, ks4 = env_ks4(nsteps);
+    // (LDS-only barriers: __syncthreads() would also wait for the acknowledgement of the last step's stores and for the operands
+    // requested two steps ahead - the very round trips the walk is built to hide)
+    lds_barrier();                              // (also: the previous step's rows are in prevs, its Zt is consumed)
+    // ---- the Khatri-Rao tile of this step: Zt[i][z] = prev_i[a] phi_i[s], left z = a d + s, right z = s Dp + a ----
+    {
+        const int row = tid >> 5, a = tid & 31;  // 16 rows x 32 bond entries
+        const double pa = (a < Dp && row < count) ? (first ? 1.0 : prevs[row * EW_PS + a]) : 0.0;
+        if (a < Dp) {
+            for (int s = 0; s < d; ++s) Zt[row * EW_ZS + (left_side ? a * d + s : s * Dp + a)] = pa * ph[row * EW_PHS + s];
+        }
+        for (int z = Z + a; z < ZP; z += 32) Zt[row * EW_ZS + z] = 0.0;
+    }
+    lds_barrier();
+    ahead();
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+    if (nt * 16 < Dout) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int step = q * ks4 + u;
+            acc = mfma_f64(Zt[i16 * EW_ZS + 4 * min(step, nsteps - 1) + kq], bv[u], acc);      // (bv is zero beyond the contraction)
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) part[(q * 2 + nt) * 256 + r * 64 + lane] = acc[r];
+    lds_barrier();
+    {
+        const int tnt = tid >> 8, e = tid & 255;
+        const double sum = (part[tnt * 256 + e] + part[(2 + tnt) * 256 + e]) + (part[(4 + tnt) * 256 + e] + part[(6 + tnt) * 256 + e]);
+        const int i = ((e >> 4) & 3) + 4 * (e >> 6), c = tnt * 16 + (e & 15);
+        if (i < count && c < Dout) {
+            if (WT) __hip_atomic_store(out + (int64_t)i * cap + c, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else out[(int64_t)i * cap + c] = sum;
+        }
+        prevs[i * EW_PS + c] = sum;
+    }
+}
+
 }  // namespace mpst

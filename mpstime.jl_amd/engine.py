@@ -617,9 +617,10 @@ class SweepEngine:
         return {k: (us[i], int(cnt[i])) for i, k in enumerate(L.KERNEL_CLASSES)}
 
     def info(self):
-        out = (C.c_int32 * 21)()
-        self._chk(self.lib.mpst_get_info_n(self.ctx, out, 21))
+        out = (C.c_int32 * 23)()
+        self._chk(self.lib.mpst_get_info_n(self.ctx, out, 23))
         return {"four_launch_chain": bool(out[18]), "tail_redos": out[19], "tail_side_workgroups": bool(out[20]),
+                "rebuild_side": bool(out[21]), "rebuild_side_steps": out[22],
                 "subspace_attempted": out[16], "subspace_accepted": out[17], "fused": bool(out[0]), "large_bond": bool(out[1]), "nparts": out[2], "nchunks": out[3], "cap": out[4],
                 "ranks": out[5], "graph": bool(out[6]), "library_eig_fallbacks": out[7], "persistent_tridiag_aborts": out[8],
                 "xcd_local_misplaced": out[9], "sliced_bond_gemms": bool(out[10]), "grad_shares": out[11],
