@@ -248,7 +248,9 @@ __device__ __forceinline__ int vsw(int c, int j) { return c * 16 + ((j + 2 * c) 
 template <bool DENSE>
 __device__ __forceinline__ void tri_core(const double* __restrict__ G, const int n, const TriShared t, double* __restrict__ Vd,
                                          unsigned long long* stamps) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (the wave's index in a scalar register: what it decides in the reflector loop - live, helper, retired, the reflector a wave still has
+    // to write out - is then scalar too, branches and all, and the loop's lane-invariant integers fit the vector registers it has left)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (stamps && tid == 0) {
         stamps[0] = __builtin_amdgcn_s_memrealtime();
         stamps[6] = __builtin_readcyclecounter();
@@ -1092,8 +1094,9 @@ __device__ __forceinline__ void trivec_body(const View& v, int lid, int going_le
 // The role sits behind a block-index branch at the top of the kernel and is INLINED there: as a called function it has to save the
 // callee-saved VGPRs it touches (188 bytes of scratch per lane instead of 20 for every workgroup of the launch, whatever the function's
 // linkage) and the sweep measured SLOWER than without side workgroups (profiles/tail_side_workgroups.md); inlined, the eigenvector
-// workgroups' code keeps its 128 registers, its 20 bytes of scratch and its four spilled registers with their reloads where they
-// were.  What keeps the role itself within the launch's 128 registers per lane:
+// workgroups' code keeps its 128 registers and its register allocation (20 bytes of scratch and four spilled registers then; none
+// since tri_core keeps the wave index in a scalar register, profiles/bond_roundtrips.md).  What keeps the role itself within the
+// launch's 128 registers per lane:
 // bt_new's entries are requested a batch ahead of their MFMAs instead of all 32 up front, and d == 4 has no code path of its own (the
 // general one forms the same products of the same two factors).
 // Eight waves: wave w owns columns 16w .. 16w+15 of P, the same batches into the same two accumulators as the tail's own product; the

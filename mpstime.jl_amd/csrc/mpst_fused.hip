@@ -366,15 +366,152 @@ __device__ __forceinline__ double step_from_parts(const View& v, double* red, do
     return (v.optimiser == MPST_OPT_TSGO) ? v.eta / nrm : v.eta;
 }
 
+// ---- operand traffic of gram_upd_body.  A half batch is 8 k-steps (32 of the contraction) of both panels, bt and the gradient: two of
+// them fill the registers one full batch of 16 k-steps used to, so that one can be in flight while the other is consumed.  Every load
+// is unconditional, from a clamped address, and the lane predicate goes on the VALUE when it is consumed (gram_half): a load under a
+// lane predicate becomes a branch around it whose join waits for the data - one L2 round trip per k-step (see tail_chain_request).
+// Going right the contraction index is the fast one in memory and the MFMA layout (lane = row i, k-step entry kq) makes every load
+// touch 16 cache lines for 32 bytes each, each line four times.  There a lane requests in ROW layout instead - 16 lanes side by side
+// along k, four rows per load: every line once - forms its entries of bt_new and turns them into the MFMA layout through a panel in
+// LDS that belongs to its wave (GramSrc::pan; no barrier: a wave's LDS operations stay in order).  The same fma per entry, the same
+// operand in the same MFMA: the same bits.
+constexpr int GT_LD = 34;           // row stride of a panel: the 32 lanes of a half wave read (row i, entry kq) from 32 different bank pairs
+struct GramOps { double a_bt[8], a_g[8], b_bt[8], b_g[8]; };
+struct GramSrc {
+    const double *bt, *g;
+    int64_t ra, rb, sa_m, sa_k, L;  // offsets of the (clamped) rows m and n of the two panels, strides of a row and of k, entries per class
+    int kbeg, kend, kq, K;          // the wave's range of the contraction, the lane's k within a step, the contraction's length
+    int i16, m0, n0, n;             // row layout (ROWS, going right): the lane's place along k, the panels' first rows, the matrix' dimension
+    double* pan;                    // [2][16][GT_LD] the wave's two panels
+};
+struct GramDst {
+    double *btn, *btnT;             // where a diagonal tile puts bt_new (null: not a diagonal tile / no transposed copy wanted)
+    int m, X;
+};
+__device__ __forceinline__ void gram_next(int& c, int& j, int nh) {
+    if (++j >= nh) {
+        j = 0;
+        ++c;
+    }
+}
+// row layout: slot sl of a lane is row gram_row(kq, sl >> 1) of the panel, entry i16 + 16 (sl & 1) of the half batch (the two rows of a
+// half wave lie 8 apart: its 32 writes to a panel go to 32 different bank pairs)
+__device__ __forceinline__ int gram_row(int kq, int jj) { return 8 * (kq & 1) + 4 * (kq >> 1) + jj; }
+template <bool ROWS>
+__device__ __forceinline__ void gram_request(GramOps& o, const GramSrc& s, int c, int j) {
+    const int64_t base = (int64_t)c * s.L;
+    if constexpr (ROWS) {
+        const double* pbt = s.bt + base;
+        const double* pg = s.g + base;
+        const int kh = s.kbeg + 32 * j + s.i16;
+#pragma unroll
+        for (int sl = 0; sl < 8; ++sl) {
+            const int row = gram_row(s.kq, sl >> 1);
+            const int64_t ko = min(kh + 16 * (sl & 1), s.K - 1);          // (sa_k == 1)
+            const int64_t oa = (int64_t)min(s.m0 + row, s.n - 1) * s.sa_m + ko, ob = (int64_t)min(s.n0 + row, s.n - 1) * s.sa_m + ko;
+            o.a_bt[sl] = pbt[oa];
+            o.a_g[sl] = pg[oa];
+            o.b_bt[sl] = pbt[ob];
+            o.b_g[sl] = pg[ob];
+        }
+        return;
+    }
+    const double* abt = s.bt + base + s.ra;
+    const double* ag = s.g + base + s.ra;
+    const double* bbt = s.bt + base + s.rb;
+    const double* bg = s.g + base + s.rb;
+    const int kh = s.kbeg + 32 * j + s.kq;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int64_t ko = (int64_t)min(kh + 4 * u, s.K - 1) * s.sa_k;
+        o.a_bt[u] = abt[ko];
+        o.a_g[u] = ag[ko];
+        o.b_bt[u] = bbt[ko];
+        o.b_g[u] = bg[ko];
+    }
+}
+// Half batch (c, j), whose operands are in o: form the entries of bt_new, hand o to the next half batch to request, store (diagonal
+// tiles), multiply.  The MFMA sequence is the one of whole batches of 16 k-steps: a batch whose second half lies beyond the wave's range
+// still runs its eight zero-operand steps (an exact +0 each).
+template <bool ROWS>
+__device__ __forceinline__ void gram_half(GramOps& o, const GramSrc& s, const GramDst& t, const double step, const bool mv, const bool nv,
+                                          int& c, int& j, int& rc, int& rj, const int nh, const int ncl, d4& acc) {
+    const int kh = s.kbeg + 32 * j + s.kq;
+    const int64_t base = (int64_t)c * s.L;
+    double a[8], bb[8];
+    if constexpr (ROWS) {
+        double* pa = s.pan;
+        double* pb = s.pan + 16 * GT_LD;
+        const int k0 = s.kbeg + 32 * j + s.i16;
+        double va[8];
+#pragma unroll
+        for (int sl = 0; sl < 8; ++sl) {
+            asm volatile("" : "+v"(o.a_bt[sl]), "+v"(o.a_g[sl]), "+v"(o.b_bt[sl]), "+v"(o.b_g[sl]));
+            const int row = gram_row(s.kq, sl >> 1), e = s.i16 + 16 * (sl & 1);
+            const bool kv = k0 + 16 * (sl & 1) < s.kend;
+            va[sl] = (s.m0 + row < s.n && kv) ? fma(-step, o.a_g[sl], o.a_bt[sl]) : 0.0;
+            const double vb = (s.n0 + row < s.n && kv) ? fma(-step, o.b_g[sl], o.b_bt[sl]) : 0.0;
+            pa[row * GT_LD + e] = va[sl];
+            pb[row * GT_LD + e] = vb;
+        }
+        if (rc < ncl) gram_request<ROWS>(o, s, rc, rj);
+        if (t.btn) {
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) {
+                const int row = gram_row(s.kq, sl >> 1), k = k0 + 16 * (sl & 1);
+                if (s.m0 + row < s.n && k < s.kend) t.btn[base + (int64_t)(s.m0 + row) * s.sa_m + k] = va[sl];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            a[u] = pa[s.i16 * GT_LD + 4 * u + s.kq];
+            bb[u] = pb[s.i16 * GT_LD + 4 * u + s.kq];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            // (the values named to the compiler here, all of them needed: it cannot sink a load behind the select that follows)
+            asm volatile("" : "+v"(o.a_bt[u]), "+v"(o.a_g[u]), "+v"(o.b_bt[u]), "+v"(o.b_g[u]));
+            const bool kv = kh + 4 * u < s.kend;
+            a[u] = (mv && kv) ? fma(-step, o.a_g[u], o.a_bt[u]) : 0.0;
+            bb[u] = (nv && kv) ? fma(-step, o.b_g[u], o.b_bt[u]) : 0.0;
+        }
+        if (rc < ncl) gram_request<ROWS>(o, s, rc, rj);
+        if (t.btn) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (mv && kh + 4 * u < s.kend) t.btn[base + s.ra + (int64_t)(kh + 4 * u) * s.sa_k] = a[u];
+        }
+    }
+    gram_next(rc, rj, nh);
+    if (t.btnT) {                           // (m = x, k = y): the same entries as [c][y][x] for k_bond_tail
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (mv && kh + 4 * u < s.kend) t.btnT[base + (int64_t)(kh + 4 * u) * t.X + t.m] = a[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+        acc = mfma_f64(a[u], bb[u], acc);               // (operands beyond the contraction are zero: an exact +0, no predicate)
+    if (!(j & 1) && j == nh - 1) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = mfma_f64(0.0, 0.0, acc);
+    }
+    gram_next(c, j, nh);
+}
+
 // Gram matrix of bt_new = bt - step*grad viewed as the matrix decomposeBT hands to svd, one 16 x 16 tile per
 // workgroup, K split over the 4 waves.  The diagonal tiles see every entry of bt_new exactly once (their A-operand
 // panel) and write it to v.btn - a second buffer, the other tiles are still reading the old one.
-__device__ __forceinline__ void gram_upd_body(const View& v, int lid, int going_left, int first_iter, const int tile) {
-    __shared__ double part[4][256];
-    __shared__ double red[4];
+template <bool ROWS>
+__device__ __forceinline__ void gram_upd_dir(const View& v, int lid, const int going_left, int first_iter, const int tile,
+                                             double (&part)[4][256], double (&red)[4], double (&pan)[4][2 * 16 * GT_LD]) {
     const BondDimsF b = bond_dims_f(v, lid);
     const int n = going_left ? b.Y : b.X;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;     // (uniform: the wave's range and its branches are scalar)
     const int tn = (n + 15) >> 4;
     const bool live = tile < tn * tn;
     const int m0 = (tile / tn) * 16, n0 = (tile % tn) * 16;
@@ -390,19 +527,19 @@ __device__ __forceinline__ void gram_upd_body(const View& v, int lid, int going_
     const int kq4 = (((K + 3) >> 2) + 3) & ~3;
     const int kbeg = wave * kq4, kend = min(K, (wave + 1) * kq4);
     const int64_t sa_m = going_left ? 1 : b.Y, sa_k = going_left ? b.Y : 1;
-    // The first batch of operands (all of them for the headline shapes) is requested BEFORE the step size is formed:
-    // the norm reduction (a dependent global round trip + two barriers) then overlaps the operand latency.
-    double a_bt[16], a_g[16], b_bt[16], b_g[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const int k = kbeg + 4 * u + kq;
-        const bool kv = k < kend;
-        const int64_t ia = (int64_t)m * sa_m + (int64_t)k * sa_k, ib = (int64_t)nn * sa_m + (int64_t)k * sa_k;
-        a_bt[u] = (mv && kv) ? v.bt[ia] : 0.0;
-        a_g[u] = (mv && kv) ? g[ia] : 0.0;
-        b_bt[u] = (nv && kv) ? v.bt[ib] : 0.0;
-        b_g[u] = (nv && kv) ? g[ib] : 0.0;
-    }
+    // The operands travel in half batches (GramOps), two register sets: the first two live half batches - every operand of the headline
+    // shapes, both classes going right, both halves of the one batch going left - are requested BEFORE the step size is formed (the norm
+    // reduction, a dependent global round trip + two barriers, then overlaps the operand latency); half batch i + 2 is requested into the
+    // set half batch i has just left, in front of i's MFMAs.
+    const GramSrc src = {v.bt, g, (int64_t)min(m, n - 1) * sa_m, (int64_t)min(nn, n - 1) * sa_m, sa_m, sa_k, b.L, kbeg, kend, kq, K, i, m0, n0, n, pan[wave]};
+    const int nh = (max(kend - kbeg, 0) + 31) >> 5;         // live half batches per class
+    const int ncl = nh ? nc : 0;
+    GramOps o0, o1;
+    int rc = 0, rj = 0;                                     // the next half batch to request: class, half
+    if (rc < ncl) gram_request<ROWS>(o0, src, rc, rj);
+    gram_next(rc, rj, nh);
+    if (rc < ncl) gram_request<ROWS>(o1, src, rc, rj);
+    gram_next(rc, rj, nh);
     double nrm;
     const double step = step_from_parts(v, red, &nrm);
     if (tile == 0 && threadIdx.x == 0) {
@@ -413,41 +550,13 @@ __device__ __forceinline__ void gram_upd_body(const View& v, int lid, int going_
         if (v.trace) v.trace[v.trace_it] = bond_loss(v);      // "Loss before step i" of the last iteration
     }
     if (!live) return;
+    const GramDst dst = {diag ? v.btn : nullptr, (diag && !going_left) ? v.btnT : nullptr, m, b.X};
     d4 acc = {0, 0, 0, 0};
-    for (int c = 0; c < nc; ++c) {
-        const int64_t base = (int64_t)c * b.L;
-        for (int k0 = kbeg; k0 < kend; k0 += 64) {
-            double a[16], bb[16];
-            int64_t ia[16];
-            const bool first = c == 0 && k0 == kbeg;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int k = k0 + 4 * u + kq;
-                const bool kv = k < kend;
-                ia[u] = base + (int64_t)m * sa_m + (int64_t)k * sa_k;
-                const int64_t ib = base + (int64_t)nn * sa_m + (int64_t)k * sa_k;
-                if (first) {
-                    a[u] = fma(-step, a_g[u], a_bt[u]);
-                    bb[u] = fma(-step, b_g[u], b_bt[u]);
-                } else {
-                    a[u] = (mv && kv) ? fma(-step, g[ia[u]], v.bt[ia[u]]) : 0.0;
-                    bb[u] = (nv && kv) ? fma(-step, g[ib], v.bt[ib]) : 0.0;
-                }
-            }
-            if (diag) {
-#pragma unroll
-                for (int u = 0; u < 16; ++u)
-                    if (mv && k0 + 4 * u + kq < kend) v.btn[ia[u]] = a[u];
-                if (v.btnT && !going_left) {        // (m = x, k = y): the same entries as [c][y][x] for k_bond_tail
-#pragma unroll
-                    for (int u = 0; u < 16; ++u)
-                        if (mv && k0 + 4 * u + kq < kend) v.btnT[base + (int64_t)(k0 + 4 * u + kq) * b.X + m] = a[u];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-                acc = mfma_f64(a[u], bb[u], acc);           // (operands beyond the contraction are zero: an exact +0, no predicate)
-        }
+    int cc = 0, cj = 0;                                     // the half batch being consumed
+    while (cc < ncl) {
+        gram_half<ROWS>(o0, src, dst, step, mv, nv, cc, cj, rc, rj, nh, ncl, acc);
+        if (cc >= ncl) break;
+        gram_half<ROWS>(o1, src, dst, step, mv, nv, cc, cj, rc, rj, nh, ncl, acc);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) part[wave][r * 64 + lane] = acc[r];
@@ -461,6 +570,15 @@ __device__ __forceinline__ void gram_upd_body(const View& v, int lid, int going_
             if (row < n && col < n) v.gram[(int64_t)row * n + col] = sum;
         }
     }
+}
+
+// (a body per direction: one register allocation each - as one body with a run-time switch the two layouts' operands met in 288 registers)
+__device__ __forceinline__ void gram_upd_body(const View& v, int lid, int going_left, int first_iter, const int tile) {
+    __shared__ double part[4][256];
+    __shared__ double red[4];
+    __shared__ double pan[4][2 * 16 * GT_LD];       // (going right only)
+    if (going_left) gram_upd_dir<false>(v, lid, 1, first_iter, tile, part, red, pan);
+    else gram_upd_dir<true>(v, lid, 0, first_iter, tile, part, red, pan);
 }
 
 // ---- environment update + back-split in one launch ---------------------------------------------------------------
@@ -1639,13 +1757,13 @@ __device__ __forceinline__ void tail_split_request(const View& v, const BondDims
     const int K = going_left ? b.Y : b.X;
     const int ks4 = (((K + 3) >> 2) + 3) >> 2;
     const int mm = (going_left ? m0 : n0) + i16, mmc = min(mm, (going_left ? b.X : b.Y) - 1);
-    const bool mv = live && mm < (going_left ? b.X : b.Y);
-    const int kbeg = 4 * ks4 * rg, kend = min(K, 4 * ks4 * (rg + 1));
+    const int kbeg = 4 * ks4 * rg;
+    // (unconditional, from a clamped address: see tail_chain_request.  The RAW value stays in R and tail_split_job drops what lies beyond
+    // the operand: with the select here the compiler sank each load under the lane predicate again, eight round trips in a row)
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-        const int k = kbeg + 4 * u + kq, kc = min(k, K - 1);
-        const double x = going_left ? Bc[(int64_t)mmc * b.Y + kc] : Bc[(int64_t)kc * b.Y + mmc];      // (unconditional: see tail_chain_request)
-        R[u] = (mv && k < kend) ? x : 0.0;
+        const int kc = min(kbeg + 4 * u + kq, K - 1);
+        R[u] = going_left ? Bc[(int64_t)mmc * b.Y + kc] : Bc[(int64_t)kc * b.Y + mmc];
     }
 }
 __device__ __forceinline__ void tail_split_job(const View& v, const BondDimsF& b, int lid, int going_left, int host, int nhost, const double (&R)[16],
@@ -1676,9 +1794,18 @@ __device__ __forceinline__ void tail_split_job(const View& v, const BondDimsF& b
                 ev[u] = (kcol < nk && k < kend) ? Ev[(int64_t)k * ldE + kcol] : 0.0;
             }
             asm volatile("" ::: "memory");
+            // the bt_new operand as requested (tail_split_request), zero beyond the matrix and beyond the wave's range (c < C here: live)
+            const bool mv = (going_left ? m0 : n0) + i16 < (going_left ? b.X : b.Y);
+            double ru[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                double x = R[u];
+                asm volatile("" : "+v"(x));
+                ru[u] = (mv && kbeg + 4 * u + kq < kend) ? x : 0.0;
+            }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                if (kbeg + 4 * u < kend) p = going_left ? mfma_f64(R[u], ev[u], p) : mfma_f64(ev[u], R[u], p);
+                if (kbeg + 4 * u < kend) p = going_left ? mfma_f64(ru[u], ev[u], p) : mfma_f64(ev[u], ru[u], p);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) spart[wave * 256 + r * 64 + lane] = p[r];
