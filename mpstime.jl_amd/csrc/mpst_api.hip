@@ -1227,7 +1227,6 @@ int batch_run(void* const* ctxs, int32_t K, mpst_sweep_stats* out) {
 // mpst_set_dataset and mpst_encode_[split_]dataset run every check that can reject the call before they touch the context: a
 // rejected call leaves it exactly as it was.  The commit releases the old set, builds the new one aside and moves it in complete; an
 // allocation or a copy that fails in between leaves the set empty (N = 0, no buffers), never N > 0 over missing buffers.
-bool basis_is_complex(int basis) { return basis == MPST_BASIS_FOURIER || basis == MPST_BASIS_STOUDENMIRE || basis == MPST_BASIS_SAHAND; }
 bool dtype_is_f32(int dtype) { return dtype == MPST_F32 || dtype == MPST_C64; }
 
 // dst[b][a] = src[a][b] over rows of `row` bytes: series-major [N][T][row] <-> site-major [T][N][row]
@@ -1253,103 +1252,6 @@ void set_ctx_dtype(Ctx* c, int dtype) {
     c->typed = dtype != MPST_F64 || getenv("MPST_TYPED") != nullptr;
 }
 
-// a closed-form basis of dimension d: on its own (mpst_encode_dataset / _values) or as the auxiliary basis of a split one
-int basis_validate(Ctx* c, int basis, int d, bool split) {
-    if (basis < MPST_BASIS_LEGENDRE || basis > MPST_BASIS_UNIFORM)
-        return fail(c, MPST_ERR_UNSUPPORTED, split ? "split bases are implemented over the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)"
-                                                   : "device-side encoding implements the closed-form bases (Legendre, Fourier, Stoudenmire, Sahand, Uniform)");
-    const int odd = split ? MPST_ERR_UNSUPPORTED : MPST_ERR_INVALID;
-    if (basis == MPST_BASIS_STOUDENMIRE && d != 2) return fail(c, odd, "Stoudenmire Angle encoding only supports d = 2!");
-    if (basis == MPST_BASIS_SAHAND && d % 2) return fail(c, odd, "Sahand encoding only supports even dimension");
-    return 0;
-}
-
-// the checks of a split request (include/mpstime_hip.h); on success eo->basis is the auxiliary basis
-int split_validate(Ctx* c, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp) {
-    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-    if (!sp || !sp->bins) return fail(c, MPST_ERR_INVALID, "NULL split options or bin edges");
-    if (sp->nbins < 1 || sp->nbins > 512) return fail(c, MPST_ERR_INVALID, "nbins must lie in 1 .. 512 (got %d)", (int)sp->nbins);
-    if (sp->aux_dim < 1 || (int64_t)sp->nbins * sp->aux_dim != d)
-        return fail(c, MPST_ERR_INVALID, "The auxilliary basis dimension (%d) must evenly divide the total feature dimension (%d): d = nbins * aux_dim, nbins = %d",
-                    (int)sp->aux_dim, (int)d, (int)sp->nbins);       // get_nbins_safely, splitbases.jl:2-9
-    if (sp->per_site != 0 && sp->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
-    if (int rc = basis_validate(c, sp->aux_basis, sp->aux_dim, true)) return rc;
-    const int64_t nsite = sp->per_site ? T : 1, ne = sp->nbins + 1;
-    for (int64_t t = 0; t < nsite; ++t)
-        for (int64_t k = 0; k + 1 < ne; ++k)
-            if (!(sp->bins[t * ne + k] <= sp->bins[t * ne + k + 1]))
-                return fail(c, MPST_ERR_INVALID, "bin edges must be non-decreasing (site %lld, edges %lld and %lld: %g, %g)", (long long)t, (long long)k,
-                            (long long)(k + 1), sp->bins[t * ne + k], sp->bins[t * ne + k + 1]);
-    eo->basis = sp->aux_basis;
-    return 0;
-}
-
-// the checks of a Sahand-Legendre request (include/mpstime_hip.h); eo->basis is ignored and left alone: the states are doubles
-bool kde_site_is_zero(const mpst_kde_opts* kd, int64_t site, int32_t d) {
-    for (int64_t q = 0; q < (int64_t)d * d; ++q)
-        if (kd->cvecs[site * d * d + q] != 0.0) return false;
-    return true;
-}
-int kde_validate(Ctx* c, int32_t T, int32_t d, const mpst_kde_opts* kd) {
-    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-    if (!kd || !kd->lo || !kd->step || !kd->coef || !kd->minx || !kd->scale || !kd->cvecs)
-        return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
-    if (kd->npoints < 3) return fail(c, MPST_ERR_INVALID, "a density estimate has at least 3 grid points (got %d)", (int)kd->npoints);
-    if (kd->per_site != 0 && kd->per_site != 1) return fail(c, MPST_ERR_INVALID, "per_site must be 0 or 1");
-    if (d < 1 || d > 16) return fail(c, MPST_ERR_INVALID, "the Sahand-Legendre bases are encoded for d = 1 .. 16 (got %d)", (int)d);
-    const int64_t nsite = kd->per_site ? T : 1;
-    auto bad = [](double v) { return !(v > 0.0) || !std::isfinite(v); };
-    for (int64_t t = 0; t < nsite; ++t) {
-        if (kde_site_is_zero(kd, t, d)) continue;
-        if (bad(kd->step[t]) || bad(kd->scale[t]) || bad(kd->minx[t]))
-            return fail(c, MPST_ERR_INVALID, "site %lld: step, scale and minx must be positive and finite (got %g, %g, %g)", (long long)t,
-                        kd->step[t], kd->scale[t], kd->minx[t]);
-    }
-    return 0;
-}
-// the checks of a projected-basis request (include/mpstime_hip.h): every entry the kernel turns into a trip count or an index.
-// eo->basis is ignored and left alone
-constexpr int32_t PROJ_MAX_D = 16, PROJ_MAX_LEGENDRE = 7 * PROJ_MAX_D, PROJ_MAX_FOURIER = 5 * PROJ_MAX_D;
-int proj_validate(Ctx* c, int32_t T, int32_t d, const mpst_proj_opts* pj) {
-    if (T < 1) return fail(c, MPST_ERR_INVALID, "bad dimensions");
-    if (!pj || !pj->orders) return fail(c, MPST_ERR_INVALID, "NULL projected-basis options or order table");
-    const bool fourier = pj->basis == MPST_BASIS_FOURIER;
-    if (!fourier && pj->basis != MPST_BASIS_LEGENDRE && pj->basis != MPST_BASIS_LEGENDRE_NO_NORM)
-        return fail(c, MPST_ERR_INVALID, "a projected basis is Legendre, Legendre without norm or Fourier (got basis %d)", (int)pj->basis);
-    if (d < 1 || d > PROJ_MAX_D) return fail(c, MPST_ERR_INVALID, "the projected bases are encoded for d = 1 .. %d (got %d)", (int)PROJ_MAX_D, (int)d);
-    const int32_t cap = fourier ? PROJ_MAX_FOURIER : PROJ_MAX_LEGENDRE;
-    if (pj->max_order < 0 || pj->max_order > cap)
-        return fail(c, MPST_ERR_INVALID, "max_order must be within 0 .. %d (got %d)", (int)cap, (int)pj->max_order);
-    for (int64_t q = 0; q < (int64_t)T * d; ++q) {
-        const int32_t o = pj->orders[q];
-        if ((o < 0 && !fourier) || o > pj->max_order || o < -pj->max_order)
-            return fail(c, MPST_ERR_INVALID, "site %lld, slot %lld: order %d outside %s%d .. %d", (long long)(q / d), (long long)(q % d), (int)o,
-                        fourier ? "-" : "", fourier ? (int)pj->max_order : 0, (int)pj->max_order);
-    }
-    if (pj->basis == MPST_BASIS_LEGENDRE) {
-        if (!pj->inv_norm) return fail(c, MPST_ERR_INVALID, "NULL inv_norm for the normalised projected Legendre basis");
-        for (int32_t t = 0; t < T; ++t)
-            if (!(pj->inv_norm[t] > 0.0) || !std::isfinite(pj->inv_norm[t]))
-                return fail(c, MPST_ERR_INVALID, "site %d: inv_norm must be positive and finite (got %g)", (int)t, pj->inv_norm[t]);
-    }
-    return 0;
-}
-
-// A basis that comes with fitted tables instead of eo->basis: Sahand-Legendre (kd) or projected (pj).  `kind` says which entry point
-// was called, so that a NULL struct is that entry point's error; only that kind's pointer is ever set
-struct FittedBasis {
-    enum Kind { NONE, KDE, PROJ } kind = NONE;
-    const mpst_kde_opts* kd = nullptr;
-    const mpst_proj_opts* pj = nullptr;
-    static FittedBasis kde(const mpst_kde_opts* kd) { FittedBasis fb; fb.kind = KDE; fb.kd = kd; return fb; }
-    static FittedBasis proj(const mpst_proj_opts* pj) { FittedBasis fb; fb.kind = PROJ; fb.pj = pj; return fb; }
-};
-// the closed-form basis a request encodes with (a Sahand-Legendre request: none - a real one stands in wherever only real / complex
-// matters; a projected request: its family)
-int request_basis(const mpst_encode_opts* eo, const FittedBasis& fb) {
-    return fb.pj ? fb.pj->basis : fb.kd ? MPST_BASIS_LEGENDRE_NO_NORM : eo->basis;
-}
-
 bool fits_sigmoid(const mpst_encode_opts* eo) { return eo->sigmoid_transform && eo->fit_sigmoid && !eo->is_test; }
 int preprocess_validate(Ctx* c, const mpst_encode_opts* eo, int64_t N, int32_t T) {
     if (eo->fit_sigmoid && eo->is_test) return fail(c, MPST_ERR_INVALID, "fit_sigmoid: the RobustSigmoid is fitted on the training set only");
@@ -1358,8 +1260,14 @@ int preprocess_validate(Ctx* c, const mpst_encode_opts* eo, int64_t N, int32_t T
     return 0;
 }
 
-// What mpst_set_dataset (encoded values of the given dtype) and, with eo set, mpst_encode_[split_]dataset (raw values through eo,
-// split: over sp; dtype from the context or the basis) ask for
+// the verdict of mpst_encode_plan.h on a request's basis, reported like every other check
+int basis_validate(Ctx* c, const EncodeBasis& basis, int32_t T, int32_t d) {
+    const EncodeReject r = encode_basis_validate(basis, T, d);
+    return r.code ? fail(c, r.code, "%s", r.text.c_str()) : 0;
+}
+
+// What mpst_set_dataset (encoded values of the given dtype) and, with eo set, the mpst_encode_*dataset entry points (raw values through
+// eo into `basis`; dtype from the context or the basis) ask for
 struct DataSetRequest {
     int which;
     const int32_t* label_idx;
@@ -1369,24 +1277,17 @@ struct DataSetRequest {
     const int64_t* n_global_per_class;
     bool have_values;
     mpst_encode_opts* eo = nullptr;
-    bool split = false;
-    const mpst_split_opts* sp = nullptr;
-    FittedBasis fb;                         // a Sahand-Legendre basis (mpst_encode_kde_dataset) or a projected one (mpst_encode_proj_dataset)
+    EncodeBasis basis;
 };
 
 // Every check that can reject the call, in the order the entry points report them; fills r.dtype of an encode call and the plan.
 // Reads the context, changes nothing of it.
 int dataset_validate(Ctx* c, DataSetRequest& r, DataSetPlan* plan) {
-    if (r.eo) {
-        if (int rc = r.fb.kind == FittedBasis::PROJ ? proj_validate(c, r.T, r.d, r.fb.pj)
-                     : r.fb.kind == FittedBasis::KDE ? kde_validate(c, r.T, r.d, r.fb.kd)
-                     : r.split ? split_validate(c, r.T, r.d, r.eo, r.sp) : basis_validate(c, r.eo->basis, r.d, false))
-            return rc;
-    }
+    if (int rc = r.eo ? basis_validate(c, r.basis, r.T, r.d) : 0) return rc;
     if (r.which != MPST_TRAIN && r.which != MPST_TEST) return fail(c, MPST_ERR_INVALID, "which must be 0 (train) or 1 (test)");
     if (r.eo) {
         // the element type: what mpst_set_dtype / the other data set fixed (opts.dtype), else the basis' own (Float64 / ComplexF64)
-        const bool bcx = basis_is_complex(request_basis(r.eo, r.fb));
+        const bool bcx = r.basis.is_complex();
         r.dtype = c->have_dtype ? c->dtype : (bcx ? MPST_C128 : MPST_F64);
         if (bcx && (r.dtype == MPST_F64 || r.dtype == MPST_F32))
             return fail(c, MPST_ERR_INVALID, "Using a complex valued encoding but the MPS is real. If using a complex-valued custom encoding, set 'dtype <: Complex' in MPSOptions");   // RealRealHighDimension.jl:462-464
@@ -1468,52 +1369,15 @@ int timed_launch(Ctx* c, double* seconds, Launch launch) {
 
 // preprocessing + encoding of X[N][T] into dphi ([T][N][d] doubles, or (re, im) pairs for the Fourier basis): shared by
 // mpst_encode_dataset (dphi = the data set's product states) and mpst_encode_values (dphi = scratch, copied out)
-// sp: a split basis over eo->basis (its edges are uploaded for the call), or null; fb: a Sahand-Legendre or a projected basis (its
-// tables are uploaded for the call), or neither.  eo has passed preprocess_validate, the tables their own checks.
-int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
-                       const FittedBasis& fb, double* dphi, double* oob_fix, double* seconds) {
+// `basis` has passed basis_validate, eo preprocess_validate.  The basis' tables (mpst_encode_plan.h) are uploaded for the call - nothing
+// reads them once the states are written -, so the context holds nothing of a call that fails later.
+int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const EncodeBasis& basis, double* dphi,
+                double* oob_fix, double* seconds) {
     int rc;
-    const mpst_kde_opts* kd = fb.kd;
-    const mpst_proj_opts* pj = fb.pj;
-    // the projected bases' tables: per site the d orders in ascending order, then the slot of each (int32), and the norms (doubles,
-    // the normalised Legendre basis only).  The sort (stable, so equal orders keep their slots' order) turns the site's list into
-    // what k_encode_proj walks once.  They belong to the call like the tables below
-    DevBuf<int32_t> ptab;
-    DevBuf<double> pinv;
-    if (pj) {
-        std::vector<int32_t> tab((size_t)T * 2 * d);
-        for (int32_t t = 0; t < T; ++t) {
-            int32_t* ord = tab.data() + (size_t)t * 2 * d;
-            int32_t* slot = ord + d;
-            const int32_t* src = pj->orders + (size_t)t * d;
-            for (int32_t j = 0; j < d; ++j) slot[j] = j;
-            std::stable_sort(slot, slot + d, [&](int32_t a, int32_t b) { return src[a] < src[b]; });
-            for (int32_t j = 0; j < d; ++j) ord[j] = src[slot[j]];
-        }
-        if ((rc = upload(c, ptab, tab))) return rc;
-        if (pj->basis == MPST_BASIS_LEGENDRE && (rc = upload(c, pinv, std::vector<double>(pj->inv_norm, pj->inv_norm + T)))) return rc;
-    }
-    DevBuf<double> dbins, dX, part, lohi, fix;      // released on every exit path, the HIPC early returns included
-    // the Sahand-Legendre tables, packed [lo | step | minx | scale | coef | cvecs]: one upload.  Like the bin edges they belong to the
-    // call - nothing reads them once the states are written -, so the context holds nothing of a call that fails later
-    DevBuf<double> ktab;
-    DevBuf<int32_t> kzero;
-    const int64_t ks = kd ? (kd->per_site ? T : 1) : 0, kcoef_n = kd ? ks * ((int64_t)kd->npoints + 2) : 0;
-    if (kd) {
-        std::vector<int32_t> zero((size_t)ks);
-        for (int64_t t = 0; t < ks; ++t) zero[(size_t)t] = kde_site_is_zero(kd, t, d);
-        std::vector<double> tab;
-        tab.reserve((size_t)(4 * ks + kcoef_n + ks * d * d));
-        for (const double* p : {kd->lo, kd->step, kd->minx, kd->scale}) tab.insert(tab.end(), p, p + ks);
-        tab.insert(tab.end(), kd->coef, kd->coef + kcoef_n);
-        tab.insert(tab.end(), kd->cvecs, kd->cvecs + ks * d * d);
-        if ((rc = upload(c, kzero, zero)) || (rc = upload(c, ktab, tab))) return rc;
-    }
-    if (sp) {
-        const size_t nedge = (size_t)(sp->per_site ? T : 1) * (size_t)(sp->nbins + 1);
-        if ((rc = dalloc(c, dbins, (int64_t)nedge))) return rc;
-        HIPC(c, hipMemcpy(dbins, sp->bins, nedge * sizeof(double), hipMemcpyHostToDevice));
-    }
+    const EncodeTables tab = encode_tables(basis, T, d);
+    DevBuf<double> tf64, dX, part, lohi, fix;       // released on every exit path, the HIPC early returns included
+    DevBuf<int32_t> ti32;
+    if ((!tab.f64.empty() && (rc = upload(c, tf64, tab.f64))) || (!tab.i32.empty() && (rc = upload(c, ti32, tab.i32)))) return rc;
     if ((rc = dalloc(c, dX, N * T)) || (rc = dalloc(c, part, 512)) || (rc = dalloc(c, lohi, 2))) return rc;
     const bool test = eo->is_test != 0;
     if (test && eo->rescale_out_of_bounds && (rc = dalloc(c, fix, 2 * N))) return rc;
@@ -1538,30 +1402,23 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     }
     EncDev e{};
     e.N = N; e.T = T; e.d = d;
-    const int basis = request_basis(eo, fb);
-    e.norm = basis == MPST_BASIS_LEGENDRE;
-    e.fourier = basis_is_complex(basis);
-    e.basis = basis;
-    e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax; e.is_test = test;
+    e.kind = basis.kind;
+    e.basis = basis.family();
+    e.fourier = basis.is_complex();
+    e.sigmoid = eo->sigmoid_transform; e.minmax = eo->minmax;
     e.med = eo->median; e.s = eo->iqr / 1.35;
     e.lb = eo->data_lb; e.ub = eo->data_ub; e.a = eo->range_a; e.b = eo->range_b;
-    const int bd = sp ? sp->aux_dim : d;         // the closed-form basis' own dimension
+    const int bd = basis.aux_dim(d);
     e.nrm = std::sqrt(std::sqrt((2 * bd + 1) / 2.0) * bd);
     e.lohi = lohi; e.fix = fix;
-    if (sp) {
-        e.bins = dbins; e.bin_stride = sp->per_site ? sp->nbins + 1 : 0;
-        e.nbins = sp->nbins; e.aux_dim = sp->aux_dim;
-    }
-    if (kd) {
-        const double* p = ktab;
-        e.kde_lo = p; e.kde_step = p + ks; e.kde_minx = p + 2 * ks; e.kde_scale = p + 3 * ks; e.kde_coef = p + 4 * ks;
-        e.kde_cvecs = p + 4 * ks + kcoef_n;
-        e.kde_zero = kzero; e.kde_npoints = kd->npoints; e.kde_per_site = kd->per_site;
-    }
-    if (pj) {
-        e.proj_tab = ptab;
-        e.proj_inv = pj->basis == MPST_BASIS_LEGENDRE ? (const double*)pinv : nullptr;
-    }
+    auto f64 = [&](const EncodeSpan& s) { return s.off < 0 ? nullptr : (const double*)tf64 + s.off; };
+    auto i32 = [&](const EncodeSpan& s) { return s.off < 0 ? nullptr : (const int32_t*)ti32 + s.off; };
+    e.bins = f64(tab.bins); e.bin_stride = tab.bin_stride;
+    if (const mpst_split_opts* sp = basis.sp()) { e.nbins = sp->nbins; e.aux_dim = sp->aux_dim; }
+    e.kde_lo = f64(tab.kde_lo); e.kde_step = f64(tab.kde_step); e.kde_minx = f64(tab.kde_minx); e.kde_scale = f64(tab.kde_scale);
+    e.kde_coef = f64(tab.kde_coef); e.kde_cvecs = f64(tab.kde_cvecs); e.kde_zero = i32(tab.kde_zero);
+    if (const mpst_kde_opts* kd = basis.kd()) { e.kde_npoints = kd->npoints; e.kde_per_site = kd->per_site; }
+    e.proj_tab = i32(tab.proj_tab); e.proj_inv = f64(tab.proj_inv);
     if ((rc = timed_launch(c, &secs, [&] {
             launch_encode(e, dX, dphi, part, lohi, fix, !test && eo->minmax, c->stream);
             return hipGetLastError();
@@ -1578,22 +1435,20 @@ int encode_core(Ctx* c, const double* X, int64_t N, int32_t T, int32_t d, mpst_e
     return 0;
 }
 
-// mpst_encode_dataset and, with split = true, mpst_encode_split_dataset, with fb, mpst_encode_kde_dataset / mpst_encode_proj_dataset
+// the four mpst_encode_*dataset entry points: `basis` says which
 int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d, int32_t C,
-                          mpst_encode_opts* eo, bool split, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
-                          double* seconds, const FittedBasis& fb = FittedBasis()) {
+                   mpst_encode_opts* eo, const EncodeBasis& basis, const int64_t* n_global_per_class, double* oob_fix, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo) return fail(c, MPST_ERR_INVALID, "NULL encode options");
-    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, split, sp, fb};
-    if (fb.kind == FittedBasis::KDE && !fb.kd) return fail(c, MPST_ERR_INVALID, "NULL density-estimate options or table");
+    DataSetRequest r{which, label_idx, N, T, d, C, 0, n_global_per_class, X != nullptr, eo, basis};
     return dataset_set(c, r, [&](double* dphi) {
-        const bool bcx = basis_is_complex(request_basis(eo, fb));
-        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, sp, fb, dphi, oob_fix, seconds);
+        const bool bcx = basis.is_complex();
+        if (r.dtype == (bcx ? MPST_C128 : MPST_F64)) return encode_core(c, X, N, T, d, eo, basis, dphi, oob_fix, seconds);
         // the basis' own type (fp64, real or pairs) aside, then cast to the context's
         DevBuf<double> tmp;
         int rc;
-        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, sp, fb, tmp, oob_fix, seconds))) return rc;
+        if ((rc = dalloc(c, tmp, N * T * d * (bcx ? 2 : 1))) || (rc = encode_core(c, X, N, T, d, eo, basis, tmp, oob_fix, seconds))) return rc;
         launch_tcast(tmp, bcx ? 1 : 0, dphi, c->zw == 2, dtype_is_f32(r.dtype), N * T * d, c->stream);
         HIPC(c, hipGetLastError());
         HIPC(c, hipStreamSynchronize(c->stream));
@@ -1601,21 +1456,19 @@ int encode_dataset(void* ctx, int which, const double* X, const int32_t* label_i
     });
 }
 
-// mpst_encode_values and, with split = true, mpst_encode_split_values, with fb, mpst_encode_kde_values / mpst_encode_proj_values
-int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, bool split, const mpst_split_opts* sp,
-                         void* phi_out, double* oob_fix, double* seconds, const FittedBasis& fb = FittedBasis()) {
+// the four mpst_encode_*values entry points: `basis` says which
+int encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const EncodeBasis& basis, void* phi_out,
+                  double* oob_fix, double* seconds) {
     Ctx* c = (Ctx*)ctx;
     if (!c) return MPST_ERR_INVALID;
     if (!eo || !X || !phi_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
     if (N <= 0 || T < 1 || d < 1 || d > 64) return fail(c, MPST_ERR_INVALID, "bad dimensions");
     int rc;
-    if ((rc = fb.kind == FittedBasis::PROJ ? proj_validate(c, T, d, fb.pj) : fb.kind == FittedBasis::KDE ? kde_validate(c, T, d, fb.kd) : split ? split_validate(c, T, d, eo, sp) : basis_validate(c, eo->basis, d, false)) ||
-        (rc = preprocess_validate(c, eo, N, T)))
-        return rc;
+    if ((rc = basis_validate(c, basis, T, d)) || (rc = preprocess_validate(c, eo, N, T))) return rc;
     HIPC(c, hipSetDevice(c->device));
-    const size_t w = (size_t)d * (basis_is_complex(request_basis(eo, fb)) ? 2 : 1);
+    const size_t w = (size_t)d * (basis.is_complex() ? 2 : 1);
     DevBuf<double> dphi;
-    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, sp, fb, dphi, oob_fix, seconds))) return rc;
+    if ((rc = dalloc(c, dphi, (int64_t)(N * T * w))) || (rc = encode_core(c, X, N, T, d, eo, basis, dphi, oob_fix, seconds))) return rc;
     std::vector<double> tmp((size_t)N * T * w);
     HIPC(c, hipMemcpy(tmp.data(), dphi, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
     transpose_rows(phi_out, tmp.data(), T, N, w * sizeof(double));
@@ -1817,45 +1670,45 @@ int mpst_set_dataset(void* ctx, int which, const void* phi, const int32_t* label
 
 int mpst_encode_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                         int32_t C, mpst_encode_opts* eo, const int64_t* n_global_per_class, double* oob_fix, double* seconds) {
-    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds);
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, EncodeBasis::closed(eo), n_global_per_class, oob_fix, seconds);
 }
 
 int mpst_encode_split_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                               int32_t C, mpst_encode_opts* eo, const mpst_split_opts* sp, const int64_t* n_global_per_class, double* oob_fix,
                               double* seconds) {
-    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, true, sp, n_global_per_class, oob_fix, seconds);
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, EncodeBasis::split(sp), n_global_per_class, oob_fix, seconds);
 }
 
 int mpst_encode_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, void* phi_out, double* oob_fix,
                        double* seconds) {
-    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds);
+    return encode_values(ctx, X, N, T, d, eo, EncodeBasis::closed(eo), phi_out, oob_fix, seconds);
 }
 
 int mpst_encode_split_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_split_opts* sp,
                              void* phi_out, double* oob_fix, double* seconds) {
-    return encode_values(ctx, X, N, T, d, eo, true, sp, phi_out, oob_fix, seconds);
+    return encode_values(ctx, X, N, T, d, eo, EncodeBasis::split(sp), phi_out, oob_fix, seconds);
 }
 
 int mpst_encode_kde_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                             int32_t C, mpst_encode_opts* eo, const mpst_kde_opts* kd, const int64_t* n_global_per_class, double* oob_fix,
                             double* seconds) {
-    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, FittedBasis::kde(kd));
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, EncodeBasis::kde(kd), n_global_per_class, oob_fix, seconds);
 }
 
 int mpst_encode_kde_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_kde_opts* kd,
                            void* phi_out, double* oob_fix, double* seconds) {
-    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, FittedBasis::kde(kd));
+    return encode_values(ctx, X, N, T, d, eo, EncodeBasis::kde(kd), phi_out, oob_fix, seconds);
 }
 
 int mpst_encode_proj_dataset(void* ctx, int which, const double* X, const int32_t* label_idx, int64_t N, int32_t T, int32_t d,
                              int32_t C, mpst_encode_opts* eo, const mpst_proj_opts* pj, const int64_t* n_global_per_class, double* oob_fix,
                              double* seconds) {
-    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, false, nullptr, n_global_per_class, oob_fix, seconds, FittedBasis::proj(pj));
+    return encode_dataset(ctx, which, X, label_idx, N, T, d, C, eo, EncodeBasis::proj(pj), n_global_per_class, oob_fix, seconds);
 }
 
 int mpst_encode_proj_values(void* ctx, const double* X, int64_t N, int32_t T, int32_t d, mpst_encode_opts* eo, const mpst_proj_opts* pj,
                             void* phi_out, double* oob_fix, double* seconds) {
-    return encode_values(ctx, X, N, T, d, eo, false, nullptr, phi_out, oob_fix, seconds, FittedBasis::proj(pj));
+    return encode_values(ctx, X, N, T, d, eo, EncodeBasis::proj(pj), phi_out, oob_fix, seconds);
 }
 
 int mpst_get_encoded(void* ctx, int which, double* phi_out) {

@@ -138,20 +138,21 @@ template <bool SCALE> __device__ __forceinline__ void enc_fourier(double x, int 
         outc[2 * k + 1] = enc_w<SCALE>(sn * inv, w);
     }
 }
+// P_k(x) by Bonnet's recursion from p1 = P_{k-1}(x) and p0 = P_{k-2}(x), which move on by one order
+__device__ __forceinline__ double bonnet_step(int k, double x, double& p0, double& p1) {
+    if (k == 0) return 1.0;
+    if (k == 1) return x;
+    const int m = k - 1;
+    const double p = ((2 * m + 1) * x * p1 - m * p0) / (m + 1);
+    p0 = p1;
+    p1 = p;
+    return p;
+}
 // Bonnet recursion, then sqrt((2k+1)/2) (normalised Legendre), then the optional 1/nrm (bases.jl:77-92)
 template <bool SCALE> __device__ __forceinline__ void enc_legendre(double x, int d, bool norm, double nrm, double w, double* out) {
     double p0 = 1.0, p1 = x;
     for (int k = 0; k < d; ++k) {
-        double p;
-        if (k == 0) p = 1.0;
-        else if (k == 1) p = x;
-        else {
-            const int m = k - 1;
-            p = ((2 * m + 1) * x * p1 - m * p0) / (m + 1);
-            p0 = p1;
-            p1 = p;
-        }
-        double v = p * sqrt((2.0 * k + 1.0) / 2.0);
+        double v = bonnet_step(k, x, p0, p1) * sqrt((2.0 * k + 1.0) / 2.0);
         if (norm) v = v / nrm;
         out[k] = enc_w<SCALE>(v, w);
     }
@@ -176,13 +177,31 @@ __device__ __forceinline__ double enc_value(const EncDev& e, const double* __res
     return (e.b - e.a) * x + e.a;
 }
 
-// one thread per (site, series); consecutive threads = consecutive series, so the d values every
-// thread writes are contiguous across the wave ([T][N][d] site-major, the sweep's layout)
-__global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+// The front end of the four encoding kernels: one thread per (site t, series i), idx = t N + i; consecutive threads = consecutive
+// series, so the values every thread writes are contiguous across the wave ([T][N][d] site-major, the sweep's layout).  x = enc_value
+// of (t, i).  Not live: the thread has nothing to evaluate - it lies past the last value or, KIND = KDE, at a site whose coefficients
+// are all zero: its d zeros are written here and none of the site's tables, its value included, is read
+struct EncAt {
+    int64_t idx, t, i;
+    double x;
+    bool live;
+};
+template <int KIND> __device__ __forceinline__ EncAt enc_at(const EncDev& e, const double* __restrict__ X, double* __restrict__ phi) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= e.N * e.T) return;
+    if (idx >= e.N * e.T) return {idx, 0, 0, 0.0, false};
     const int64_t t = idx / e.N, i = idx - t * e.N;
-    const double x = enc_value(e, X, t, i);
+    if constexpr (KIND == EncodeBasis::KDE) {
+        if (e.kde_zero[e.kde_per_site ? t : 0]) {
+            for (int n = 0; n < e.d; ++n) phi[idx * e.d + n] = 0.0;
+            return {idx, t, i, 0.0, false};
+        }
+    }
+    return {idx, t, i, enc_value(e, X, t, i), true};
+}
+
+__global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
+    const auto [idx, t, i, x, live] = enc_at<EncodeBasis::CLOSED>(e, X, phi);
+    if (!live) return;
     enc_basis<false>(e.basis, x, e.d, e.nrm, 1.0, phi + idx * e.d * (e.fourier ? 2 : 1));
 }
 
@@ -192,10 +211,8 @@ __global__ __launch_bounds__(256) void k_encode(EncDev e, const double* __restri
 // edge, both neighbours at 0.5 -, the auxiliary basis is evaluated at a + x_prop in selected bins only, the others are zeroed.
 // An empty bin (dx = 0) gives x_prop = +-inf or NaN, which every comparison rejects, as on the host.
 __global__ __launch_bounds__(256) void k_encode_split(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= e.N * e.T) return;
-    const int64_t t = idx / e.N, i = idx - t * e.N;
-    const double x = enc_value(e, X, t, i);
+    const auto [idx, t, i, x, live] = enc_at<EncodeBasis::SPLIT>(e, X, phi);
+    if (!live) return;
     const double* __restrict__ bins = e.bins + t * e.bin_stride;
     const int nb = e.nbins, w = e.aux_dim * (e.fourier ? 2 : 1);       // doubles per bin
     double* out = phi + idx * nb * w;
@@ -221,17 +238,11 @@ __global__ __launch_bounds__(256) void k_encode_split(EncDev e, const double* __
 // The spline index is clamped to 1 .. K, so the three reads stay inside the K + 2 coefficients whatever x is.  A site whose
 // coefficients are all zero (nothing to fit there) writes zeros and reads none of its tables.
 __global__ __launch_bounds__(256) void k_encode_kde(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= e.N * e.T) return;
-    const int64_t t = idx / e.N, i = idx - t * e.N;
+    const auto [idx, t, i, x, live] = enc_at<EncodeBasis::KDE>(e, X, phi);
+    if (!live) return;
     const int64_t s = e.kde_per_site ? t : 0;
     const int d = e.d;
     double* out = phi + idx * d;
-    if (e.kde_zero[s]) {
-        for (int n = 0; n < d; ++n) out[n] = 0.0;
-        return;
-    }
-    const double x = enc_value(e, X, t, i);
     const int K = e.kde_npoints;
     const double lo = e.kde_lo[s], step = e.kde_step[s];
     double p = 0.0;
@@ -264,10 +275,8 @@ __global__ __launch_bounds__(256) void k_encode_kde(EncDev e, const double* __re
 // Bounds: q runs over 0 .. d-1, so the reads stay inside the site's 2 d entries; the slots are a permutation of 0 .. d-1 and the
 // orders are within 0 .. 7 * 16 (the host built and checked both); x enters no index, so a NaN value only gives NaN states.
 __global__ __launch_bounds__(256) void k_encode_proj(EncDev e, const double* __restrict__ X, double* __restrict__ phi) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= e.N * e.T) return;
-    const int64_t t = idx / e.N, i = idx - t * e.N;
-    const double x = enc_value(e, X, t, i);
+    const auto [idx, t, i, x, live] = enc_at<EncodeBasis::PROJ>(e, X, phi);
+    if (!live) return;
     const int d = e.d;
     const int32_t* __restrict__ ord = e.proj_tab + t * 2 * d;
     const int32_t* __restrict__ slot = ord + d;
@@ -288,17 +297,9 @@ __global__ __launch_bounds__(256) void k_encode_proj(EncDev e, const double* __r
     double p0 = 1.0, p1 = x;
     int q = 0;
     for (int k = 0; k <= last; ++k) {
-        double p;
-        if (k == 0) p = 1.0;
-        else if (k == 1) p = x;
-        else {
-            const int m = k - 1;
-            p = ((2 * m + 1) * x * p1 - m * p0) / (m + 1);
-            p0 = p1;
-            p1 = p;
-        }
+        const double pk = bonnet_step(k, x, p0, p1);
         if (ord[q] != k) continue;
-        double v = p * sqrt((2.0 * k + 1.0) / 2.0);
+        double v = pk * sqrt((2.0 * k + 1.0) / 2.0);
         if (e.proj_inv) v = v * inv;
         for (; q < d && ord[q] == k; ++q) out[slot[q]] = v;
         if (q == d) break;
@@ -345,10 +346,12 @@ void launch_encode(const EncDev& e, const double* X, double* phi, double* part, 
     }
     if (fix) hipLaunchKernelGGL(k_enc_series_fix, dim3((unsigned)((e.N + 3) / 4)), dim3(256), 0, s, e, X, fix);
     const dim3 grid((unsigned)((e.N * e.T + 255) / 256));
-    if (e.proj_tab) hipLaunchKernelGGL(k_encode_proj, grid, dim3(256), 0, s, e, X, phi);
-    else if (e.kde_coef) hipLaunchKernelGGL(k_encode_kde, grid, dim3(256), 0, s, e, X, phi);
-    else if (e.bins) hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi);
-    else hipLaunchKernelGGL(k_encode, grid, dim3(256), 0, s, e, X, phi);
+    switch (e.kind) {
+        case EncodeBasis::PROJ: hipLaunchKernelGGL(k_encode_proj, grid, dim3(256), 0, s, e, X, phi); break;
+        case EncodeBasis::KDE: hipLaunchKernelGGL(k_encode_kde, grid, dim3(256), 0, s, e, X, phi); break;
+        case EncodeBasis::SPLIT: hipLaunchKernelGGL(k_encode_split, grid, dim3(256), 0, s, e, X, phi); break;
+        default: hipLaunchKernelGGL(k_encode, grid, dim3(256), 0, s, e, X, phi);
+    }
 }
 
 }  // namespace mpst

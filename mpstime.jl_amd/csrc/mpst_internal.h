@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/mpstime_hip.h"
 #include "mpst_dataset_plan.h"
+#include "mpst_encode_plan.h"
 #include "mpst_query_plan.h"
 
 namespace mpst {
@@ -651,30 +652,32 @@ void launch_split(const View& v, int lid, int going_left, hipStream_t s);
 enum { ENV_M_E = 0, ENV_M_SITE = 1, ENV_M_SITE_T = 2 };
 void launch_env(const View& v, int site, int left_side, const double* prev, int prev_bond,
                 int mode, int out_bond, double* out, hipStream_t s, int bt_lid = -1);   // bt_lid: also assemble that bond's tensor
-// device-side preprocessing + encoding (mpst_encode.hip)
+// device-side preprocessing + encoding (mpst_encode.hip).  The table pointers lie inside the call's two uploads (EncodeTables,
+// mpst_encode_plan.h); those of another kind are null
 struct EncDev {
     int64_t N;
     int32_t T, d;
-    int32_t norm, sigmoid, minmax, is_test;
+    int32_t kind;           // EncodeBasis::Kind: which of k_encode / k_encode_split / k_encode_kde / k_encode_proj runs
+    int32_t sigmoid, minmax;
     int32_t fourier;        // 1: complex basis (Fourier, Stoudenmire, Sahand), phi holds (re, im) pairs
-    int32_t basis;          // MPST_BASIS_*
+    int32_t basis;          // MPST_BASIS_* the kernel evaluates (EncodeBasis::family)
     double med, s;          // robust sigmoid: 1 / (1 + exp(-(x - med) / s)), s = iqr / 1.35
     double lb, ub, a, b;    // data_bounds and the basis' input range
     double nrm;             // legendre: sqrt(Pl(1, d; normalized) * d)
     const double* lohi;     // device [2] min, max of the (sigmoid-transformed) training data
     const double* fix;      // device [N][2] per-series (shift, scale) of the out-of-bounds rescale, or null
-    // split bases (k_encode_split; bins == null: k_encode): `basis` is the auxiliary basis, nrm its Legendre norm, d = nbins * aux_dim
-    const double* bins;     // device [T][nbins + 1] edges (bin_stride = nbins + 1) or [nbins + 1] shared by all sites (bin_stride = 0)
+    // SPLIT: `basis` is the auxiliary basis, nrm its Legendre norm, d = nbins * aux_dim
+    const double* bins;     // [T][nbins + 1] edges (bin_stride = nbins + 1) or [nbins + 1] shared by all sites (bin_stride = 0)
     int64_t bin_stride;
     int32_t nbins, aux_dim;
-    // Sahand-Legendre bases (k_encode_kde; kde_coef == null: the kernels above): the tables of site t start at index t * kde_per_site
-    const double *kde_lo, *kde_step, *kde_coef;       // device [S], [S], [S][kde_npoints + 2]: the density's grid and spline coefficients
-    const double *kde_minx, *kde_scale, *kde_cvecs;   // device [S], [S], [S][d][d]
-    const int32_t* kde_zero;                          // device [S]: 1 where the site's coefficients are all zero
+    // KDE: the tables of site t start at index t * kde_per_site
+    const double *kde_lo, *kde_step, *kde_coef;       // [S], [S], [S][kde_npoints + 2]: the density's grid and spline coefficients
+    const double *kde_minx, *kde_scale, *kde_cvecs;   // [S], [S], [S][d][d]
+    const int32_t* kde_zero;                          // [S]: 1 where the site's coefficients are all zero
     int32_t kde_npoints, kde_per_site;
-    // projected bases (k_encode_proj; proj_tab == null: the kernels above): `basis` is the family
-    const int32_t* proj_tab;                          // device [T][2 d]: the site's d orders in ascending order, then the slot of each
-    const double* proj_inv;                           // device [T]: 1 / norm of the site (MPST_BASIS_LEGENDRE), or null
+    // PROJ: `basis` is the family
+    const int32_t* proj_tab;                          // [T][2 d]: the site's d orders in ascending order, then the slot of each
+    const double* proj_inv;                           // [T]: 1 / norm of the site (MPST_BASIS_LEGENDRE), or null
 };
 size_t order_stats_temp_bytes(int64_t n);
 hipError_t launch_order_stats(const double* X, double* sorted, void* temp, size_t temp_bytes, int64_t n, double* out3, hipStream_t s);

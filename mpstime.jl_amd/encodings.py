@@ -838,6 +838,18 @@ class FittedEncoder:
         inv = projected_legendre_inv_norm(orders) if basis == "Legendre_Norm" else np.ones(len(orders))
         return dict(basis=basis, orders=np.ascontiguousarray(orders, dtype=np.int32), inv_norm=np.ascontiguousarray(inv, dtype=np.float64))
 
+    def device_kwargs(self):
+        """the keyword argument SweepEngine.encode_dataset / encode_values take this encoding's fitted tables by: {} for an encoding
+        without any (the closed-form bases), else its ``bins``, ``kde`` or ``orders`` under that name; None for a fitted encoding the
+        device does not encode"""
+        if self.enc.init is None:
+            return {}
+        for key in ("bins", "kde", "orders"):
+            tables = getattr(self, key)
+            if tables is not None:
+                return {key: tables}
+        return None
+
 
 def fit_encoding(enc: Encoding, X_norm, y, opts: MPSOptions):
     """The fit step of encode_safe_dataset (encodings.jl:129-132): ``(encoding_args, encoder)``.  ``X_norm`` is the training

@@ -97,24 +97,6 @@ def _dtype_of(x):
     return dt if dt in DTYPES else np.dtype(np.float64)
 
 
-def _device_basis(basis):
-    """(closed-form basis name - of the auxiliary basis for a split encoding -, its input range, is split) of what encode_dataset /
-    encode_values were handed: a name or an Encoding.  Raises MPSTError(UNSUPPORTED) for what the device does not encode."""
-    from .encodings import Encoding, model_encoding
-    rng, split = (-1.0, 1.0), False
-    try:
-        enc = basis if isinstance(basis, Encoding) else model_encoding(basis)
-        split = enc.aux_enc is not None
-        # canonical name; :Legendre is :Legendre_No_Norm (options.jl:245-246)
-        basis, rng = (enc.aux_enc.name if split else enc.name), (enc.range or rng)
-    except Exception:
-        pass
-    if basis not in L.BASIS:
-        raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, split bases over them and - "
-                                                  f"with kde= / orders=, their fitted encoder - the Sahand-Legendre and the projected bases, not {basis!r}")
-    return basis, rng, split
-
-
 def _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds):
     """mpst_encode_opts of a training set (``norms`` None: nothing fitted yet, fit_sigmoid left to the caller) or of a test set with
     the training fit's ``norms``."""
@@ -163,12 +145,6 @@ def _kde_opts(kde, d, T):
     return kd, arr
 
 
-def _kde_basis(basis, kde):
-    """what _device_basis returns, for a call with ``kde`` tables: eo.basis is ignored, the range is the encoding's"""
-    from .encodings import Encoding
-    return "Legendre_No_Norm", (tuple(basis.range) if isinstance(basis, Encoding) and basis.range else (-1.0, 1.0)), False
-
-
 def _proj_opts(orders, d, T):
     """mpst_proj_opts of a fitted projected encoding - ``orders`` is its FittedEncoder (``fit_encoding(...)[1]``) or that encoder's
     ``orders`` tables - and the arrays the struct points into (keep them alive over the call).  The shapes are checked here: the
@@ -190,16 +166,39 @@ def _proj_opts(orders, d, T):
     return pj, (o, inv)
 
 
-def _fitted_basis(basis, kde, orders):
-    """what _device_basis returns, for a call with ``kde`` or ``orders`` tables, which exclude each other"""
+COMPLEX_BASES = ("Fourier", "Stoudenmire", "Sahand")     # the closed-form bases whose states are complex
+
+
+def _basis_request(basis, d, T, bins=None, kde=None, orders=None):
+    """What encode_dataset / encode_values were handed - a name or an Encoding and, for a fitted encoding, its tables - as the library
+    takes it: (canonical name of the closed-form basis the kernel evaluates - the auxiliary basis of a split encoding, the family of a
+    projected one; a Sahand-Legendre call ignores it -, its input range, whether the states are complex, the infix of the entry points
+    mpst_encode_<infix>dataset / mpst_encode_<infix>values, (the options struct they take after eo or None, the arrays it points into:
+    keep them alive over the call)).  Raises MPSTError(UNSUPPORTED) for what the device does not encode."""
+    from .encodings import Encoding, model_encoding
     if kde is not None and orders is not None:
         raise ValueError("kde= and orders= belong to different encodings: pass one of them")
-    if kde is not None:
-        return _kde_basis(basis, kde)
-    tab = getattr(orders, "orders", orders)
-    if not isinstance(tab, dict) or tab.get("basis") not in ("Legendre_Norm", "Legendre_No_Norm", "Fourier"):
-        raise ValueError("a projected encoding is encoded with the orders its fit selected: pass orders (fit_encoding(...)[1])")
-    return (tab["basis"],) + _kde_basis(basis, orders)[1:]              # the family decides real / complex; eo.basis itself is ignored
+    rng = (-1.0, 1.0)
+    if kde is not None or orders is not None:
+        rng = tuple(basis.range) if isinstance(basis, Encoding) and basis.range else rng
+        if kde is not None:
+            return "Legendre_No_Norm", rng, False, "kde_", _kde_opts(kde, d, T)
+        tab = getattr(orders, "orders", orders)
+        if not isinstance(tab, dict) or tab.get("basis") not in ("Legendre_Norm", "Legendre_No_Norm", "Fourier"):
+            raise ValueError("a projected encoding is encoded with the orders its fit selected: pass orders (fit_encoding(...)[1])")
+        return tab["basis"], rng, tab["basis"] in COMPLEX_BASES, "proj_", _proj_opts(orders, d, T)
+    split = False
+    try:
+        enc = basis if isinstance(basis, Encoding) else model_encoding(basis)
+        split = enc.aux_enc is not None
+        # canonical name; :Legendre is :Legendre_No_Norm (options.jl:245-246)
+        basis, rng = (enc.aux_enc.name if split else enc.name), (enc.range or rng)
+    except Exception:
+        pass
+    if basis not in L.BASIS:
+        raise L.MPSTError(L.MPST_ERR_UNSUPPORTED, f"device-side encoding implements the closed-form bases {sorted(L.BASIS)}, split bases over them and - "
+                                                  f"with kde= / orders=, their fitted encoder - the Sahand-Legendre and the projected bases, not {basis!r}")
+    return basis, rng, basis in COMPLEX_BASES, "split_" if split else "", _split_opts(basis, d, T, bins) if split else (None, None)
 
 
 class SweepEngine:
@@ -285,11 +284,11 @@ class SweepEngine:
         with ``kde``, its fitted encoder (``fit_encoding(...)[1]``); a projected encoding through mpst_encode_proj_dataset with
         ``orders``, its fitted encoder or that encoder's ``orders`` tables."""
         from .encodings import Norms
-        basis, _, split = _device_basis(basis) if kde is None and orders is None else _fitted_basis(basis, kde, orders)
         X = np.ascontiguousarray(X_sorted, dtype=np.float64)
         lab = np.ascontiguousarray(label_index, dtype=np.int32)
         N, T = X.shape
         d = int(d if d is not None else self.d)
+        basis, _, cx, infix, (bopts, _keep) = _basis_request(basis, d, T, bins, kde, orders)
         eo = _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds)
         if norms is None and sigmoid_transform:
             if sigmoid_fit is not None:                 # (median, iqr) fitted elsewhere, e.g. over all shards
@@ -303,20 +302,11 @@ class SweepEngine:
         head = (self.ctx, which, X.ctypes.data_as(dp), lab.ctypes.data_as(C.POINTER(C.c_int32)), N, T, d, int(C_classes), C.byref(eo))
         tail = (gc.ctypes.data_as(C.POINTER(C.c_int64)) if gc is not None else None, fix.ctypes.data_as(dp) if fix is not None else None,
                 C.byref(sec))
-        if kde is not None:
-            kd, _keep = _kde_opts(kde, d, T)
-            self._chk(self.lib.mpst_encode_kde_dataset(*head, C.byref(kd), *tail))
-        elif orders is not None:
-            pj, _keep = _proj_opts(orders, d, T)
-            self._chk(self.lib.mpst_encode_proj_dataset(*head, C.byref(pj), *tail))
-        elif split:
-            sp, _keep = _split_opts(basis, d, T, bins)
-            self._chk(self.lib.mpst_encode_split_dataset(*head, C.byref(sp), *tail))
-        else:
-            self._chk(self.lib.mpst_encode_dataset(*head, *tail))
+        own = () if bopts is None else (C.byref(bopts),)
+        self._chk(getattr(self.lib, f"mpst_encode_{infix}dataset")(*head, *own, *tail))
         self.T, self.d, self.C = T, d, int(C_classes)
         self.N[which] = N
-        self.dtype = self._ctx_dtype(basis)
+        self.dtype = self._ctx_dtype(cx)
         if norms is None:
             out = Norms(sigmoid=(eo.median, eo.iqr) if sigmoid_transform else None, minmax=(eo.lo, eo.hi) if minmax else None)
             return out, sec.value
@@ -332,34 +322,23 @@ class SweepEngine:
         A split encoding with its fitted ``bins`` goes through mpst_encode_split_values, a Sahand-Legendre encoding with its fitted
         encoder ``kde`` through mpst_encode_kde_values, a projected encoding with its fitted encoder ``orders`` through
         mpst_encode_proj_values (complex128 for projected Fourier), as in encode_dataset."""
-        basis, basis_range, split = _device_basis(basis) if kde is None and orders is None else _fitted_basis(basis, kde, orders)
         X = np.ascontiguousarray(X, dtype=np.float64)
         N, T = X.shape
+        basis, basis_range, cx, infix, (bopts, _keep) = _basis_request(basis, int(d), T, bins, kde, orders)
         if enc_range is None:
             enc_range = basis_range if (sigmoid_transform or minmax or norms is not None) else (0.0, 1.0)
         eo = _encode_opts(basis, sigmoid_transform, minmax, data_bounds, enc_range, norms, rescale_out_of_bounds)
         if norms is None:
             eo.fit_sigmoid = int(bool(sigmoid_transform))
-        cx = basis in ("Fourier", "Stoudenmire", "Sahand")
         out = np.zeros((N, T, int(d)), dtype=np.complex128 if cx else np.float64)
         sec = C.c_double()
-        head = (self.ctx, X.ctypes.data_as(C.POINTER(C.c_double)), N, T, int(d), C.byref(eo))
-        if kde is not None:
-            kd, _keep = _kde_opts(kde, int(d), T)
-            self._chk(self.lib.mpst_encode_kde_values(*head, C.byref(kd), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
-        elif orders is not None:
-            pj, _keep = _proj_opts(orders, int(d), T)
-            self._chk(self.lib.mpst_encode_proj_values(*head, C.byref(pj), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
-        elif split:
-            sp, _keep = _split_opts(basis, int(d), T, bins)
-            self._chk(self.lib.mpst_encode_split_values(*head, C.byref(sp), out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
-        else:
-            self._chk(self.lib.mpst_encode_values(*head, out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
+        own = () if bopts is None else (C.byref(bopts),)
+        self._chk(getattr(self.lib, f"mpst_encode_{infix}values")(self.ctx, X.ctypes.data_as(C.POINTER(C.c_double)), N, T, int(d), C.byref(eo), *own,
+                                                                 out.ctypes.data_as(C.c_void_p), None, C.byref(sec)))
         return out, sec.value
 
-    def _ctx_dtype(self, basis):
+    def _ctx_dtype(self, cx):
         """element type after a device-side encoding: what set_dtype fixed, else the basis' own (float64 / complex128)"""
-        cx = basis in ("Fourier", "Stoudenmire", "Sahand")
         if getattr(self, "_dtype_fixed", False):
             return self.dtype
         return np.dtype(np.complex128 if cx else np.float64)

@@ -273,15 +273,11 @@ def _fit_device_encoded(W, X_train, y_train, X_test, y_test, opts, enc, class_ke
             # the one fit of the encoding's arguments: on the host, from the training matrix through the host transform
             # (encodings.jl:130-131); the device encodes both data sets with these bins
             _, encoder = fit_encoding(enc, transform_train_data(Xs, opts, enc.range)[0], ys, opts)
-            if encoder.bins is not None:
-                common.update(basis=enc, bins=encoder.bins)
-            elif encoder.kde is not None:
-                common.update(basis=enc, kde=encoder)
-            elif encoder.orders is not None:
-                common.update(basis=enc, orders=encoder)
-            else:
+            tables = encoder.device_kwargs()
+            if tables is None:
                 raise NotImplementedError(f"device_encode with the data-driven encoding {enc.name}: only split bases, the "
                                           "Sahand-Legendre bases and the projected bases are encoded on the device")
+            common.update(basis=enc, **tables)
         norms, _ = eng.encode_dataset(0, Xs, li, C, **common)
         train_states = EncodedTimeSeriesSet(eng.get_encoded(0), ys, li, Xs, counts)
         test_states = EncodedTimeSeriesSet.empty()
