@@ -621,7 +621,8 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
  * [1] the sweep with the densities and selections (k_imp_left).  After mpst_site_conditionals: (walk, grid phase); after
  * mpst_window_conditionals: (walk, window kernel); after mpst_marginal_conditionals: (walk, grid phase); after
  * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel); after
- * mpst_prefix_marginals: (environment kernel k_prefix_env, walk-and-score kernel k_prefix_score). */
+ * mpst_prefix_marginals: (environment kernel k_prefix_env, walk-and-score kernel k_prefix_score); after mpst_segment_marginals: (the two
+ * table kernels k_segment_left and k_prefix_env, the walk kernel k_segment_walk). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid
@@ -629,7 +630,8 @@ int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
  * out[1] = 1 when the sweep over the sites (impute_at!, src/Imputation/MPS_methods.jl:103-177) ran for sixteen instances per
  * workgroup (closed-form densities and panels that fit the LDS; otherwise one instance per workgroup - same results);
  * out[2] = the workgroups of the environment pass (one per instance, whatever the number of trajectories), out[3] = the chains
- * (instance, trajectory) the sweep ran for. */
+ * (instance, trajectory) the sweep ran for.  After mpst_segment_marginals: out[0] = out[1] = 0, out[2] = the blocks of series its walk
+ * kernel was launched for, out[3] = the (series, start) items it walked. */
 int  mpst_get_impute_info(void* ctx, int32_t* out, int32_t n);
 
 int  mpst_normalize(void* ctx);
@@ -732,6 +734,32 @@ int  mpst_get_tail_phases(void* ctx, double* us /*[55]*/);
  * d > 16, C > 16; MPST_ERR_NOMEM: the (label_site + 1) C + (T - label_site) tables of chi_max^2 elements do not fit the query budget - they
  * are not cut over t.  A rejected call leaves the context as it was. */
 int  mpst_prefix_marginals(void* ctx, const mpst_impute_model* m, double* logp_out /* [N][T+1][C] */, double* seconds /* may be NULL */);
+
+/* Segment marginals: for every series i, every class c, every start a and every width w = 1 .. max_width with a + w <= T the log
+ * likelihood of the values of the sites a .. a+w-1 ALONE, every other site summed out - what mpst_marginal_model gives for the mask that
+ * is set everywhere but on the segment:
+ *     logp_out[i][a][w-1][c] = ln l_c(i; a, w),   l_c(i; a, w) = Re sum_xy E[x][y] G_c^{a+w}[x][y],
+ * E the walk from the table entry L^a through the known sites a .. a+w-1, E <- M_j^T E conj(M_j), M_j = sum_q conj(phi[i][j][q])
+ * W_j[:, q, :]; L^t the density recursion of mpst_marginal_model from the left end through the sites 0 .. t-1 and G^t the one from the
+ * right end through T-1 .. t, all of them missing.  Both tables depend on the model only and are computed once per call; a series costs
+ * T * max_width known-site steps, whatever T - w is.
+ *   m           as in mpst_marginal_model: the label slice of the model AS STORED; label_idx is not read, all of phi is; real and complex
+ *               models, compute MPST_COMPUTE_F64
+ *   max_width   1 .. T
+ *   logp_out[N][T][max_width][C]   entries with a + w > T are NaN.  An entry is -INFINITY where a closing form or the trace of a step is
+ *               not a positive finite number, and so is every wider entry of that start: for all classes while the walk is left of the
+ *               label site, for the class at hand from the label site on.  A table chain that vanishes gives -INFINITY wherever it is
+ *               needed.  Never NaN inside the triangle for finite input.
+ *   lnorm_out[C]   ln ||W_c||^2, what subtracting gives the likelihood under the normalised class state; may be NULL
+ * seconds (may be NULL): device time of the call; mpst_get_impute_phases then returns (table kernels, walk kernel).  The result of a
+ * (series, start) pair depends neither on how the series are cut into blocks (free device memory, MPST_IMPUTE_CHUNK_GB) nor on what
+ * travels along: no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: NULL m / logp_out, max_width outside 1..T, a malformed model; MPST_ERR_UNSUPPORTED: compute other than
+ * MPST_COMPUTE_F64, chi_max > 128, d > 16, C > 16; MPST_ERR_NOMEM: the (T + 1)(C + 1) tables of chi_max^2 elements (and beyond the LDS
+ * limit the scratch of the walk's resident workgroups) do not fit the query budget - they are not cut.  A rejected call leaves the
+ * context as it was. */
+int  mpst_segment_marginals(void* ctx, const mpst_impute_model* m, int32_t max_width, double* logp_out /* [N][T][max_width][C] */,
+                            double* lnorm_out /* [C], may be NULL */, double* seconds /* may be NULL */);
 
 #ifdef __cplusplus
 }

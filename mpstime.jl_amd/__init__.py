@@ -26,6 +26,8 @@ from .conditionals import (SiteConditionals, site_conditionals, anomaly_scores, 
 from .overlaps import ModelOverlaps, model_overlaps, class_overlaps
 from .prefix import (EarlyClassification, prefix_log_marginals, prefix_posteriors, classify_early, early_accuracy_curve,
                      causal_scores)
+from .segments import (BestSegment, segment_log_marginals, segment_posteriors, classify_segment, segment_evidence,
+                       most_discriminative_segment, segment_accuracy_map)
 from .summary import get_training_summary, training_stats, sweep_summary, print_opts
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
                      BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
@@ -44,7 +46,8 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "window_conditionals_model", "window_anomaly_scores", "MarginalConditionals", "marginal_conditionals", "marginal_conditionals_model",
            "impute_marginal", "forecast",
            "ModelOverlaps", "model_overlaps", "class_overlaps", "EarlyClassification", "prefix_log_marginals", "prefix_posteriors",
-           "classify_early", "early_accuracy_curve", "causal_scores", "get_training_summary", "training_stats", "sweep_summary", "print_opts",
+           "classify_early", "early_accuracy_curve", "causal_scores", "BestSegment", "segment_log_marginals", "segment_posteriors", "classify_segment",
+           "segment_evidence", "most_discriminative_segment", "segment_accuracy_map", "get_training_summary", "training_stats", "sweep_summary", "print_opts",
            "sahand_legendre", "sahand_legendre_encode", "UnivariateKDE", "kde", "kde_pdf",
            "legendre", "legendre_no_norm", "fourier", "series_expand", "construct_kerneldensity_wavefunction", "project_legendre", "project_fourier",
            "projected_legendre_encode", "projected_legendre_encode_no_norm", "projected_fourier_encode"]

@@ -17,6 +17,7 @@
 #include "mpst_batch_groups.h"
 #include "mpst_bond_plan.h"
 #include "mpst_prefix_plan.h"
+#include "mpst_segment_plan.h"
 
 using namespace mpst;
 
@@ -2791,6 +2792,71 @@ static int run_prefix(Ctx* c, const ImpModel& m, const PrefixRequest& r) {
     }, PrefixHooks{c, r, lp, (T + 1) * Cn});
 }
 
+// One mpst_segment_marginals call
+struct SegmentRequest {
+    int32_t C, label_site, max_width;
+    double *logp_out, *lnorm_out, *seconds;
+};
+// what a segment call does around its blocks: a block's results are its own on the device and go to the caller's array after its walk,
+// outside the phases
+struct SegmentHooks {
+    Ctx* c; double* host_logp; double* dev_logp; int64_t per;           // per: doubles of one instance, T * max_width * C
+    bool own_begin() const { return true; }
+    int prepare() { return 0; }
+    int before(int64_t, int64_t) { return 0; }
+    int after(int64_t i0, int64_t cnt) {
+        HIPC(c, hipMemcpyAsync(host_logp + (size_t)(i0 * per), dev_logp, (size_t)(cnt * per) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+// The segment marginals of a request: the L and G tables of the model and the scratch of the walk's resident workgroups live for the
+// whole call and must fit the budget as they are; a block of instances brings only its own results (mpst_segment_plan.h: segment_plan).
+// The phases are the two table kernels, which the first block launches ahead of its walk, and the walk.  The context's launch figures
+// (mpst_get_impute_info) become (0, 0, blocks of the walk, (series, start) items).
+constexpr int SEGMENT_MAX_CLASSES = 16;
+static int run_segment(Ctx* c, const ImpModel& m, const SegmentRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1, Cn = r.C;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc, cus = 0;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    const bool big = prefix_big_route(m.cap, m.is_complex != 0);
+    const SegmentPlan p = segment_plan(N, m.T, Cn, r.label_site, m.cap, zw, r.max_width, big, cus, free_b, chunk_gb_override());
+    if (p.nomem)
+        return fail(c, MPST_ERR_NOMEM, "the %lld tables of the model and the walk's scratch need %.3f GB of device memory, the budget of a query is "
+                    "%.3f GB: they are not cut", (long long)p.mats, (double)p.table_bytes / (double)(1ull << 30),
+                    query_budget(free_b, chunk_gb_override()) / (double)(1ull << 30));
+    const int64_t mat = (int64_t)m.cap * m.cap * zw;
+    DevBuf<double> L, G, lnL, lnG, wl, wr, work, lp;
+    if ((rc = dalloc(c, L, segment_left_mats(m.T, Cn, r.label_site) * mat)) || (rc = dalloc(c, G, prefix_table_mats(m.T, Cn, r.label_site) * mat)) ||
+        (rc = dalloc(c, lnL, (T + 1) * Cn)) || (rc = dalloc(c, lnG, (T + 1) * Cn)) ||
+        (big && ((rc = dalloc(c, wl, (int64_t)Cn * PREFIX_ENV_BIG_MATS * mat)) || (rc = dalloc(c, wr, (int64_t)Cn * PREFIX_ENV_BIG_MATS * mat)) ||
+                 (rc = dalloc(c, work, p.walk_wgs * SEGMENT_BIG_MATS * mat)))) ||
+        (rc = dalloc(c, lp, p.chunk * T * r.max_width * Cn))) return rc;
+    SegmentArgs g{};
+    g.L = L, g.lnL = lnL, g.G = G, g.lnG = lnG, g.work_left = wl, g.work_right = wr, g.work = work, g.logp = lp;
+    g.C = Cn, g.max_width = r.max_width;
+    int blocks = 0;
+    rc = run_blocks(c, N, p.chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        if (blocks == 0 && launch_segment_tables(m, g, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the segment table kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        ++blocks;
+        HIPC(c, hipEventRecord(mid, c->stream));
+        if (launch_segment_walk(m, g, p.walk_wgs, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the segment walk did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, SegmentHooks{c, r.logp_out, lp, T * r.max_width * Cn});
+    if (rc) return rc;
+    c->impute_trig = c->impute_batched = 0;
+    c->impute_env_wgs = blocks;
+    c->impute_chains = (int)std::min<int64_t>(N * T, INT32_MAX);
+    if (r.lnorm_out) HIPC(c, hipMemcpy(r.lnorm_out, lnG, (size_t)Cn * sizeof(double), hipMemcpyDeviceToHost));      // lnG[0][c] = ln ||W_c||^2
+    return 0;
+}
+
 // One mpst_marginal_conditionals call: the mask and the values (either may be NULL), the grid, and the six outputs, each of which may be NULL
 struct MargcondRequest {
     const mpst_sitecond_opts* o;
@@ -3133,6 +3199,23 @@ int mpst_prefix_marginals(void* ctx, const mpst_impute_model* h, double* logp_ou
     DevModel dm;
     if ((rc = upload_model(c, h, cap, false, &dm))) return rc;
     return run_prefix(c, dm.view, PrefixRequest{h->C, h->label_site, logp_out, seconds});
+}
+
+int mpst_segment_marginals(void* ctx, const mpst_impute_model* h, int32_t max_width, double* logp_out, double* lnorm_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !logp_out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    int cap = 0, rc;
+    if ((rc = check_model_shape(c, h, true, false, &cap))) return rc;
+    if (max_width < 1 || max_width > h->T) return fail(c, MPST_ERR_INVALID, "max_width must lie in 1 .. T = %d (got %d)", (int)h->T, (int)max_width);
+    if (h->compute != MPST_COMPUTE_F64) return fail(c, MPST_ERR_UNSUPPORTED, "segment marginals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if ((rc = check_model_types(c, h, false))) return rc;
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > SEGMENT_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "segment marginals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT, SEGMENT_MAX_CLASSES,
+                    cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, false, &dm))) return rc;
+    return run_segment(c, dm.view, SegmentRequest{h->C, h->label_site, max_width, logp_out, lnorm_out, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

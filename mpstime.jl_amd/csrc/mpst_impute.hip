@@ -33,6 +33,7 @@
 // chi = 64 (complex fp64: 48); beyond that k_imp_right_big works out of global scratch.
 #include "mpst_internal.h"
 #include "mpst_prefix_plan.h"
+#include "mpst_segment_plan.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1721,6 +1722,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_window.inl"
 #include "mpst_margcond.inl"
 #include "mpst_prefix.inl"
+#include "mpst_segment.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -1862,6 +1864,16 @@ hipError_t impute_init_attrs(int device) {
                                              (int)prefix_env_lds_bytes(impute_lds_chi_limit(false, false), false)),
                          hipFuncSetAttribute((const void*)k_prefix_env<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)prefix_env_lds_bytes(impute_lds_chi_limit(true, false), true))})
+        if (e != hipSuccess) return e;
+    // segment marginals: the left table keeps the prefix recursion's three matrices, the walk the environment pass's four
+    for (hipError_t e : {hipFuncSetAttribute((const void*)k_segment_left<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)prefix_env_lds_bytes(impute_lds_chi_limit(false, false), false)),
+                         hipFuncSetAttribute((const void*)k_segment_left<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)prefix_env_lds_bytes(impute_lds_chi_limit(true, false), true)),
+                         hipFuncSetAttribute((const void*)k_segment_walk<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(false, false), false, false)),
+                         hipFuncSetAttribute((const void*)k_segment_walk<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(true, false), true, false))})
         if (e != hipSuccess) return e;
     if (device >= 0 && device < 64) done.fetch_or(1ull << device, std::memory_order_release);
     return hipSuccess;
@@ -2026,6 +2038,38 @@ int launch_prefix_score(const ImpModel& v, const PrefixArgs& g, hipStream_t s) {
     const dim3 grid((unsigned)((g.count + SC_B - 1) / SC_B));
     if (v.is_complex) hipLaunchKernelGGL((k_prefix_score<true>), grid, dim3(SC_T), 0, s, v, g);
     else hipLaunchKernelGGL((k_prefix_score<false>), grid, dim3(SC_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// segment marginals: the left table (k_segment_left) and the right one (k_prefix_env as it is, on a PrefixArgs of this call), a
+// workgroup per class each
+int launch_segment_tables(const ImpModel& v, const SegmentArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)g.C);
+    const bool big = prefix_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : prefix_env_lds_bytes(v.cap, v.is_complex != 0);
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_segment_left<true, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_segment_left<true, false>), grid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_segment_left<false, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_segment_left<false, false>), grid, dim3(IMP_T), lds, s, v, g);
+    }
+    if (hipGetLastError() != hipSuccess) return -1;
+    PrefixArgs p{};
+    p.G = g.G, p.lnG = g.lnG, p.work = g.work_right, p.C = g.C;
+    return launch_prefix_env(v, p, s);
+}
+// ... and the walk of a chunk, a (series, start) item at a time on persistent workgroups
+int launch_segment_walk(const ImpModel& v, const SegmentArgs& g, int64_t walk_wgs, hipStream_t s) {
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(walk_wgs, g.count * v.T)));
+    const bool big = prefix_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : right_lds_bytes(v.cap, v.is_complex != 0, false);
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_segment_walk<true, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_segment_walk<true, false>), grid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_segment_walk<false, true>), grid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_segment_walk<false, false>), grid, dim3(IMP_T), lds, s, v, g);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

@@ -836,6 +836,23 @@ bool prefix_big_route(int cap, bool cx);
 // not read, v.compute_f32 must be 0.  0, or -1 on a launch error
 int launch_prefix_env(const ImpModel& v, const PrefixArgs& g, hipStream_t s);
 int launch_prefix_score(const ImpModel& v, const PrefixArgs& g, hipStream_t s);
+// segment marginals (k_segment_left, k_prefix_env, k_segment_walk; mpst_segment.inl): what the kernels take by value, for one chunk of instances
+struct SegmentArgs {
+    double* L;                  // [segment_left_mats][cap * cap] (pairs): L_c^t at trace one, leading dimension chi_t (mpst_segment_plan.h: the slots)
+    double* lnL;                // [T + 1][C]: ln tr of the recursion up to bond t
+    double* G;                  // [prefix_table_mats][cap * cap] (pairs) and
+    double* lnG;                // [T + 1][C]: the tables of k_prefix_env
+    double* work_left;          // [C][PREFIX_ENV_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null: k_segment_left's
+    double* work_right;         // ... and k_prefix_env's
+    double* work;               // [walk workgroups][SEGMENT_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null
+    double* logp;               // [chunk][T][max_width][C], the chunk's own
+    int64_t first, count;       // the instances of this chunk
+    int C, max_width;
+};
+// both tables of a model (a workgroup per class each), once per call; then the walk of a chunk on at most walk_wgs persistent workgroups,
+// a (series, start) item at a time.  v.label is not read, v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_segment_tables(const ImpModel& v, const SegmentArgs& g, hipStream_t s);
+int launch_segment_walk(const ImpModel& v, const SegmentArgs& g, int64_t walk_wgs, hipStream_t s);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 // stage 0 tri (or tri + vec merged), 1 vec, 2 fin; side (stage 0, merged only): the launch carries the tail's side workgroups

@@ -544,6 +544,13 @@ class SweepEngine:
         from .prefix import prefix_model
         return prefix_model(self, W, phi, compute=compute, label_site=label_site)
 
+    def segment_model(self, W, phi, max_width, label_site=None):
+        """mpst_segment_marginals: (logp (N, T, max_width, C), lnorm (C,), seconds), the log likelihood of the values of the sites
+        a .. a+w-1 alone under every class, every other site marginalised, for every start a and width w <= max_width; see
+        ``segments.segment_model``."""
+        from .segments import segment_model
+        return segment_model(self, W, phi, max_width, label_site=label_site)
+
     def site_conditionals(self, W, phi, label_index, x, grid_x, grid_phi, levels=None, get_wmad=True, compute="f64", label_site=None):
         """mpst_site_conditionals: the leave-one-out conditional p(x_t | x_{!=t}) of every site of every COMPLETE series, each under
         the class ``label_index[i]``; see ``conditionals.site_conditionals_model``.  Returns (nll, pit, median, err, q, seconds)."""
@@ -568,7 +575,8 @@ class SweepEngine:
 
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call; after ``site_conditionals``: (walk, grid phase);
-        after ``window_conditionals``: (walk, window kernel); after ``marginal_conditionals``: (walk, grid phase)."""
+        after ``window_conditionals``: (walk, window kernel); after ``marginal_conditionals``: (walk, grid phase); after ``segment_model``:
+        (table kernels, walk kernel)."""
         out = np.zeros(2)
         self._chk(self.lib.mpst_get_impute_phases(self.ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return float(out[0]), float(out[1])
@@ -576,7 +584,8 @@ class SweepEngine:
     def impute_info(self):
         """how the last imputation call ran: {"closed_form_densities": bool (Fourier / Legendre grid states on a uniform grid),
         "batched_sweep": bool (sixteen chains per workgroup), "env_workgroups": workgroups of the environment pass (one per
-        instance), "chains": (instance, trajectory) pairs the sweep ran for}"""
+        instance), "chains": (instance, trajectory) pairs the sweep ran for}; after ``segment_model``: "env_workgroups" is the number of
+        blocks of series the walk kernel was launched for and "chains" the (series, start) items it walked"""
         out = (C.c_int32 * 4)()
         self._chk(self.lib.mpst_get_impute_info(self.ctx, out, 4))
         return {"closed_form_densities": bool(out[0]), "batched_sweep": bool(out[1]), "env_workgroups": int(out[2]), "chains": int(out[3])}
