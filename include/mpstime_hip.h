@@ -622,7 +622,8 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
  * mpst_window_conditionals: (walk, window kernel); after mpst_marginal_conditionals: (walk, grid phase); after
  * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel); after
  * mpst_prefix_marginals: (environment kernel k_prefix_env, walk-and-score kernel k_prefix_score); after mpst_segment_marginals: (the two
- * table kernels k_segment_left and k_prefix_env, the walk kernel k_segment_walk). */
+ * table kernels k_segment_left and k_prefix_env, the walk kernel k_segment_walk); after mpst_rolling_forecasts: (tables + rows + score,
+ * grid phase). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid
@@ -631,7 +632,8 @@ int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
  * workgroup (closed-form densities and panels that fit the LDS; otherwise one instance per workgroup - same results);
  * out[2] = the workgroups of the environment pass (one per instance, whatever the number of trajectories), out[3] = the chains
  * (instance, trajectory) the sweep ran for.  After mpst_segment_marginals: out[0] = out[1] = 0, out[2] = the blocks of series its walk
- * kernel was launched for, out[3] = the (series, start) items it walked. */
+ * kernel was launched for, out[3] = the (series, start) items it walked.  After mpst_rolling_forecasts: out[0] = out[1] = 0, out[2] = the
+ * blocks of series, out[3] = the blocks of targets the chains of a block of series were cut into. */
 int  mpst_get_impute_info(void* ctx, int32_t* out, int32_t n);
 
 int  mpst_normalize(void* ctx);
@@ -760,6 +762,37 @@ int  mpst_prefix_marginals(void* ctx, const mpst_impute_model* m, double* logp_o
  * context as it was. */
 int  mpst_segment_marginals(void* ctx, const mpst_impute_model* m, int32_t max_width, double* logp_out /* [N][T][max_width][C] */,
                             double* lnorm_out /* [C], may be NULL */, double* seconds /* may be NULL */);
+
+/* Rolling-origin forecasts: for every COMPLETE series i, every origin t = 0 .. T-1 and every horizon h = 1 .. max_horizon with
+ * u = t + h - 1 < T the predictive distribution of x_u given x_0 .. x_{t-1} ONLY, every site from t on but u summed over its physical
+ * index - what mpst_marginal_conditionals gives at site u for the suffix mask of t (missing[i][j] = j >= t), for all origins from one
+ * row walk per series against model-only tables:
+ *     rho_c[s, s'] = x_t K_c^{t,u}[s, s'] x_t^H,   K_c^{u,u}[s, s'] = W_u[:, s, :] G_c^{u+1} W_u[:, s', :]^H,
+ *     K_c^{t,u}[s, s'] = sum_q W_t[:, q, :] K_c^{t+1,u}[s, s'] W_t[:, q, :]^H,
+ * x_t the walk of mpst_prefix_marginals through the sites 0 .. t-1 and G its table; then p_k = max(Re(g_k^H rho g_k), 0) on the grid
+ * states of site u and everything as in mpst_marginal_conditionals.
+ *   m           as in mpst_marginal_conditionals, all of phi is read; label_idx[i] = c in 0 .. C-1: rho = rho_c under the label slice c as
+ *               stored; label_idx[i] = -1: the class mixture rho = sum_c rho_c with every class at its stored scale, i.e. weighted by the
+ *               likelihood of the first t values under it (the posterior of mpst_prefix_marginals at length t); real and complex models,
+ *               compute MPST_COMPUTE_F64
+ *   max_horizon 1 .. T
+ *   x[N][T]     the observed values for pit_out (encoding domain); NULL: no pit
+ *   grid_x, grid_phi, ngrid, o   as in mpst_site_conditionals; a per-site table is read at the target u
+ *   outputs [N][T][max_horizon], entry [i][t][h-1], each may be NULL: nll_out (-ln of the density of the encoded state of x_u, +INFINITY
+ *               where its numerator is not positive), pit_out (the cdf at x[i][u]), med_out, err_out (WMAD), mean_out,
+ *               q_out[N][T][max_horizon][nq].  Exactly NaN where t + h > T; NaN in every output of a triple whose normalisation is not a
+ *               positive finite number - every origin > j of a series whose encoded state at site j is all zero; never NaN otherwise.
+ * seconds (may be NULL): device time of the call; mpst_get_impute_phases then returns (tables + rows + score, grid phase) and
+ * mpst_get_impute_info out[2] = the blocks of series, out[3] = the blocks of targets of a block of series.  The result of a triple
+ * depends neither on how the series and the targets are cut into blocks (free device memory, MPST_IMPUTE_CHUNK_GB) nor on what travels
+ * along: no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: NULL m / grid / o, every output NULL, pit_out without x, ngrid < 2, bad levels, max_horizon outside 1..T, label_idx
+ * outside -1 .. C-1, a malformed model; MPST_ERR_UNSUPPORTED: MPST_COMPUTE_F32, chi_max > 128, d > 16, C > 16; MPST_ERR_NOMEM: G / lnG
+ * and the table kernel's scratch do not fit the query budget - they are not cut.  A rejected call leaves the context as it was. */
+int  mpst_rolling_forecasts(void* ctx, const mpst_impute_model* m, int32_t max_horizon, const double* x /* [N][T], NULL: no pit */,
+                            const double* grid_x, const void* grid_phi, int32_t ngrid, const mpst_sitecond_opts* o,
+                            double* nll_out, double* pit_out, double* med_out, double* err_out, double* mean_out,
+                            double* q_out /* [N][T][H][nq] */, double* seconds);
 
 #ifdef __cplusplus
 }

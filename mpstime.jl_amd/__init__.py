@@ -28,6 +28,8 @@ from .prefix import (EarlyClassification, prefix_log_marginals, prefix_posterior
                      causal_scores)
 from .segments import (BestSegment, segment_log_marginals, segment_posteriors, classify_segment, segment_evidence,
                        most_discriminative_segment, segment_accuracy_map)
+from .rolling import (RollingForecasts, Backtest, rolling_forecasts, rolling_forecasts_model, backtest, horizon_errors_from,
+                      interval_coverage_from, pinball_loss_from, valid_forecast_triangle)
 from .summary import get_training_summary, training_stats, sweep_summary, print_opts
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
                      BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
@@ -47,7 +49,9 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "impute_marginal", "forecast",
            "ModelOverlaps", "model_overlaps", "class_overlaps", "EarlyClassification", "prefix_log_marginals", "prefix_posteriors",
            "classify_early", "early_accuracy_curve", "causal_scores", "BestSegment", "segment_log_marginals", "segment_posteriors", "classify_segment",
-           "segment_evidence", "most_discriminative_segment", "segment_accuracy_map", "get_training_summary", "training_stats", "sweep_summary", "print_opts",
+           "segment_evidence", "most_discriminative_segment", "segment_accuracy_map", "RollingForecasts", "Backtest", "rolling_forecasts",
+           "rolling_forecasts_model", "backtest", "horizon_errors_from", "interval_coverage_from", "pinball_loss_from", "valid_forecast_triangle",
+           "get_training_summary", "training_stats", "sweep_summary", "print_opts",
            "sahand_legendre", "sahand_legendre_encode", "UnivariateKDE", "kde", "kde_pdf",
            "legendre", "legendre_no_norm", "fourier", "series_expand", "construct_kerneldensity_wavefunction", "project_legendre", "project_fourier",
            "projected_legendre_encode", "projected_legendre_encode_no_norm", "projected_fourier_encode"]

@@ -155,6 +155,8 @@ SYMBOLS = {
     "mpst_get_info_n": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "mpst_prefix_marginals": (C.c_int, [_vp, C.POINTER(ImputeModel), _dp, _dp]),
     "mpst_segment_marginals": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp, _dp]),
+    "mpst_rolling_forecasts": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp, _vp, _i32, C.POINTER(SiteCondOpts), _dp, _dp, _dp, _dp, _dp,
+                               _dp, _dp]),
 }
 
 _lib = None

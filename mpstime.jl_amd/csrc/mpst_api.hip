@@ -18,6 +18,7 @@
 #include "mpst_bond_plan.h"
 #include "mpst_prefix_plan.h"
 #include "mpst_segment_plan.h"
+#include "mpst_rolling_plan.h"
 
 using namespace mpst;
 
@@ -2930,6 +2931,86 @@ static int run_margcond(Ctx* c, const ImpModel& m, const MargcondRequest& r) {
     }, MargcondHooks{c, T, nq, {nll, pit, med, err, mean, q}, {r.nll_out, r.pit_out, r.med_out, r.err_out, r.mean_out, nq > 0 ? r.q_out : nullptr}});
 }
 
+// One mpst_rolling_forecasts call: the horizons, the values (may be NULL), the grid, and the six outputs, each of which may be NULL
+struct RollingRequest {
+    const mpst_sitecond_opts* o;
+    int32_t C, label_site, max_horizon;
+    const double *x, *grid_x;
+    const void* grid_phi;
+    int32_t ngrid;
+    double *nll_out, *pit_out, *med_out, *err_out, *mean_out, *q_out, *seconds;
+};
+// The rolling forecasts of a request (mpst_rolling_plan.h: rolling_plan).  G / lnG and the scratch of the table kernel live for the
+// whole call and must fit the budget as they are; the chains are cut over blocks of targets, the series over blocks by what is left.  A
+// block of series walks its rows, then takes the blocks of targets one after the other - the chains of a block of targets, then the score
+// of every (origin, horizon) whose target lies in it - and finishes with the grid phase: with more than one block of series the chains
+// are formed again for each.  The phases are (tables + rows + score, grid phase).
+constexpr int ROLLING_MAX_CLASSES = 16;
+static int run_rolling(Ctx* c, const ImpModel& m, const RollingRequest& r) {
+    const int64_t N = m.N, T = m.T, H = r.max_horizon;
+    const int zw = m.is_complex ? 2 : 1, nq = r.o->nq, Cn = r.C;
+    const bool per_site = r.o->grid_per_site == 1;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const bool big = prefix_big_route(m.cap, m.is_complex != 0);
+    const int outputs = (r.nll_out ? 1 : 0) + (r.pit_out ? 1 : 0) + (r.med_out ? 1 : 0) + (r.err_out ? 1 : 0) + (r.mean_out ? 1 : 0) + nq;
+    const RollingPlan p = rolling_plan(N, m.T, Cn, r.label_site, m.cap, m.d, zw, r.max_horizon, outputs, big, free_b, chunk_gb_override());
+    if (p.nomem)
+        return fail(c, MPST_ERR_NOMEM, "the tables of the model and the table kernel's scratch need %.3f GB of device memory, the budget of a query is "
+                    "%.3f GB: they are not cut", (double)p.fixed_bytes / (double)(1ull << 30),
+                    query_budget(free_b, chunk_gb_override()) / (double)(1ull << 30));
+    const int64_t chunk = p.chunk, mat = (int64_t)m.cap * m.cap * zw, trip = chunk * T * H;
+    DevBuf<double> dx, gx, gp, lev, nll, pit, med, err, mean, q, G, lnG, wenv, K, work, rows, lrow, rho, pb, sb;
+    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, grid_doubles(m, per_site, r.ngrid))) ||
+        (rc = dalloc(c, G, prefix_table_mats(m.T, Cn, r.label_site) * mat)) || (rc = dalloc(c, lnG, (T + 1) * Cn)) ||
+        (big && (rc = dalloc(c, wenv, (int64_t)Cn * PREFIX_ENV_BIG_MATS * mat))) ||
+        (rc = dalloc(c, K, p.tblock * rolling_target_mats(r.max_horizon, Cn, m.d) * mat)) || (rc = dalloc(c, work, p.table_wgs * mat)) ||
+        (rc = dalloc(c, rows, chunk * T * Cn * m.cap * zw)) || (rc = dalloc(c, lrow, chunk * T * Cn)) ||
+        (rc = dalloc(c, rho, trip * m.d * m.d * zw)) || (rc = dalloc(c, pb, p.grid_wgs * r.ngrid)) || (rc = dalloc(c, sb, p.grid_wgs * r.ngrid)) ||
+        (r.x && (rc = dalloc(c, dx, N * T))) || (nq > 0 && ((rc = dalloc(c, lev, nq)) || (rc = dalloc(c, q, trip * nq)))) ||
+        (r.nll_out && (rc = dalloc(c, nll, trip))) || (r.pit_out && (rc = dalloc(c, pit, trip))) || (r.med_out && (rc = dalloc(c, med, trip))) ||
+        (r.err_out && (rc = dalloc(c, err, trip))) || (r.mean_out && (rc = dalloc(c, mean, trip)))) return rc;
+    HIPC(c, hipMemcpy(gx, r.grid_x, (size_t)r.ngrid * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)grid_doubles(m, per_site, r.ngrid) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.x) HIPC(c, hipMemcpy(dx, r.x, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+    if (nq > 0) HIPC(c, hipMemcpy(lev, r.o->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+    RollingArgs g{};
+    g.x = dx, g.grid_x = gx, g.grid_phi = gp, g.levels = lev;
+    g.grid_site_stride = per_site ? (int64_t)r.ngrid * m.d * zw : 0;
+    g.nll = nll, g.pit = pit, g.med = med, g.err = err, g.mean = mean, g.q = q;
+    g.G = G, g.lnG = lnG, g.K = K, g.work = work, g.rows = rows, g.lrow = lrow, g.rho = rho, g.pbuf = pb, g.sbuf = sb;
+    g.C = Cn, g.H = r.max_horizon, g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.o->get_err ? 1 : 0;
+    int blocks = 0, tblocks = 0;
+    rc = run_blocks(c, N, chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        if (blocks == 0) {
+            PrefixArgs e{};
+            e.G = G, e.lnG = lnG, e.work = wenv, e.C = Cn;
+            if (launch_prefix_env(m, e, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the environment kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+        }
+        ++blocks;
+        if (launch_rolling_rows(m, g, c->stream) < 0) return fail(c, MPST_ERR_DEVICE, "the rolling row kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+        for (int64_t u0 = 0; u0 < T; u0 += p.tblock) {
+            g.u0 = (int)u0, g.u1 = (int)std::min<int64_t>(T, u0 + p.tblock);
+            if (blocks == 1) ++tblocks;
+            if (launch_rolling_tables(m, g, p.table_wgs, c->stream) < 0)
+                return fail(c, MPST_ERR_DEVICE, "the rolling table and score kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        }
+        HIPC(c, hipEventRecord(mid, c->stream));
+        if (launch_rolling_grid(m, g, std::min<int64_t>(p.grid_wgs, cnt * T * H), c->stream) < 0)
+            return fail(c, MPST_ERR_DEVICE, "the rolling grid kernel did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, MargcondHooks{c, T * H, nq, {nll, pit, med, err, mean, q}, {r.nll_out, r.pit_out, r.med_out, r.err_out, r.mean_out, nq > 0 ? r.q_out : nullptr}});
+    if (rc) return rc;
+    c->impute_trig = c->impute_batched = 0;
+    c->impute_env_wgs = blocks;
+    c->impute_chains = tblocks;
+    return 0;
+}
+
 int mpst_get_impute_phases(void* ctx, double* seconds_out) {
     Ctx* c = (Ctx*)ctx;
     if (!c || !seconds_out) return MPST_ERR_INVALID;
@@ -3216,6 +3297,32 @@ int mpst_segment_marginals(void* ctx, const mpst_impute_model* h, int32_t max_wi
     DevModel dm;
     if ((rc = upload_model(c, h, cap, false, &dm))) return rc;
     return run_segment(c, dm.view, SegmentRequest{h->C, h->label_site, max_width, logp_out, lnorm_out, seconds});
+}
+
+int mpst_rolling_forecasts(void* ctx, const mpst_impute_model* h, int32_t max_horizon, const double* x, const double* grid_x, const void* grid_phi,
+                           int32_t ngrid, const mpst_sitecond_opts* o, double* nll_out, double* pit_out, double* med_out, double* err_out,
+                           double* mean_out, double* q_out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !grid_x || !grid_phi || !o) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    if (!nll_out && !pit_out && !med_out && !err_out && !mean_out && !q_out) return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
+    if (pit_out && !x) return fail(c, MPST_ERR_INVALID, "pit_out needs the values x");
+    if (ngrid < 2) return fail(c, MPST_ERR_INVALID, "fewer than 2 grid values");
+    int cap = 0, rc;
+    if ((rc = check_grid_per_site(c, o->grid_per_site)) || (rc = check_levels(c, o->nq, o->levels, q_out))) return rc;
+    if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is forecast under its own class, or under the mixture (-1)");
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, false))) return rc;
+    for (int64_t i = 0; i < h->N; ++i)
+        if (h->label_idx[i] < -1 || h->label_idx[i] >= h->C) return fail(c, MPST_ERR_INVALID, "label_idx[%lld] outside -1 .. C - 1", (long long)i);
+    if (max_horizon < 1 || max_horizon > h->T) return fail(c, MPST_ERR_INVALID, "max_horizon must lie in 1 .. T = %d (got %d)", (int)h->T, (int)max_horizon);
+    if (h->compute == MPST_COMPUTE_F32) return fail(c, MPST_ERR_UNSUPPORTED, "rolling forecasts run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > ROLLING_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "rolling forecasts hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT,
+                    ROLLING_MAX_CLASSES, cap, h->d, h->C);
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_rolling(c, dm.view, RollingRequest{o, h->C, h->label_site, max_horizon, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out,
+                                                  mean_out, o->nq > 0 ? q_out : nullptr, seconds});
 }
 
 // ---- entanglement analysis (mpst_analysis.hip) ----------------------------------------------------------------------------

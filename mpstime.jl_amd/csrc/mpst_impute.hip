@@ -34,6 +34,7 @@
 #include "mpst_internal.h"
 #include "mpst_prefix_plan.h"
 #include "mpst_segment_plan.h"
+#include "mpst_rolling_plan.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1723,6 +1724,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_margcond.inl"
 #include "mpst_prefix.inl"
 #include "mpst_segment.inl"
+#include "mpst_rolling.inl"
 
 static size_t right_lds_bytes(int cap, bool cx, bool f32) {
     const int cp = (cap + 15) & ~15;
@@ -2070,6 +2072,32 @@ int launch_segment_walk(const ImpModel& v, const SegmentArgs& g, int64_t walk_wg
         if (big) hipLaunchKernelGGL((k_segment_walk<false, true>), grid, dim3(IMP_T), 0, s, v, g);
         else hipLaunchKernelGGL((k_segment_walk<false, false>), grid, dim3(IMP_T), lds, s, v, g);
     }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// rolling-origin forecasts: the rows of a chunk, sixteen series per workgroup
+int launch_rolling_rows(const ImpModel& v, const RollingArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)((g.count + SC_B - 1) / SC_B));
+    if (v.is_complex) hipLaunchKernelGGL((k_roll_rows<true>), grid, dim3(SC_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_roll_rows<false>), grid, dim3(SC_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... the chains of a block of targets, then the score of every (tile, origin) against them
+int launch_rolling_tables(const ImpModel& v, const RollingArgs& g, int64_t table_wgs, hipStream_t s) {
+    const int64_t items = (int64_t)(g.u1 - g.u0) * g.C * rolling_pairs(v.d);
+    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(table_wgs, items)));
+    const dim3 sgrid((unsigned)(((g.count + SC_B - 1) / SC_B) * v.T));
+    if (v.is_complex) hipLaunchKernelGGL((k_roll_tables<true>), tgrid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_roll_tables<false>), tgrid, dim3(IMP_T), 0, s, v, g);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (v.is_complex) hipLaunchKernelGGL((k_roll_score<true>), sgrid, dim3(SC_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_roll_score<false>), sgrid, dim3(SC_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and the grid phase of a chunk, a (series, origin, horizon) triple at a time
+int launch_rolling_grid(const ImpModel& v, const RollingArgs& g, int64_t grid_wgs, hipStream_t s) {
+    const dim3 grid((unsigned)grid_wgs);
+    if (v.is_complex) hipLaunchKernelGGL((k_roll_grid<true>), grid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_roll_grid<false>), grid, dim3(IMP_T), 0, s, v, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace mpst

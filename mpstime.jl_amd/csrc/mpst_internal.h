@@ -853,6 +853,33 @@ struct SegmentArgs {
 // a (series, start) item at a time.  v.label is not read, v.compute_f32 must be 0.  0, or -1 on a launch error
 int launch_segment_tables(const ImpModel& v, const SegmentArgs& g, hipStream_t s);
 int launch_segment_walk(const ImpModel& v, const SegmentArgs& g, int64_t walk_wgs, hipStream_t s);
+// rolling-origin forecasts (k_roll_rows, k_prefix_env, k_roll_tables, k_roll_score, k_roll_grid; mpst_rolling.inl): what the kernels take by
+// value, for one chunk of instances and one block of targets
+struct RollingArgs {
+    const double* x;            // [N][T] observed values (encoding domain); null: no pit
+    const double* grid_x;       // [ngrid]
+    const double* grid_phi;     // [ngrid][d] or [T][ngrid][d] (pairs: complex)
+    int64_t grid_site_stride;
+    const double* levels;       // [nq]
+    double *nll, *pit, *med, *err, *mean, *q;   // [chunk][T][H] ([chunk][T][H][nq]), the chunk's own; null: skipped
+    double* G;                  // [prefix_table_mats][cap * cap] (pairs) and
+    double* lnG;                // [T + 1][C]: the tables of k_prefix_env
+    double* K;                  // [tblock][H][C][pairs][cap * cap] (pairs): K_c^{t,u}[s,s'] at the scale lnG[t][c], leading dimension chi_t
+    double* work;               // [table workgroups][cap * cap] (pairs)
+    double* rows;               // [chunk][T][C][cap] (pairs): the normalised row of every origin and class
+    double* lrow;               // [chunk][T][C]: its log, -inf once the row has vanished
+    double* rho;                // [chunk][T][H][d * d] (pairs)
+    double *pbuf, *sbuf;        // [grid workgroups][ngrid]
+    int64_t first, count;       // the instances of this chunk
+    int C, H, u0, u1;           // classes, horizons, the targets [u0, u1) of this block of tables
+    int ngrid, nq, get_err;
+};
+// the rows of a chunk (sixteen series per workgroup); the tables of the targets g.u0 .. g.u1 - 1 on table_wgs workgroups and the score
+// of every (origin, horizon) whose target lies there; the grid phase of a chunk on grid_wgs workgroups.  v.label is read (-1: the class
+// mixture), v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_rolling_rows(const ImpModel& v, const RollingArgs& g, hipStream_t s);
+int launch_rolling_tables(const ImpModel& v, const RollingArgs& g, int64_t table_wgs, hipStream_t s);
+int launch_rolling_grid(const ImpModel& v, const RollingArgs& g, int64_t grid_wgs, hipStream_t s);
 constexpr int IMPUTE_SEED_MAX_SITES = 1 << 20, IMPUTE_SEED_MAX_TRIALS = 1 << 12;      // the generator's counter packs (site, trial) into one word
 // mpst_eig.hip
 // stage 0 tri (or tri + vec merged), 1 vec, 2 fin; side (stage 0, merged only): the launch carries the tail's side workgroups

@@ -551,6 +551,14 @@ class SweepEngine:
         from .segments import segment_model
         return segment_model(self, W, phi, max_width, label_site=label_site)
 
+    def rolling_model(self, W, phi, label_index, max_horizon, x, grid_x, grid_phi, levels=None, get_wmad=True, label_site=None):
+        """mpst_rolling_forecasts: (nll, pit, median, err, mean, q, seconds), (N, T, max_horizon) arrays with entry [i, t, h - 1] for the
+        predictive distribution of site t + h - 1 given the first t values; ``label_index`` -1 asks for the class mixture; see
+        ``rolling.rolling_forecasts_model``."""
+        from .rolling import rolling_forecasts_model
+        return rolling_forecasts_model(self, W, phi, label_index, max_horizon, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad,
+                                       label_site=label_site)
+
     def site_conditionals(self, W, phi, label_index, x, grid_x, grid_phi, levels=None, get_wmad=True, compute="f64", label_site=None):
         """mpst_site_conditionals: the leave-one-out conditional p(x_t | x_{!=t}) of every site of every COMPLETE series, each under
         the class ``label_index[i]``; see ``conditionals.site_conditionals_model``.  Returns (nll, pit, median, err, q, seconds)."""
@@ -576,7 +584,7 @@ class SweepEngine:
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call; after ``site_conditionals``: (walk, grid phase);
         after ``window_conditionals``: (walk, window kernel); after ``marginal_conditionals``: (walk, grid phase); after ``segment_model``:
-        (table kernels, walk kernel)."""
+        (table kernels, walk kernel); after ``rolling_model``: (tables + rows + score, grid phase)."""
         out = np.zeros(2)
         self._chk(self.lib.mpst_get_impute_phases(self.ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return float(out[0]), float(out[1])
@@ -585,7 +593,8 @@ class SweepEngine:
         """how the last imputation call ran: {"closed_form_densities": bool (Fourier / Legendre grid states on a uniform grid),
         "batched_sweep": bool (sixteen chains per workgroup), "env_workgroups": workgroups of the environment pass (one per
         instance), "chains": (instance, trajectory) pairs the sweep ran for}; after ``segment_model``: "env_workgroups" is the number of
-        blocks of series the walk kernel was launched for and "chains" the (series, start) items it walked"""
+        blocks of series the walk kernel was launched for and "chains" the (series, start) items it walked; after ``rolling_model``:
+        the blocks of series and the blocks of targets of a block of series"""
         out = (C.c_int32 * 4)()
         self._chk(self.lib.mpst_get_impute_info(self.ctx, out, 4))
         return {"closed_form_densities": bool(out[0]), "batched_sweep": bool(out[1]), "env_workgroups": int(out[2]), "chains": int(out[3])}
