@@ -51,7 +51,7 @@ extern "C" {
 /* 2: mpst_get_info writes 16 entries (1: 12), mpst_set_dtype / mpst_get_info_n added, element types other than Float64
  *    accepted by mpst_set_dataset / mpst_set_mps.  A host compares mpst_version() with the header it was built against.
  *    The number moves when a declared function or struct changes its layout or meaning; functions added beside the existing
- *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis, mpst_window_conditionals, mpst_marginal_conditionals) and entries appended to a getter that takes its length
+ *    ones (mpst_impute_traj, mpst_impute_model_traj, mpst_impute_dist, mpst_impute_model_dist, mpst_marginal_model, mpst_site_conditionals, mpst_pair_analysis, mpst_window_conditionals, mpst_marginal_conditionals, mpst_observed_conditionals) and entries appended to a getter that takes its length
  *    (mpst_get_impute_info) leave every existing caller valid and do not move it. */
 #define MPST_ABI_VERSION 2
 
@@ -623,7 +623,7 @@ int  mpst_model_overlaps(void* ctx, const mpst_impute_model* models /* [K] */, i
  * mpst_marginal_model, which has one kernel: (its device seconds, 0); after mpst_pair_analysis: (pair walk, entropy kernel); after
  * mpst_prefix_marginals: (environment kernel k_prefix_env, walk-and-score kernel k_prefix_score); after mpst_segment_marginals: (the two
  * table kernels k_segment_left and k_prefix_env, the walk kernel k_segment_walk); after mpst_rolling_forecasts: (tables + rows + score,
- * grid phase). */
+ * grid phase); after mpst_observed_conditionals: (operators + walk, grid phase). */
 int  mpst_get_impute_phases(void* ctx, double* seconds_out /*[2]*/);
 /* How the last imputation call ran (at most n entries): out[0] = 1 when the grid states were recognised as the Fourier basis
  * (src/Encodings/bases.jl:23-42) on a uniform grid and the conditional densities |rho phi(x)|^2 and their cumulative trapezoid
@@ -793,6 +793,62 @@ int  mpst_rolling_forecasts(void* ctx, const mpst_impute_model* m, int32_t max_h
                             const double* grid_x, const void* grid_phi, int32_t ngrid, const mpst_sitecond_opts* o,
                             double* nll_out, double* pit_out, double* med_out, double* err_out, double* mean_out,
                             double* q_out /* [N][T][H][nq] */, double* seconds);
+
+/* Observed conditionals: mpst_marginal_conditionals with a MEASUREMENT at every site in place of "known exactly" / "missing" (DESIGN.md
+ * 29).  Site (i, t) has a kind and two parameters a[i][t], b[i][t] in the encoding's domain:
+ *     MPST_OBS_EXACT     the value is x[i][t], state phi[i][t]                  E = phi phi^H
+ *     MPST_OBS_MISSING   nothing observed                                       E = 1
+ *     MPST_OBS_GAUSS     y = a, noise sd b > 0:  k_k = exp(-(x_k - a)^2 / (2 b^2)) / (b sqrt(2 pi))
+ *     MPST_OBS_INTERVAL  a <= x <= b:            k_k = 1 if a <= x_k <= b (as doubles), else 0
+ *                                                                               E[s, s'] = sum_k w_k k_k g_k[s] conj(g_k[s'])
+ *     MPST_OBS_OPERATOR  the caller's Hermitian d x d matrix                    E = E_user[i][t]
+ * w_k the weights of cumul_trapz_even on the grid (dx / 2 at the two ends, dx inside), g_k row k of site t's grid table.  The density
+ * walk steps through a site with operator E as L' = sum_{s'} B_{s'}^T L conj(A_{s'}), B_{s'} = sum_s conj(E[s, s']) A_s, A_s =
+ * W_t[:, s, :] (and alike from the right); rho_t, p_k, Z and the selection rules are those of mpst_marginal_conditionals - site t's own
+ * observation never enters rho_t.
+ *   m, grid_x, grid_phi, ngrid, o   as in mpst_marginal_conditionals; phi[i][t] is read at the EXACT sites, and at a MISSING site only
+ *                     when x[i][t] is finite
+ *   kind[N][T]        MPST_OBS_*; NULL: every site EXACT
+ *   a, b [N][T]       read at the GAUSS and INTERVAL sites only; may be NULL when there are none
+ *   E_user[N][T][d][d]   row-major, (re, im) pairs for MPST_DTYPE_C64; read at the OPERATOR sites only; may be NULL when there are none
+ *   x[N][T]           the value of an EXACT site, the held-out true value of a MISSING one or NaN; NULL: no value anywhere (pit must
+ *                     then be NULL, nll_obs of an EXACT site is still given)
+ * Outputs (mpst_observed_out), each may be NULL and is then skipped, at least one must be given.  Per (i, t), [N][T]:
+ *   pred_med, pred_err, pred_mean, pred_q[N][T][nq]   median, WMAD, mean and levels of p: the true value given the OTHER sites' observations
+ *   post_med, post_err, post_mean, post_q[N][T][nq]   the same of k_k p_k: the true value given ALL observations.  Equal to the predictive
+ *                     group at a MISSING site; NaN at EXACT and OPERATOR sites and where trapz(k p) is not a positive finite number
+ *   nll_obs           -ln(tr(E_t rho_t) / Z), the leave-one-out score of the observation as it was made: at an EXACT site the nll of
+ *                     mpst_marginal_conditionals; at a MISSING site the held-out score of a finite x[i][t], else NaN; +inf where the
+ *                     numerator is not positive
+ *   pit               at EXACT sites (and at a MISSING site with a finite x[i][t]) as in mpst_marginal_conditionals; NaN elsewhere
+ * Per series: logev[N], the natural log of the un-normalised chain value under class label_idx[i] - the logs of the traces the left
+ * walk divides by plus ln tr(E_{T-1} rho_{T-1}); ln ||W_c||^2 for a row of MISSING sites; -inf where a trace is not a positive finite
+ * number.  E_out[N][T][d][d] (layout of E_user): the operators the walk used, EXACT and MISSING sites written as phi phi^H and 1.
+ * seconds (may be NULL): device time; mpst_get_impute_phases then returns (operators + walk, grid phase).  Results depend neither on how
+ * the series are cut into blocks nor on what travels along: no floating-point atomics, one reduction order.
+ * MPST_ERR_INVALID: what mpst_marginal_conditionals refuses, and: out NULL or every output NULL, a kind outside 0 .. 4, GAUSS with b not
+ * a positive finite number or a not finite, INTERVAL with a > b or an end that is not finite, a GAUSS / INTERVAL site with a or b NULL,
+ * an OPERATOR site with E_user NULL; MPST_ERR_UNSUPPORTED as there.  A rejected call leaves the context as it was. */
+enum { MPST_OBS_EXACT = 0, MPST_OBS_MISSING = 1, MPST_OBS_GAUSS = 2, MPST_OBS_INTERVAL = 3, MPST_OBS_OPERATOR = 4 };
+typedef struct {
+    double* pred_med;
+    double* pred_err;
+    double* pred_mean;
+    double* pred_q;     /* [N][T][nq] */
+    double* post_med;
+    double* post_err;
+    double* post_mean;
+    double* post_q;     /* [N][T][nq] */
+    double* nll_obs;
+    double* pit;
+    double* logev;      /* [N] */
+    void* E_out;        /* [N][T][d][d] */
+} mpst_observed_out;
+int  mpst_observed_conditionals(void* ctx, const mpst_impute_model* m, const uint8_t* kind /* [N][T], NULL = all EXACT */,
+                                const double* a, const double* b /* [N][T] */,
+                                const void* E_user /* [N][T][d][d], read at OPERATOR sites only, may be NULL */,
+                                const double* x /* [N][T] */, const double* grid_x, const void* grid_phi, int32_t ngrid,
+                                const mpst_sitecond_opts* o, mpst_observed_out* out, double* seconds /* may be NULL */);
 
 #ifdef __cplusplus
 }

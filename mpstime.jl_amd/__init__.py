@@ -30,6 +30,8 @@ from .segments import (BestSegment, segment_log_marginals, segment_posteriors, c
                        most_discriminative_segment, segment_accuracy_map)
 from .rolling import (RollingForecasts, Backtest, rolling_forecasts, rolling_forecasts_model, backtest, horizon_errors_from,
                       interval_coverage_from, pinball_loss_from, valid_forecast_triangle)
+from .observations import (ObservationModel, ObservedConditionals, gaussian_noise, interval_observations, observed_conditionals,
+                           observed_conditionals_model, denoise, noisy_log_likelihoods, noisy_class_posteriors, classify_noisy)
 from .summary import get_training_summary, training_stats, sweep_summary, print_opts
 from .tuning import (tune, evaluate, eval_loss, fit_batch, BatchFit, MPSRandomSearch, TuningLoss, ClassificationLoss, MisclassificationRate,
                      BalancedMisclassificationRate, ImputationLoss, make_windows, make_stratified_cvfolds, classify_many)
@@ -51,6 +53,8 @@ __all__ = ["SweepEngine", "comm_library", "sweep_batch", "sweep_batch_multi", "M
            "classify_early", "early_accuracy_curve", "causal_scores", "BestSegment", "segment_log_marginals", "segment_posteriors", "classify_segment",
            "segment_evidence", "most_discriminative_segment", "segment_accuracy_map", "RollingForecasts", "Backtest", "rolling_forecasts",
            "rolling_forecasts_model", "backtest", "horizon_errors_from", "interval_coverage_from", "pinball_loss_from", "valid_forecast_triangle",
+           "ObservationModel", "ObservedConditionals", "gaussian_noise", "interval_observations", "observed_conditionals",
+           "observed_conditionals_model", "denoise", "noisy_log_likelihoods", "noisy_class_posteriors", "classify_noisy",
            "get_training_summary", "training_stats", "sweep_summary", "print_opts",
            "sahand_legendre", "sahand_legendre_encode", "UnivariateKDE", "kde", "kde_pdf",
            "legendre", "legendre_no_norm", "fourier", "series_expand", "construct_kerneldensity_wavefunction", "project_legendre", "project_fourier",

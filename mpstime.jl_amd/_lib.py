@@ -82,6 +82,11 @@ class SiteCondOpts(C.Structure):        # mpst_sitecond_opts
                 ("levels", C.POINTER(C.c_double))]
 
 
+class ObservedOut(C.Structure):         # mpst_observed_out
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in ("pred_med", "pred_err", "pred_mean", "pred_q", "post_med", "post_err", "post_mean", "post_q",
+                                                     "nll_obs", "pit", "logev")] + [("E_out", C.c_void_p)]
+
+
 SYMBOLS = {
     "mpst_version": (C.c_int, []),
     "mpst_last_error": (C.c_char_p, [_vp]),
@@ -157,6 +162,8 @@ SYMBOLS = {
     "mpst_segment_marginals": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp, _dp]),
     "mpst_rolling_forecasts": (C.c_int, [_vp, C.POINTER(ImputeModel), _i32, _dp, _dp, _vp, _i32, C.POINTER(SiteCondOpts), _dp, _dp, _dp, _dp, _dp,
                                _dp, _dp]),
+    "mpst_observed_conditionals": (C.c_int, [_vp, C.POINTER(ImputeModel), C.POINTER(C.c_uint8), _dp, _dp, _vp, _dp, _dp, _vp, _i32,
+                                             C.POINTER(SiteCondOpts), C.POINTER(ObservedOut), _dp]),
 }
 
 _lib = None

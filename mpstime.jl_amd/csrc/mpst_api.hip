@@ -19,6 +19,7 @@
 #include "mpst_prefix_plan.h"
 #include "mpst_segment_plan.h"
 #include "mpst_rolling_plan.h"
+#include "mpst_observed_plan.h"
 
 using namespace mpst;
 
@@ -2931,6 +2932,100 @@ static int run_margcond(Ctx* c, const ImpModel& m, const MargcondRequest& r) {
     }, MargcondHooks{c, T, nq, {nll, pit, med, err, mean, q}, {r.nll_out, r.pit_out, r.med_out, r.err_out, r.mean_out, nq > 0 ? r.q_out : nullptr}});
 }
 
+// One mpst_observed_conditionals call: the kinds and parameters (validated by the entry point), the grid, and the outputs
+struct ObservedRequest {
+    const mpst_sitecond_opts* o;
+    const uint8_t* kind;
+    const double *a, *b;
+    const void* E_user;
+    const double *x, *grid_x;
+    const void* grid_phi;
+    int32_t ngrid;
+    const mpst_observed_out* out;
+    double* seconds;
+};
+// what an observed-conditionals call does around its blocks: the caller's operators of a block go to the device before its kernels, its
+// outputs are its own on the device and go to the caller's arrays after them, both outside the phases
+struct ObservedHooks {
+    Ctx* c; int64_t T, op; int nq;          // op: doubles of one operator
+    const double* E_user; double* devE;
+    double* dev[12]; double* host[12];      // the ten per-site outputs (q: 3 and 7), logev, E_out
+    bool own_begin() const { return true; }
+    int prepare() { return 0; }
+    int before(int64_t i0, int64_t cnt) {
+        if (E_user) HIPC(c, hipMemcpyAsync(devE, E_user + (size_t)(i0 * T * op), (size_t)(cnt * T * op) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+    int after(int64_t i0, int64_t cnt) {
+        for (int k = 0; k < 12; ++k) {
+            if (!host[k]) continue;
+            const int64_t per = k == 10 ? 1 : k == 11 ? T * op : T * ((k == 3 || k == 7) ? nq : 1);
+            HIPC(c, hipMemcpyAsync(host[k] + (size_t)(i0 * per), dev[k], (size_t)(cnt * per) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+// The observed conditionals of a request: run_margcond's scratch plus the operators of a block (mpst_observed_plan.h:
+// observed_plan_block).  The phases are (operators + walk, grid phase); the grid phase runs only if a per-site output is asked for.
+static int run_observed(Ctx* c, const ImpModel& m, const ObservedRequest& r) {
+    const int64_t N = m.N, T = m.T;
+    const int zw = m.is_complex ? 2 : 1, nq = r.o->nq;
+    const bool per_site = r.o->grid_per_site == 1;
+    const mpst_observed_out& u = *r.out;
+    hipError_t ea = impute_init_attrs(c->device);
+    if (ea != hipSuccess) return fail(c, MPST_ERR_DEVICE, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));
+    size_t free_b = 0;
+    int rc;
+    if ((rc = free_device_bytes(c, &free_b))) return rc;
+    const bool big = margcond_big_route(m.cap, m.is_complex != 0);
+    double* const site_out[10] = {u.pred_med, u.pred_err, u.pred_mean, nq > 0 ? u.pred_q : nullptr, u.post_med, u.post_err, u.post_mean,
+                                  nq > 0 ? u.post_q : nullptr, u.nll_obs, u.pit};
+    int outputs = 0;
+    bool grid = false;
+    for (int k = 0; k < 10; ++k)
+        if (site_out[k]) outputs += (k == 3 || k == 7) ? nq : 1, grid = true;
+    const ObservedBlock blk = observed_plan_block(N, m.T, m.cap, m.d, zw, outputs, big, free_b, chunk_gb_override());
+    const int64_t chunk = blk.chunk, mat = (int64_t)m.cap * m.cap * zw, op = (int64_t)m.d * m.d * zw;
+    const bool soft = r.a && r.b;
+    DevBuf<double> dx, da, db, gx, gp, lev, so[10], logev, E, dens, rho, work, pb, sb;
+    DevBuf<uint8_t> kind;
+    if ((rc = dalloc(c, gx, r.ngrid)) || (rc = dalloc(c, gp, grid_doubles(m, per_site, r.ngrid))) || (rc = dalloc(c, dens, chunk * T * mat)) ||
+        (rc = dalloc(c, rho, chunk * T * op)) || (rc = dalloc(c, E, chunk * T * op)) || (rc = dalloc(c, logev, chunk)) ||
+        (big && (rc = dalloc(c, work, chunk * MARGCOND_BIG_MATS * mat))) ||
+        (rc = dalloc(c, pb, blk.grid_wgs * r.ngrid)) || (rc = dalloc(c, sb, blk.grid_wgs * r.ngrid)) ||
+        (r.x && (rc = dalloc(c, dx, N * T))) || (r.kind && (rc = dalloc(c, kind, N * T))) ||
+        (soft && ((rc = dalloc(c, da, N * T)) || (rc = dalloc(c, db, N * T)))) || (nq > 0 && (rc = dalloc(c, lev, nq)))) return rc;
+    for (int k = 0; k < 10; ++k)
+        if (site_out[k] && (rc = dalloc(c, so[k], chunk * T * ((k == 3 || k == 7) ? nq : 1)))) return rc;
+    HIPC(c, hipMemcpy(gx, r.grid_x, (size_t)r.ngrid * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(gp, r.grid_phi, (size_t)grid_doubles(m, per_site, r.ngrid) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.x) HIPC(c, hipMemcpy(dx, r.x, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+    if (r.kind) HIPC(c, hipMemcpy(kind, r.kind, (size_t)(N * T), hipMemcpyHostToDevice));
+    if (soft) {
+        HIPC(c, hipMemcpy(da, r.a, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(db, r.b, (size_t)(N * T) * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (nq > 0) HIPC(c, hipMemcpy(lev, r.o->levels, (size_t)nq * sizeof(double), hipMemcpyHostToDevice));
+    ObsArgs g{};
+    g.kind = kind, g.a = da, g.b = db, g.x = dx, g.grid_x = gx, g.grid_phi = gp, g.levels = lev;
+    g.grid_site_stride = per_site ? (int64_t)r.ngrid * m.d * zw : 0;
+    g.pred_med = so[0], g.pred_err = so[1], g.pred_mean = so[2], g.pred_q = so[3];
+    g.post_med = so[4], g.post_err = so[5], g.post_mean = so[6], g.post_q = so[7], g.nll = so[8], g.pit = so[9];
+    g.logev = logev, g.E = E, g.dens = dens, g.rho = rho, g.work = work, g.pbuf = pb, g.sbuf = sb;
+    g.ngrid = r.ngrid, g.nq = nq, g.get_err = r.o->get_err ? 1 : 0;
+    ObservedHooks hooks{c, T, op, nq, (const double*)r.E_user, E, {}, {}};
+    for (int k = 0; k < 10; ++k) hooks.dev[k] = so[k], hooks.host[k] = site_out[k];
+    hooks.dev[10] = logev, hooks.host[10] = u.logev;
+    hooks.dev[11] = E, hooks.host[11] = (double*)u.E_out;
+    return run_blocks(c, N, chunk, true, r.seconds, [&](int64_t i0, int64_t cnt, hipEvent_t mid) {
+        g.first = i0, g.count = cnt;
+        if (launch_observed(m, g, std::min<int64_t>(blk.grid_wgs, cnt * T), grid, c->stream, mid) < 0)
+            return fail(c, MPST_ERR_DEVICE, "the observed-conditional kernels did not launch: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }, hooks);
+}
+
 // One mpst_rolling_forecasts call: the horizons, the values (may be NULL), the grid, and the six outputs, each of which may be NULL
 struct RollingRequest {
     const mpst_sitecond_opts* o;
@@ -3264,6 +3359,48 @@ int mpst_marginal_conditionals(void* ctx, const mpst_impute_model* h, const uint
     if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
     return run_margcond(c, dm.view, MargcondRequest{o, missing, x, grid_x, grid_phi, ngrid, nll_out, pit_out, med_out, err_out, mean_out,
                                                     o->nq > 0 ? q_out : nullptr, seconds});
+}
+
+int mpst_observed_conditionals(void* ctx, const mpst_impute_model* h, const uint8_t* kind, const double* a, const double* b, const void* E_user,
+                               const double* x, const double* grid_x, const void* grid_phi, int32_t ngrid, const mpst_sitecond_opts* o,
+                               mpst_observed_out* out, double* seconds) {
+    Ctx* c = (Ctx*)ctx;
+    if (!c) return MPST_ERR_INVALID;
+    if (!h || !grid_x || !grid_phi || !o || !out) return fail(c, MPST_ERR_INVALID, "NULL argument");
+    const bool any_q = out->pred_q || out->post_q;
+    if (!out->pred_med && !out->pred_err && !out->pred_mean && !out->post_med && !out->post_err && !out->post_mean && !any_q && !out->nll_obs &&
+        !out->pit && !out->logev && !out->E_out)
+        return fail(c, MPST_ERR_INVALID, "every output is NULL: nothing to compute");
+    if (out->pit && !x) return fail(c, MPST_ERR_INVALID, "pit needs the values x");
+    if (ngrid < 2) return fail(c, MPST_ERR_INVALID, "fewer than 2 grid values");
+    int cap = 0, rc;
+    if ((rc = check_grid_per_site(c, o->grid_per_site)) || (rc = check_levels(c, o->nq, o->levels, out->pred_q ? out->pred_q : out->post_q))) return rc;
+    if (!h->label_idx) return fail(c, MPST_ERR_INVALID, "label_idx is NULL: every series is conditioned under its own class");
+    if ((rc = check_model_shape(c, h, true, true, &cap)) || (rc = check_model_types(c, h, true))) return rc;
+    if (h->compute == MPST_COMPUTE_F32) return fail(c, MPST_ERR_UNSUPPORTED, "observed conditionals run in fp64 only (compute = MPST_COMPUTE_F64)");
+    if (cap > CAP_LIMIT || h->d > 16 || h->C > MARGCOND_MAX_CLASSES)
+        return fail(c, MPST_ERR_UNSUPPORTED, "observed conditionals hold chi_max <= %d, d <= 16 and C <= %d (got %d, %d, %d)", CAP_LIMIT,
+                    MARGCOND_MAX_CLASSES, cap, h->d, h->C);
+    if (kind) {
+        const int64_t n = (int64_t)h->N * h->T;
+        for (int64_t e = 0; e < n; ++e) {
+            const long long i = (long long)(e / h->T);
+            const int t = (int)(e % h->T), k = kind[e];
+            if (k > MPST_OBS_OPERATOR) return fail(c, MPST_ERR_INVALID, "kind[%lld][%d] = %d is not one of MPST_OBS_* (0 .. 4)", i, t, k);
+            if (k == MPST_OBS_OPERATOR && !E_user) return fail(c, MPST_ERR_INVALID, "kind[%lld][%d] is MPST_OBS_OPERATOR and E_user is NULL", i, t);
+            if (k != MPST_OBS_GAUSS && k != MPST_OBS_INTERVAL) continue;
+            if (!a || !b) return fail(c, MPST_ERR_INVALID, "kind[%lld][%d] = %d needs a and b", i, t, k);
+            const bool fin = a[e] - a[e] == 0.0 && b[e] - b[e] == 0.0;
+            if (k == MPST_OBS_GAUSS && !(fin && b[e] > 0.0))
+                return fail(c, MPST_ERR_INVALID, "MPST_OBS_GAUSS at [%lld][%d]: a = %g must be finite and b = %g a positive finite number", i, t, a[e], b[e]);
+            if (k == MPST_OBS_INTERVAL && !(fin && a[e] <= b[e]))
+                return fail(c, MPST_ERR_INVALID, "MPST_OBS_INTERVAL at [%lld][%d]: the ends a = %g <= b = %g must be finite", i, t, a[e], b[e]);
+        }
+    }
+    DevModel dm;
+    if ((rc = upload_model(c, h, cap, true, &dm))) return rc;
+    return run_observed(c, dm.view, ObservedRequest{o, kind, kind ? a : nullptr, kind ? b : nullptr, kind ? E_user : nullptr, x, grid_x, grid_phi,
+                                                    ngrid, out, seconds});
 }
 
 int mpst_prefix_marginals(void* ctx, const mpst_impute_model* h, double* logp_out, double* seconds) {

@@ -1722,6 +1722,7 @@ template <typename R, bool CX, int OCC, bool TRIG = false, bool DIST = false> __
 #include "mpst_sitecond.inl"
 #include "mpst_window.inl"
 #include "mpst_margcond.inl"
+#include "mpst_observed.inl"
 #include "mpst_prefix.inl"
 #include "mpst_segment.inl"
 #include "mpst_rolling.inl"
@@ -1860,6 +1861,11 @@ hipError_t impute_init_attrs(int device) {
     for (hipError_t e : {hipFuncSetAttribute((const void*)k_mc_walk<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)right_lds_bytes(impute_lds_chi_limit(false, false), false, false)),
                          hipFuncSetAttribute((const void*)k_mc_walk<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(true, false), true, false))})
+        if (e != hipSuccess) return e;
+    for (hipError_t e : {hipFuncSetAttribute((const void*)k_obs_walk<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)right_lds_bytes(impute_lds_chi_limit(false, false), false, false)),
+                         hipFuncSetAttribute((const void*)k_obs_walk<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)right_lds_bytes(impute_lds_chi_limit(true, false), true, false))})
         if (e != hipSuccess) return e;
     for (hipError_t e : {hipFuncSetAttribute((const void*)k_prefix_env<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2019,6 +2025,29 @@ int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStr
     if (mid) (void)hipEventRecord(mid, s);
     if (v.is_complex) hipLaunchKernelGGL((k_mc_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
     else hipLaunchKernelGGL((k_mc_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// observed conditionals of a chunk: the operators of its soft sites, the walk (a workgroup per instance), an event, and - with `grid` -
+// the grid phase, a workgroup per (instance, site) pair at a time
+int launch_observed(const ImpModel& v, const ObsArgs& g, int64_t grid_wgs, bool grid, hipStream_t s, hipEvent_t mid) {
+    const dim3 wgrid((unsigned)g.count), ggrid((unsigned)grid_wgs);
+    const bool big = margcond_big_route(v.cap, v.is_complex != 0);
+    const size_t lds = big ? 0 : right_lds_bytes(v.cap, v.is_complex != 0, false);
+    if (v.is_complex) hipLaunchKernelGGL((k_obs_operator<true>), ggrid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_obs_operator<false>), ggrid, dim3(IMP_T), 0, s, v, g);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (v.is_complex) {
+        if (big) hipLaunchKernelGGL((k_obs_walk<true, true>), wgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_obs_walk<true, false>), wgrid, dim3(IMP_T), lds, s, v, g);
+    } else {
+        if (big) hipLaunchKernelGGL((k_obs_walk<false, true>), wgrid, dim3(IMP_T), 0, s, v, g);
+        else hipLaunchKernelGGL((k_obs_walk<false, false>), wgrid, dim3(IMP_T), lds, s, v, g);
+    }
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (mid) (void)hipEventRecord(mid, s);
+    if (!grid) return 0;
+    if (v.is_complex) hipLaunchKernelGGL((k_obs_grid<true>), ggrid, dim3(IMP_T), 0, s, v, g);
+    else hipLaunchKernelGGL((k_obs_grid<false>), ggrid, dim3(IMP_T), 0, s, v, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // prefix marginals: the tables of the model, a workgroup per class

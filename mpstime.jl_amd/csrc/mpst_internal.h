@@ -820,6 +820,30 @@ bool margcond_big_route(int cap, bool cx);
 // the walk (a workgroup per instance), an event, the grid phase on grid_wgs workgroups; v.label is read, v.compute_f32 must be 0.
 // 0, or -1 on a launch error
 int launch_margcond(const ImpModel& v, const McArgs& g, int64_t grid_wgs, hipStream_t s, hipEvent_t mid);
+// observed conditionals (k_obs_operator, k_obs_walk, k_obs_grid; mpst_observed.inl): what the kernels take by value, for one chunk of instances
+struct ObsArgs {
+    const uint8_t* kind;        // [N][T] MPST_OBS_* or null (every site exact)
+    const double *a, *b;        // [N][T] the parameters of the GAUSS and INTERVAL sites; null when there are none
+    const double* x;            // [N][T] values (encoding domain) of the exact sites and held-out values of the missing ones, NaN where there is none; may be null
+    const double* grid_x;       // [ngrid]
+    const double* grid_phi;     // [ngrid][d] or [T][ngrid][d] (pairs: complex)
+    int64_t grid_site_stride;
+    const double* levels;       // [nq]
+    double *pred_med, *pred_err, *pred_mean, *pred_q;       // [chunk][T] ([chunk][T][nq]), the chunk's own; null: skipped
+    double *post_med, *post_err, *post_mean, *post_q;
+    double *nll, *pit;          // [chunk][T]
+    double* logev;              // [chunk]
+    double* E;                  // [chunk][T][d * d] (pairs): the operator of every site; the OPERATOR sites' come from the host
+    double* dens;               // [chunk][T][cap * cap] (pairs): slot t holds R_{t+1} at trace one, leading dimension chi_{t+1}
+    double* rho;                // [chunk][T][d * d] (pairs)
+    double* work;               // [chunk][MARGCOND_BIG_MATS][cap * cap] (pairs) beyond the LDS limit, else null
+    double *pbuf, *sbuf;        // [grid workgroups][ngrid]
+    int64_t first, count;       // the instances of this chunk
+    int ngrid, nq, get_err;
+};
+// the operators (grid_wgs workgroups), the walk (a workgroup per instance; margcond_big_route picks its route), an event, and with `grid`
+// the grid phase on grid_wgs workgroups; v.label is read, v.compute_f32 must be 0.  0, or -1 on a launch error
+int launch_observed(const ImpModel& v, const ObsArgs& g, int64_t grid_wgs, bool grid, hipStream_t s, hipEvent_t mid);
 // prefix marginals (k_prefix_env, k_prefix_score; mpst_prefix.inl): what both kernels take by value, for one chunk of instances
 struct PrefixArgs {
     double* G;                  // [prefix_table_mats][cap * cap] (pairs): G_c^t at trace one, leading dimension chi_t (mpst_prefix_plan.h: the slots)

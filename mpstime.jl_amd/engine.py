@@ -574,6 +574,15 @@ class SweepEngine:
         return marginal_conditionals_model(self, W, phi, label_index, missing, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad,
                                            label_site=label_site)
 
+    def observed_conditionals(self, W, phi, label_index, model, x, grid_x, grid_phi, levels=None, get_wmad=True, label_site=None,
+                              return_operators=False):
+        """mpst_observed_conditionals: ``marginal_conditionals`` with a measurement - exact, missing, Gaussian noise, an interval or
+        an operator - at every site (``model``: an ``observations.ObservationModel`` in the encoding's domain); see
+        ``observations.observed_conditionals_model``.  Returns an ``ObservedConditionals``."""
+        from .observations import observed_conditionals_model
+        return observed_conditionals_model(self, W, phi, label_index, model, x, grid_x, grid_phi, levels=levels, get_wmad=get_wmad,
+                                           label_site=label_site, return_operators=return_operators)
+
     def window_conditionals(self, W, phi, label_index, max_width, label_site=None):
         """mpst_window_conditionals: -ln P(x_t .. x_{t+w-1} | the rest) of every COMPLETE series, every start t and every width
         w <= ``max_width``, each under the class ``label_index[i]``; see ``conditionals.window_conditionals_model``.
@@ -584,7 +593,8 @@ class SweepEngine:
     def impute_phases(self):
         """(environment pass, density sweep) device seconds of the last imputation call; after ``site_conditionals``: (walk, grid phase);
         after ``window_conditionals``: (walk, window kernel); after ``marginal_conditionals``: (walk, grid phase); after ``segment_model``:
-        (table kernels, walk kernel); after ``rolling_model``: (tables + rows + score, grid phase)."""
+        (table kernels, walk kernel); after ``rolling_model``: (tables + rows + score, grid phase); after ``observed_conditionals``:
+        (operators + walk, grid phase)."""
         out = np.zeros(2)
         self._chk(self.lib.mpst_get_impute_phases(self.ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return float(out[0]), float(out[1])
